@@ -11,8 +11,14 @@ GPU in 32 batches of 32:
     clip    percentile threshold per tensor                            (k_hist_percentile)
 so `--steps K` times K sweeps (~35 ms each) and `metric` / `config.workload` say N = 1024 whatever K is.
 
-The same JSON line carries, as `"mse"`, BASELINE configs[2]: the `-A mse` (OCTAV) sweep, N = 4096 images per GPU in 128
-batches of 32 through ops.octav_batch (one-read form) + the per-tensor clip — timed the same way over `--mse-steps` sweeps.
+A plain run sets up, warms up, times the K sweeps of the headline, writes the last timed sweep's outputs when
+`--dump-outputs DIR` is given (DIR/<name>.npy, float32 / float64) and prints the record line; everything described below
+besides the headline (the other sweeps, the fake-quant and end-to-end objects, the CPU baseline, the `details` line) runs
+only with `--full`.
+
+With `--full` the same JSON line carries, as `"mse"`, BASELINE configs[2]: the `-A mse` (OCTAV) sweep, N = 4096 images per
+GPU in 128 batches of 32 through ops.octav_batch (one-read form) + the per-tensor clip — timed the same way over
+`--mse-steps` sweeps (`--algo mse` makes it the headline, timed over `--steps` sweeps).
 
 `value` is whole-job images/s of the hist sweep; `roofline` is the hist kernel's (duration by HIP events on the launch
 stream inside the timed region) and carries the other objects' headline scalars (`roofline.mse` = configs[2], `.mse_jitter`,
@@ -20,8 +26,8 @@ stream inside the timed region) and carries the other objects' headline scalars 
 the set in one launch], `.e2e` = per algorithm [calibration images/s of a fresh CLI process, images/s of the network forward]);
 `cpu_baseline` times the CPU oracle (a port of the reference's
 arithmetic) on a bounded sample of the same activations on the host cores of this box, rank 0, N = 1 only.
-TWO lines are printed: `{"details": {...}}` (every object in full: workload strings, prediction statistics, the e2e split)
-and then the record's line (< 2 KB).
+With `--full` TWO lines are printed: `{"details": {...}}` (every object in full: workload strings, prediction statistics,
+the e2e split) and then the record's line (< 2 KB).
 
 Multi-GPU: launched by torch.distributed.run (one rank per GPU) — or, when started plainly with --gpus N > 1, this script
 starts the N ranks itself as child processes (before anything touches the GPU) and relays rank 0's line.  Images are
@@ -63,8 +69,19 @@ def parse():
                    help="launcher / rendezvous / collective plumbing only, on CPU tensors (no kernels, no GPU): what the "
                         "world_size-2 gloo test on the build box runs")
     p.add_argument("--algo", choices=["hist", "mse"], default="hist",
-                   help="which sweep is the headline `value` (the other one is still reported: mse as the `mse` object)")
-    return p.parse_args()
+                   help="which sweep is the headline `value`, timed over --steps sweeps (with --full the other one is still "
+                        "reported: mse as the `mse` object over --mse-steps sweeps)")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything besides the headline: the other sweep, the jitter / feature-map / ViT / 448 x 448 mse "
+                        "objects, fake-quant, the end-to-end CLI runs, the CPU baseline, and print the `details` line first")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the headline's last timed sweep computed as DIR/<name>.npy")
+    a = p.parse_args()
+    if not a.full:   # a plain run measures the headline only: every side object off
+        a.mse_jitter, a.cpu_seconds, a.e2e_images, a.real_images, a.vit_images, a.big_images, a.fq_reps = "", 0.0, 0, 0, 0, 0, 0
+        if a.algo == "hist":
+            a.mse_steps = 0
+    return a
 
 
 def self_launch(a):
@@ -85,6 +102,15 @@ def self_launch(a):
     sys.stdout.write(out.decode())
     sys.stdout.flush()
     sys.exit(max(abs(c) for c in codes))
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: DIR/<name>.npy per device tensor, float32 kept, every other dtype as float64 (int64 counts below 2^53)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), x if x.dtype == np.float32 else x.astype(np.float64))
 
 
 def cpu_baseline(algo, bins, tensors, budget_s):
@@ -258,27 +284,35 @@ def main():
                 coll_ev.append((c0, c1))
         return acc.hist_percentile(0.99999)
 
-    for _ in range(a.warmup):
-        hist_sweep(False)
-    fence()
-    t0 = time.perf_counter()
-    clip = None
-    for _ in range(a.steps):
-        clip = hist_sweep(True)
-    fence()
-    dt_local = time.perf_counter() - t0
-    dt_hist = max_over_ranks(dt_local)
-    if use_dist:   # every rank's own rate (images/s over its own clock), gathered for the line
-        rates = [torch.zeros(1, dtype=torch.float64, device=dev if backend == "nccl" else "cpu") for _ in range(world)]
-        dist.all_gather(rates, torch.tensor([N_HIST * a.steps / dt_local], dtype=torch.float64, device=rates[0].device))
-        per_rank_rates = [float(r.item()) for r in rates]
-    else:
-        per_rank_rates = [N_HIST * a.steps / dt_local]
-    hist_kern_ms = sum(s.elapsed_time(e) for s, e in hist_ev) / max(1, len(hist_ev))
-    # RCCL's three all-reduces of a sweep (MIN + MAX of the ranges, SUM of the [T, bins] int64 histograms), milliseconds per sweep
-    coll_ms = round(sum(s.elapsed_time(e) for s, e in coll_ev) / max(1, a.steps), 4) if coll_ev else None
-    hist_checksum = int(acc.hist.sum().item())        # = elements x images x ranks when every rank's counts arrived
-    clip_checksum = float(clip.double().abs().sum().item())
+    run_hist = a.full or a.algo == "hist"      # (a plain `--algo mse` run times the mse sweep alone)
+    dt_hist = per_rank_rates = coll_ms = hist_checksum = clip_checksum = None
+    hist_kern_ms = 0.0
+    if run_hist:
+        for _ in range(a.warmup):
+            hist_sweep(False)
+        fence()
+        t0 = time.perf_counter()
+        clip = None
+        for _ in range(a.steps):
+            clip = hist_sweep(True)
+        fence()
+        dt_local = time.perf_counter() - t0
+        dt_hist = max_over_ranks(dt_local)
+        if use_dist:   # every rank's own rate (images/s over its own clock), gathered for the line
+            rates = [torch.zeros(1, dtype=torch.float64, device=dev if backend == "nccl" else "cpu") for _ in range(world)]
+            dist.all_gather(rates, torch.tensor([N_HIST * a.steps / dt_local], dtype=torch.float64, device=rates[0].device))
+            per_rank_rates = [float(r.item()) for r in rates]
+        else:
+            per_rank_rates = [N_HIST * a.steps / dt_local]
+        if a.dump_outputs and a.algo == "hist" and rank == 0:
+            # what a caller of the sweep receives: the clip per tensor, and the ranges and histograms it derives from
+            dump_outputs(a.dump_outputs, {"hist_clip": clip, "hist_range_min": acc.gmin, "hist_range_max": acc.gmax,
+                                          "hist_counts": acc.hist})
+        hist_kern_ms = sum(s.elapsed_time(e) for s, e in hist_ev) / max(1, len(hist_ev))
+        # RCCL's three all-reduces of a sweep (MIN + MAX of the ranges, SUM of the [T, bins] int64 histograms), milliseconds per sweep
+        coll_ms = round(sum(s.elapsed_time(e) for s, e in coll_ev) / max(1, a.steps), 4) if coll_ev else None
+        hist_checksum = int(acc.hist.sum().item())        # = elements x images x ranks when every rank's counts arrived
+        clip_checksum = float(clip.double().abs().sum().item())
 
     # ------------------------------------------------------------------ -A mse (OCTAV), N = 4096 per GPU
     # A timed sweep is ONE COLD calibration run (forward_net.py:297-340: one independent pass over the shard): the plan forgets
@@ -286,12 +320,12 @@ def main():
     # do in a fresh process.  The pool holds more distinct batches than the prediction remembers (2 epochs of
     # ops._ONEREAD_EPOCH batches), so no batch is ever predicted from itself.
     mse, mse_jitter, vit_mse, mse_real, mse_big, mse_lanes1 = None, {}, None, {}, None, None
-    if a.mse_steps > 0:
+    if a.mse_steps > 0 or not run_hist:
         import ctypes
         form = ops._default_form()
         pipeline = os.environ.get("DPL_OCTAV_PIPELINE", "1") != "0" and form == "tail"
         pipe = ops.OctavPipeline(False, dev) if pipeline else None
-        pipe1 = ops.OctavPipeline(False, dev, lanes=1) if pipeline else None    # the schedule forward_net_octav runs (below)
+        pipe1 = ops.OctavPipeline(False, dev, lanes=1) if pipeline and a.full else None    # the schedule forward_net_octav runs (below)
         min_pool = 2 * ops._ONEREAD_EPOCH + 1
         # DPL_BENCH_FAIL_EVERY=n (a tuning aid, not the headline workload): the C ABI's test hook makes every n-th pair's walk
         # report a missed prediction, to price the device-side rescue of such pairs
@@ -299,7 +333,7 @@ def main():
         if inject > 0:
             _hip.lib().dpl_test_hook_exact_fail_every(inject)
 
-        def run_mse(mpool, steps, jit, plan=plan, n_images=N_MSE, net="ResNet-50", pipe=pipe):
+        def run_mse(mpool, steps, jit, plan=plan, n_images=N_MSE, net="ResNet-50", pipe=pipe, dump=False):
             mse_ev, mse_coll = [], []
             mpool = [plan.bind(x) for x in mpool]
             B, T, E = plan.batch, plan.T, sum(plan.elems)        # (the ViT object runs its own plan through the same code)
@@ -347,13 +381,15 @@ def main():
                 mclip = mse_sweep(True)
             fence()
             dt_mse = max_over_ranks(time.perf_counter() - t0)
+            if dump and rank == 0:     # the sweep's clip per tensor, and this rank's per-image OCTAV rows it derives from
+                dump_outputs(a.dump_outputs, {"mse_clip": mclip, "mse_rows": rows})
             mse_ms = sum(s.elapsed_time(e) for s, e in mse_ev) / max(1, len(mse_ev)) / n_mse_batches   # per batch, in the sweep
             mse_bytes = 4 * E * B          # credited: ONE read of the batch, whatever the form actually reads
             mse_ach = mse_bytes / (mse_ms * 1e-3) / 1e9 if mse_ms > 0 else 0.0
             # parity spot check against the CPU oracle (checker, after the timed region): 8 (image, tensor) pairs of the last batch
             last = mpool[(n_mse_batches - 1) % len(mpool)]
-            ok, worst = True, 0.0
-            if rank == 0:
+            ok, worst = (True, 0.0) if a.full else (None, None)      # (a plain `--algo mse` run compares nothing)
+            if rank == 0 and a.full:
                 from oracle import np_oracle as O
                 import numpy as np
                 rs = np.random.RandomState(7)
@@ -397,7 +433,7 @@ def main():
 
         if len(pool) < min_pool and rank == 0:
             print(f"bench.py: --pool {len(pool)} < {min_pool}: batches repeat inside the prediction's memory", file=sys.stderr)
-        mse = run_mse(pool, a.mse_steps, jitter)
+        mse = run_mse(pool, a.steps if a.algo == "mse" else a.mse_steps, jitter, dump=bool(a.dump_outputs) and a.algo == "mse")
         # Everything below characterises ONE GPU (other schedules, other activations, other shapes, the fake-quant kernels, the CLI end
         # to end, the CPU baseline) and is reported by the N = 1 run.  A run over several ranks measures the sharded path — the hist
         # sweep and the mse sweep with their collectives — and nothing else: N processes building ViT sessions, 448 x 448 pools and
@@ -732,7 +768,7 @@ def main():
     if mse_lanes1 is not None:
         mse_lanes1["roofline"]["kernel"] = "OCTAV batch on ONE stream (OctavPipeline(lanes=1): forward_net.forward_net_octav's schedule; the rescue beside the next batch)"
     images = N_HIST * world * a.steps
-    hist_rate = images / dt_hist
+    hist_rate = images / dt_hist if run_hist else None
     headline_mse = a.algo == "mse" and mse is not None
 
     def brief(o, short=False):
@@ -757,7 +793,8 @@ def main():
     full = {
         "hist": {"images_per_s": hist_rate, "ms_per_step": dt_hist / a.steps * 1e3, "roofline": hist_roof,
                  "algorithmic_GBps_job": 8 * E * images / dt_hist / 1e9, "hist_checksum": hist_checksum,
-                 "hist_checksum_expected": E * N_HIST * world, "clip_checksum": clip_checksum, "collectives_ms_per_sweep": coll_ms},
+                 "hist_checksum_expected": E * N_HIST * world, "clip_checksum": clip_checksum, "collectives_ms_per_sweep": coll_ms}
+                if run_hist else None,
         "mse": mse, "mse_lanes1": mse_lanes1, "mse_jitter": mse_jitter or None, "fake_quant": fake_quant, "vit_mse": vit_mse, "mse_448": mse_big,
         "mse_feature_maps": mse_real or None, "e2e": e2e,
     }
@@ -817,18 +854,18 @@ def main():
         "metric": "calibration images/sec (whole node) + achieved HBM GB/s, ResNet-50 ONNX N=%d, -A %s"
                   % ((N_MSE, "mse") if headline_mse else (N_HIST, "hist")),
         "value": round(mse["value"] if headline_mse else hist_rate, 1), "unit": "images/s", "n_gpus": world,
-        "steps": a.mse_steps if headline_mse else a.steps, "warmup": a.warmup,
+        "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": round(mse["ms_per_step"] if headline_mse else dt_hist / a.steps * 1e3, 4),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": (f"ResNet-50 activation set (T={T}, {E} fp32 elems/img), -A mse (OCTAV), N={N_MSE} per GPU in batches of {B}, cold sweeps"
                                 if headline_mse else
                                 f"ResNet-50 ONNX activation set (T={T}, {E} fp32 elems/img), -A hist --bins {a.bins}, N={N_HIST} per GPU in "
                                 f"{n_hist_batches} batches of {B}: range pass + histogram pass + percentile clip"),
-                   "device": devname, "hist_checksum_ok": hist_checksum == E * N_HIST * world,
+                   "device": devname, "hist_checksum_ok": hist_checksum == E * N_HIST * world if run_hist else None,
                    "world_size_seen_by_backend": dist.get_world_size() if use_dist else 1,
                    "backend": (backend + (" (RCCL)" if backend == "nccl" else "")) if use_dist else None,
                    "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version()) if (use_dist and backend == "nccl") else None,
-                   "per_rank_images_per_s": [round(r) for r in per_rank_rates],
+                   "per_rank_images_per_s": [round(r) for r in per_rank_rates] if run_hist else None,
                    "collectives_ms_per_sweep": coll_ms},
         "roofline": roof,
     }
@@ -849,7 +886,8 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except Exception:   # noqa: BLE001
             pass
-        print(json.dumps({"details": full}), flush=True)
+        if a.full:
+            print(json.dumps({"details": full}), flush=True)
         line = json.dumps(out)
         # (the driver keeps the last 2 000 characters of stdout as `tail`: should the line ever outgrow that, the side objects go
         # first — they are all in the details line above —, never the contract's fields)

@@ -17,9 +17,9 @@ KERNELS="k_octav|k_abs_hist|k_minmax|k_hist|k_fake_quant"
 # A warm-up process first: the MIOpen user find-db of a fresh box is empty, and the library's Find benchmark over every convolution
 # configuration of the fake-quantised forward (8 launches of its naive kernel each, profiles/r06/conv_repro.md) would sit in the trace
 python3 scripts/fq_forward_run.py > $OUT/warm.log 2>&1
-python3 bench.py --cpu-seconds 0 --e2e-images 0 --vit-images 0 --real-images 0 --big-images 0 --mse-jitter "" --steps 1 --warmup 0 --mse-steps 0 --fq-reps 1 >> $OUT/warm.log 2>&1
+python3 bench.py --full --cpu-seconds 0 --e2e-images 0 --vit-images 0 --real-images 0 --big-images 0 --mse-jitter "" --steps 1 --warmup 0 --mse-steps 0 --fq-reps 1 >> $OUT/warm.log 2>&1
 python3 scripts/mse_run.py vit 2 2 >> $OUT/warm.log 2>&1
-BENCH="python3 bench.py --cpu-seconds 0 --e2e-images 0 --vit-images 0 --real-images 0 --big-images 0 --mse-jitter"
+BENCH="python3 bench.py --full --cpu-seconds 0 --e2e-images 0 --vit-images 0 --real-images 0 --big-images 0 --mse-jitter"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- $BENCH "" > $OUT/bench_stats.json 2> $OUT/stats.err
 python3 scripts/summarize_prof.py stats $OUT/stats $OUT/kernel_stats.md > /dev/null
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv 2>/dev/null

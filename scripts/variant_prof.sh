@@ -7,7 +7,7 @@ ARGS=$1; PAT=$2; shift 2
 export TMPDIR=/tmp
 for V in "$@"; do
   DPL_HIPCC_EXTRA="$V" python3 -m dipoorlet_amd.csrc.build --force > /dev/null 2>&1 || { echo "build failed: $V"; continue; }
-  rm -rf /tmp/vp; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/vp -o b -- python3 bench.py --cpu-seconds 0 $ARGS > /tmp/vp.json 2>/dev/null
+  rm -rf /tmp/vp; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/vp -o b -- python3 bench.py --full --cpu-seconds 0 $ARGS > /tmp/vp.json 2>/dev/null
   echo "== [$V] $(python3 -c "import json;d=json.load(open('/tmp/vp.json'));print('img/s %.0f' % d['value'])")"
   python3 - "$PAT" <<'PY'
 import csv, glob, re, sys

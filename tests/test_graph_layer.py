@@ -145,7 +145,7 @@ def test_wire_format_scalar_and_attr_types(tmp_path):
     assert r.inputs == [("a", 1, [1, 0, 3])]
 
 
-def test_fold_batchnorm_keeps_the_function():
+def test_fold_batchnorm_keeps_the_function(tmp_path):
     """ONNXGraph.fold_batchnorm (the Conv + BN fusion onnxsim performs for the reference): same outputs, no BN left,
     a bias is created where the layer had none, a BN with a second consumer of its input is left alone."""
     from dipoorlet_amd.models import _B
@@ -184,7 +184,7 @@ def test_fold_batchnorm_keeps_the_function():
     out = GraphSession(graph, device="cpu").run_named(inp, ["output", "sum"])
     for a, b in zip(out, ref):
         np.testing.assert_allclose(a.numpy(), b.numpy(), rtol=2e-5, atol=2e-6)
-    path = graph.save_onnx_model("/tmp/_folded_bn_test")                # round-trips through the writer / reader
+    path = graph.save_onnx_model(str(tmp_path / "folded_bn.onnx"))     # round-trips through the writer / reader
     again = GraphSession(ONNXGraph.load(path), device="cpu").run_named(inp, ["output"])[0]
     np.testing.assert_allclose(again.numpy(), ref[0].numpy(), rtol=2e-5, atol=2e-6)
 

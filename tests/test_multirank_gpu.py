@@ -69,7 +69,7 @@ def test_bench_two_ranks_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["DPL_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--mse-steps", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--mse-steps", "1",
                         "--e2e-images", "0", "--vit-images", "0", "--real-images", "0", "--fq-reps", "0", "--mse-jitter", "", "--pool", "5",
                         "--cpu-seconds", "0"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -96,7 +96,7 @@ def test_bench_one_rank_over_rccl():
         port = sk.getsockname()[1]
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     env.pop("DPL_DIST_BACKEND", None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--mse-steps", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--steps", "1", "--warmup", "1", "--mse-steps", "1",
                         "--e2e-images", "0", "--vit-images", "0", "--real-images", "0", "--fq-reps", "0", "--mse-jitter", "", "--pool", "5",
                         "--cpu-seconds", "0"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -262,7 +262,7 @@ def test_bench_four_ranks_on_one_gpu():
     """`bench.py --gpus 4` for real on the box's one GPU (gloo; --pool 3 keeps four ranks' resident batches small): rank-indexed
     seeds, the ranges / histogram all-reduces and the gather of the OCTAV rows at world size 4, four per-rank rates, the
     collectives' milliseconds of both sweeps in rank 0's line — what the driver's N = 4 run does above the backend string.
-    With the DEFAULT side-object flags, as the driver passes none: over more than one rank the run measures the sharded path
+    With --full and the DEFAULT side-object flags, as the driver passes none: over more than one rank the run measures the sharded path
     (hist + mse with their collectives) and nothing else — no ViT / 448 x 448 / jitter / one-stream / fake-quant objects, no CLI
     children, no CPU baseline on any rank (they characterise one GPU and are the N = 1 run's)."""
     import subprocess
@@ -272,7 +272,7 @@ def test_bench_four_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["DPL_DIST_BACKEND"] = "gloo"
     t0 = time.perf_counter()
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "1", "--mse-steps", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "4", "--steps", "1", "--warmup", "1", "--mse-steps", "1",
                         "--pool", "3"], env=env, capture_output=True, text=True, timeout=1200)
     wall = time.perf_counter() - t0
     assert r.returncode == 0, r.stderr[-2000:]
@@ -299,3 +299,38 @@ def test_bench_refuses_more_rccl_ranks_than_gpus():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "0", "--mse-steps", "0",
                         "--e2e-images", "0", "--fq-reps", "0", "--cpu-seconds", "0", "--pool", "1"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "need" in (r.stderr + r.stdout)
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_it(tmp_path):
+    """`bench.py` without --full: the hist sweep alone, --steps timed sweeps, the record line only (no side objects, no CPU
+    baseline, no details line), and with --dump-outputs the last timed sweep's clip / ranges / histograms as .npy files — the
+    same bits from two processes, since the inputs are seeded."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "DPL_DIST_BACKEND")}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--pool", "2", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [x for x in r.stdout.strip().splitlines() if x.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "images/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert line["config"]["hist_checksum_ok"] is True and line["cpu_baseline"] is None
+        assert all(line["roofline"][k] is None for k in ("mse", "mse_lanes1", "mse_jitter", "mse_feature_maps", "mse_vit", "mse_448"))
+        assert "fake_quant" not in line["roofline"] and "e2e" not in line["roofline"]
+        got = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert sorted(got) == ["hist_clip", "hist_counts", "hist_range_max", "hist_range_min"]
+        assert sum(x.nbytes for x in got.values()) <= 64 << 20
+        assert got["hist_clip"].shape == (123, 2) and got["hist_clip"].dtype == np.float32
+        assert got["hist_range_min"].dtype == got["hist_range_max"].dtype == np.float32
+        assert got["hist_counts"].shape == (123, 2048) and got["hist_counts"].dtype == np.float64
+        assert got["hist_counts"].sum() == 1024 * 26598376
+        assert np.all(got["hist_range_min"] <= got["hist_range_max"])
+        dumps.append(got)
+    for k, v in dumps[0].items():
+        assert np.array_equal(v, dumps[1][k]), k
