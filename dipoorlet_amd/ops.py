@@ -244,6 +244,7 @@ class OctavTailPlan:
         self.n_multi = int(self.sizes.n_multi)
         self._single = None     # (state, rescue, list0, list1) of octav_batch
         self.fallback = None    # the compaction route's lists: allocated when a batch first reports unfinished pairs
+        self.fallback_block = None  # ... whole-batch ones, bound to every job of octav_batch(inline=True): allocated by its first call
 
     def __del__(self):
         try:
@@ -421,7 +422,7 @@ def _default_form():
     return form
 
 
-def octav_batch(plan, tensors, dynamic_sym, states=None, compact=None, form=None):
+def octav_batch(plan, tensors, dynamic_sym, states=None, compact=None, form=None, inline=False):
     """OCTAV for every (image, tensor) pair of one batch -> fp32 device tensor [B, T, 3] = (s, min, max).
 
     Forms (all end on the reference's result, forward_net.py:323-330):
@@ -431,7 +432,10 @@ def octav_batch(plan, tensors, dynamic_sym, states=None, compact=None, form=None
                            exact two-read route (csrc/octav_tail.hpp).  Pairs of up to 64 slices (a pair above one slice —
                            dpl_octav_slice_cap() elements — is streamed slice by slice and walked by a merge kernel; a set with
                            a larger pair runs 'bracket'); every buffer is sized by the C ABI (dpl_octav_plan_*, OctavTailPlan).
-                           This call reads the batch's control block back (one host synchronisation); OctavPipeline defers that
+                           This call reads the batch's control block back (one host synchronisation); OctavPipeline defers that;
+                           inline=True runs the compaction route inline instead, on a whole-batch fallback block (OctavTailPlan.
+                           fallback_block: 8 bytes per element of the batch, allocated by the plan's first such call) — no host
+                           synchronisation, the rows final in stream order (the custom ops, torch_ops.py)
       'bracket'            two reads: statistics + exact log-scale histogram, bracket walk, gather of the marked
                            bins, exact per-pair iteration; pairs it cannot serve finish on the compaction route
       'compact'            evaluation at s_0 + tail compaction, then per-pair iteration over shrinking lists
@@ -449,7 +453,7 @@ def octav_batch(plan, tensors, dynamic_sym, states=None, compact=None, form=None
     if form == "tail":
         tp = plan.octav_tail()
         if tp is not None:
-            return _octav_batch_tail(plan, tp, tensors, dynamic_sym, states)
+            return _octav_batch_tail(plan, tp, tensors, dynamic_sym, states, inline)
         mode = 2            # a pair above 64 slices: the two-read form
     w = plan.work("octav", per_image=True)
     n_pairs = plan.n_pairs
@@ -479,23 +483,27 @@ def octav_batch(plan, tensors, dynamic_sym, states=None, compact=None, form=None
     return out
 
 
-def _octav_batch_tail(plan, tp, tensors, dynamic_sym, states_out=None):
+def _octav_batch_tail(plan, tp, tensors, dynamic_sym, states_out=None, inline=False):
     """One batch of the exact-tail form on the caller's stream.  The compaction route (flat distributions, values beyond 2^14,
-    lists beyond their regions: rare) needs lists for the pairs that take it, which exist from the first batch on that asks for
-    them — so this reads the batch's control block back (the one host synchronisation of this call; OctavPipeline defers it)."""
+    a bin of 2^20 values, lists beyond their regions: rare) needs lists for the pairs that take it, which exist from the first
+    batch on that asks for them — so this reads the batch's control block back (the one host synchronisation of this call;
+    OctavPipeline defers it).  inline: the whole-batch lists (tp.fallback_block) are bound to the job instead, and
+    dpl_octav_oneread_finish runs the route in stream order — nothing is read back."""
     L = _hip.lib()
     tab = plan.seg_table(tensors)
     state, rescue, l0, l1 = tp.single()
     k = tp.calls
     tp.calls = k + 1
-    job = tp.bind(state, rescue, l0, l1, tab, k, 1 if dynamic_sym else 0)
-    job.compaction_inline = 0
+    if inline and tp.fallback_block is None:
+        tp.fallback_block = tp.new("fallback")
+    job = tp.bind(state, rescue, l0, l1, tab, k, 1 if dynamic_sym else 0, tp.fallback_block if inline else None)
     for fn in ("dpl_octav_oneread_prepare", "dpl_octav_oneread_stream", "dpl_octav_oneread_finish"):
         _hip.check(getattr(L, fn)(C.byref(job), _stream()), fn)
     csz = C.sizeof(_hip.OctavState)
-    ctl = _hip.OctavState.from_buffer_copy(state[plan.n_pairs * csz:(plan.n_pairs + 1) * csz].cpu().numpy().tobytes())
-    if ctl.cnt_le:
-        tp.fallback = tp.compaction(job, state, torch.cuda.current_stream(plan.device), tp.fallback)
+    if not inline:
+        ctl = _hip.OctavState.from_buffer_copy(state[plan.n_pairs * csz:(plan.n_pairs + 1) * csz].cpu().numpy().tobytes())
+        if ctl.cnt_le:
+            tp.fallback = tp.compaction(job, state, torch.cuda.current_stream(plan.device), tp.fallback)
     out = torch.empty(plan.batch, plan.T, 3, dtype=torch.float32, device=plan.device)
     _hip.check(L.dpl_octav_finalize(_ptr(state), plan.n_pairs, _ptr(out), _stream()), "dpl_octav_finalize")
     if states_out is not None:      # (the caller's view of the pairs' states and the control block, as the other forms leave them)

@@ -23,9 +23,11 @@ Over every tensor of a batch of images in ONE launch — what the reference's lo
 No allocation inside except the outputs, no host synchronisation: everything a launch needs besides its inputs — the work
 decomposition of the tensor set, the pointer-table slots, accumulators, OCTAV workspace — belongs to a plan cached on
 (per-image sizes, batch, device) and is built by the FIRST call with that key; later calls only launch.  The OCTAV ops run the
-exact-tail form through an ops.OctavPipeline on the caller's stream: the control block of a batch (how many pairs were rescued;
-whether a pair is left for the rare compaction route) is read from pinned memory a few calls later, never waited for — the result
-rows are ordered behind the kernels on the device (a stream wait).
+exact-tail form on the caller's stream (ops.octav_batch(inline=True)): the rare pairs that neither the walk nor the rescue finish
+(values of 2^14 and above or +-inf, a log bin of 2^20 values or more) take the compaction route in the same stream order, on a
+whole-batch fallback block the plan allocates with its first OCTAV call — 8 bytes per element of the batch, twice the batch's
+activations, held as long as the plan is cached.  Nothing is read back: the rows are final once the caller's stream reaches them,
+and no reference to the inputs outlives the call.  (A set with a pair above 64 slices runs the two-read form, as octav_batch does.)
 """
 import ctypes
 from typing import List, Tuple
@@ -46,7 +48,7 @@ class _Cached:
         self.plan = ops.TensorSetPlan(elems, batch, device)
         self.device = device
         self.acc = {}        # bins -> CalibAccumulators (min / max encodings, histogram ranges; hist: the caller's tensor)
-        self.pipes = {}      # dynamic_sym -> OctavPipeline on the caller's stream
+        self.octav_done = torch.cuda.Event()    # behind the last OCTAV call: its workspace is the plan's one set of buffers
         self.fq = {}         # parameter identity -> FakeQuantSet
 
     def accumulators(self, bins):
@@ -55,12 +57,6 @@ class _Cached:
             a = self.acc[bins] = ops.CalibAccumulators(self.plan.T, self.device, bins)
             a.ranges = torch.empty(a.n * ctypes.sizeof(_hip.HistRange), dtype=torch.uint8, device=self.device)
         return a
-
-    def pipeline(self, dynamic_sym):
-        p = self.pipes.get(bool(dynamic_sym))
-        if p is None:
-            p = self.pipes[bool(dynamic_sym)] = ops.OctavPipeline(bool(dynamic_sym), self.device, lanes=1)
-        return p
 
 
 def _cached(xs, batch=None):
@@ -179,12 +175,10 @@ def _(hist, gmin, gmax, threshold):
 def _octav(xs, dynamic_sym, batch=None):
     xs = _contig(xs)
     c = _cached(xs, batch)
-    pipe = c.pipeline(dynamic_sym)
-    out = pipe.submit(c.plan, xs)
-    ps = pipe._plans.get(id(c.plan))
-    if ps is not None:      # (the exact-tail form: the rows are written on the pipeline's side stream — order this stream behind it)
-        done = ps["sets"][(ps["calls"] - 1) % len(ps["sets"])]["done"]
-        torch.cuda.current_stream(c.device).wait_event(done)
+    stream = torch.cuda.current_stream(c.device)
+    stream.wait_event(c.octav_done)     # (a caller that switches streams: the last call's kernels are done with the workspace)
+    out = ops.octav_batch(c.plan, xs, dynamic_sym, inline=True)
+    c.octav_done.record(stream)
     return out
 
 

@@ -79,6 +79,20 @@ def _batch(seed0):
     return host, [torch.from_numpy(h).cuda() for h in host]
 
 
+def _route_batch(seed0):
+    """_batch with a pair of the OCTAV compaction route in it (a value of 2^14 in image 1 of the 150 528-element ReLU tensor)."""
+    host, dev = _batch(seed0)
+    host[1][1, 4321] = 2.0 ** 14
+    dev[1][1, 4321] = 2.0 ** 14
+    return host, dev
+
+
+def _close(a, b, tol=1e-5):
+    """test_hip_parity's bound: |a - b| <= tol * max(1, |b|); NaN where the oracle gives NaN."""
+    a, b = float(a), float(b)
+    return (np.isnan(a) and np.isnan(b)) or a == b or abs(a - b) <= tol * max(1.0, abs(b))
+
+
 @pytest.mark.gpu
 def test_batched_ops_against_oracle():
     """minmax_batched / abs_hist_batched_ / octav_batched / fake_quant_set over every tensor of a batch in one launch each, two
@@ -142,9 +156,9 @@ def test_second_call_allocates_only_outputs_and_does_not_synchronise():
     are built), then again on NEW input tensors of the same geometry under torch.cuda.set_sync_debug_mode('error') with the
     caching allocator's allocation count read before and after: the difference is the op's outputs, nothing else."""
     T = len(SET)
-    _, first = _batch(11)
-    _, second = _batch(12)
-    _, third = _batch(13)
+    _, first = _route_batch(11)
+    host2, second = _route_batch(12)
+    _, third = _route_batch(13)
     mins = torch.full((T,), float("inf"), device="cuda")
     maxs = torch.full((T,), float("-inf"), device="cuda")
     hist = torch.zeros(T, 2048, dtype=torch.int64, device="cuda")
@@ -180,3 +194,17 @@ def test_second_call_allocates_only_outputs_and_does_not_synchronise():
             after = torch.cuda.memory_stats()["allocation.all.allocated"]
             assert after - before == n_out, (name, after - before, n_out)
     torch.cuda.synchronize()
+    # the second batch's OCTAV rows, read as a torch caller reads them (no pipeline sync()): final, the route pair's included
+    names = list(calls)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        x = host2[1].reshape(-1)
+        s = keep[names.index("octav")].cpu().numpy()
+        assert s[1] == x.min() and s[2] == x.max() and _close(s[0], O.octav_scale(x, 1)), (s, O.octav_scale(x, 1))
+        rows = keep[names.index("octav_batched")].cpu().numpy()
+        for t in range(T):
+            for b in range(B):
+                mn, mx = O.minmax(host2[t][b])
+                want = O.octav_scale(host2[t][b], 1)
+                assert rows[b, t, 1] == mn and rows[b, t, 2] == mx, (SET[t], b)
+                assert _close(rows[b, t, 0], want), (SET[t], b, rows[b, t, 0], want)
