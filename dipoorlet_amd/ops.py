@@ -935,6 +935,11 @@ def cos_accumulate(a, b, acc, slot=0):
     _require_cuda(b, "b")
     if a.numel() != b.numel():
         raise _hip.DipoorletHipError("cos_accumulate: size mismatch")
+    # (the kernel adds three fp64 values at acc + 3 * slot: a slot the accumulator does not hold would be written past its end)
+    if not (isinstance(acc, torch.Tensor) and acc.device == a.device and acc.dtype == torch.float64 and acc.is_contiguous()):
+        raise _hip.DipoorletHipError("cos_accumulate: acc must be a contiguous fp64 tensor on a's device")
+    if not 0 <= int(slot) < acc.numel() // 3:
+        raise _hip.DipoorletHipError(f"cos_accumulate: slot {slot} outside an accumulator of {acc.numel() // 3} slots")
     _hip.check(_hip.lib().dpl_cos_accumulate(_ptr(a), _ptr(b), a.numel(), _ptr(acc), slot, _stream()),
                "dpl_cos_accumulate")
     return acc

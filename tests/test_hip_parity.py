@@ -1196,3 +1196,357 @@ def test_pipeline_streams_run_beside_the_callers_stream(dev):
     ext.synchronize()
     assert float(y) == 28.0
     _hip.check(_hip.lib().dpl_stream_destroy(h), "dpl_stream_destroy")
+
+
+# ------------------------------------------------------------------ the side kernels at their edges, against fp64 / numpy
+def _same_f32(got, want):
+    """fp32 bit for bit, except that any NaN equals any NaN (the kernel writes the canonical quiet NaN, numpy returns the one it
+    met) and -0.0 equals +0.0: fminf / fmaxf may return either zero of a (-0, +0) pair, and so may numpy's vectorised min / max
+    (the reference's np.min over a row of ±0 is a zero of either sign, the same number)."""
+    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
+    same_bits = got.view(np.uint32) == want.view(np.uint32)
+    return same_bits | (np.isnan(got) & np.isnan(want)) | ((got == 0) & (want == 0))
+
+
+def test_rowwise_minmax_vs_numpy_rows_off_16_bytes(dev):
+    """k_rowwise_minmax (every per-channel weight range, weight_clip_val.json) against the reference's np.min / np.max over
+    tensor.reshape(c, -1) (basic_algorithm.py:72-91).  cols % 4 != 0 puts row r's start at byte 4 r cols, off 16 B: the scalar
+    head and tail of stream_span; each row's extreme sits at its first element, its last, or one past its first 16-B boundary.
+    Then NaN in ONE row (its neighbours stay finite), ±inf, all-equal rows, denormals, ±0, and the `out=` slices at an odd
+    offset that find_clip_val_minmax_weight writes through."""
+    from dipoorlet_amd import ops
+    rng = np.random.default_rng(71)
+    for cols in (1, 2, 3, 5, 9, 49, 63, 64, 65, 255, 257, 4097):
+        for rows in (1, 3, 64, 1000):
+            w = rng.standard_normal((rows, cols)).astype(np.float32)
+            r = np.arange(rows)
+            head = (-r * cols) % 4              # elements of row r in front of its first 16-B boundary (the buffer is aligned)
+            at = [np.zeros(rows, np.int64), np.full(rows, cols - 1), np.minimum(head + 1, cols - 1)]
+            w[r, np.choose(r % 3, at)] = np.float32(8) + r.astype(np.float32)
+            w[r, np.choose((r + 1) % 3, at)] = np.float32(-8) - r.astype(np.float32)    # (cols < 3: the same element)
+            lo, hi = ops.rowwise_minmax(torch.from_numpy(w).to(dev))
+            assert _same_f32(lo.cpu().numpy(), w.min(1)).all(), (rows, cols)
+            assert _same_f32(hi.cpu().numpy(), w.max(1)).all(), (rows, cols)
+    # special values, one kind per row, on rows of 49 (every start off 16 B but the first) and of 1 (a bias, a BN vector)
+    den = np.float32(1e-40)
+    for cols in (49, 1):
+        w = rng.standard_normal((12, cols)).astype(np.float32)
+        w[1, cols // 2] = np.nan                                 # NaN: this row only
+        w[3, -1] = np.inf
+        w[4, 0] = -np.inf
+        w[5, :] = np.float32(1.5)                                # all equal
+        w[6, :] = den * rng.integers(-5, 6, cols).astype(np.float32)   # denormals
+        w[7, :] = np.where(rng.integers(0, 2, cols) == 0, np.float32(-0.0), np.float32(0.0))
+        w[8, 0], w[8, -1] = np.inf, -np.inf
+        w[9, 0] = np.inf
+        w[9, -1] = np.nan                                        # NaN beside inf: NaN
+        w[10, :] = np.float32(-0.0)
+        w[11, :] = -den
+        lo, hi = ops.rowwise_minmax(torch.from_numpy(w).to(dev))
+        lo, hi = lo.cpu().numpy(), hi.cpu().numpy()
+        assert _same_f32(lo, w.min(1)).all() and _same_f32(hi, w.max(1)).all(), (cols, lo, hi)
+        assert np.isnan(lo[[1, 9]]).all() and np.isnan(hi[[1, 9]]).all()
+        assert not np.isnan(np.delete(lo, [1, 9])).any() and not np.isnan(np.delete(hi, [1, 9])).any()
+    # through out= slices of one result buffer at an odd offset; the values around the slices stay
+    w = rng.standard_normal((37, 9)).astype(np.float32)
+    res = torch.full((2, 45), 7.0, dtype=torch.float32, device=dev)
+    off = 5
+    ops.rowwise_minmax(torch.from_numpy(w).to(dev), out=(res[0, off:off + 37], res[1, off:off + 37]))
+    got = res.cpu().numpy()
+    assert _same_f32(got[0, off:off + 37], w.min(1)).all() and _same_f32(got[1, off:off + 37], w.max(1)).all()
+    assert (np.delete(got, np.s_[off:off + 37], axis=1) == 7.0).all()
+
+
+def _weight_graph():
+    """Depthwise Conv (rows of 9) -> BatchNormalization -> PRelu (slope [C, 1, 1]) -> ConvTranspose (weight [C_in, C_out, 3, 3],
+    ranged on its [1, 0, 2, 3] view) -> GlobalAveragePool -> Flatten -> Gemm (transB = 1): every kind of initializer
+    find_clip_val_minmax_weight ranges."""
+    from dipoorlet_amd.models import _B
+    g = _B(83)
+    x = g.conv("input", 8, 8, 3, 1, 1, "dw", groups=8)
+    x = g.node("BatchNormalization", [x, g.b("bn.scale", 8, 1.0), g.b("bn.bias", 8), g.b("bn.mean", 8),
+                                      g.const("bn.var", np.abs(g.rng.standard_normal(8)).astype(np.float32) + 0.5)],
+               out="bn_out", epsilon=1e-5)
+    x = g.node("PRelu", [x, g.const("prelu.slope", (g.rng.standard_normal((8, 1, 1)) * 0.1).astype(np.float32))], out="prelu_out")
+    x = g.node("ConvTranspose", [x, g.w("ct.weight", (8, 5, 3, 3)), g.b("ct.bias", 5)], out="ct_out", kernel_shape=[3, 3],
+               pads=[1, 1, 1, 1], strides=[1, 1], dilations=[1, 1], group=1)
+    x = g.node("GlobalAveragePool", [x], out="gap_out")
+    x = g.node("Flatten", [x], out="flat_out", axis=1)
+    x = g.node("Gemm", [x, g.w("fc.weight", (10, 5)), g.b("fc.bias", 10)], out="fc_out", alpha=1.0, beta=1.0, transB=1)
+    return g.finish("input", [1, 8, 10, 10], x)
+
+
+def test_weight_ranges_of_a_graph_with_and_without_resident_constants(dev):
+    """find_clip_val_minmax_weight (basic_algorithm.py:72-91) over a depthwise Conv, BN parameters, a PRelu slope, a
+    ConvTranspose (the [1, 0, 2, 3] view) and a Gemm — with a session whose constants are resident (views of one device
+    buffer) and without one (each initializer uploaded) — equals the reference's numpy, bit for bit."""
+    from dipoorlet_amd.executor import GraphSession
+    from dipoorlet_amd.tensor_cali.basic_algorithm import find_clip_val_minmax_weight
+    g = _weight_graph()
+    want = {}
+    for node in g.graph.node:
+        if node.op_type not in ("Conv", "Gemm", "ConvTranspose", "PRelu", "BatchNormalization"):
+            continue
+        for name in list(node.input)[1:]:
+            t = np.asarray(g.get_initializer(name))
+            if t.ndim < 1:
+                continue
+            if node.op_type == "ConvTranspose" and name == node.input[1]:
+                t = t.transpose([1, 0, 2, 3])
+            want[name] = [np.min(t.reshape((t.shape[0], -1)), -1), np.max(t.reshape((t.shape[0], -1)), -1)]
+    assert len(want) == 11 and want["ct.weight"][0].shape == (5,) and want["dw.weight"][0].shape == (8,)
+    for session in (None, GraphSession(g, device=dev)):
+        got = find_clip_val_minmax_weight(g, None, session=session)
+        assert sorted(got) == sorted(want)
+        for name, (lo, hi) in want.items():
+            assert got[name][0].shape == lo.shape and got[name][1].shape == hi.shape, name
+            assert _same_f32(got[name][0], lo).all() and _same_f32(got[name][1], hi).all(), (name, session is None)
+
+
+def _cos_sums(a, b):
+    """(Σab, Σaa, Σbb) per row in fp64 (products of two fp32 values are exact in fp64): utils.py:273-278's partial sums."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.stack([(a * b).sum(-1), (a * a).sum(-1), (b * b).sum(-1)], -1)
+
+
+def test_cos_per_image_vs_fp64_unaligned_segments(dev):
+    """k_cos_items (--profiling's per-layer cosine, profiling.py:74) against fp64 numpy per (image, tensor): per-image segments
+    of 1, 3, 5, 1023 ... elements start off 16 B (the scalar path), 802816-element tensors are cut into several work items, a
+    zero tensor (Σaa = 0), a == b (Σab is the same sum as Σaa), magnitudes around 1e18 (fp64 squares are finite where fp32
+    sums would overflow).  Balanced items and one item of 1024 elements per workgroup (an item of an unaligned segment starts
+    off 16 B as the segment does)."""
+    from dipoorlet_amd import ops
+    rng = np.random.default_rng(73)
+    sizes = [1, 3, 4, 5, 1023, 1025, 4097, 50001, 802816]
+    for B in (1, 3, 5):
+        a = [rng.standard_normal((B, e)).astype(np.float32) for e in sizes]
+        b = [(np.float32(0.9) * x + np.float32(0.3) * rng.standard_normal(x.shape).astype(np.float32)).astype(np.float32) for x in a]
+        a[4][:] = 0                                   # a zero tensor
+        b[2], b[5] = a[2].copy(), a[5].copy()         # a == b
+        a[6] *= np.float32(1e18)                      # a*a, b*b around 1e36: finite in fp64
+        b[6] *= np.float32(3e18)
+        ta = [torch.from_numpy(x).to(dev) for x in a]
+        tb = [torch.from_numpy(x).to(dev) for x in b]
+        for chunk in (None, 1024):
+            plan = ops.TensorSetPlan(sizes, B, dev, chunk_elems=chunk)
+            got = ops.cos_per_image(plan, ta, tb).cpu().numpy()
+            assert got.shape == (B, len(sizes), 3)
+            for t in range(len(sizes)):
+                np.testing.assert_allclose(got[:, t], _cos_sums(a[t], b[t]), rtol=1e-12, atol=0, err_msg=f"B={B} t={t} {chunk}")
+            assert (got[:, 4, :2] == 0).all()               # (Σab = Σaa = 0 exactly)
+            assert np.array_equal(got[:, 2, 0], got[:, 2, 1]) and np.array_equal(got[:, 5, 0], got[:, 5, 2])
+
+
+def test_cos_accumulate_slots_tails_and_refusals(dev):
+    """k_cos_acc (utils.py:273-278 partial sums into acc[slot]) against fp64 numpy: slot > 0, two accumulations into the same
+    slot, n % 4 in {1, 2, 3}, the other slots untouched.  A buffer off 16 B, an accumulator of the wrong type or one without
+    the slot are refused on the host before any launch, and the accumulator keeps its values."""
+    from dipoorlet_amd import _hip, ops
+    rng = np.random.default_rng(75)
+    acc = torch.zeros(4, 3, dtype=torch.float64, device=dev)
+    for n in (1, 2, 3, 5, 4097, 123458, 1000003):
+        acc.zero_()
+        pairs = [(rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32)) for _ in range(2)]
+        pairs[0] = (pairs[0][0], pairs[0][0] * np.float32(0.9) + pairs[0][1] * np.float32(0.3))
+        pairs[1] = (pairs[1][0] * np.float32(1e18), pairs[1][0] * np.float32(7e17) + pairs[1][1] * np.float32(1e17))
+        for a, b in pairs:
+            ops.cos_accumulate(torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev), acc, slot=2)
+        got = acc.cpu().numpy()
+        want = _cos_sums(*pairs[0]) + _cos_sums(*pairs[1])
+        np.testing.assert_allclose(got[2], want, rtol=1e-12, atol=0, err_msg=str(n))
+        assert (np.delete(got, 2, axis=0) == 0).all(), n
+    before = acc.clone()
+    buf = torch.ones(1026, device=dev)
+    with pytest.raises(_hip.DipoorletHipError):
+        ops.cos_accumulate(buf[1:1025], buf[:1024], acc, slot=1)          # 4 B off 16
+    with pytest.raises(_hip.DipoorletHipError):
+        ops.cos_accumulate(buf[:1024], buf[2:1026], acc, slot=1)          # 8 B off 16
+    with pytest.raises(_hip.DipoorletHipError):
+        ops.cos_accumulate(buf[:1024], buf[:1024], acc, slot=4)           # no slot 4 in a [4, 3] accumulator
+    with pytest.raises(_hip.DipoorletHipError):
+        ops.cos_accumulate(buf[:1024], buf[:1024], acc.float(), slot=0)   # fp32: the kernel adds fp64
+    assert torch.equal(acc, before)
+
+
+def _percentile_cases(bins, rng):
+    """(hist, gmin, gmax) of constructed histograms for `bins` bins, and the thresholds to ask: power-of-two totals whose
+    cumulative sum reaches 0.5 / 0.75 EXACTLY at the end of bin 0, 63, 64 or bins - 1 (1.0 there), random counts above 2^24
+    (fl32(count) rounds), an all-zero histogram; ranges symmetric and not, so that max(-clip, gmin) and min(clip, gmax) pick
+    either side."""
+    ranges = [(-1.0, 1.0), (-0.25, 3.0), (-5.0, 0.5), (0.0, 2.0), (-2.0, -0.5), (-1e-3, 1e-3)]
+    cases, thrs = [], {0.5, 0.75, 1.0, 0.99999, 0.999, 1.5}
+    total = 1 << 20
+    for target in sorted({0, 63, 64, bins - 1}):
+        if target >= bins:
+            continue
+        for thr in ((1.0,) if target == bins - 1 else (0.5, 0.75)):
+            need = int(thr * total)
+            h = np.zeros(bins, np.int64)
+            h[target] = need if target == 0 else need // 3 + 1
+            if target:
+                h[:target] += rng.multinomial(need - h[target], np.full(target, 1.0 / target))
+            if need < total:
+                h[target + 1:] += rng.multinomial(total - need, np.full(bins - target - 1, 1.0 / (bins - target - 1)))
+            assert h.sum() == total and h[:target + 1].sum() == need
+            cases.append(h)
+    for scale in (1 << 26, 1 << 40):                 # above 2^24: fl32(count) is not count
+        h = rng.integers(0, scale, bins).astype(np.int64)
+        h[rng.integers(0, bins, bins // 3)] = 0
+        cases.append(h)
+    cases.append(np.zeros(bins, np.int64))           # never reached: [gmin, gmax]
+    out = [(h, *ranges[i % len(ranges)]) for i, h in enumerate(cases)]
+    return out, sorted(thrs)
+
+
+def test_hist_percentile_constructed_histograms_vs_oracle(dev):
+    """k_hist_percentile (every -A hist clip, basic_algorithm.py:40-53) bit for bit against O.hist_percentile on histograms
+    built here rather than taken from k_abs_hist: the threshold met exactly on a bin boundary, in bin 0, at bins 63 / 64 (the
+    end of a 64-bin chunk and the start of the next), in the last bin (the partial-chunk walk for bins % 64 != 0), never
+    reached, an empty histogram, counts above 2^24.  Many slots with different outcomes in one launch; the torch op on single
+    rows agrees."""
+    import dipoorlet_amd.torch_ops  # noqa: F401  (registers torch.ops.dipoorlet)
+    from dipoorlet_amd import ops
+    rng = np.random.default_rng(77)
+    for bins in (1, 63, 64, 65, 127, 128, 129, 2048, 2049, 16384):
+        cases, thrs = _percentile_cases(bins, rng)
+        acc = ops.CalibAccumulators(len(cases), dev, bins)
+        acc.set_minmax(torch.tensor([c[1] for c in cases], dtype=torch.float32, device=dev),
+                       torch.tensor([c[2] for c in cases], dtype=torch.float32, device=dev))
+        acc.hist_prepare()
+        acc.hist.copy_(torch.from_numpy(np.stack([c[0] for c in cases])))
+        found = set()
+        for thr in thrs:
+            got = acc.hist_percentile(thr).cpu().numpy()
+            for s, (h, gmin, gmax) in enumerate(cases):
+                want = np.asarray(O.hist_percentile(h, gmin, gmax, bins, thr), np.float32)
+                assert np.array_equal(got[s].view(np.uint32), want.view(np.uint32)), (bins, thr, s, got[s], want)
+                found.add(tuple(want.tolist()))
+            for s in (0, len(cases) - 1):
+                one = torch.ops.dipoorlet.hist_percentile(acc.hist[s].contiguous(), cases[s][1], cases[s][2], thr).cpu().numpy()
+                assert np.array_equal(one.view(np.uint32), got[s].view(np.uint32)), (bins, thr, s)
+        assert len(found) >= min(bins, 4), bins                 # (the slots do not all give one answer)
+    # where fl32(count) decides: counts 2^24 + 1 and 2^24 - 1 over a total of 2^25.  fl32(2^24 + 1) = 2^24, so bin 0 holds exactly
+    # 0.5 and a threshold of 0.5 + 2^-25 is reached in bin 1 (with the exact count it would be reached in bin 0)
+    h = np.array([(1 << 24) + 1, (1 << 24) - 1], np.int64)
+    thr = 0.5 + 2.0 ** -25
+    assert (1 << 24) + 1 >= thr * (1 << 25)                     # (exact counts: bin 0)
+    want = np.asarray(O.hist_percentile(h, -4.0, 4.0, 2, thr), np.float32)
+    assert want[1] == np.float32(1.5 * 4.0 / 2)                 # (the reference's fl32 counts: bin 1)
+    got = torch.ops.dipoorlet.hist_percentile(torch.from_numpy(h).to(dev), -4.0, 4.0, thr).cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (got, want)
+
+
+def test_channel_diff_sum_at_the_shapes_bias_correction_meets(dev):
+    """k_channel_diff_sum (bias_correction.py:9-13's sum of fp - q per channel) against fp64 numpy: Gemm outputs [n, C] (the
+    lane-per-channel path) with n up to 4096 and C around 64, Conv1d outputs [n, C, L] with L % 4 in {0, 1, 3} from aligned
+    bases and from bases one element off, a = 1e6 + δ (the fp64 sum of exact fp32 differences: no cancellation error),
+    accumulation over 5 chunks."""
+    from dipoorlet_amd import ops
+    rng = np.random.default_rng(79)
+    shapes = [(n, C) for n in (1, 7, 4096) for C in (1, 63, 64, 65, 1000)]
+    shapes += [(n, C, L) for n, C in ((3, 5), (8, 64)) for L in (12, 13, 15, 4)]
+    for shape in shapes:
+        for off in (0, 1):
+            size = int(np.prod(shape))
+            fa = torch.from_numpy(rng.standard_normal(size + 1).astype(np.float32)).to(dev)
+            fb = torch.from_numpy(rng.standard_normal(size + 1).astype(np.float32)).to(dev)
+            a, b = fa[off:off + size].reshape(shape), fb[off:off + size].reshape(shape)
+            a64, b64 = a.cpu().numpy().astype(np.float64), b.cpu().numpy().astype(np.float64)
+            axes = tuple(i for i in range(len(shape)) if i != 1)
+            want = (a64 - b64).sum(axis=axes)
+            np.testing.assert_allclose(ops.channel_diff_sum(a, b).cpu().numpy(), want, rtol=1e-12, atol=1e-12,
+                                       err_msg=f"{shape} off {off}")
+    # cancellation: a = 1e6 + δ, b = 1e6 + δ' (fp32 spacing 1/16 there): every a - b is exact in fp64, so is their sum
+    for shape in ((4096, 65), (7, 64), (8, 64, 13), (3, 5, 12)):
+        acc, want = None, 0.0
+        for _ in range(5):                                       # 5 chunks into one accumulator
+            base = np.float32(1e6)
+            a = (base + rng.integers(-40, 41, shape).astype(np.float32) / np.float32(16)).astype(np.float32)
+            b = (base + rng.integers(-40, 41, shape).astype(np.float32) / np.float32(16)).astype(np.float32)
+            acc = ops.channel_diff_sum(torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev), acc)
+            axes = tuple(i for i in range(len(shape)) if i != 1)
+            want = want + (a.astype(np.float64) - b.astype(np.float64)).sum(axis=axes)
+        np.testing.assert_allclose(acc.cpu().numpy(), want, rtol=1e-12, atol=0, err_msg=str(shape))
+
+
+def _matmul_f64(a, b):
+    """a @ b in fp64 with IEEE semantics for every term (0 * inf = NaN, inf - inf = NaN): BLAS on the finite rows and columns,
+    explicit sums of products on the rows of a and the columns of b that hold a NaN or an inf."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    out = np.where(np.isfinite(a), a, 0) @ np.where(np.isfinite(b), b, 0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for m in np.nonzero(~np.isfinite(a).all(1))[0]:
+            out[m] = (a[m][:, None] * b).sum(0)
+        for n in np.nonzero(~np.isfinite(b).all(0))[0]:
+            out[:, n] = (a * b[:, n]).sum(1)
+    return out
+
+
+def _same_specials_and_close(got, want, atol):
+    """NaN, +inf and -inf exactly where fp64 numpy puts them and nowhere else; the finite values within atol."""
+    got = np.asarray(got, np.float64)
+    for f in (np.isnan, np.isposinf, np.isneginf):
+        assert np.array_equal(f(got), f(want)), (f.__name__, np.argwhere(f(got) != f(want))[:5])
+    fin = np.isfinite(want)
+    np.testing.assert_allclose(got[fin], want[fin], rtol=0, atol=atol)
+
+
+def test_gemm_small_nan_and_inf_stay_in_their_rows_and_columns(dev):
+    """dpl_gemm_small with a NaN in one row of A and an inf in one column of B (a whole column and a single element): the result
+    holds NaN / ±inf exactly where fp64 numpy does — the NaN row, the inf columns — and nowhere else, at shapes where the padded
+    tiles (M % 32, N % 64 != 0) and the split-K sum (K cut into several ranges) would carry them over.  alpha = 0 with a finite
+    product gives beta * bias exactly."""
+    from dipoorlet_amd import ops
+    rng = np.random.default_rng(81)
+    for M, K, N, trans_b in [(5, 40, 9, False), (64, 2048, 1000, True), (33, 65, 70, False), (7, 8200, 64, False),
+                             (40, 300, 129, True), (1, 1, 1, False)]:
+        a = rng.standard_normal((M, K)).astype(np.float32)
+        w = rng.standard_normal((K, N)).astype(np.float32)
+        a[M - 1, rng.integers(K)] = np.nan                     # a row in the last (partial) row tile
+        w[rng.integers(K), N - 1] = np.inf                      # one element: column N-1 is ±inf by the sign of a's entry
+        if N > 2:
+            w[:, N // 2] = -np.inf                              # a whole column: ±inf terms of both signs, NaN
+            w[0, 1] = np.inf                                    # and an inf that meets the NaN row
+        bias = rng.standard_normal(N).astype(np.float32)
+        bt = torch.from_numpy(w.T.copy()).to(dev).t() if trans_b else torch.from_numpy(w).to(dev)
+        for alpha, beta in ((1.0, 1.0), (0.5, -2.0)):
+            got = ops.gemm_small(torch.from_numpy(a).to(dev), bt, torch.from_numpy(bias).to(dev), alpha, beta).cpu().numpy()
+            with np.errstate(invalid="ignore"):
+                want = alpha * _matmul_f64(a, w) + beta * bias.astype(np.float64)
+            _same_specials_and_close(got, want, 2e-6 * (np.sqrt(K) * abs(alpha) + abs(beta)) * max(1.0, np.sqrt(K) / 8))
+    # alpha = 0, a finite product: beta * bias, bit for bit (0 * a finite sum is a zero)
+    for M, K, N in ((33, 65, 70), (7, 8200, 64)):
+        a = rng.standard_normal((M, K)).astype(np.float32)
+        w = rng.standard_normal((K, N)).astype(np.float32)
+        bias = rng.standard_normal((M, N)).astype(np.float32)
+        got = ops.gemm_small(torch.from_numpy(a).to(dev), torch.from_numpy(w).to(dev), torch.from_numpy(bias).to(dev), 0.0, 1.5)
+        assert np.array_equal(got.cpu().numpy(), np.float32(1.5) * bias), (M, K, N)
+
+
+def test_executor_gemm_attributes_and_3d_matmul_vs_onnx_definition(dev):
+    """The executor's Gemm against the ONNX definition Y = alpha * A' B' + beta * C in fp64 (A' = A^T when transA = 1, B' = B^T
+    when transB = 1; C broadcast from [], [1], [N], [M, 1] or [M, N]), and MatMul with a 3-D left operand."""
+    from dipoorlet_amd.executor import _OPS
+    from dipoorlet_amd.onnx_io import Node
+    rng = np.random.default_rng(85)
+    M, K, N = 19, 70, 33
+    for trans_a in (0, 1):
+        for trans_b in (0, 1):
+            for c_shape in ((), (1,), (N,), (M, 1), (M, N)):
+                alpha, beta = (0.75, -1.25) if (trans_a + trans_b) % 2 else (2.0, 0.5)
+                a = rng.standard_normal((K, M) if trans_a else (M, K)).astype(np.float32)
+                b = rng.standard_normal((N, K) if trans_b else (K, N)).astype(np.float32)
+                c = rng.standard_normal(c_shape).astype(np.float32)
+                node = Node("Gemm", ["a", "b", "c"], ["y"], name="gemm", attrs={"transA": trans_a, "transB": trans_b,
+                                                                                 "alpha": alpha, "beta": beta})
+                y = _OPS["Gemm"](None, node, *(torch.from_numpy(np.asarray(v)).to(dev) for v in (a, b, c))).cpu().numpy()
+                a64, b64 = a.astype(np.float64), b.astype(np.float64)
+                want = alpha * ((a64.T if trans_a else a64) @ (b64.T if trans_b else b64)) + beta * c.astype(np.float64)
+                assert y.shape == (M, N), (trans_a, trans_b, c_shape)
+                np.testing.assert_allclose(y, want, rtol=0, atol=2e-6 * (np.sqrt(K) * abs(alpha) + abs(beta)) * 4,
+                                           err_msg=f"transA={trans_a} transB={trans_b} C{c_shape}")
+    a = rng.standard_normal((2, 17, 96)).astype(np.float32)
+    b = rng.standard_normal((96, 40)).astype(np.float32)
+    y = _OPS["MatMul"](None, None, torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)).cpu().numpy()
+    assert y.shape == (2, 17, 40)
+    np.testing.assert_allclose(y, a.astype(np.float64) @ b.astype(np.float64), rtol=0, atol=2e-6 * np.sqrt(96) * 4)
