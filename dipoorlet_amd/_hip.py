@@ -12,7 +12,7 @@ import os
 import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# DPL_LIB: another build of the same sources (kernel-tuning variants, scripts/variant_*.sh); never a different code path
+# DPL_LIB: another build of the same sources (the host-sanitizer build of scripts/asan_host_check.sh); never a different code path
 LIB_PATH = os.environ.get("DPL_LIB") or os.path.join(_HERE, "csrc", "libdipoorlet_hip.so")
 
 ABI_VERSION = 21

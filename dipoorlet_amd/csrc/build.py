@@ -34,7 +34,6 @@ def build(force=False, verbose=False):
         return OUT
     cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC",
            "-fno-fast-math", "-ffp-contract=off", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-o", OUT] + SRC
-    cmd += os.environ.get("DPL_HIPCC_EXTRA", "").split()  # tuning knobs (-DDPL_...=N), see scripts/variant_bench.sh
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)

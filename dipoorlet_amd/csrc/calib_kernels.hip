@@ -127,7 +127,6 @@ struct HistOp {
         const float a = fabsf(x);
         const bool nz = (a != 0.0f);
         nonzero += nz;
-#ifndef DPL_HIST_PLAIN
         if (kFast) {
             // (11 vector instructions per element where the form below takes 13 — what matters once the chip runs warm and
             // the shader clock comes down: DESIGN 3e.  No clamp: a <= last gives a * inv <= bins * (1 + 1e-6) + rounding, the
@@ -140,7 +139,6 @@ struct HistOp {
             }
             return;
         }
-#endif
         int i;
         if (kFast) {
             i = (int)__fmul_rn(a, inv);  // v_cvt_i32_f32 saturates and maps NaN to 0
@@ -952,17 +950,12 @@ int dpl_fake_quant_pre(int32_t pre, const float* d_x, const float* d_x2, float* 
         return fail_msg("dpl_fake_quant_pre: n_channels and inner must be in [1, 2^32)");
     // A contiguous chunk of 3072 elements (12 KiB read + 12 KiB written) per workgroup, whatever the tensor's size (a multiple of
     // 1024 elements: every chunk starts on a 16-byte boundary of an aligned tensor).  Measured on the tensors a fake-quantised
-    // ResNet-50 forward at batch 64 runs this on (26 - 205 MB, distinct buffers in rotation, scripts/fq_blocks_ab.py), fraction of
+    // ResNet-50 forward at batch 64 runs this on (26 - 205 MB, distinct buffers in rotation), fraction of
     // 8 TB/s by chunk: 1024: 0.61 / 0.52 (205 MB / 26 MB), 2048: 0.72 / 0.57, 3072: 0.76 / 0.56, 4096: 0.75 / 0.54, 8192: 0.78 /
     // 0.54, 12288: 0.72 / 0.43 — and rounds 3 - 4's rule (n / 4096 elements, at least 4096: 50 KB chunks for a 205 MB tensor):
     // 0.70 / 0.54.  The Q/DQ nodes of that forward: 0.61 -> 0.65 of the roofline (bench.py `fake_quant.product_forward`).
-    // DPL_FQ_CHUNK: a tuning aid.
-    static const int64_t chunk_elems = [] {
-        const char* e = getenv("DPL_FQ_CHUNK");
-        const int64_t v = e ? atoll(e) : 0;
-        return v >= 1024 ? (v + 1023) / 1024 * 1024 : (int64_t)3072;
-    }();
-    int64_t chunk = chunk_elems;
+    constexpr int64_t kFqChunk = 3072;
+    int64_t chunk = kFqChunk;
     if ((n + chunk - 1) / chunk > 0x40000000ll) chunk = ((n + 0x3FFFFFFFll) / 0x40000000ll + 1023) / 1024 * 1024;
     if (chunk > 0xFFFFFC00ll) chunk = 0xFFFFFC00ll;
     const int64_t blocks = (n + chunk - 1) / chunk;

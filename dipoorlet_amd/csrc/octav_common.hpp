@@ -1,6 +1,6 @@
-// Shared by the OCTAV translation units (octav_kernels.hip: full / compaction / two-read bracket forms;
-// octav_resident.hip: the single-read register-resident form): the fixed-point step, the log-scale histogram
-// geometry and the bracket walk over its bin edges.
+// Shared by the OCTAV translation units (octav_kernels.hip: full / compaction / two-read bracket forms and the rescue's
+// gather; octav_tail_host.hip: the one-read exact-tail form and its rescue walk): the fixed-point step, the log-scale
+// histogram geometry and the bracket walk over its bin edges.
 #pragma once
 #include "common.hpp"
 
@@ -32,12 +32,6 @@ __device__ __forceinline__ OctavStep octav_step(double sum, unsigned long long c
 }
 
 
-#ifndef DPL_MARGIN0
-#define DPL_MARGIN0 0
-#endif
-#ifndef DPL_MARGIN
-#define DPL_MARGIN 0
-#endif
 constexpr int kLogNB = 2048;
 constexpr int kLogShift = 17;                               // 23 - 6: six mantissa bits per bin
 constexpr uint32_t kLogKey0 = (uint32_t)(127 - 18) << 6;    // key of 2^-18
@@ -46,6 +40,7 @@ constexpr int kBitmapRow = kLogWords + 2;                   // + the gather rang
 constexpr int kLogMaxMarked = 256;
 constexpr uint32_t kSmallPair = 16384;                      // pairs this small are gathered whole
 constexpr uint32_t kRescueUnit = 16384;                     // elements of a pair one workgroup of k_octav_rescue_gather re-reads
+constexpr unsigned kRescueGrid = 512;                       // workgroups of the rescue's persistent kernels (gather and walk)
 
 // Capacity (elements, a multiple of 32: whole 128-byte lines) of the LIST REGION of one slice of n elements in the one-read
 // forms' list buffers.  The exact-tail form lists ~0.5 - 1.5 % of a pair (a wave's budget: kTailAllow0 + what it has seen >> 6,
@@ -118,18 +113,17 @@ __device__ __forceinline__ BracketResult bracket_marks(const uint32_t* n_ge, con
         // i.e. only at the fixed point, where the excursion beyond the edge values is second order; together
         // with the fp32 rounding of the true iterate that can put an iterate one bin outside the bracket
         // with a probability of order 1e-4 per pair.  The exact walk verifies every iterate and such a pair
-        // simply finishes on the compaction route; a margin bin on either side (DPL_MARGIN=1) would more
-        // than double the values gathered (2.2 % -> 4.9 % on ResNet-50 activations) to avoid that.
-        const int ml = jl - (itn == 0 ? DPL_MARGIN0 : DPL_MARGIN), mh = jh + (itn == 0 ? DPL_MARGIN0 : DPL_MARGIN);
-        for (int w0 = ml >> 5; w0 <= mh >> 5; ++w0) {   // one LDS read-modify-write per word
-            const int lo_b = max(ml, w0 << 5) & 31, hi_b = min(mh, (w0 << 5) + 31) & 31;
+        // simply finishes on the compaction route; a margin bin on either side would more than double the
+        // values gathered (2.2 % -> 4.9 % on ResNet-50 activations) to avoid that.
+        for (int w0 = jl >> 5; w0 <= jh >> 5; ++w0) {   // one LDS read-modify-write per word
+            const int lo_b = max(jl, w0 << 5) & 31, hi_b = min(jh, (w0 << 5) + 31) & 31;
             const uint32_t mask = (0xFFFFFFFFu >> (31 - hi_b)) & (0xFFFFFFFFu << lo_b);
             const uint32_t old = bm[w0];
             bm[w0] = old | mask;
             marked += __popc(mask & ~old);
         }
-        out.jmin = ml < out.jmin ? ml : out.jmin;
-        out.jmax = mh > out.jmax ? mh : out.jmax;
+        out.jmin = jl < out.jmin ? jl : out.jmin;
+        out.jmax = jh > out.jmax ? jh : out.jmax;
         if (marked > kLogMaxMarked) {
             r = 1u;
             break;

@@ -748,10 +748,7 @@ __global__ __launch_bounds__(kBlock) void k_octav_bracket(dpl_octav_state* __res
 // rebasing is needed per element and zeros / padding / out-of-window values fall on words that are never set.
 // The append is branch-free: every element is written at the lane's queue tail and the tail only advances for a
 // survivor (2 VALU + 1 LDS write per element instead of a predicated block per element).
-#ifndef DPL_QUEUE_CAP
-#define DPL_QUEUE_CAP 32
-#endif
-constexpr int kQueueCap = DPL_QUEUE_CAP;     // a tile adds at most 16: flush once a queue holds more than cap - 16
+constexpr int kQueueCap = 32;                // a tile adds at most 16: flush once a queue holds more than cap - 16
 constexpr int kQueueStride = kQueueCap + 1;  // entries per lane (+1: the branch-free append writes one past the fill)
 constexpr int kKeyWords = (1 << (31 - kLogShift)) / 32;   // 512
 constexpr int kKeyWord0 = (int)(kLogKey0 >> 5);           // word of the window's first bin (kLogKey0 is a multiple of 32)
@@ -900,19 +897,11 @@ __global__ __launch_bounds__(kBlock) void k_octav_rescue_gather(const uint32_t* 
 // in the bin - instead of walking the whole gathered list.  The totals above a bin are the suffix rows the bracket
 // kernel left in the histogram buffers.  An iterate that lands in an unmarked bin sends the pair to the
 // compaction route.
-#ifndef DPL_EXACT_BLOCK
-#define DPL_EXACT_BLOCK 128   // threads per pair
-#endif
-#ifndef DPL_EXACT_WAVES
-#define DPL_EXACT_WAVES 4
-#endif
-#ifndef DPL_EXACT_REGS
-#define DPL_EXACT_REGS 16
-#endif
-constexpr int kExactBlock = DPL_EXACT_BLOCK;
-constexpr int kExactRegs = DPL_EXACT_REGS;  // values of the current bin held per lane (128 * 16 = 2 K)
+constexpr int kExactBlock = 128;   // threads per pair
+constexpr int kExactWaves = 4;     // waves per SIMD k_octav_exact is bounded for
+constexpr int kExactRegs = 16;     // values of the current bin held per lane (128 * 16 = 2 K)
 
-__global__ __launch_bounds__(kExactBlock, DPL_EXACT_WAVES) void k_octav_exact(dpl_octav_state* __restrict__ st,
+__global__ __launch_bounds__(kExactBlock, kExactWaves) void k_octav_exact(dpl_octav_state* __restrict__ st,
                                                               dpl_octav_state* __restrict__ ctl,
                                                               const uint32_t* __restrict__ pair_order,
                                                               const uint32_t* __restrict__ lh_cnt,
@@ -1120,20 +1109,17 @@ __global__ __launch_bounds__(kExactBlock, DPL_EXACT_WAVES) void k_octav_exact(dp
 int g_exact_fail_every = 0;   // dpl_test_hook_exact_fail_every
 int g_rescue_fail_every = 0;  // dpl_test_hook_rescue_fail_every
 
-#ifndef DPL_RESCUE_GRID
-#define DPL_RESCUE_GRID 512
-#endif
 // (octav_tail_host.hip) gather pass of the rescue: see k_octav_rescue_gather
 int dpl_octav_rescue_gather_launch(const uint32_t* d_missed, dpl_octav_state* d_states, int64_t n_pairs, const dpl_span* d_pair_spans,
                                    const float* const* d_seg_ptrs, const uint32_t* d_bm_rows, const uint64_t* d_pair_base,
                                    float* d_list1, hipStream_t st) {
-    hipLaunchKernelGGL(k_octav_rescue_gather, dim3(DPL_RESCUE_GRID), dim3(kBlock), (size_t)kBlock * kQueueStride * sizeof(uint32_t), st,
+    hipLaunchKernelGGL(k_octav_rescue_gather, dim3(kRescueGrid), dim3(kBlock), (size_t)kBlock * kQueueStride * sizeof(uint32_t), st,
                        d_missed, d_states + n_pairs, d_states, d_pair_spans, d_seg_ptrs, d_bm_rows, d_pair_base, d_list1);
     DPL_LAUNCH_CHECK("k_octav_rescue_gather");
     return 0;
 }
 
-// The compaction route on its own, for the pairs a histogram form marked mode 1 (shared with octav_resident.hip).
+// The compaction route on its own, for the pairs a histogram form marked mode 1 (shared with octav_tail_host.hip).
 int dpl_octav_fallback_route(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin, int64_t n_blocks,
                              const float* const* d_seg_ptrs, dpl_octav_state* d_states, int64_t n_pairs,
                              const dpl_span* d_pair_spans, const uint64_t* d_pair_base, const uint32_t* d_pair_order,

@@ -28,41 +28,14 @@
 // >= the final theta; a theta that ends up too high costs a rescue, never a wrong result.
 #pragma once
 
-#ifndef DPL_TAIL_TAU_SHIFT
-#define DPL_TAIL_TAU_SHIFT 8      // a pair asks for the bin above which n >> 8 of its n elements lie (measured: 7 -> 8 -2 %, 9 the same with four times the rescues at +-30 %)
-#endif
-#ifndef DPL_TAIL_BUDGET_SHIFT
-#define DPL_TAIL_BUDGET_SHIFT 6   // a wave may list kTailAllow0 + (elements it has seen >> 6) values before it raises theta
-#endif
-#ifndef DPL_TAIL_ALLOW0
-#define DPL_TAIL_ALLOW0 2048
-#endif
-#ifndef DPL_TAIL_OCC
-#define DPL_TAIL_OCC 4
-#endif
-#ifndef DPL_TAIL_QUEUE_CAP
-#define DPL_TAIL_QUEUE_CAP 512    // entries of a wave's survivor queue (flushed above 256): 8 KiB per workgroup, which the walk's suffix counts reuse
-#endif
-#ifndef DPL_TAIL_VEC
-#define DPL_TAIL_VEC 12           // 16-byte vectors per thread the walk keeps the list in (1024 values each); longer lists are streamed from L2
-#endif
-constexpr int kTailQueueCap = DPL_TAIL_QUEUE_CAP;
+constexpr int kTailTauShift = 8;        // a pair asks for the bin above which n >> 8 of its n elements lie (measured: 7 -> 8 -2 %, 9 the same with four times the rescues at +-30 %)
+constexpr int kTailBudgetShift = 6;     // a wave may list kTailAllow0 + (elements it has seen >> 6) values before it raises theta
+constexpr uint32_t kTailAllow0 = 2048;
+constexpr int kTailOcc = 4;             // waves per SIMD the streaming kernels are bounded for
+constexpr int kTailQueueCap = 512;      // entries of a wave's survivor queue (flushed above 256): 8 KiB per workgroup, which the walk's suffix counts reuse
+constexpr int kTailVec = 12;            // 16-byte vectors per thread the walk keeps the list in (1024 values each); longer lists are streamed from L2
 constexpr int kTailLdsB = kWaves * kTailQueueCap * 4;
 static_assert(kTailQueueCap >= 512 && kTailLdsB >= kLogNB * 4, "a vector may add 256 survivors past the flush mark; the walk keeps its suffix counts in the queues' space");
-constexpr int kTailVec = DPL_TAIL_VEC;
-constexpr int kTailTauShift = DPL_TAIL_TAU_SHIFT;
-constexpr int kTailBudgetShift = DPL_TAIL_BUDGET_SHIFT;
-constexpr uint32_t kTailAllow0 = DPL_TAIL_ALLOW0;
-
-#ifdef DPL_RES_PROF
-// (stamps taken inside a branch are kept in registers and added at the end: an add is a global read-modify-write, and one in the
-// middle of the walk would be measured by the next stamp)
-#define DPL_PROF_KEEP(slot, a, b) prof_keep[slot] = (b) - (a)
-#define DPL_PROF_FLUSH() do { if (threadIdx.x == 0) { g_res_prof[(blockIdx.x & 4095u) * 8 + 1] += prof_keep[1]; g_res_prof[(blockIdx.x & 4095u) * 8 + 2] += prof_keep[2]; } } while (0)
-#else
-#define DPL_PROF_KEEP(slot, a, b) do {} while (0)
-#define DPL_PROF_FLUSH() do {} while (0)
-#endif
 
 struct TailArgs {
     uint32_t* vis_w;             // [T, kLogWords]: word 0 of a tensor's row = kLogNB - (lowest bin its pairs asked for this epoch); 0: none
@@ -76,15 +49,10 @@ struct TailArgs {
 // One pair, streamed: min / max, the exact log-scale histogram (ONE non-returning 64-bit LDS add per element) and the values
 // at or above the current threshold bin -> the wave's dense LDS queue -> the pair's list.  Leaves the per-wave ranges in
 // sh.red_*, the number of listed values in sh.cursor, the final threshold bin in sh.tail_j.
-// (Inlined: as a function of its own — round 3's stream_slice — its prologue saves two dozen callee-saved registers per lane to
-// scratch and restores them at the end: 97 MB written and 97 MB read per ResNet-50 batch, found in the WRITE_SIZE counter.)
-#ifdef DPL_TAIL_NOINLINE
-__device__ __attribute__((noinline)) void stream_tail(
-#else
-__device__ __forceinline__ void stream_tail(
-#endif
-const float* __restrict__ pg, uint32_t cnt, uint32_t* __restrict__ dst,
-                                                      Shared& sh, dpl_octav_state* __restrict__ ctl, const bool adaptive) {
+// (Inlined: as an out-of-line function, its prologue saves two dozen callee-saved registers per lane to scratch and restores
+// them at the end: 97 MB written and 97 MB read per ResNet-50 batch, found in the WRITE_SIZE counter.)
+__device__ __forceinline__ void stream_tail(const float* __restrict__ pg, uint32_t cnt, uint32_t* __restrict__ dst,
+                                            Shared& sh, dpl_octav_state* __restrict__ ctl, const bool adaptive) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const lptr_u64 l_packed = (lptr_u64)(lds_raw);
     const uint32_t tid = threadIdx.x;
@@ -160,17 +128,9 @@ const float* __restrict__ pg, uint32_t cnt, uint32_t* __restrict__ dst,
         const bool in = t < kWin;
         const lptr_u64 slot = in ? l_packed + t + 1u : dummy;
         rare |= in ? 0u : bits;
-#if !defined(DPL_TAIL_ABL_NOHIST)   // (ablation builds, timing only: scripts/tail_ablate.sh)
         (void)__hip_atomic_fetch_add(slot, (1ull << kPackShift) | (unsigned long long)(bits & 0x7FFFFFu), __ATOMIC_RELAXED,
                                      __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-        asm volatile("" ::"v"(slot));
-#endif
-#if defined(DPL_TAIL_ABL_NOLIST)
-        return false;
-#else
         return (int32_t)t >= jm1;
-#endif
     };
     auto put = [&](uint32_t bits, bool f) {
         const unsigned long long m = __builtin_amdgcn_ballot_w64(f);
@@ -184,7 +144,7 @@ const float* __restrict__ pg, uint32_t cnt, uint32_t* __restrict__ dst,
     };
     uint32_t rare_n = 0u;
     for_each_tile<kThreads>(pg, cnt, [&](const f4 (&t)[4], uint32_t base, bool full) {
-        if (tail > (uint32_t)(kTailQueueCap - 256)) {   // the regular flush: BEFORE the tile is consumed, AFTER all of it has arrived (stream_slice)
+        if (tail > (uint32_t)(kTailQueueCap - 256)) {   // the regular flush: BEFORE the tile is consumed, AFTER all of it has arrived
             asm volatile("" ::"v"(t[3].w));
             flush();
         }
@@ -215,11 +175,8 @@ const float* __restrict__ pg, uint32_t cnt, uint32_t* __restrict__ dst,
             put(b2, f2);
             put(b3, f3);
             if (tail > (uint32_t)(kTailQueueCap - 256)) flush();   // (a pair that lists most of what it reads: a small pair, a cold start)
-#ifdef DPL_TAIL_FENCE
-            DPL_SCHED_FENCE();
-#endif
         }
-        if (__any((rare & 0x7FFFFFFFu) != 0u)) {   // non-zero values outside the window (and NaNs): summed directly, as stream_slice does
+        if (__any((rare & 0x7FFFFFFFu) != 0u)) {   // non-zero values outside the window (and NaNs): summed directly
             double fs = 0.0;
             uint32_t c = 0u, nn = 0u;
 #pragma unroll
@@ -278,10 +235,7 @@ const float* __restrict__ pg, uint32_t cnt, uint32_t* __restrict__ dst,
 //     per lane and a DPP sum, no exchange, no barrier;
 //   * lists beyond that (a cold start, a pair much brighter than its tensor's history) take the round-3 shape: rows spread over
 //     the workgroup, partial sums exchanged through LDS.
-#ifndef DPL_TAIL_SURV_VEC
-#define DPL_TAIL_SURV_VEC 5
-#endif
-constexpr int kSurvVec = DPL_TAIL_SURV_VEC;          // 16-byte vectors per lane a wave holds the surviving values in
+constexpr int kSurvVec = 5;                          // 16-byte vectors per lane a wave holds the surviving values in
 constexpr uint32_t kFitCap = kSurvVec * 4 * kWave;   // values one wave's registers hold (a list this short is loaded there whole)
 // ... and what the compaction's staging area holds (group totals, 3 KiB, + the staging area share the queues' space)
 constexpr uint32_t kSurvCap = kFitCap * 4 <= (uint32_t)(kTailLdsB - 3072) ? kFitCap : (uint32_t)(kTailLdsB - 3072) / 4;
@@ -297,9 +251,6 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
     dpl_octav_state* me = st + pair;
     const unsigned long long n_pair = n_merged ? n_merged : (unsigned long long)cnt;   // (n_merged: a pair of several slices, k_octav_tail_merge)
     const bool small = !n_merged && cnt <= kSmallCap;
-#ifdef DPL_RES_PROF
-    unsigned long long prof_keep[3] = {0ull, 0ull, 0ull};
-#endif
     const unsigned long long* packed = reinterpret_cast<const unsigned long long*>(lds_raw);   // the histogram: intact to the end
     uint32_t* tn = reinterpret_cast<uint32_t*>(lds_raw + kLdsA);                                // [256] counts above a group
     double* ts = reinterpret_cast<double*>(lds_raw + kLdsA + 1024);                             // [256] sums above a group
@@ -338,7 +289,6 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
     } else {
         load_rows(v, std::integral_constant<int, kVecT>{}, 0u);
     }
-    DPL_PROF_T(wt0);
     // ---- totals above every group of 8 bins (thread t: bins 2040 - 8 t .. 2047 - 8 t, one exponent: integer sums, ONE conversion)
     constexpr int kPerT = kLogNB / kThreads;
     static_assert(kPerT == 8, "a thread owns eight bins: an eighth of an octave");
@@ -475,10 +425,6 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
             if (!step((unsigned long long)cc, tm)) break;
         }
     };
-    DPL_PROF_T(wt1);
-#ifdef DPL_RES_PROF
-    unsigned long long wt2m = wt1;   // (end of wave 0's bounded steps)
-#endif
     if (w == 0) {
         // ---- the pair's statistics (stream_tail left them per wave), s_0, the route
         const float gmn = fminf(fminf(sh.red_mn[0], sh.red_mn[1]), fminf(sh.red_mn[2], sh.red_mn[3]));
@@ -536,9 +482,6 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
             s_above = lk_s;
             // 1: this wave finishes alone (the list fits its registers); 2: after a compaction; 3: the workgroup, rows + exchange
             if (!bad) path = fits ? 1u : ((lk_n + lk_c <= kSurvCap && n_rows <= (uint32_t)kVecT) ? 2u : 3u);
-#ifdef DPL_RES_PROF
-            wt2m = __builtin_readcyclecounter();
-#endif
             if (path == 1u) walk_alone();
         }
         if (lane == 0) {
@@ -695,10 +638,6 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
     }
     __syncthreads();
     bad = sh.w_bad;
-    DPL_PROF_T(wt3);
-    DPL_PROF_KEEP(1, wt1, wt2m);
-    DPL_PROF_KEEP(2, wt2m, wt3);
-    DPL_PROF_T(wt4);
     // ---- a pair this form could not finish is RESCUED (as walk_pair does): exact bracket, re-read of the pair alone, verified
     // walk.  The bracket walk wants the suffix totals of every bin: only now are they written out (over the packed histogram)
     bool rescued = false;
@@ -799,18 +738,10 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
         // history: the bin this pair asked for (whatever became of its walk)
         if (!small && route != 0u) atomicMax(fa.vis_w + (size_t)tensor * kLogWords, (uint32_t)kLogNB - sh.jwant);
     }
-    DPL_PROF_T(wt5);
-    DPL_PROF_ADD(0, wt0, wt1);
-    DPL_PROF_FLUSH();
-    DPL_PROF_ADD(3, wt4, wt5);
-    if (tid == 0) {
-        g_prof_iters_add(blockIdx.x, evals);
-        DPL_PROF_L(L_listed);
-    }
 }
 
 // One workgroup per pair (largest first): the pair's only HBM read, then its walk.
-__global__ __launch_bounds__(kThreads, DPL_TAIL_OCC) void k_octav_tail(
+__global__ __launch_bounds__(kThreads, kTailOcc) void k_octav_tail(
     const dpl_work_item* __restrict__ slices, const float* const* __restrict__ segs, dpl_octav_state* __restrict__ st,
     uint32_t n_tensors, const uint64_t* __restrict__ pair_base, float* __restrict__ list0, dpl_octav_state* __restrict__ ctl,
     const dpl_span* __restrict__ spans, unsigned long long* __restrict__ rows, const TailArgs fa) {
@@ -818,7 +749,6 @@ __global__ __launch_bounds__(kThreads, DPL_TAIL_OCC) void k_octav_tail(
     unsigned long long* l_packed = reinterpret_cast<unsigned long long*>(lds_raw);
     __shared__ Shared sh;
     const uint32_t tid = threadIdx.x;
-    DPL_PROF_T(kt0);
     const dpl_work_item it = slices[blockIdx.x];
     const bool part = it.reserved > 1u;    // a slice of a pair of several (uniform): streamed like a pair, its row left for k_octav_tail_merge
     const uint32_t pair = it.slot, cnt = it.count;
@@ -851,7 +781,6 @@ __global__ __launch_bounds__(kThreads, DPL_TAIL_OCC) void k_octav_tail(
     __syncthreads();
     stream_tail(pg, cnt, reinterpret_cast<uint32_t*>(list0 + list_at), sh, ctl, !small);
     __syncthreads();   // every LDS histogram add has landed; the per-wave ranges and the out-of-window sums are in sh
-    DPL_PROF_T(kt1);
     if (part) {
         // the packed histogram row (16 KiB per 4 MiB read), the list's length and final threshold bin in its word 0; range,
         // out-of-window sums and NaN flag by atomics on the pair's freshly initialised state
@@ -874,24 +803,7 @@ __global__ __launch_bounds__(kThreads, DPL_TAIL_OCC) void k_octav_tail(
         }
         return;
     }
-#if defined(DPL_TAIL_ABL_NOWALK)
-    if (tid == 0) {
-        st[pair].done = 1u;
-        st[pair].s = sh.red_mx[0];
-    }
-#if defined(DPL_TAIL_ABL_DELAY)   // a stand-in for the walk's latency: DPL_TAIL_ABL_DELAY ticks spent by every wave (1) or by wave 0 alone (2: the others exit)
-    if (DPL_TAIL_ABL_WHO == 2 && tid >= kWave) return;
-    {
-        const unsigned long long t0 = __builtin_readcyclecounter();
-        while (__builtin_readcyclecounter() - t0 < (unsigned long long)DPL_TAIL_ABL_DELAY) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
-    return;
-#endif
     walk_tail<kTailVec>(pair, tensor, lds_raw, sh, st, ctl, pair_base, list0, fa, cnt);
-    DPL_PROF_T(kt2);
-    DPL_PROF_ADD(4, kt0, kt1);
-    DPL_PROF_ADD(5, kt1, kt2);
 }
 
 // ---- pairs of more than one slice (> 1 044 480 elements: the packed histogram's 20-bit counts) -------------------------------
@@ -901,7 +813,7 @@ __global__ __launch_bounds__(kThreads, DPL_TAIL_OCC) void k_octav_tail(
 // NaN flag.  k_octav_tail_merge, one workgroup per such pair behind it: the rows added up in LDS (a bin that holds 2^20 values or
 // more does not fit the packed word: such a pair goes to the compaction route), the slices' lists moved together, then the
 // SAME walk (walk_tail) over the merged histogram and list.
-__global__ __launch_bounds__(kThreads, DPL_TAIL_OCC) void k_octav_tail_merge(
+__global__ __launch_bounds__(kThreads, kTailOcc) void k_octav_tail_merge(
     const dpl_work_item* __restrict__ slices, dpl_octav_state* __restrict__ st, uint32_t n_tensors,
     const uint64_t* __restrict__ pair_base, float* __restrict__ list0, dpl_octav_state* __restrict__ ctl,
     const dpl_span* __restrict__ spans, const unsigned long long* __restrict__ rows, const uint32_t* __restrict__ pair_order,

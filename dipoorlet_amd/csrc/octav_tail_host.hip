@@ -25,51 +25,22 @@
 
 namespace {
 
-// keeps the scheduler from interleaving the unrolled per-vector bodies (their temporaries would not fit beside the slice)
-#define DPL_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
-#ifndef DPL_RES_VEC
-#define DPL_RES_VEC 16
-#endif
-#ifndef DPL_WALK_OCC
-#define DPL_WALK_OCC 4
-#endif
-constexpr int kVec = DPL_RES_VEC;                               // 16-byte vectors per thread the rescue walk keeps a list in
+constexpr int kVec = 16;                                        // 16-byte vectors per thread the rescue walk keeps a list in
+constexpr int kWalkOcc = 4;                                     // waves per SIMD k_octav_walk_rescue is bounded for
 constexpr int kOver = 4;                                         // rows of a list beyond the resident ones streamed per step of an iteration
 constexpr uint32_t kSmallCap = 20480;                           // pairs this small list their whole window (every step of their walk is exact)
 static_assert(kSmallCap == kListWhole, "a small pair's list region must hold the whole pair (list_cap_of)");
-#ifndef DPL_SLICE_CAP
-#define DPL_SLICE_CAP 1044480
-#endif
-constexpr uint32_t kCap = DPL_SLICE_CAP;                        // elements of a slice (streamed tile by tile)
+constexpr uint32_t kCap = 1044480;                              // elements of a slice (streamed tile by tile)
 static_assert(kCap < (1u << 20) && kCap % 4096u == 0u, "a slice's bin counts must fit the packed field");
 constexpr uint32_t kMaxCluster = 64;                            // slices of one pair at most
 constexpr int64_t kPlanEpoch = 8;   // batches per threshold-history epoch (dpl_octav_plan_bind)
-#ifndef DPL_RESCUE_GRID
-#define DPL_RESCUE_GRID 512
-#endif
-constexpr unsigned kRescueGrid = DPL_RESCUE_GRID;   // workgroups of the rescue's persistent kernels
 constexpr int kPredRow = 2 * kLogWords;             // u32 words of a tensor's row in d_pred (word 0: the threshold snapshot)
 constexpr int kRescRow = kLogNB + kLogNB / 2;   // u64 words of a rescued pair's row: 2048 suffix sums (fp64) + 2048 suffix counts (u32)
 
 // LDS of the streaming kernel: [A: packed histogram 16 KiB | one dummy word per lane][B: the waves' survivor queues, octav_tail.hpp]
 constexpr int kLdsA = kLogNB * 8 + kWave * 8;                   // + the lanes' dummy words
-
-#ifdef DPL_RES_PROF
-// phase cycle counters of a tuning build (scripts/res_prof.py): [workgroup][8] u64, accumulated by thread 0
-__device__ unsigned long long g_res_prof[4096 * 8];
-#define DPL_PROF_T(var) const unsigned long long var = __builtin_readcyclecounter()
-#define DPL_PROF_ADD(slot, a, b) do { if (threadIdx.x == 0) g_res_prof[(blockIdx.x & 4095u) * 8 + (slot)] += (b) - (a); } while (0)
-__device__ __forceinline__ void g_prof_iters_add(uint32_t b, uint32_t it) { g_res_prof[(b & 4095u) * 8 + 7] += it; }
-#define DPL_PROF_L(len) g_res_prof[(blockIdx.x & 4095u) * 8 + 6] += (len)
-#else
-#define DPL_PROF_L(len) do {} while (0)
-__device__ __forceinline__ void g_prof_iters_add(uint32_t, uint32_t) {}
-#define DPL_PROF_T(var) do {} while (0)
-#define DPL_PROF_ADD(slot, a, b) do {} while (0)
-#endif
 
 struct Shared {
     double red_d[kWaves];
@@ -203,7 +174,6 @@ __device__ __forceinline__ void walk_rescued(
     dpl_octav_state* me = st + pair;
     if (me->mode != 3u || me->done) return;
     if (me->n_elems == 0ull) return;   // an empty pair: nothing was streamed
-    DPL_PROF_T(pt0);
     const float* lp = list_rescue + pair_base[pair];
     f4 v[kVecT];
     // the list: ONE segment at the start of the pair's region; 1024 values per ROW (one 16-byte vector per thread)
@@ -241,8 +211,6 @@ __device__ __forceinline__ void walk_rescued(
         sh.route = me->len[0] > (uint32_t)(pair_base[pair + 1] - pair_base[pair]) ? 1u : 2u;
     }
     __syncthreads();
-    DPL_PROF_T(pt1);
-    DPL_PROF_ADD(0, pt0, pt1);
     const uint32_t route = __builtin_amdgcn_readfirstlane(sh.route);
     uint32_t bad = route == 1u ? 1u : 0u;
     float s = sh.s0;
@@ -274,8 +242,6 @@ __device__ __forceinline__ void walk_rescued(
         if (!bad) enter(jb);
         uint32_t par = 0u;   // alternating slots: a wave may write iteration k + 1's partials while another still reads k's
         uint32_t done = 0u;
-        DPL_PROF_T(pt2);
-        DPL_PROF_ADD(1, pt1, pt2);
         while (!done && !bad) {
             // values of bin jb above s: bit patterns in (bits(s), lower edge of bin jb + 1), i.e. d = u - bits(s) - 1 below
             // `span` (unsigned: anything at or below s wraps around).  Four VALU instructions per value — the count is a
@@ -348,9 +314,6 @@ __device__ __forceinline__ void walk_rescued(
                 }
             }
         }
-        DPL_PROF_T(pt3);
-        DPL_PROF_ADD(2, pt2, pt3);
-        if (tid == 0) g_prof_iters_add(blockIdx.x, iters);
     }
     if (tid == 0) {
         if (bad) {
@@ -368,14 +331,11 @@ __device__ __forceinline__ void walk_rescued(
     }
 }
 
-#ifndef DPL_TAIL_LDS_PAD
-#define DPL_TAIL_LDS_PAD 0   // (occupancy experiments: extra dynamic LDS per workgroup)
-#endif
 #include "octav_tail.hpp"
 
 // The rescue walk: a small persistent grid over the list of rescued pairs — usually empty, and a launch that has nothing to do
 // should not have thousands of workgroups to schedule between those of the next batch's streaming kernel.
-__global__ __launch_bounds__(kThreads, DPL_WALK_OCC) void k_octav_walk_rescue(
+__global__ __launch_bounds__(kThreads, kWalkOcc) void k_octav_walk_rescue(
     dpl_octav_state* __restrict__ st, dpl_octav_state* __restrict__ ctl, const uint64_t* __restrict__ pair_base, int max_iters,
     int fail_every, const uint32_t* __restrict__ rescue_bm, const uint32_t* __restrict__ missed,
     const float* __restrict__ list_rescue, const unsigned long long* __restrict__ resc) {
@@ -401,19 +361,6 @@ int dpl_octav_fallback_route(const dpl_work_item* d_items, int64_t n_items, cons
                              float* d_list0, float* d_list1, int dynamic_sym, int max_iters, hipStream_t st);
 
 extern "C" {
-
-#ifdef DPL_RES_PROF
-int dpl_res_prof_read(unsigned long long* host_out, int reset) {   // tuning builds only
-    hipError_t e = hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_res_prof), sizeof(unsigned long long) * 4096 * 8);
-    if (e != hipSuccess) return fail("dpl_res_prof_read", e);
-    if (reset) {
-        static unsigned long long z[4096 * 8];
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_res_prof), z, sizeof(z));
-        if (e != hipSuccess) return fail("dpl_res_prof_read", e);
-    }
-    return 0;
-}
-#endif
 
 uint32_t dpl_octav_slice_cap(void) { return kCap; }
 uint32_t dpl_octav_list_cap(uint64_t n_elements) { return list_cap_of(n_elements); }
@@ -519,7 +466,7 @@ int dpl_octav_oneread_stream(const dpl_octav_oneread_job* j, dpl_stream_t s) {
     DPL_JOB_CHECK("dpl_octav_oneread_stream");
     const TailArgs fa{j->d_vis + (int64_t)j->write_epoch * j->n_tensors * kLogWords, j->d_pred, j->d_rescue_bm, j->d_missed,
                       reinterpret_cast<unsigned long long*>(j->d_resc), j->dynamic_sym, j->max_iters, g_exact_fail_every};
-    const size_t lds = (size_t)(kLdsA + kTailLdsB + DPL_TAIL_LDS_PAD);
+    const size_t lds = (size_t)(kLdsA + kTailLdsB);
     // (a slice of a pair above one slice — the first items of d_slices, largest first — leaves its row in d_lh ...)
     hipLaunchKernelGGL(k_octav_tail, dim3((unsigned)j->n_slices), dim3(kThreads), lds, (hipStream_t)s, j->d_slices,
                        j->d_seg_ptrs, j->d_states, (uint32_t)j->n_tensors, j->d_pair_base, j->d_list0, j->d_states + j->n_pairs,

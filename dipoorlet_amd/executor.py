@@ -944,11 +944,10 @@ class GraphSession(ActivationSession):
     def _run_env(self, inputs, batch, keep=None):
         if getattr(self, "_conv_threads", None):
             # the first forward WAITS for the convolution threads instead of racing them (two threads resolving the same
-            # configuration at the same time both pay for it): DPL_PREWARM_WAIT=0 races, for A/B
-            if os.environ.get("DPL_PREWARM_WAIT", "1") != "0":
-                with _wall("warm_wait_convs_s"):
-                    for t in self._conv_threads:
-                        t.join()
+            # configuration at the same time both pay for it)
+            with _wall("warm_wait_convs_s"):
+                for t in self._conv_threads:
+                    t.join()
             self._conv_threads = None
         if getattr(self, "_consts_host", None) is not None and self._consts_copied.query():
             self._consts_host = None

@@ -24,7 +24,7 @@ from .platform_settings import platform_setting_table
 from .utils import logger, mark
 
 DEFAULT_BATCH = 64   # images per forward (ResNet-50's fp32 forward runs 12 % more images per second than at 32; the statistics kernels run at the
-                     # same fraction of the HBM roofline at 32 and 64: same-box A/B of the CLI, scripts/e2e_dbg.sh)
+                     # same fraction of the HBM roofline at 32 and 64: same-box A/B of the CLI)
 
 
 class ActivationSession:

@@ -45,11 +45,6 @@ def _upload_struct_array(arr, n, device):
 DEFAULT_BLOCKS = {"minmax": 256, "hist": 768, "octav": 1024, "cos": 512, "fq": 65536}   # measured optima per kernel family
 
 
-def _blocks_for(kind):
-    v = os.environ.get("DPL_BLOCKS_" + kind.upper())
-    return int(v) if v else DEFAULT_BLOCKS[kind]
-
-
 class WorkSet:
     """Device-resident work decomposition of one launch: items (+ block_begin for the balanced form)."""
 
@@ -92,7 +87,7 @@ class TensorSetPlan:
 
     def work(self, kind, per_image=False):
         """WorkSet for kernel family `kind` in {'minmax', 'hist', 'octav', 'cos', 'fq'}."""
-        nb = None if self.chunk else max(1, min(_blocks_for(kind), (self.total + 4095) // 4096))
+        nb = None if self.chunk else max(1, min(DEFAULT_BLOCKS[kind], (self.total + 4095) // 4096))
         key = (per_image, nb)
         w = self._work.get(key)
         if w is None:
@@ -141,7 +136,7 @@ class TensorSetPlan:
         if getattr(self, "_octav_tail", None) is None:
             arr, ns = _hip._span_array(self._spans(True))
             L = _hip.lib()
-            handle = L.dpl_octav_plan_create(C.addressof(arr), ns, self.T, max(1, min(_blocks_for("octav"), (self.total + 4095) // 4096)))
+            handle = L.dpl_octav_plan_create(C.addressof(arr), ns, self.T, max(1, min(DEFAULT_BLOCKS["octav"], (self.total + 4095) // 4096)))
             if not handle:
                 self._octav_tail = False
             else:
@@ -913,7 +908,7 @@ class FakeQuantSet:
                                            int(qlo), int(qhi))
         self.d_params = _upload_struct_array(rows, plan.T, plan.device)
         # the balanced partition over the batch's tensors (slot = tensor): 65536 workgroups of ~52 KB on the ResNet-50 set, so
-        # that the resident ones read and write a dense window as the dispatcher hands them out (scripts/fq_set_blocks.py: with
+        # that the resident ones read and write a dense window as the dispatcher hands them out (measured: with
         # 1024 resident workgroups of 3.3 MB each the read + write stream reaches 0.73 of 8 TB/s on some boxes of the pool and
         # 0.60 - 0.62 on others; 65536: 0.70 - 0.73 on both kinds)
         self.work = plan.work("fq")
