@@ -1,5 +1,5 @@
 """`python -m dipoorlet_amd -M model.onnx -I calib_dir -N 1024 -A hist -D trt` — the reference's CLI
-(dipoorlet/__main__.py:23-161) over the MI355X calibration core.
+(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, is this project's addition).
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
@@ -30,9 +30,10 @@ def build_parser():
     for flag in ("--we", "--bc", "--update_bn", "--adaround", "--brecq", "--drop", "--savefp", "--stpu_wg",
                  "--skip_prof_layer", "--slurm", "--mpirun", "--sparse", "--optim_transformer"):
         p.add_argument(flag, default=False, action="store_true")
-    p.add_argument("-A", "--act_quant", choices=["minmax", "hist", "mse"], default="mse",
+    p.add_argument("-A", "--act_quant", choices=["minmax", "hist", "mse", "kl"], default="mse",
                    help="minmax / hist: bit-exact clip ranges; mse (OCTAV): within 1e-5 * max(1, |ref|) of the reference's, repeating "
-                        "to about 1e-6 relative from run to run (DPL_OCTAV_FORM=bracket: the bit-stable two-read form)")
+                        "to about 1e-6 relative from run to run (DPL_OCTAV_FORM=bracket: the bit-stable two-read form); kl: entropy "
+                        "search on the |x| histogram (not in the reference; honours --bins, ignores --threshold)")
     p.add_argument("-D", "--deploy", choices=["trt", "stpu", "magicmind", "rv", "atlas", "snpe", "ti", "imx"],
                    required=True)
     p.add_argument("--bins", default=2048, type=int)  # the reference omits type= and crashes on a CLI value

@@ -1,6 +1,7 @@
 // MI355X (gfx950 / CDNA4) activation-calibration kernels + C ABI (include/dipoorlet_hip.h).
 //
-// Everything here is an HBM-bound streaming reduction / scatter-add: no MFMA.  Design rules
+// Everything here but the entropy search (K4b: fp64 arithmetic on an LDS-resident row) is an HBM-bound streaming
+// reduction / scatter-add: no MFMA.  Design rules
 // (guides: cdna_hip_programming.md G2/G11/G12/G13, MI355X_MICROARCH.md §LDS/§HBM):
 //   * 16 B per lane coalesced loads (global_load_dwordx4), several independent loads in flight,
 //     one workgroup per work item (a contiguous chunk of ONE tensor), >> 256 workgroups per launch;
@@ -264,6 +265,20 @@ __global__ void k_hist_prepare(const float* __restrict__ gmin, const float* __re
     out[i] = r;
 }
 
+// The fp32 clip range of a histogram search that ends on bin `found` (-1: none, the range itself): the centre of that bin,
+// basic_algorithm.py:42-53.  Shared by the percentile and the entropy search.
+__device__ __forceinline__ void store_bin_clip(int found, float gmin, float gmax, int bins, float* __restrict__ clip) {
+    float lo = gmin, hi = gmax;
+    if (found >= 0) {
+        const float dmax = py_max(-gmin, gmax);  // basic_algorithm.py:42
+        const float cv = __fmul_rn((float)found + 0.5f, __fdiv_rn(dmax, (float)bins));
+        lo = py_max(-cv, gmin);
+        hi = py_min(cv, gmax);
+    }
+    clip[0] = lo;
+    clip[1] = hi;
+}
+
 // ================================================================ K4: percentile clip (basic_algorithm.py:40-53)
 // One wave per slot.  The cumulative sum is a SEQUENTIAL fp64 accumulation in bin order (the >=
 // threshold test is order sensitive), so lanes load 64 bins at a time and the wave walks them in order
@@ -309,16 +324,151 @@ __global__ __launch_bounds__(kWave) void k_hist_percentile(const uint64_t* __res
         }
         if (reached) found = base + __builtin_ctzll(reached);
     }
-    if (lane == 0) {
-        float lo = gmin, hi = gmax;
-        if (found >= 0) {
-            const float dmax = py_max(-gmin, gmax);  // basic_algorithm.py:42
-            const float cv = __fmul_rn((float)found + 0.5f, __fdiv_rn(dmax, (float)bins));
-            lo = py_max(-cv, gmin);
-            hi = py_min(cv, gmax);
+    if (lane == 0) store_bin_clip(found, gmin, gmax, bins, clip + 2 * slot);
+}
+
+// ================================================================ K4b: entropy (KL-divergence) clip — beyond the reference
+// The definition is this project's own (tests/kl_model.py): for every candidate i in [levels, bins] — keep bins
+// [0, i), outliers folded into bin i - 1 — the divergence between the kept histogram p and its image q on `levels` groups
+// (group j = bins [j i / L, (j + 1) i / L), a group's mass WITHOUT the outliers spread over its bins where p != 0), both
+// smoothed (zeros -> eps, taken evenly from the non-zeros) and normalised.
+//
+// grid = (candidate chunk, tensor).  A workgroup holds its tensor's row in LDS as an exclusive prefix sum of the counts (u64;
+// a count is the difference of two neighbours) and the non-zero flags as one 64-bit mask and one running count per 64 bins, so
+// a group's mass is two LDS reads and its live-bin count two reads and two popcounts, whatever the group's length: 8 B per bin,
+// 133 KB with the masks at 16384 bins (one workgroup per CU there; 2048 bins: 19 KB).  One wave per candidate at a time, lanes own bins; the
+// group of a bin is ((b + 1) L - 1) / i (the divisors are wave-uniform: their reciprocals leave the loop).  Everything that
+// does not depend on the bin is formed analytically per candidate: the number of non-zero bins of p and of q (q has one fewer
+// exactly when the last group holds nothing but outliers), the two smoothing amounts, the two sums (sum p' = N - n1 e1 + z eps),
+// and the z bins where p is zero, which all contribute the same term.  Counts convert to fp64 exactly (a calibration set stays
+// far below 2^53 elements).  A lane adds its bins in order, the 64 partial sums meet in a fixed shuffle tree, one lane stores:
+// no floating-point atomics, two calls give the same bits, and a candidate's value does not depend on the launch's geometry.
+// Candidates cost in proportion to i: they are dealt round-robin to the chunks and, inside a chunk, to the four waves.
+constexpr double kKlEps = 1e-4;
+
+__device__ __forceinline__ uint32_t kl_live_below(const uint64_t* __restrict__ mask, const uint32_t* __restrict__ bcnt, uint32_t x) {
+    const uint32_t k = x >> 6;   // bins [0, x) with a non-zero count
+    return bcnt[k] + (uint32_t)__popcll(mask[k] & ((1ull << (x & 63u)) - 1ull));
+}
+
+__global__ __launch_bounds__(kBlock) void k_hist_kl(const uint64_t* __restrict__ hist, int bins, int levels, int n_chunks,
+                                                     double* __restrict__ div) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t kl_lds[];
+    const uint32_t nblk = ((uint32_t)bins + 63u) >> 6;
+    uint64_t* cs = kl_lds;                     // [bins + 1] exclusive prefix sum of the counts
+    uint64_t* mask = cs + bins + 1;            // [nblk + 1] bit b & 63 of mask[b >> 6]: count of bin b != 0 (the last entry is 0)
+    uint64_t* part = mask + nblk + 1;          // [kBlock] the scan's per-thread sums
+    uint32_t* bcnt = reinterpret_cast<uint32_t*>(part + kBlock);   // [nblk + 1] non-zero bins below bin 64 k
+    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const uint32_t slot = blockIdx.x / (uint32_t)n_chunks, chunk = blockIdx.x % (uint32_t)n_chunks;
+    const uint64_t* __restrict__ h = hist + (uint64_t)slot * (uint64_t)bins;
+    double* __restrict__ out = div + (uint64_t)slot * ((uint64_t)bins + 1u);
+    const uint32_t L = (uint32_t)levels, C = (uint32_t)n_chunks, nb = (uint32_t)bins;
+
+    // ---- the row: prefix sums (a contiguous run of bins per thread, then the threads' sums) and the non-zero masks
+    {
+        const uint32_t per = (nb + kBlock - 1) / kBlock;
+        const uint32_t b0 = tid * per < nb ? tid * per : nb, b1 = b0 + per < nb ? b0 + per : nb;
+        uint64_t s = 0;
+        for (uint32_t b = b0; b < b1; ++b) s += h[b];
+        part[tid] = s;
+        for (uint32_t k = wave; k < nblk; k += kBlock / kWave) {
+            const uint32_t b = k * kWave + lane;
+            const uint64_t m = __ballot(b < nb && h[b] != 0ull);
+            if (lane == 0) mask[k] = m;
         }
-        clip[2 * slot] = lo;
-        clip[2 * slot + 1] = hi;
+        if (tid == 0) mask[nblk] = 0ull;
+        __syncthreads();
+        uint64_t off = 0;
+        for (uint32_t j = 0; j < (uint32_t)kBlock; ++j) off += j < tid ? part[j] : 0ull;   // (one address per step: a broadcast)
+        for (uint32_t b = b0; b < b1; ++b) {
+            cs[b] = off;
+            off += h[b];
+        }
+        if (tid == kBlock - 1) cs[nb] = off;
+        for (uint32_t k = tid; k <= nblk; k += kBlock) {
+            uint32_t a = 0;
+            for (uint32_t j = 0; j < nblk; ++j) a += j < k ? (uint32_t)__popcll(mask[j]) : 0u;
+            bcnt[k] = a;
+        }
+        __syncthreads();
+    }
+    // ---- candidates below `levels` are not admissible
+    for (uint32_t i = chunk + tid * C; i < L; i += kBlock * C) out[i] = INFINITY;
+
+    const uint64_t N = cs[nb];
+    const double dN = (double)(long long)N;
+    const uint32_t first = L + (chunk + C - L % C) % C;   // the lowest candidate >= levels of this chunk (i % C == chunk)
+    for (uint32_t i = first + wave * C; i <= nb; i += (kBlock / kWave) * C) {
+        // per candidate (wave-uniform)
+        const uint64_t csi = cs[i];
+        const uint64_t outl = N - csi;                      // the outliers, folded into bin i - 1 of p
+        const uint32_t s_last = (uint32_t)(((uint64_t)(L - 1u) * i) / L);
+        const uint32_t woke = (csi == cs[i - 1] && outl != 0ull) ? 1u : 0u;   // bin i - 1 is empty and live through the outliers alone
+        const uint32_t n1p = kl_live_below(mask, bcnt, i) + woke;
+        const uint32_t n1q = n1p - ((csi == cs[s_last] && outl != 0ull) ? 1u : 0u);   // (q of that bin is zero: its group holds no mass)
+        double res = INFINITY;
+        if (n1p != 0u && n1q != 0u) {
+            const uint32_t zp = i - n1p, zq = i - n1q;
+            const double e1p = kKlEps * (double)zp / (double)n1p;
+            const double e1q = kKlEps * (double)zq / (double)n1q;
+            if (e1p < 1.0 && e1q < 1.0) {
+                const double Sp = dN - (double)n1p * e1p + (double)zp * kKlEps;
+                const double Sq = (double)(long long)csi - (double)n1q * e1q + (double)zq * kKlEps;
+                double acc = 0.0;
+                for (uint32_t b = lane; b < i; b += kWave) {
+                    uint64_t pb = cs[b + 1] - cs[b];
+                    if (b == i - 1u) pb += outl;
+                    if (pb != 0ull) {
+                        const uint32_t g = ((b + 1u) * L - 1u) / i;      // (at most 2^28: bins, levels <= 16384)
+                        const uint32_t s0 = (g * i) / L, s1 = ((g + 1u) * i) / L;
+                        const uint64_t G = cs[s1] - cs[s0];
+                        double qs = kKlEps;
+                        if (G != 0ull) {
+                            const uint32_t live = kl_live_below(mask, bcnt, s1) - kl_live_below(mask, bcnt, s0) + (s1 == i ? woke : 0u);
+                            qs = (double)(long long)G / (double)live - e1q;
+                        }
+                        const double P = ((double)(long long)pb - e1p) / Sp, Q = qs / Sq;
+                        acc += P * log(P / Q);
+                    }
+                }
+                acc = wave_sum(acc);
+                const double Pz = kKlEps / Sp, Qz = kKlEps / Sq;     // the zp bins where p (and with it q) is zero
+                res = acc + (double)zp * (Pz * log(Pz / Qz));
+            }
+        }
+        if (lane == 0) out[i] = res;
+    }
+}
+
+// One wave per tensor: the lowest candidate with the least divergence (NaN never wins; -1: none is admissible) and its clip.
+__global__ __launch_bounds__(kWave) void k_hist_kl_pick(const double* __restrict__ div, const float* __restrict__ gmin_a,
+                                                         const float* __restrict__ gmax_a, int bins, int32_t* __restrict__ best,
+                                                         float* __restrict__ clip) {
+    const int slot = blockIdx.x;
+    const int lane = threadIdx.x;
+    const double* __restrict__ d = div + (uint64_t)slot * ((uint64_t)bins + 1u);
+    double bv = INFINITY;
+    int bi = -1;
+    for (int i = lane; i <= bins; i += kWave) {
+        const double v = d[i];
+        if (v < bv) {   // (ascending i: the first of equal values stays)
+            bv = v;
+            bi = i;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(bv, o, kWave);
+        const int oi = __shfl_xor(bi, o, kWave);
+        if (ov < bv || (ov == bv && oi >= 0 && (bi < 0 || oi < bi))) {
+            bv = ov;
+            bi = oi;
+        }
+    }
+    if (lane == 0) {
+        best[slot] = bi;
+        store_bin_clip(bi >= 0 ? bi - 1 : -1, gmin_a[slot], gmax_a[slot], bins, clip + 2 * slot);
     }
 }
 
@@ -923,6 +1073,28 @@ int dpl_hist_percentile(const uint64_t* d_hist, const float* d_min, const float*
     hipLaunchKernelGGL(k_hist_percentile, dim3((unsigned)n_slots), dim3(kWave), 0, (hipStream_t)s, d_hist, d_min,
                        d_max, bins, threshold, d_clip);
     DPL_LAUNCH_CHECK("k_hist_percentile");
+    return 0;
+}
+
+int dpl_hist_kl(const uint64_t* d_hist, const float* d_min, const float* d_max, int64_t n_slots, int bins, int levels,
+                double* d_div, int32_t* d_best, float* d_clip, dpl_stream_t s) {
+    if (bins < 1 || bins > DPL_MAX_BINS) return fail_msg("dpl_hist_kl: bins must be in [1, 16384]");
+    if (levels < 2 || levels > bins) return fail_msg("dpl_hist_kl: levels must be in [2, bins]");
+    if (n_slots <= 0) return 0;
+    // candidate chunks per tensor: about 1024 workgroups per launch, and no fewer than eight candidates per workgroup
+    const int64_t n_cand = (int64_t)bins - levels + 1;
+    int64_t chunks = (1024 + n_slots - 1) / n_slots;
+    if (chunks > n_cand / 8) chunks = n_cand / 8;
+    if (chunks < 1) chunks = 1;
+    if (n_slots * chunks > 0x7FFFFFFFll) return fail_msg("dpl_hist_kl: too many slots");
+    const size_t nblk = ((size_t)bins + 63) / 64;
+    const size_t lds = ((size_t)bins + 1 + nblk + 1 + kBlock) * sizeof(uint64_t) + (nblk + 1) * sizeof(uint32_t);
+    hipLaunchKernelGGL(k_hist_kl, dim3((unsigned)(n_slots * chunks)), dim3(kBlock), lds, (hipStream_t)s, d_hist, bins, levels,
+                       (int)chunks, d_div);
+    DPL_LAUNCH_CHECK("k_hist_kl");
+    hipLaunchKernelGGL(k_hist_kl_pick, dim3((unsigned)n_slots), dim3(kWave), 0, (hipStream_t)s, d_div, d_min, d_max, bins,
+                       d_best, d_clip);
+    DPL_LAUNCH_CHECK("k_hist_kl_pick");
     return 0;
 }
 

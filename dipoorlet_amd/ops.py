@@ -400,6 +400,20 @@ class CalibAccumulators:
                    "dpl_hist_percentile")
         return clip
 
+    def hist_kl(self, levels):
+        """Entropy (KL-divergence) clip search on the accumulated histograms (k_hist_kl; the definition: tests/kl_model.py)
+        -> (clip [n, 2] fp32, best [n] int32: the number of bins kept, -1 where no candidate is admissible and the clip is the
+        range, div [n, bins + 1] fp64: every candidate's divergence, +inf where not admissible or below `levels`)."""
+        levels = int(levels)
+        if not (2 <= levels <= self.bins):
+            raise _hip.DipoorletHipError(f"hist_kl: levels must be in [2, bins = {self.bins}], got {levels}")
+        clip = torch.empty(self.n, 2, dtype=torch.float32, device=self.device)
+        best = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        div = torch.empty(self.n, self.bins + 1, dtype=torch.float64, device=self.device)
+        _hip.check(_hip.lib().dpl_hist_kl(_ptr(self.hist), _ptr(self.gmin), _ptr(self.gmax), self.n, self.bins, levels,
+                                          _ptr(div), _ptr(best), _ptr(clip), _stream()), "dpl_hist_kl")
+        return clip, best, div
+
 
 _OCTAV_MAX_ITERS = 20  # forward_net.py:325
 

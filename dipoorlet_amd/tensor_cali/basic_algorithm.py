@@ -1,6 +1,7 @@
 """Activation clip-range search: the three registry algorithms of the reference
 (dipoorlet/tensor_cali/basic_algorithm.py:8-69) plus the per-channel weight ranges (:72-91), computed
-on the MI355X.
+on the MI355X — and, in a registry of its own (tensor_cali_extensions), the entropy search `kl` the reference
+never shipped.
 
 Registry keys, call form and return type are the reference's: `tensor_cali_dispatcher(key, graph, args)`
 -> {tensor_name: [lo, hi]} with numpy scalars (they must support .tolist(), utils.py:314-316); an
@@ -18,12 +19,19 @@ import torch
 from .. import ops
 from ..dist_helper import gather_rows, merge_hist, merge_ranges
 from ..forward_net import (CalibrationRun, forward_get_minmax, forward_net_octav, hist_pass)
-from ..platform_settings import LAYER_HAS_WEIGHT
+from ..platform_settings import LAYER_HAS_WEIGHT, platform_setting_table
 from ..utils import dispatch_functool, logger
 
 
 @dispatch_functool
 def tensor_cali_dispatcher(*args, **kwargs):
+    logger.info("Calibration Algorithm Not Found!")
+
+
+@dispatch_functool
+def tensor_cali_extensions(*args, **kwargs):
+    """Algorithms beyond the reference's three: same call form as tensor_cali_dispatcher, a registry of its own (the reference
+    answers their keys with "Calibration Algorithm Not Found!", and tensor_cali_dispatcher keeps doing so)."""
     logger.info("Calibration Algorithm Not Found!")
 
 
@@ -49,12 +57,12 @@ def find_clip_val_minmax(onnx_graph, args, run=None, **kwargs):
     return _as_clip_dict(run.names, gmin, gmax)
 
 
-@tensor_cali_dispatcher.register("hist")
-def find_clip_val_hist(onnx_graph, args, store_stats=None, run=None, **kwargs):
-    """basic_algorithm.py:25-54 — percentile (cumulative mass >= args.threshold) of the |x| histogram.
+def _hist_statistics(onnx_graph, args, store_stats=None, run=None):
+    """The two sweeps of the histogram algorithms (ranges, then |x| histograms over them) and their merge over ranks
+    -> (acc, names): ops.CalibAccumulators with gmin / gmax / hist of every tensor, and the tensors' names.
 
     store_stats = {'minmax': {name: {'min': [...], 'max': [...]}}, 'hist': {name: int64[bins]}} skips the
-    sweeps (the reference's unused hook, :26-29) and only runs the percentile search on the device."""
+    sweeps (the reference's unused hook, basic_algorithm.py:26-29): the statistics are installed as given."""
     bins = int(args.bins)  # the reference leaves a CLI --bins as str and crashes at :47; int() is the fix
     if store_stats:
         names = list(store_stats["hist"].keys())
@@ -75,7 +83,36 @@ def find_clip_val_hist(onnx_graph, args, store_stats=None, run=None, **kwargs):
         if _merged(args):
             merge_hist(acc.hist, args.world_size)
         names = run.names
+    return acc, names
+
+
+@tensor_cali_dispatcher.register("hist")
+def find_clip_val_hist(onnx_graph, args, store_stats=None, run=None, **kwargs):
+    """basic_algorithm.py:25-54 — percentile (cumulative mass >= args.threshold) of the |x| histogram.
+
+    store_stats: _hist_statistics — only the percentile search runs on the device."""
+    acc, names = _hist_statistics(onnx_graph, args, store_stats, run)
     clip = acc.hist_percentile(float(args.threshold))
+    return _as_clip_dict(names, clip[:, 0], clip[:, 1])
+
+
+def kl_levels(deploy):
+    """Quantisation levels per sign of the platform's activations: 2 ** (bit_width - 1) of its qi_params."""
+    return 2 ** (int(platform_setting_table[deploy]["qi_params"]["bit_width"]) - 1)
+
+
+@tensor_cali_extensions.register("kl")
+def find_clip_val_kl(onnx_graph, args, store_stats=None, run=None, **kwargs):
+    """Entropy calibration — not in the reference, which names "kl" in its --bins help and never shipped one: the clip that
+    loses the least information (KL divergence) when the |x| histogram is cut at a candidate bin and quantised to the platform's
+    levels.  The definition is this project's (tests/kl_model.py), searched on the device in one launch (k_hist_kl)
+    over the very histograms `-A hist` accumulates — same sweeps, same merge over ranks, same store_stats hook.
+    args.threshold is not used; args.bins must be at least the platform's levels (128)."""
+    levels = kl_levels(args.deploy)
+    if int(args.bins) < levels:
+        raise ValueError(f"-A kl needs --bins >= {levels} (the quantisation levels of '{args.deploy}'), got {int(args.bins)}")
+    acc, names = _hist_statistics(onnx_graph, args, store_stats, run)
+    clip, _, _ = acc.hist_kl(levels)
     return _as_clip_dict(names, clip[:, 0], clip[:, 1])
 
 

@@ -3,7 +3,8 @@ from . import basic_algorithm as _algo
 
 
 def tensor_calibration(onnx_graph, args):
-    """-> (activation clip ranges from the algorithm registered under args.act_quant, per-channel weight ranges).
+    """-> (activation clip ranges from the algorithm registered under args.act_quant — in the reference's registry or, for
+    keys beyond it ('kl'), in tensor_cali_extensions —, per-channel weight ranges).
     Every rank calls this; the activation statistics are merged over ranks inside the algorithm.
 
     The reference walks the initializers for the weight ranges and then lets the algorithm build its ORT session
@@ -13,13 +14,17 @@ def tensor_calibration(onnx_graph, args):
     from ..forward_net import WALL, CalibrationRun, wall
     WALL.clear()      # (the host-wall breakdown --timing_json reports is this calibration's, not the process's)
     run = None
-    if args.act_quant in _algo.tensor_cali_dispatcher.registry:
+    # a reference key goes to the reference's registry; any other to the extensions', whose default is the reference's answer
+    registry = _algo.tensor_cali_dispatcher
+    if args.act_quant not in registry.registry:
+        registry = _algo.tensor_cali_extensions
+    if args.act_quant in registry.registry:
         run = CalibrationRun(onnx_graph, args)
     try:
         with wall("weight_ranges_s"):
             ranges = {"weight": _algo.find_clip_val_minmax_weight(onnx_graph, args, session=run.session if run else None)}
         with wall("activation_algorithm_s"):
-            ranges["act"] = _algo.tensor_cali_dispatcher(args.act_quant, onnx_graph, args, run=run)
+            ranges["act"] = registry(args.act_quant, onnx_graph, args, run=run)
     finally:
         if run is not None:
             run.close()

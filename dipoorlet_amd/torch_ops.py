@@ -7,6 +7,7 @@ Per tensor:
     dipoorlet::minmax(Tensor x) -> Tensor                      [2] fp32 (min, max); NaN if x holds one
     dipoorlet::abs_hist_(Tensor x, float dmax, int bins, Tensor(a!) hist) -> ()      hist += np.histogram(|x|, bins, (0, dmax))
     dipoorlet::hist_percentile(Tensor hist, float gmin, float gmax, float threshold) -> Tensor   [2] fp32 clip
+    dipoorlet::hist_kl(Tensor hist, float gmin, float gmax, int levels) -> Tensor                [2] fp32 clip (entropy search)
     dipoorlet::octav(Tensor x, bool dynamic_sym) -> Tensor     [3] fp32 (s, min, max) (forward_net.py:315-330)
     dipoorlet::rowwise_minmax(Tensor w2d) -> (Tensor, Tensor)
     dipoorlet::fake_quant(Tensor x, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor
@@ -38,7 +39,7 @@ from . import _hip, ops
 
 _PLANS = {}
 _PLANS_MAX = 32
-_RANGE = {}          # device index -> fp32 [2]: the (gmin, gmax) argument of hist_percentile
+_RANGE = {}          # device index -> fp32 [2]: the (gmin, gmax) argument of hist_percentile / hist_kl
 
 
 class _Cached:
@@ -150,16 +151,22 @@ def abs_hist_batched_(xs: List[torch.Tensor], mins: torch.Tensor, maxs: torch.Te
     _hist_into(c, xs, int(bins), hist)
 
 
-@torch.library.custom_op("dipoorlet::hist_percentile", mutates_args=(), device_types="cuda")
-def hist_percentile(hist: torch.Tensor, gmin: float, gmax: float, threshold: float) -> torch.Tensor:
-    if hist.dtype != torch.int64 or not hist.is_contiguous():
-        raise ValueError("hist must be a contiguous int64 tensor")
-    bins = hist.numel()
+def _range_of(hist, gmin, gmax):
+    """The device's fp32 [2] holding (gmin, gmax), filled on the current stream."""
     rng = _RANGE.get(hist.device.index)
     if rng is None:
         rng = _RANGE[hist.device.index] = torch.empty(2, dtype=torch.float32, device=hist.device)
     rng[0].fill_(float(gmin))
     rng[1].fill_(float(gmax))
+    return rng
+
+
+@torch.library.custom_op("dipoorlet::hist_percentile", mutates_args=(), device_types="cuda")
+def hist_percentile(hist: torch.Tensor, gmin: float, gmax: float, threshold: float) -> torch.Tensor:
+    if hist.dtype != torch.int64 or not hist.is_contiguous():
+        raise ValueError("hist must be a contiguous int64 tensor")
+    bins = hist.numel()
+    rng = _range_of(hist, gmin, gmax)
     clip = torch.empty(2, dtype=torch.float32, device=hist.device)
     _hip.check(_hip.lib().dpl_hist_percentile(ops._ptr(hist), ops._ptr(rng[0:1]), ops._ptr(rng[1:2]), 1, bins, float(threshold),
                                               ops._ptr(clip), ops._stream()), "dpl_hist_percentile")
@@ -168,6 +175,25 @@ def hist_percentile(hist: torch.Tensor, gmin: float, gmax: float, threshold: flo
 
 @hist_percentile.register_fake
 def _(hist, gmin, gmax, threshold):
+    return hist.new_empty(2, dtype=torch.float32)
+
+
+@torch.library.custom_op("dipoorlet::hist_kl", mutates_args=(), device_types="cuda")
+def hist_kl(hist: torch.Tensor, gmin: float, gmax: float, levels: int) -> torch.Tensor:
+    if hist.dtype != torch.int64 or not hist.is_contiguous():
+        raise ValueError("hist must be a contiguous int64 tensor")
+    bins = hist.numel()
+    rng = _range_of(hist, gmin, gmax)
+    clip = torch.empty(2, dtype=torch.float32, device=hist.device)
+    best = torch.empty(1, dtype=torch.int32, device=hist.device)
+    div = torch.empty(bins + 1, dtype=torch.float64, device=hist.device)      # (the search's workspace: an output of the C ABI)
+    _hip.check(_hip.lib().dpl_hist_kl(ops._ptr(hist), ops._ptr(rng[0:1]), ops._ptr(rng[1:2]), 1, bins, int(levels), ops._ptr(div),
+                                      ops._ptr(best), ops._ptr(clip), ops._stream()), "dpl_hist_kl")
+    return clip
+
+
+@hist_kl.register_fake
+def _(hist, gmin, gmax, levels):
     return hist.new_empty(2, dtype=torch.float32)
 
 

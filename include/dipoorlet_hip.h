@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 21 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_* */
+#define DPL_ABI_VERSION 22 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 
 typedef void* dpl_stream_t; /* hipStream_t */
@@ -124,6 +124,16 @@ int dpl_abs_hist_accumulate(const dpl_work_item* d_items, int64_t n_items, const
 /* ---- percentile clip: replaces the python loop of basic_algorithm.py:40-53. d_clip: fp32 [n_slots,2]. */
 int dpl_hist_percentile(const uint64_t* d_hist, const float* d_min, const float* d_max, int64_t n_slots,
                         int bins, double threshold, float* d_clip, dpl_stream_t s);
+
+/* ---- entropy (KL-divergence) clip on the same histogram: beyond the reference, which names "kl" in its --bins help and never
+ *      shipped one.  For every candidate i in [levels, bins] (keep bins [0, i), outliers folded into bin i - 1) the divergence
+ *      between the kept histogram and its image on `levels` groups, both smoothed with eps = 1e-4; the clip is the centre of bin
+ *      i* - 1 for the lowest i* of least divergence, in fp32 as dpl_hist_percentile ends.  The definition is tests/kl_model.py.
+ *      d_div fp64 [n_slots, bins + 1] is caller-provided workspace AND output (the divergence of every candidate, +inf where not
+ *      admissible or i < levels); d_best int32 [n_slots] (i*, -1: none -> the clip is [min, max]); d_clip fp32 [n_slots, 2].
+ *      2 <= levels <= bins <= DPL_MAX_BINS.  No floating-point atomics: two calls give the same bits. */
+int dpl_hist_kl(const uint64_t* d_hist, const float* d_min, const float* d_max, int64_t n_slots, int bins,
+                int levels, double* d_div, int32_t* d_best, float* d_clip, dpl_stream_t s);
 
 /* ---- OCTAV ("mse"): replaces forward_net.py:315-330 per (image,tensor) pair (slot = pair).
  *      dpl_octav_run enqueues the first pass plus 20 (pass, update) rounds; converged pairs exit early. */
