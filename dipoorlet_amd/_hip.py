@@ -15,8 +15,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPL_LIB: another build of the same sources (the host-sanitizer build of scripts/asan_host_check.sh); never a different code path
 LIB_PATH = os.environ.get("DPL_LIB") or os.path.join(_HERE, "csrc", "libdipoorlet_hip.so")
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 MAX_BINS = 16384
+HIST_SPEC_MAX_TENSORS = 2048
 
 
 class Span(C.Structure):
@@ -94,6 +95,10 @@ SIGNATURES = {
     "dpl_minmax_encode": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P]),
     "dpl_hist_prepare": (C.c_int, [_P, _P, _I64, C.c_int, _P, _P]),
     "dpl_abs_hist_accumulate": (C.c_int, [_P, _I64, _P, _I64, _P, _P, C.c_int, _P, _P]),
+    "dpl_hist_spec_entry_bytes": (_U64, [_I64, C.c_int]),
+    "dpl_minmax_hist_accumulate": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P, _I64, C.c_int, _P, _P]),
+    "dpl_hist_spec_accumulate": (C.c_int, [_P, _P, _I64, _I64, _P, _P, C.c_int, _P, _P, _P]),
+    "dpl_hist_spec_cuts": (C.c_int, [_P, _P, _I64, _I64, _P, _P]),
     "dpl_hist_percentile": (C.c_int, [_P, _P, _P, _I64, C.c_int, _DBL, _P, _P]),
     "dpl_hist_kl": (C.c_int, [_P, _P, _P, _I64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "dpl_octav_init": (C.c_int, [_P, _I64, C.c_int, _P]),

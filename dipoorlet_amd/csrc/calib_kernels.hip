@@ -29,6 +29,35 @@ struct MinMaxOp {
     }
 };
 
+// Workgroup reduction of the lanes' MinMaxOp and the three atomics into the slot's accumulators (s_mn / s_mx / s_nan: one word per wave).
+__device__ __forceinline__ void minmax_commit(const MinMaxOp& op, uint32_t slot, float* s_mn, float* s_mx, uint32_t* s_nan,
+                                              uint32_t* __restrict__ min_enc, uint32_t* __restrict__ max_enc,
+                                              uint32_t* __restrict__ nan_flag) {
+    float mn = wave_min(op.mn), mx = wave_max(op.mx);
+    uint32_t nn = __any(op.nan) ? 1u : 0u;
+    const int w = threadIdx.x / kWave;
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        s_mn[w] = mn;
+        s_mx[w] = mx;
+        s_nan[w] = nn;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int j = 1; j < kBlock / kWave; ++j) {
+            mn = fminf(mn, s_mn[j]);
+            mx = fmaxf(mx, s_mx[j]);
+            nn |= s_nan[j];
+        }
+        if (mn <= mx) {  // false only when the chunk held nothing but NaN
+            atomicMin(min_enc + slot, enc_f32(mn));
+            atomicMax(max_enc + slot, enc_f32(mx));
+        }
+        if (nn) atomicOr(nan_flag + slot, 1u);
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(kBlock) void k_minmax(const dpl_work_item* __restrict__ items,
                                                     const uint32_t* __restrict__ bb,
                                                     const float* const* __restrict__ segs,
@@ -42,29 +71,7 @@ __global__ __launch_bounds__(kBlock) void k_minmax(const dpl_work_item* __restri
         const dpl_work_item it = items[k];
         MinMaxOp op{INFINITY, -INFINITY, 0u};
         stream_span(segs[it.seg] + it.offset, it.count, op);
-        float mn = wave_min(op.mn), mx = wave_max(op.mx);
-        uint32_t nn = __any(op.nan) ? 1u : 0u;
-        const int w = threadIdx.x / kWave;
-        if ((threadIdx.x & (kWave - 1)) == 0) {
-            s_mn[w] = mn;
-            s_mx[w] = mx;
-            s_nan[w] = nn;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int j = 1; j < kBlock / kWave; ++j) {
-                mn = fminf(mn, s_mn[j]);
-                mx = fmaxf(mx, s_mx[j]);
-                nn |= s_nan[j];
-            }
-            if (mn <= mx) {  // false only when the chunk held nothing but NaN
-                atomicMin(min_enc + it.slot, enc_f32(mn));
-                atomicMax(max_enc + it.slot, enc_f32(mx));
-            }
-            if (nn) atomicOr(nan_flag + it.slot, 1u);
-        }
-        __syncthreads();
+        minmax_commit(op, it.slot, s_mn, s_mx, s_nan, min_enc, max_enc, nan_flag);
     }
 }
 
@@ -77,14 +84,18 @@ __global__ void k_minmax_init(uint32_t* mn, uint32_t* mx, uint32_t* nan, int64_t
     }
 }
 
+// The fp32 range of a slot's accumulators: NaN for both when the slot saw a NaN or no data (shared by k_minmax_finalize and the
+// range pass's snapshot, k_hist_snapshot: one piece of device code, so the two cannot disagree in a bit).
+__device__ __forceinline__ void minmax_decode(uint32_t mn, uint32_t mx, uint32_t nan, float& omn, float& omx) {
+    const bool bad = nan != 0u || mn == 0xFFFFFFFFu;
+    omn = bad ? NAN : dec_f32(mn);
+    omx = bad ? NAN : dec_f32(mx);
+}
+
 __global__ void k_minmax_finalize(const uint32_t* mn, const uint32_t* mx, const uint32_t* nan, int64_t n,
                                   float* omn, float* omx) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const bool bad = nan[i] != 0u || mn[i] == 0xFFFFFFFFu;
-        omn[i] = bad ? NAN : dec_f32(mn[i]);
-        omx[i] = bad ? NAN : dec_f32(mx[i]);
-    }
+    if (i < n) minmax_decode(mn[i], mx[i], nan[i], omn[i], omx[i]);
 }
 
 __global__ void k_minmax_encode(const float* mn, const float* mx, int64_t n, uint32_t* emn, uint32_t* emx,
@@ -160,10 +171,7 @@ struct HistOp {
 };
 
 template <bool kFast>
-__device__ __forceinline__ void hist_body(const dpl_work_item& it, const float* const* __restrict__ segs,
-                                          const dpl_hist_range& r, int bins, uint64_t* __restrict__ hist,
-                                          uint32_t* lds, uint32_t* s_nz) {
-    HistOp<kFast> op;
+__device__ __forceinline__ void hist_op_init(HistOp<kFast>& op, const dpl_hist_range& r, int bins, uint32_t* lds) {
     op.lds = lds;
     op.first = r.first;
     op.last = r.last;
@@ -173,8 +181,14 @@ __device__ __forceinline__ void hist_body(const dpl_work_item& it, const float* 
     op.last_bin = bins - 1;
     op.fbins = (float)bins;
     op.nonzero = 0u;
-    stream_span(segs[it.seg] + it.offset, it.count, op);
-    const uint32_t nzw = wave_sum(op.nonzero);
+}
+
+// The workgroup's LDS counters of one item -> the slot's row of `out` (uint64: the accumulated histogram; uint32: a batch's own
+// counts in the range pass, where a tensor of fewer than 2^32 elements cannot overflow a counter).
+template <class Count>
+__device__ __forceinline__ void hist_flush(uint32_t nonzero, const dpl_work_item& it, const dpl_hist_range& r, int bins,
+                                           Count* __restrict__ hist, uint32_t* lds, uint32_t* s_nz) {
+    const uint32_t nzw = wave_sum(nonzero);
     if ((threadIdx.x & (kWave - 1)) == 0) s_nz[threadIdx.x / kWave] = nzw;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -187,11 +201,26 @@ __device__ __forceinline__ void hist_body(const dpl_work_item& it, const float* 
         if (top) atomicAdd(lds + bins - 1, top);
     }
     __syncthreads();
-    uint64_t* __restrict__ out = hist + (uint64_t)it.slot * (uint64_t)bins;
+    Count* __restrict__ out = hist + (uint64_t)it.slot * (uint64_t)bins;
     for (int b = threadIdx.x; b < bins; b += kBlock) {
         const uint32_t c = lds[b];
-        if (c) atomicAdd(reinterpret_cast<unsigned long long*>(out + b), (unsigned long long)c);
+        if (c) {
+            if constexpr (sizeof(Count) == 8)
+                atomicAdd(reinterpret_cast<unsigned long long*>(out + b), (unsigned long long)c);
+            else
+                atomicAdd(out + b, c);
+        }
     }
+}
+
+template <bool kFast>
+__device__ __forceinline__ void hist_body(const dpl_work_item& it, const float* const* __restrict__ segs,
+                                          const dpl_hist_range& r, int bins, uint64_t* __restrict__ hist,
+                                          uint32_t* lds, uint32_t* s_nz) {
+    HistOp<kFast> op;
+    hist_op_init(op, r, bins, lds);
+    stream_span(segs[it.seg] + it.offset, it.count, op);
+    hist_flush(op.nonzero, it, r, bins, hist, lds, s_nz);
 }
 
 __global__ __launch_bounds__(kBlock) void k_abs_hist(const dpl_work_item* __restrict__ items,
@@ -220,13 +249,13 @@ __global__ __launch_bounds__(kBlock) void k_abs_hist(const dpl_work_item* __rest
 __device__ __forceinline__ float py_max(float a, float b) { return (b > a) ? b : a; }  // python max(a, b)
 __device__ __forceinline__ float py_min(float a, float b) { return (b < a) ? b : a; }  // python min(a, b)
 
-__global__ void k_hist_prepare(const float* __restrict__ gmin, const float* __restrict__ gmax, int64_t n, int bins,
-                               dpl_hist_range* __restrict__ out) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// The histogram range of a slot from its fp32 min / max.  A histogram depends on the range through this struct alone, so two
+// ranges that agree byte for byte bin every value alike: what the range pass's speculation rests on (k_hist_snapshot,
+// k_hist_resolve).
+__device__ __forceinline__ dpl_hist_range hist_range_of(float gmin, float gmax, int bins) {
     dpl_hist_range r;
     // forward_net.py:266 — data_max = max(np.max(maxlist), -np.min(minlist))
-    const float dmax = py_max(gmax[i], -gmin[i]);
+    const float dmax = py_max(gmax, -gmin);
     float first = 0.0f, last = dmax;
     r.dmax = dmax;
     r.status = 0u;
@@ -262,7 +291,255 @@ __global__ void k_hist_prepare(const float* __restrict__ gmin, const float* __re
         if (b != bins - 1 && a >= hist_edge(b + 1, r.step, first)) ++b;
         r.zero_bin = (uint32_t)(b < 0 ? 0 : b);
     }
-    out[i] = r;
+    return r;
+}
+
+__global__ void k_hist_prepare(const float* __restrict__ gmin, const float* __restrict__ gmax, int64_t n, int bins,
+                               dpl_hist_range* __restrict__ out) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = hist_range_of(gmin[i], gmax[i], bins);
+}
+
+// ================================================================ K2s: a batch's histogram taken in the RANGE pass
+// numpy's bins depend on dmax over the whole shard, known only after the last batch — but on nothing else, and the running
+// dmax of a tensor stops moving once the batch that holds its extreme has passed.  The range pass therefore histograms every
+// batch against the range its running min / max give (a SNAPSHOT taken before the launch: other workgroups move the live
+// accumulators during it) into a per-batch ledger entry; the histogram pass compares the snapshot with the final range byte for
+// byte (k_hist_resolve), adds the rows that match and reads only the tensors whose guess was wrong (k_abs_hist_rest).  A wrong
+// guess costs what it always cost, so no count can change.  Ledger entry (dpl_hist_spec_entry_bytes):
+//   dpl_hist_range snap[n_slots] | uint32 flags[n_slots] | (16-byte aligned) uint32 counts[n_slots, bins]
+__host__ __device__ inline uint64_t spec_counts_offset(int64_t n_slots) {
+    return (((uint64_t)n_slots * (sizeof(dpl_hist_range) + sizeof(uint32_t))) + 15ull) & ~15ull;
+}
+
+// Snapshot of the provisional ranges + the entry's counts zeroed.  A slot with no data yet, a NaN flag or a range numpy would
+// refuse comes out with status != 0 ("no guess": the fused kernel takes its min / max only and k_hist_resolve never accepts it).
+__global__ __launch_bounds__(kBlock) void k_hist_snapshot(const uint32_t* __restrict__ mn, const uint32_t* __restrict__ mx,
+                                                           const uint32_t* __restrict__ nan, int64_t n, int bins,
+                                                           dpl_hist_range* __restrict__ snap, uint32_t* __restrict__ flags,
+                                                           uint32_t* __restrict__ counts) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    if (i < n) {
+        float gmin, gmax;
+        minmax_decode(mn[i], mx[i], nan[i], gmin, gmax);
+        snap[i] = hist_range_of(gmin, gmax, bins);
+        flags[i] = 0u;
+    }
+    const int64_t total = n * (int64_t)bins;
+    for (int64_t j = i; j < total; j += stride) counts[j] = 0u;
+}
+
+template <bool kFast>
+struct MinMaxHistOp {
+    MinMaxOp m;
+    HistOp<kFast> h;
+    __device__ __forceinline__ void operator()(float x) {
+        m(x);
+        h(x);
+    }
+};
+
+template <bool kFast>
+__device__ __forceinline__ void minmax_hist_body(const dpl_work_item& it, const float* const* __restrict__ segs,
+                                                 const dpl_hist_range& r, int bins, uint32_t* __restrict__ counts,
+                                                 uint32_t* lds, uint32_t* s_nz, MinMaxOp& m) {
+    MinMaxHistOp<kFast> op;
+    op.m = m;
+    hist_op_init(op.h, r, bins, lds);
+    stream_span(segs[it.seg] + it.offset, it.count, op);
+    m = op.m;
+    hist_flush(op.h.nonzero, it, r, bins, counts, lds, s_nz);
+}
+
+// k_minmax and k_abs_hist in one read: min / max / NaN into the accumulators as k_minmax does, counts against snap[slot] into the
+// ledger entry as k_abs_hist does (same HistOp, same flush).
+__global__ __launch_bounds__(kBlock) void k_minmax_hist(const dpl_work_item* __restrict__ items,
+                                                         const uint32_t* __restrict__ bb,
+                                                         const float* const* __restrict__ segs,
+                                                         uint32_t* __restrict__ min_enc, uint32_t* __restrict__ max_enc,
+                                                         uint32_t* __restrict__ nan_flag,
+                                                         const dpl_hist_range* __restrict__ snap, int bins,
+                                                         uint32_t* __restrict__ counts) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_mh[];  // bins + 1 counters, one word per wave, 3 words per wave
+    uint32_t* s_nz = lds_mh + bins + 1;
+    float* s_mn = reinterpret_cast<float*>(s_nz + kBlock / kWave);
+    float* s_mx = s_mn + kBlock / kWave;
+    uint32_t* s_nan = reinterpret_cast<uint32_t*>(s_mx + kBlock / kWave);
+    uint32_t k0, k1;
+    block_items(bb, k0, k1);
+    for (uint32_t k = k0; k < k1; ++k) {
+        const dpl_work_item it = items[k];
+        const dpl_hist_range r = snap[it.slot];
+        MinMaxOp m{INFINITY, -INFINITY, 0u};
+        if (r.status != 0u) {  // no guess for this slot (uniform branch)
+            stream_span(segs[it.seg] + it.offset, it.count, m);
+        } else {
+            for (int b = threadIdx.x; b <= bins; b += kBlock) lds_mh[b] = 0u;
+            __syncthreads();
+            if (r.exact_div)
+                minmax_hist_body<false>(it, segs, r, bins, counts, lds_mh, s_nz, m);
+            else
+                minmax_hist_body<true>(it, segs, r, bins, counts, lds_mh, s_nz, m);
+        }
+        minmax_commit(m, it.slot, s_mn, s_mx, s_nan, min_enc, max_enc, nan_flag);
+    }
+}
+
+// One workgroup per slot: the guess was right iff the snapshot equals the final range in all 32 bytes (a sign-of-zero or NaN
+// difference falls to the safe side) and numpy accepts the range.  flags[t]: 1 = the entry's row is this batch's histogram and
+// has been added; 2 = nothing to count (status != 0: k_abs_hist skips such a tensor too); 0 = to be read.
+// stats (may be null) += {pairs, pairs added, elements, elements added}.
+__global__ __launch_bounds__(kBlock) void k_hist_resolve(const dpl_hist_range* __restrict__ snap,
+                                                          const dpl_hist_range* __restrict__ fin,
+                                                          const uint32_t* __restrict__ counts, const uint64_t* __restrict__ elems,
+                                                          int bins, uint64_t* __restrict__ hist, uint32_t* __restrict__ flags,
+                                                          unsigned long long* __restrict__ stats) {
+    const uint32_t t = blockIdx.x;
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(snap + t);
+    const uint32_t* b = reinterpret_cast<const uint32_t*>(fin + t);
+    bool same = true;
+#pragma unroll
+    for (int w = 0; w < (int)(sizeof(dpl_hist_range) / 4); ++w) same = same && (a[w] == b[w]);
+    const uint32_t status = fin[t].status;
+    const bool valid = same && status == 0u;
+    if (threadIdx.x == 0) {
+        flags[t] = valid ? 1u : (status != 0u ? 2u : 0u);
+        if (stats) {
+            const unsigned long long e = elems[t];
+            atomicAdd(stats + 0, 1ull);
+            atomicAdd(stats + 2, e);
+            if (valid) {
+                atomicAdd(stats + 1, 1ull);
+                atomicAdd(stats + 3, e);
+            }
+        }
+    }
+    if (!valid) return;
+    const uint32_t* __restrict__ row = counts + (uint64_t)t * (uint64_t)bins;
+    uint64_t* __restrict__ out = hist + (uint64_t)t * (uint64_t)bins;
+    for (int j = threadIdx.x; j < bins; j += kBlock) {
+        const uint32_t c = row[j];
+        if (c) out[j] += (uint64_t)c;  // (this workgroup alone touches row t during the launch)
+    }
+}
+
+__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
+    const uint32_t lo = __shfl_up((uint32_t)v, d, kWave), hi = __shfl_up((uint32_t)(v >> 32), d, kWave);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// k_abs_hist over the tensors k_hist_resolve left (flags[t] == 0), BALANCED: the remaining tensors' elements form one stream,
+// workgroup b of G owns [cut(b), cut(b + 1)) of it, cut(b) = floor(total * b / G) rounded down to a multiple of 1024 elements
+// from the start of the tensor it falls in — the cuts dpl_build_balanced_items makes, in closed form, so every workgroup derives
+// its own share from the prefix sums (taken by each workgroup into LDS: T additions) with no list built and no host in between.
+// Tensor t is segment t, slot t, offset 0 (the per-tensor spans of a TensorSetPlan); elems[t] < 2^32.
+// (k_abs_hist_rest below; rest_prefix and rest_cut are its two steps, shared with the test hook k_hist_spec_cuts.)
+//
+// Exclusive prefix sums of the remaining tensors' element counts into P[0 .. n_tensors] (LDS), by the whole workgroup.
+__device__ __forceinline__ void rest_prefix(const uint64_t* __restrict__ elems, const uint32_t* __restrict__ flags, int n_tensors,
+                                            uint64_t* P, uint64_t* s_tot) {
+    const int per = (n_tensors + kBlock - 1) / kBlock;  // consecutive tensors per thread
+    const int t0 = (int)threadIdx.x * per;
+    uint64_t mine = 0;
+    for (int j = 0; j < per; ++j) {
+        const int t = t0 + j;
+        if (t < n_tensors && flags[t] == 0u) mine += elems[t];
+    }
+    uint64_t incl = mine;
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const uint64_t up = shfl_up_u64(incl, o);
+        if (lane >= o) incl += up;
+    }
+    if (lane == kWave - 1) s_tot[wv] = incl;
+    __syncthreads();
+    uint64_t run = incl - mine;
+    for (int w = 0; w < wv; ++w) run += s_tot[w];
+    for (int j = 0; j < per; ++j) {
+        const int t = t0 + j;
+        if (t < n_tensors) {
+            P[t] = run;
+            if (flags[t] == 0u) run += elems[t];
+        }
+    }
+    if (threadIdx.x == kBlock - 1) P[n_tensors] = run;
+    __syncthreads();
+}
+
+// Cut b of G (0 <= b <= G) of a stream of P[n_tensors] > 0 elements, and the tensor it falls in (n_tensors for the end).
+__device__ __forceinline__ void rest_cut(const uint64_t* P, int n_tensors, uint64_t G, uint64_t b, uint64_t& cut, int& at) {
+    const uint64_t total = P[n_tensors], q = total / G, rem = total % G;
+    const uint64_t target = (b >= G) ? total : q * b + (rem * b) / G;  // floor(total * b / G) without a 128-bit product
+    if (target >= total) {
+        cut = total;
+        at = n_tensors;
+        return;
+    }
+    int lo = 1, hi = n_tensors;  // first index in [1, T] with P[index] > target (exists: P[T] = total > target)
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (P[mid] > target) hi = mid; else lo = mid + 1;
+    }
+    at = lo - 1;
+    cut = P[lo - 1] + ((target - P[lo - 1]) & ~1023ull);
+}
+
+__global__ __launch_bounds__(kBlock) void k_abs_hist_rest(const uint64_t* __restrict__ elems, const uint32_t* __restrict__ flags,
+                                                           int n_tensors, const float* const* __restrict__ segs,
+                                                           const dpl_hist_range* __restrict__ ranges, int bins,
+                                                           uint64_t* __restrict__ hist) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_rest[];
+    // layout: uint64 P[n_tensors + 1] | uint64 wave totals [4] | counters [bins + 1] | s_nz [4]
+    uint64_t* P = reinterpret_cast<uint64_t*>(lds_rest);
+    uint64_t* s_tot = P + n_tensors + 1;
+    uint32_t* lds = reinterpret_cast<uint32_t*>(s_tot + kBlock / kWave);
+    uint32_t* s_nz = lds + bins + 1;
+    rest_prefix(elems, flags, n_tensors, P, s_tot);
+    if (P[n_tensors] == 0) return;
+    uint64_t cut[2];
+    int at[2];
+    rest_cut(P, n_tensors, gridDim.x, blockIdx.x, cut[0], at[0]);
+    rest_cut(P, n_tensors, gridDim.x, (uint64_t)blockIdx.x + 1, cut[1], at[1]);
+    uint64_t pos = cut[0];
+    const uint64_t end = cut[1];
+    int t = at[0];
+    while (pos < end) {  // (pos < end <= P[T], so t + 1 <= T below)
+        while (P[t + 1] <= pos) ++t;
+        const uint64_t stop = P[t + 1] < end ? P[t + 1] : end;
+        dpl_work_item it;
+        it.offset = pos - P[t];
+        it.count = (uint32_t)(stop - pos);
+        it.seg = (uint32_t)t;
+        it.slot = (uint32_t)t;
+        it.reserved = 0u;
+        const dpl_hist_range r = ranges[t];  // (status == 0: k_hist_resolve flagged every other tensor)
+        for (int b = threadIdx.x; b <= bins; b += kBlock) lds[b] = 0u;
+        __syncthreads();
+        if (r.exact_div)
+            hist_body<false>(it, segs, r, bins, hist, lds, s_nz);
+        else
+            hist_body<true>(it, segs, r, bins, hist, lds, s_nz);
+        __syncthreads();
+        pos = stop;
+    }
+}
+
+// The cuts k_abs_hist_rest works to, written out (dpl_hist_spec_cuts: what tests hold against tests/hist_spec_model.py).
+__global__ __launch_bounds__(kBlock) void k_hist_spec_cuts(const uint64_t* __restrict__ elems, const uint32_t* __restrict__ flags,
+                                                            int n_tensors, uint64_t* __restrict__ cuts) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_cuts[];
+    uint64_t* P = reinterpret_cast<uint64_t*>(lds_cuts);
+    uint64_t* s_tot = P + n_tensors + 1;
+    rest_prefix(elems, flags, n_tensors, P, s_tot);
+    if (threadIdx.x != 0) return;
+    uint64_t cut = 0;
+    int at = 0;
+    if (P[n_tensors] != 0) rest_cut(P, n_tensors, gridDim.x, blockIdx.x, cut, at);
+    cuts[blockIdx.x] = cut;
+    if (blockIdx.x + 1 == gridDim.x) cuts[gridDim.x] = P[n_tensors];
 }
 
 // The fp32 clip range of a histogram search that ends on bin `found` (-1: none, the range itself): the centre of that bin,
@@ -1064,6 +1341,69 @@ int dpl_abs_hist_accumulate(const dpl_work_item* d_items, int64_t n_items, const
                        ((size_t)bins + 1 + kBlock / kWave) * sizeof(uint32_t), (hipStream_t)s, d_items, d_block_begin,
                        d_seg_ptrs, d_ranges, bins, d_hist);
     DPL_LAUNCH_CHECK("k_abs_hist");
+    return 0;
+}
+
+uint64_t dpl_hist_spec_entry_bytes(int64_t n_slots, int bins) {
+    if (n_slots < 0 || bins < 1 || bins > DPL_MAX_BINS) return 0;
+    return spec_counts_offset(n_slots) + (uint64_t)n_slots * (uint64_t)bins * sizeof(uint32_t);
+}
+
+int dpl_minmax_hist_accumulate(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin,
+                               int64_t n_blocks, const float* const* d_seg_ptrs, uint32_t* d_min_enc, uint32_t* d_max_enc,
+                               uint32_t* d_nan, int64_t n_slots, int bins, void* d_entry, dpl_stream_t s) {
+    if (bins < 1 || bins > DPL_MAX_BINS) return fail_msg("dpl_minmax_hist_accumulate: bins must be in [1, 16384]");
+    if (!d_entry || ((uintptr_t)d_entry & 15u)) return fail_msg("dpl_minmax_hist_accumulate: d_entry must be 16-byte aligned");
+    if (n_slots <= 0 || n_slots > 0x7FFFFFFFll) return fail_msg("dpl_minmax_hist_accumulate: n_slots out of range");
+    if (n_items <= 0) return 0;
+    if (int e = check_blocks("dpl_minmax_hist_accumulate", n_items, d_block_begin, n_blocks)) return e;
+    dpl_hist_range* snap = (dpl_hist_range*)d_entry;
+    uint32_t* flags = (uint32_t*)(snap + n_slots);
+    uint32_t* counts = (uint32_t*)((char*)d_entry + spec_counts_offset(n_slots));
+    int64_t zb = grid_for(n_slots * (int64_t)bins, kBlock * 8);
+    if (zb < grid_for(n_slots, kBlock)) zb = grid_for(n_slots, kBlock);
+    if (zb > 1024) zb = 1024;
+    hipLaunchKernelGGL(k_hist_snapshot, dim3((unsigned)zb), dim3(kBlock), 0, (hipStream_t)s, d_min_enc, d_max_enc, d_nan,
+                       n_slots, bins, snap, flags, counts);
+    DPL_LAUNCH_CHECK("k_hist_snapshot");
+    hipLaunchKernelGGL(k_minmax_hist, dim3((unsigned)n_blocks), dim3(kBlock),
+                       ((size_t)bins + 1 + 4 * (kBlock / kWave)) * sizeof(uint32_t), (hipStream_t)s, d_items, d_block_begin,
+                       d_seg_ptrs, d_min_enc, d_max_enc, d_nan, snap, bins, counts);
+    DPL_LAUNCH_CHECK("k_minmax_hist");
+    return 0;
+}
+
+int dpl_hist_spec_accumulate(void* d_entry, const uint64_t* d_elems, int64_t n_slots, int64_t n_blocks,
+                             const float* const* d_seg_ptrs, const dpl_hist_range* d_ranges, int bins, uint64_t* d_hist,
+                             uint64_t* d_stats, dpl_stream_t s) {
+    if (bins < 1 || bins > DPL_MAX_BINS) return fail_msg("dpl_hist_spec_accumulate: bins must be in [1, 16384]");
+    if (!d_entry || ((uintptr_t)d_entry & 15u)) return fail_msg("dpl_hist_spec_accumulate: d_entry must be 16-byte aligned");
+    if (n_slots <= 0 || n_slots > DPL_HIST_SPEC_MAX_TENSORS)
+        return fail_msg("dpl_hist_spec_accumulate: n_slots must be in [1, DPL_HIST_SPEC_MAX_TENSORS]");
+    if (n_blocks <= 0 || n_blocks > 0x7FFFFFFFll) return fail_msg("dpl_hist_spec_accumulate: n_blocks out of range");
+    dpl_hist_range* snap = (dpl_hist_range*)d_entry;
+    uint32_t* flags = (uint32_t*)(snap + n_slots);
+    const uint32_t* counts = (const uint32_t*)((char*)d_entry + spec_counts_offset(n_slots));
+    hipLaunchKernelGGL(k_hist_resolve, dim3((unsigned)n_slots), dim3(kBlock), 0, (hipStream_t)s, snap, d_ranges, counts, d_elems,
+                       bins, d_hist, flags, (unsigned long long*)d_stats);
+    DPL_LAUNCH_CHECK("k_hist_resolve");
+    const size_t lds = ((size_t)n_slots + 1 + kBlock / kWave) * sizeof(uint64_t) + ((size_t)bins + 1 + kBlock / kWave) * sizeof(uint32_t);
+    hipLaunchKernelGGL(k_abs_hist_rest, dim3((unsigned)n_blocks), dim3(kBlock), lds, (hipStream_t)s, d_elems, flags, (int)n_slots,
+                       d_seg_ptrs, d_ranges, bins, d_hist);
+    DPL_LAUNCH_CHECK("k_abs_hist_rest");
+    return 0;
+}
+
+int dpl_hist_spec_cuts(const void* d_entry, const uint64_t* d_elems, int64_t n_slots, int64_t n_blocks, uint64_t* d_cuts,
+                       dpl_stream_t s) {
+    if (!d_entry || !d_cuts) return fail_msg("dpl_hist_spec_cuts: null argument");
+    if (n_slots <= 0 || n_slots > DPL_HIST_SPEC_MAX_TENSORS)
+        return fail_msg("dpl_hist_spec_cuts: n_slots must be in [1, DPL_HIST_SPEC_MAX_TENSORS]");
+    if (n_blocks <= 0 || n_blocks > 0x7FFFFFFFll) return fail_msg("dpl_hist_spec_cuts: n_blocks out of range");
+    const uint32_t* flags = (const uint32_t*)((const dpl_hist_range*)d_entry + n_slots);
+    hipLaunchKernelGGL(k_hist_spec_cuts, dim3((unsigned)n_blocks), dim3(kBlock),
+                       ((size_t)n_slots + 1 + kBlock / kWave) * sizeof(uint64_t), (hipStream_t)s, d_elems, flags, (int)n_slots, d_cuts);
+    DPL_LAUNCH_CHECK("k_hist_spec_cuts");
     return 0;
 }
 

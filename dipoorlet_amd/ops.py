@@ -9,6 +9,7 @@ lists (forward_net.py:204-235, 252-280, 297-340).
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -102,6 +103,13 @@ class TensorSetPlan:
             self._work[key] = w
         return w
 
+    def elems_device(self):
+        """uint64 [T] on the device: elements of every tensor of a batch (what dpl_hist_spec_accumulate partitions).  Uploaded once
+        per plan, synchronously, like the work sets: a plan's first range pass waits for that copy, no later call does."""
+        if getattr(self, "_elems_dev", None) is None:
+            self._elems_dev = torch.tensor([e * self.batch for e in self.elems], dtype=torch.int64, device=self.device)
+        return self._elems_dev
+
     def octav_scratch(self):
         """(pair_spans, pair_base u64 [B*T], pair_order, list0, list1): where each pair's data lives, and two tail lists of
         the batch's size with the pair regions laid out in pair order (32-element aligned: whole 128-byte lines)."""
@@ -166,7 +174,12 @@ class TensorSetPlan:
         """A tensor set a caller keeps RESIDENT and launches over again and again (pass 2 of `-A hist`, bench.py's pools):
         validated once, then held — the BoundSet owns references to the tensors, so their memory cannot be handed to another
         tensor while it lives, and a launch over it costs no per-tensor checks (557 tensors of a ViT-B/16 set: 0.1 - 0.2 ms of
-        host time per launch otherwise, more than the host has to spare per batch)."""
+        host time per launch otherwise, more than the host has to spare per batch).
+
+        CONTRACT: the contents of a bound set are taken as UNCHANGED between its range pass (CalibAccumulators.minmax_accumulate)
+        and its histogram pass (abs_hist_accumulate) on one accumulator: the range pass already histograms the set against the
+        running range, and the histogram pass does not read a tensor again whose guess turned out right.  A caller that rewrites
+        bound tensors in place between the two builds its accumulator with speculate=False."""
         if isinstance(tensors, BoundSet):
             if tensors.plan is not self:
                 raise _hip.DipoorletHipError("this tensor set is bound to another plan")
@@ -307,7 +320,7 @@ class OctavTailPlan:
 class BoundSet:
     """A validated, resident tensor set of one plan (TensorSetPlan.bind): the tensors, kept alive, and their device pointer
     table.  Accepted wherever a list of the set's tensors is."""
-    __slots__ = ("plan", "tensors", "table", "_host")
+    __slots__ = ("plan", "tensors", "table", "_host", "__weakref__")   # (weakly referenced by CalibAccumulators' ledger)
 
     def __init__(self, plan, tensors, table, host):
         self.plan, self.tensors, self.table, self._host = plan, tensors, table, host
@@ -323,9 +336,28 @@ class BoundSet:
 
 
 class CalibAccumulators:
-    """Persistent per-tensor statistics on the device."""
+    """Persistent per-tensor statistics on the device.
 
-    def __init__(self, n_slots, device, bins=2048):
+    speculate=True: the range pass over a BoundSet (per_image=False) also histograms the batch, against the range the running
+    min / max give before that launch, into a ledger entry of this accumulator ([T, bins] uint32 counts per bound set); the
+    histogram pass over the same BoundSet adds the rows whose guessed range turned out to be the final one — byte for byte, so the
+    counts are the ones a second read would give — and reads only the other tensors (dpl_hist_spec_accumulate).  A running
+    dmax stops moving once the batch that holds the tensor's extreme has passed, so about half of all (batch, tensor) pairs of a
+    shard need no second read.  The contents of a bound set must not change between the two passes (TensorSetPlan.bind);
+    speculate=False for a caller that rewrites bound tensors in place.
+
+    The ledger: one entry per bound set (a later range pass over the same set overwrites it), emptied by reset_minmax(), left
+    alone by set_minmax / hist_prepare (merged ranges decide by the same byte comparison).  Entries come from a slab this object
+    holds for its lifetime and reuses — after the first sweep a call allocates nothing, and after a plan's first range pass (which
+    uploads the plan's work set and element counts once) none waits for the device — and the ledger refers to a bound set
+    weakly: dropping the set frees its tensors.  A plan does not speculate when an entry (T * bins * 4 bytes) would exceed
+    1 / SPEC_MAX_SHARE of the batch's bytes (the zeroing and the flush of the entry would no longer be small against the read),
+    when a tensor of the batch has 2^32 elements or more (uint32 counts), above _hip.HIST_SPEC_MAX_TENSORS tensors, or in the
+    chunk_elems form: it then runs the plain range pass.  spec_stats() / spec_flags() say what was skipped."""
+
+    SPEC_MAX_SHARE = 64     # an entry may take at most 1/64 of the bytes of the batch it describes
+
+    def __init__(self, n_slots, device, bins=2048, speculate=True):
         self.n = int(n_slots)
         self.device = torch.device(device)
         self.bins = int(bins)
@@ -338,20 +370,111 @@ class CalibAccumulators:
         self.gmax = torch.empty(self.n, dtype=torch.float32, device=self.device)
         self.hist = None
         self.ranges = None
+        self.speculate = bool(speculate)
+        self._ledger = {}       # id(bound set) -> (weak reference to it, entry, T)
+        self._slab = []         # entries not in use: held for this object's lifetime, never returned to the allocator in between
+        self._spec_stats = torch.zeros(4, dtype=torch.int64, device=self.device) if self.speculate else None
         self.reset_minmax()
 
     def reset_minmax(self):
+        """Running min / max back to 'no data'; the ledger of range-pass histograms is emptied (its entries go back to the slab)."""
+        for _, entry, _ in self._ledger.values():
+            self._slab.append(entry)
+        self._ledger.clear()
         _hip.check(_hip.lib().dpl_minmax_init(_ptr(self.min_enc), _ptr(self.max_enc), _ptr(self.nan), self.n,
                                               _stream()), "dpl_minmax_init")
+
+    # ---- the ledger
+    def will_speculate(self, plan, tensors, per_image=False):
+        """Whether minmax_accumulate(plan, tensors, per_image) takes the fused path (the class docstring gives the conditions)."""
+        return (self.speculate and isinstance(tensors, BoundSet) and not per_image and plan.chunk is None
+                and 0 < plan.T <= min(self.n, _hip.HIST_SPEC_MAX_TENSORS)
+                and max(plan.elems) * plan.batch < (1 << 32)
+                and plan.T * self.bins * 4 * self.SPEC_MAX_SHARE <= plan.total * 4)
+
+    def _entry_for(self, bound):
+        rec = self._ledger.get(id(bound))
+        if rec is not None and rec[0]() is bound:
+            return rec[1]
+        # (An entry may be used on another stream than the one current when it was allocated: the CLI's range pass runs on a side
+        # stream, its histogram pass on the caller's, ordered by main.wait_stream(side).  That is safe because the slab holds every
+        # entry for this object's lifetime — no block goes back to the allocator while work on either stream may still be queued;
+        # whoever lets an accumulator go right behind a histogram pass must synchronise first, as reading acc.hist does.)
+        if self._slab:
+            entry = self._slab.pop()
+        else:
+            nbytes = int(_hip.lib().dpl_hist_spec_entry_bytes(self.n, self.bins))
+            entry = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        key, slab, ledger = id(bound), self._slab, self._ledger
+
+        def dropped(ref):           # the bound set died: its entry is free again (the ledger never kept the set alive)
+            rec = ledger.get(key)
+            if rec is not None and rec[0] is ref:
+                del ledger[key]
+                slab.append(rec[1])
+        self._ledger[key] = (weakref.ref(bound, dropped), entry, bound.plan.T)
+        return entry
+
+    def _entry_of(self, plan, tensors):
+        if not isinstance(tensors, BoundSet):
+            return None
+        rec = self._ledger.get(id(tensors))
+        if rec is None or rec[0]() is not tensors or rec[2] != plan.T:
+            return None
+        return rec[1]
+
+    def spec_stats(self, reset=False):
+        """HOST (synchronises): what the histogram passes so far skipped — {'pairs', 'pairs_skipped', 'elements',
+        'elements_skipped'} over the (batch, tensor) pairs of every abs_hist_accumulate call that found a ledger entry."""
+        v = [0, 0, 0, 0] if self._spec_stats is None else [int(x) for x in self._spec_stats.cpu().tolist()]
+        if reset and self._spec_stats is not None:
+            self._spec_stats.zero_()
+        return dict(zip(("pairs", "pairs_skipped", "elements", "elements_skipped"), v))
+
+    def spec_flags(self, tensors):
+        """HOST (synchronises): per tensor what the last abs_hist_accumulate over this bound set did — 1: the range pass's row was
+        added and the tensor not read, 2: nothing to count (range status != 0), 0: read — or None when the set has no entry."""
+        rec = self._ledger.get(id(tensors))
+        if rec is None or rec[0]() is not tensors:
+            return None
+        T = rec[2]      # (the entry is laid out for the T slots of the set's plan: dpl_hist_spec_entry_bytes)
+        off = T * C.sizeof(_hip.HistRange)
+        return rec[1][off:off + 4 * T].view(torch.int32).cpu()
+
+    def spec_cuts(self, plan, tensors):
+        """HOST (synchronises; a test hook): the n_blocks + 1 cuts the histogram pass's kernel works to for the flags this bound
+        set's entry holds now, as positions in the stream of the tensors still to be read (tests/hist_spec_model.py: cuts)."""
+        entry = self._entry_of(plan, tensors)
+        if entry is None:
+            return None
+        nb = plan.work("hist").n_blocks
+        out = torch.empty(nb + 1, dtype=torch.int64, device=self.device)
+        _hip.check(_hip.lib().dpl_hist_spec_cuts(_ptr(entry), _ptr(plan.elems_device()), plan.T, nb, _ptr(out), _stream()),
+                   "dpl_hist_spec_cuts")
+        return out.cpu()
 
     # ---- pass 1
     def minmax_accumulate(self, plan, tensors, per_image=False):
         """per_image=False: slot = tensor (n_slots = T).  per_image=True: slot = image * T + tensor
-        (n_slots = B * T), the reference's one-entry-per-image lists."""
+        (n_slots = B * T), the reference's one-entry-per-image lists.
+        A BoundSet with per_image=False also leaves the batch's histogram against the running range in the ledger (speculate)."""
         tab = plan.seg_table(tensors)
-        w = plan.work("minmax", per_image)
         if self.n < (plan.n_pairs if per_image else plan.T):
             raise _hip.DipoorletHipError("accumulator has fewer slots than the plan addresses")
+        if self.will_speculate(plan, tensors, per_image):
+            w = plan.work("hist")
+            entry = self._entry_for(tensors)
+            plan.elems_device()     # (uploaded with the plan's first range pass, not in the middle of the histogram pass)
+            _hip.check(_hip.lib().dpl_minmax_hist_accumulate(*w.args(), _ptr(tab), _ptr(self.min_enc), _ptr(self.max_enc),
+                                                             _ptr(self.nan), plan.T, self.bins, _ptr(entry), _stream()),
+                       "dpl_minmax_hist_accumulate")
+            return
+        if isinstance(tensors, BoundSet):       # (a plain range pass over a set that has an entry: the entry no longer describes it)
+            rec = self._ledger.get(id(tensors))
+            if rec is not None and rec[0]() is tensors:
+                del self._ledger[id(tensors)]
+                self._slab.append(rec[1])
+        w = plan.work("minmax", per_image)
         _hip.check(_hip.lib().dpl_minmax_accumulate(*w.args(), _ptr(tab), _ptr(self.min_enc), _ptr(self.max_enc),
                                                     _ptr(self.nan), _stream()), "dpl_minmax_accumulate")
 
@@ -381,8 +504,16 @@ class CalibAccumulators:
                                                _ptr(self.ranges), _stream()), "dpl_hist_prepare")
 
     def abs_hist_accumulate(self, plan, tensors):
+        """hist += the |x| histogram of this batch.  A BoundSet whose range pass left a ledger entry is read only where the entry's
+        guessed range is not the final one (the same counts either way)."""
         tab = plan.seg_table(tensors)
         w = plan.work("hist")
+        entry = self._entry_of(plan, tensors)
+        if entry is not None:
+            _hip.check(_hip.lib().dpl_hist_spec_accumulate(_ptr(entry), _ptr(plan.elems_device()), plan.T, w.n_blocks, _ptr(tab),
+                                                           _ptr(self.ranges), self.bins, _ptr(self.hist), _ptr(self._spec_stats),
+                                                           _stream()), "dpl_hist_spec_accumulate")
+            return
         _hip.check(_hip.lib().dpl_abs_hist_accumulate(*w.args(), _ptr(tab), _ptr(self.ranges), self.bins,
                                                       _ptr(self.hist), _stream()), "dpl_abs_hist_accumulate")
 

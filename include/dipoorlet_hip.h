@@ -25,8 +25,10 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 22 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl */
+#define DPL_ABI_VERSION 23 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+                              23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
+#define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
 typedef void* dpl_stream_t; /* hipStream_t */
 
@@ -121,6 +123,33 @@ int dpl_hist_prepare(const float* d_min, const float* d_max, int64_t n_slots, in
 int dpl_abs_hist_accumulate(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin,
                             int64_t n_blocks, const float* const* d_seg_ptrs, const dpl_hist_range* d_ranges,
                             int bins, uint64_t* d_hist, dpl_stream_t s);
+/* ---- the same histogram with the second read skipped where the range pass guessed the range right.  np.histogram's bins depend on the
+ *      shard's final dmax alone (dpl_hist_range), and a tensor's running dmax stops moving once the batch holding its extreme has
+ *      passed.  dpl_minmax_hist_accumulate is dpl_minmax_accumulate that ALSO histograms the batch against the range the accumulators
+ *      give BEFORE the launch (a snapshot: dpl_minmax_finalize + dpl_hist_prepare of the running values, through the same device
+ *      code) into a caller-owned ledger entry; dpl_hist_spec_accumulate is dpl_abs_hist_accumulate for a batch that has such an entry:
+ *      d_hist[t, :] += the entry's row where the snapshot equals d_ranges[t] in all 32 bytes and its status is 0, the kernel of
+ *      dpl_abs_hist_accumulate over the other tensors only (a balanced partition of what remains, derived on the device; no host
+ *      round trip).  The counts are the ones dpl_abs_hist_accumulate gives, provided the batch's data did not change in between.
+ *      d_entry: dpl_hist_spec_entry_bytes(n_slots, bins) bytes, 16-byte aligned:
+ *          dpl_hist_range snapshot[n_slots] | uint32 flags[n_slots] | pad to 16 | uint32 counts[n_slots, bins]
+ *      flags (written by dpl_hist_spec_accumulate): 1 = row added, the tensor was not read; 2 = status != 0, nothing to count; 0 = read.
+ *      The items of dpl_minmax_hist_accumulate are any partition with slot < n_slots and fewer than 2^32 elements per slot.
+ *      dpl_hist_spec_accumulate takes the per-tensor form: tensor t = segment t = slot t from offset 0, d_elems[t] (< 2^32) elements,
+ *      n_slots <= DPL_HIST_SPEC_MAX_TENSORS, n_blocks workgroups.  d_stats (may be NULL): uint64 [4] += {tensors, tensors not read,
+ *      elements, elements not read}. */
+uint64_t dpl_hist_spec_entry_bytes(int64_t n_slots, int bins);
+int dpl_minmax_hist_accumulate(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin,
+                               int64_t n_blocks, const float* const* d_seg_ptrs, uint32_t* d_min_enc, uint32_t* d_max_enc,
+                               uint32_t* d_nan, int64_t n_slots, int bins, void* d_entry, dpl_stream_t s);
+int dpl_hist_spec_accumulate(void* d_entry, const uint64_t* d_elems, int64_t n_slots, int64_t n_blocks,
+                             const float* const* d_seg_ptrs, const dpl_hist_range* d_ranges, int bins, uint64_t* d_hist,
+                             uint64_t* d_stats, dpl_stream_t s);
+/* TEST HOOK, not part of the stable interface (it may change or go with the kernel it describes): the cuts
+ * dpl_hist_spec_accumulate's kernel works to for the flags the entry holds now — d_cuts uint64 [n_blocks + 1],
+ * positions in the stream of the tensors still to be read (flags == 0), d_cuts[n_blocks] = its length. */
+int dpl_hist_spec_cuts(const void* d_entry, const uint64_t* d_elems, int64_t n_slots, int64_t n_blocks, uint64_t* d_cuts,
+                       dpl_stream_t s);
 /* ---- percentile clip: replaces the python loop of basic_algorithm.py:40-53. d_clip: fp32 [n_slots,2]. */
 int dpl_hist_percentile(const uint64_t* d_hist, const float* d_min, const float* d_max, int64_t n_slots,
                         int bins, double threshold, float* d_clip, dpl_stream_t s);
