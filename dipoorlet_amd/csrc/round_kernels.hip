@@ -14,7 +14,8 @@
 //                  (sparse_quant_layer.py:9-66, sparse_quant.py:107-109)
 //
 // All of it is launch- and HBM-bound elementwise work: 16 B per lane where the layout allows, fp32 arithmetic in
-// the reference's operation order (IEEE divide, no FMA contraction), fp64 block-reduced loss sums.
+// the reference's operation order (IEEE divide, no FMA contraction; the two scaled adds of SGD are fmaf because torch's
+// add(alpha=) is one), NaN handed on as torch.max / min / clamp / relu do, fp64 block-reduced loss sums.
 #include "common.hpp"
 
 #pragma clang fp contract(off)
@@ -33,17 +34,20 @@ __device__ __forceinline__ RectSig rect_sigmoid(float a) {
     const float sg = __fdiv_rn(1.0f, 1.0f + expf(-a));
     const float hr = kZetaMinusGamma * sg + kGamma;
     RectSig r;
-    r.h = fminf(fmaxf(hr, 0.0f), 1.0f);
-    r.dh = (hr >= 0.0f && hr <= 1.0f) ? (kZetaMinusGamma * (1.0f - sg)) * sg : 0.0f;
+    // comparisons and selects, not fminf / fmaxf: a NaN mask stays NaN in h (torch.clamp) and in dh (autograd's
+    // 0 * sigmoid'(NaN)), as fq_pre keeps it
+    r.h = hr < 0.0f ? 0.0f : (hr > 1.0f ? 1.0f : hr);
+    r.dh = (hr >= 0.0f && hr <= 1.0f) ? (kZetaMinusGamma * (1.0f - sg)) * sg : (hr != hr ? hr : 0.0f);
     return r;
 }
 
-// torch.maximum / minimum backward: the full gradient to the larger (smaller) side, half of it on a tie.
+// torch.maximum / minimum backward: the full gradient to the larger (smaller) side, half of it on a tie.  As in torch
+// (where(a == b, grad / 2, grad).masked_fill(a < b, 0)) a NaN passes through the value and takes the whole gradient.
 __device__ __forceinline__ float clamp_pass(float v0, float qmin, float qmax, float& v_out) {
-    const float f_lo = v0 > qmin ? 1.0f : (v0 == qmin ? 0.5f : 0.0f);
-    const float v1 = fmaxf(v0, qmin);
-    const float f_hi = v1 < qmax ? 1.0f : (v1 == qmax ? 0.5f : 0.0f);
-    v_out = fminf(v1, qmax);
+    const float f_lo = v0 == qmin ? 0.5f : (v0 < qmin ? 0.0f : 1.0f);
+    const float v1 = v0 < qmin ? qmin : v0;
+    const float f_hi = v1 == qmax ? 0.5f : (v1 > qmax ? 0.0f : 1.0f);
+    v_out = v1 > qmax ? qmax : v1;
     return f_lo * f_hi;
 }
 
@@ -210,10 +214,11 @@ __global__ __launch_bounds__(kBlock) void k_sparse_step(const float* __restrict_
         float g = __fdiv_rn(((grad_qw[i] * sp.grad_scale) * s) * pass, s) * mk;
         if (grad_w) grad_w[i] = g;
         if (sp.update) {
-            if (sp.weight_decay != 0.0f) g = g + sp.weight_decay * wi;
+            // torch's add(other, alpha) is one fused multiply-add per element; mul_ then add_ are two roundings
+            if (sp.weight_decay != 0.0f) g = fmaf(sp.weight_decay, wi, g);
             const float b = sp.first ? g : buf[i] * sp.momentum + g;
             buf[i] = b;
-            w[i] = wi + (-sp.lr) * b;
+            w[i] = fmaf(-sp.lr, b, wi);
         }
     }
 }
@@ -226,10 +231,10 @@ __global__ __launch_bounds__(kBlock) void k_l2_loss(const float* __restrict__ z,
     __shared__ double s_red[kBlock / kWave];
     double part = 0.0;
     auto one = [&](float zi, float ti) -> float {
-        const float y = relu ? fmaxf(zi, 0.0f) : zi;
+        const float y = (relu && zi < 0.0f) ? 0.0f : zi;   // NaN stays NaN (torch.relu), as does its gradient
         const float d = y - ti;
         part += (double)(d * d);
-        return (relu && !(zi > 0.0f)) ? 0.0f : coef * d;
+        return (relu && zi <= 0.0f) ? 0.0f : coef * d;
     };
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     if (kVec) {
@@ -287,7 +292,8 @@ __global__ __launch_bounds__(kBlock) void k_acti_drop_fwd(const float* __restric
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         const float xi = x[i];
         float q = rintf(__fdiv_rn(xi, scale));
-        q = fminf(fmaxf(q, qmin), qmax) * scale;
+        q = q < qmin ? qmin : q;   // torch.max / torch.min: a NaN activation stays NaN
+        q = (q > qmax ? qmax : q) * scale;
         y[i] = (!r || r[i] < prob) ? q : xi;
     }
 }
@@ -307,8 +313,9 @@ inline unsigned blocks_for(uint64_t n, int per_thread) {
 }
 
 int check_channels(const char* who, int64_t n, int64_t n_channels, int64_t inner) {
-    if (n <= 0 || n > 0xFFFFFFFFll) {
-        snprintf(g_err, sizeof(g_err), "%s: n must be in [1, 2^32)", who);
+    // the kernels index in 32 bits with a stride of up to 2^20: past 2^32 - 2^20 the loop index would wrap
+    if (n <= 0 || n > (1ll << 32) - (1ll << 20)) {
+        snprintf(g_err, sizeof(g_err), "%s: n must be in [1, 2^32 - 2^20]", who);
         return -2;
     }
     if (n_channels < 1 || inner < 1 || (n_channels > 1 && n_channels * inner != n)) {

@@ -426,29 +426,32 @@ typedef struct dpl_round_sched {
 int dpl_round_sched_advance(dpl_round_sched* d_sched, int32_t t_max, double lr, double adam_beta1, double adam_beta2,
                             dpl_stream_t s);
 
-/* wfloor = floor(w / scale);  alpha = -log((zeta - gamma) / (w / scale - wfloor - gamma) - 1) */
+/* wfloor = floor(w / scale);  alpha = -log((zeta - gamma) / (w / scale - wfloor - gamma) - 1)
+ * n in [1, 2^32 - 2^20] (32-bit indices, grid stride up to 2^20), else -2: the same for the four calls below. */
 int dpl_round_init(const float* d_w, const float* d_scale, int64_t n, int64_t n_channels, int64_t inner,
                    float* d_wfloor, float* d_alpha, dpl_stream_t s);
-/* qw = clamp?(wfloor + h(alpha)) * scale;  h = rectified sigmoid (soft) or (alpha >= 0) (hard) */
+/* qw = clamp?(wfloor + h(alpha)) * scale;  h = rectified sigmoid (soft) or (alpha >= 0) (hard).
+ * n in [1, 2^32 - 2^20]. */
 int dpl_round_quant(const float* d_wfloor, const float* d_alpha, const float* d_scale, const float* d_qmin,
                     const float* d_qmax, int64_t n, int64_t n_channels, int64_t inner, int clamp, int soft,
                     float* d_qw, dpl_stream_t s);
 /* One learning step in one pass: g = dL/d(alpha) from d_grad_qw (may be null) through the soft quantiser, plus
  * the regulariser's gradient; *d_reg_loss += lambda * sum(1 - |2h - 1|^beta) (may be null); Adam update of
  * alpha / m / v in place; d_qw_next (may be null) = the soft-quantised weight at the updated alpha;
- * d_grad_alpha (may be null) receives g. */
+ * d_grad_alpha (may be null) receives g.  n in [1, 2^32 - 2^20]. */
 int dpl_round_step(const float* d_grad_qw, const float* d_wfloor, float* d_alpha, float* d_m, float* d_v,
                    const float* d_scale, const float* d_qmin, const float* d_qmax, int64_t n, int64_t n_channels,
                    int64_t inner, const dpl_round_step_params* p, const dpl_round_sched* d_sched, float* d_qw_next,
                    float* d_grad_alpha, double* d_reg_loss, dpl_stream_t s);
 /* Sparse + quantised weight with a straight-through round (sparse_quant_layer.py:9-29, 61-66):
- * qw = clamp?(rint(w * mask / scale)) * scale; d_mask (0 / 1 per weight) may be null. */
+ * qw = clamp?(rint(w * mask / scale)) * scale; d_mask (0 / 1 per weight) may be null.  n in [1, 2^32 - 2^20]. */
 int dpl_sparse_quant(const float* d_w, const float* d_mask, const float* d_scale, const float* d_qmin,
                      const float* d_qmax, int64_t n, int64_t n_channels, int64_t inner, int clamp, float* d_qw,
                      dpl_stream_t s);
 /* Its gradient fused with torch.optim.SGD's update (sparse_quant.py:107-109: momentum, weight decay):
  * g = ((dL/dqw * grad_scale * scale) * clamp_pass) / scale * mask; d_grad_w (may be null) receives g; when `update`:
- * g += weight_decay * w; buf = first ? g : momentum * buf + g; w -= lr * buf. */
+ * g += weight_decay * w; buf = first ? g : momentum * buf + g; w -= lr * buf (the two scaled adds fused, as
+ * torch's add(alpha=) is).  n in [1, 2^32 - 2^20]. */
 int dpl_sparse_step(const float* d_grad_qw, float* d_w, const float* d_mask, float* d_momentum_buf,
                     const float* d_scale, const float* d_qmin, const float* d_qmax, int64_t n, int64_t n_channels,
                     int64_t inner, int clamp, float grad_scale, float lr, float momentum, float weight_decay, int first,
