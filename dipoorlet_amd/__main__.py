@@ -1,5 +1,5 @@
 """`python -m dipoorlet_amd -M model.onnx -I calib_dir -N 1024 -A hist -D trt` — the reference's CLI
-(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, is this project's addition).
+(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, and `-D ocp_fp8`, static OCP FP8 E4M3 scales, are this project's additions).
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
@@ -34,8 +34,8 @@ def build_parser():
                    help="minmax / hist: bit-exact clip ranges; mse (OCTAV): within 1e-5 * max(1, |ref|) of the reference's, repeating "
                         "to about 1e-6 relative from run to run (DPL_OCTAV_FORM=bracket: the bit-stable two-read form); kl: entropy "
                         "search on the |x| histogram (not in the reference; honours --bins, ignores --threshold)")
-    p.add_argument("-D", "--deploy", choices=["trt", "stpu", "magicmind", "rv", "atlas", "snpe", "ti", "imx"],
-                   required=True)
+    p.add_argument("-D", "--deploy", choices=["trt", "stpu", "magicmind", "rv", "atlas", "snpe", "ti", "imx", "ocp_fp8"],
+                   required=True, help="ocp_fp8 (not in the reference): static OCP FP8 E4M3 scales, clip / 448; with -A minmax or -A hist")
     p.add_argument("--bins", default=2048, type=int)  # the reference omits type= and crashes on a CLI value
     p.add_argument("--threshold", default=0.99999, type=float)
     p.add_argument("--ada_bs", type=int, default=64)
@@ -59,6 +59,21 @@ def build_parser():
                         "note: --update_bn also keeps the BN nodes, which it re-estimates — unlike the reference, whose "
                         "onnxsim pass has fused them before --update_bn runs)")
     return p
+
+
+def check_args(args):
+    """What a platform cannot do, said before any device work.  A floating-point grid (`-D ocp_fp8`) is reached through the
+    FakeQuant nodes only: the clip sweeps that know nothing of the grid and the transforms that run the fake-quantised forward
+    work unchanged; what assumes or learns an integer grid does not."""
+    from .platform_settings import platform_setting_table
+    if not platform_setting_table[args.deploy]["qi_params"]["type"].startswith("Float8"):
+        return
+    bad = [flag for flag, on in (("-A mse", args.act_quant == "mse"),        # OCTAV's fixed point assumes a uniform grid
+                                 ("-A kl", args.act_quant == "kl"),          # its levels are integer levels
+                                 ("--adaround", args.adaround), ("--brecq", args.brecq), ("--sparse", args.sparse)) if on]
+    if bad:     # (the three transforms learn integer rounding)
+        raise ValueError(f"-D {args.deploy} is a floating-point grid: {', '.join(bad)} not supported (they assume or learn an integer "
+                         "grid).  Supported: -A minmax, -A hist, --bc, --we, --update_bn and profiling")
 
 
 def main(argv=None):
@@ -107,6 +122,7 @@ def _main(argv=None):
     mark("main:enter")
     age_at_enter = _process_age_s()       # interpreter + imports (torch, the package) up to here
     args = build_parser().parse_args(argv)
+    check_args(args)
     if args.quant_format == "QOP":
         raise SystemExit("--quant_format QOP (onnxruntime's QOperator export, dipoorlet/utils.py:415-435) is not built: "
                          "use the default QDQ format")

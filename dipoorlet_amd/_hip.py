@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPL_LIB: another build of the same sources (the host-sanitizer build of scripts/asan_host_check.sh); never a different code path
 LIB_PATH = os.environ.get("DPL_LIB") or os.path.join(_HERE, "csrc", "libdipoorlet_hip.so")
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 MAX_BINS = 16384
 HIST_SPEC_MAX_TENSORS = 2048
 
@@ -128,6 +128,8 @@ SIGNATURES = {
     "dpl_fake_quant": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _I64, _I32, _I32, _P]),
     "dpl_fake_quant_pre": (C.c_int, [_I32, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I32, _I32, _P]),
     "dpl_fake_quant_items": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P]),
+    "dpl_fake_quant_fp8": (C.c_int, [_I32, _P, _P, _P, _I64, _P, _I64, _I64, _P]),
+    "dpl_fake_quant_fp8_items": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P]),
     "dpl_cos_accumulate": (C.c_int, [_P, _P, _I64, _P, _I64, _P]),
     "dpl_channel_diff_sum": (C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
     "dpl_cos_items_accumulate": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P]),

@@ -785,9 +785,41 @@ __device__ __forceinline__ float fq_one(float x, float scale, float zp, float ql
     return __fmul_rn(__fsub_rn(q, zp), scale);
 }
 
+// The OCP FP8 E4M3 ("e4m3fn": bias 7, 3 mantissa bits, subnormal step 2^-9, largest finite 448, no infinities) Q/DQ of one value:
+// the nearest e4m3fn value of v as fp32, round half to even (subnormals too), SATURATING (|v| > 448 and +-inf give +-448: ONNX
+// QuantizeLinear, saturate = 1), NaN stays NaN, the sign of zero is kept.  In fp32 arithmetic on the value's own exponent bits: a
+// value of binade e lies on a grid of step 2^(max(e, -6) - 3); |v| times the inverse step is exact (a power of two), v_rndne
+// rounds it half to even, times the step is exact again (a carry into the next binade lands on a value of the format).  Every
+// fp32 subnormal rounds to zero whether or not the multiply flushes it.  gfx950's v_cvt_pk_fp8_f32 / v_cvt_f32_fp8 would do the
+// same in two instructions; how they round subnormals and what they return above 448 and for NaN has not been measured on this
+// hardware (scripts/fp8_cvt_probe.hip measures it), and the kernel is bound by its 8 B per element, not by these
+// eight operations.
+__device__ __forceinline__ float e4m3_round(float v) {
+    const float a = fminf(fabsf(v), 448.f);            // saturate (a NaN comes out finite here: routed below)
+    uint32_t e = __float_as_uint(a) >> 23;             // biased exponent: binade e - 127
+    e = e < 121u ? 121u : e;                           // below 2^-6 the step stays 2^-9
+    const float step = __uint_as_float((e - 3u) << 23), inv = __uint_as_float((257u - e) << 23);      // 2^(e-130), 2^(130-e)
+    const float r = copysignf(__fmul_rn(rintf(__fmul_rn(a, inv)), step), v);
+    return v != v ? v : r;
+}
+
+// The number format of the Q/DQ pair, a compile-time parameter of the streaming skeleton below beside PRE: kFqFmtInt the integer
+// grid of fq_one (scale, zero point, [qlo, qhi]); kFqFmtE4M3 y = fl32(e4m3_round(fl32(x / scale)) * scale) — the same shape, two
+// single fp32 operations around the rounding; zero point / qlo / qhi are not read (zp_p may be null).
+enum { kFqFmtInt = 0, kFqFmtE4M3 = 1 };
+template <int FMT>
+__device__ __forceinline__ float fq_elem(float x, float scale, float zp, float qlo, float qhi) {
+    if (FMT == kFqFmtE4M3) return __fmul_rn(e4m3_round(__fdiv_rn(x, scale)), scale);
+    return fq_one(x, scale, zp, qlo, qhi);
+}
+template <int FMT>
+__device__ __forceinline__ float fq_zp(const int32_t* __restrict__ zp_p, uint32_t c) {
+    return FMT == kFqFmtInt ? (float)zp_p[c] : 0.f;
+}
+
 // What the producer of a fake-quantised tensor would have written, applied on the way in (the reference's merge-ReLU rule puts
 // most activation Q/DQ pairs directly behind a ReLU, quantize.py:50-55): kFqPreNone x; kFqPreRelu torch.relu(x) = np.maximum(x, 0)
-// (NaN stays NaN; -0 and +0 quantise alike); kFqPreAddRelu relu(x + x2), the residual Add of a bottleneck and its ReLU (one fp32
+// (NaN stays NaN; -0 and +0 quantise alike on an integer grid, FP8 keeps the zero's sign); kFqPreAddRelu relu(x + x2), the residual Add of a bottleneck and its ReLU (one fp32
 // addition, rounded to nearest, as torch.add).
 enum { kFqPreNone = 0, kFqPreRelu = 1, kFqPreAddRelu = 2 };
 template <int PRE>
@@ -802,7 +834,7 @@ __device__ __forceinline__ float fq_pre(float x, float x2) {
 // 16-byte vectors per lane in flight, non-temporal loads and stores (each byte is touched once).  The channel of a vector needs no
 // division in the loop: a lane's (column, channel) advance by a constant per step — 1024 elements = (1024 / inner) rows and
 // (1024 % inner) columns, both computed once per chunk on the scalar unit — with one conditional wrap each.
-template <int PRE>
+template <int PRE, int FMT>
 __device__ __forceinline__ void fq_span(const float* __restrict__ x, const float* __restrict__ x2, float* __restrict__ y, uint64_t e0,
                                         uint32_t cnt, const float* __restrict__ scale_p, const int32_t* __restrict__ zp_p,
                                         uint32_t n_channels, uint32_t inner, float qlo, float qhi) {
@@ -819,7 +851,7 @@ __device__ __forceinline__ void fq_span(const float* __restrict__ x, const float
         uint32_t col = (uint32_t)(e % inner), c = (uint32_t)((e / inner) % n_channels);
         const uint32_t step_cols = (uint32_t)kBlock % inner, step_ch = ((uint32_t)kBlock / inner) % n_channels;
         for (uint32_t i = tid; i < cnt; i += kBlock) {
-            ys[i] = fq_one(fq_pre<PRE>(xs[i], x2s[i]), scale_p[c], (float)zp_p[c], qlo, qhi);
+            ys[i] = fq_elem<FMT>(fq_pre<PRE>(xs[i], x2s[i]), scale_p[c], fq_zp<FMT>(zp_p, c), qlo, qhi);
             col += step_cols;
             c += step_ch;
             if (col >= inner) {
@@ -846,7 +878,7 @@ __device__ __forceinline__ void fq_span(const float* __restrict__ x, const float
         step_cols = (4u * kBlock) % inner;
         step_ch = ((4u * kBlock) / inner) % n_channels;
     }
-    const float sc1 = scale_p[0], zp1 = (float)zp_p[0];
+    const float sc1 = scale_p[0], zp1 = fq_zp<FMT>(zp_p, 0u);
     const bool straddle = per_channel && (inner & 3u) != 0u;   // (uniform) a vector may end in the next channel's row
     struct Set {
         f4 v[4];
@@ -864,11 +896,11 @@ __device__ __forceinline__ void fq_span(const float* __restrict__ x, const float
                     i0 + u * kBlock < nvec ? __builtin_nontemporal_load(x2v + i0 + u * kBlock) : f4{0.f, 0.f, 0.f, 0.f};
             if (per_channel) {   // (uniform)
                 st.sc[u] = scale_p[c];
-                st.zp[u] = zp_p[c];
+                if (FMT == kFqFmtInt) st.zp[u] = zp_p[c];
                 if (straddle) {
                     const uint32_t cn = c + 1u < n_channels ? c + 1u : 0u;
                     st.sc2[u] = scale_p[cn];
-                    st.zp2[u] = zp_p[cn];
+                    if (FMT == kFqFmtInt) st.zp2[u] = zp_p[cn];
                     st.left[u] = inner - col;
                 }
                 col += step_cols;
@@ -885,7 +917,7 @@ __device__ __forceinline__ void fq_span(const float* __restrict__ x, const float
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (i0 + u * kBlock < nvec) {
-                const float sc = per_channel ? st.sc[u] : sc1, zp = per_channel ? (float)st.zp[u] : zp1;
+                const float sc = per_channel ? st.sc[u] : sc1, zp = per_channel && FMT == kFqFmtInt ? (float)st.zp[u] : zp1;
                 if (PRE != kFqPreNone) {
                     const f4 w = st.w[PRE == kFqPreAddRelu ? u : 0];
                     st.v[u].x = fq_pre<PRE>(st.v[u].x, w.x);
@@ -894,17 +926,17 @@ __device__ __forceinline__ void fq_span(const float* __restrict__ x, const float
                     st.v[u].w = fq_pre<PRE>(st.v[u].w, w.w);
                 }
                 if (straddle) {   // (uniform)
-                    const float scb = st.sc2[u], zpb = (float)st.zp2[u];
+                    const float scb = st.sc2[u], zpb = FMT == kFqFmtInt ? (float)st.zp2[u] : 0.f;
                     const uint32_t l = st.left[u];
-                    st.v[u].x = fq_one(st.v[u].x, sc, zp, qlo, qhi);
-                    st.v[u].y = fq_one(st.v[u].y, l > 1u ? sc : scb, l > 1u ? zp : zpb, qlo, qhi);
-                    st.v[u].z = fq_one(st.v[u].z, l > 2u ? sc : scb, l > 2u ? zp : zpb, qlo, qhi);
-                    st.v[u].w = fq_one(st.v[u].w, l > 3u ? sc : scb, l > 3u ? zp : zpb, qlo, qhi);
+                    st.v[u].x = fq_elem<FMT>(st.v[u].x, sc, zp, qlo, qhi);
+                    st.v[u].y = fq_elem<FMT>(st.v[u].y, l > 1u ? sc : scb, l > 1u ? zp : zpb, qlo, qhi);
+                    st.v[u].z = fq_elem<FMT>(st.v[u].z, l > 2u ? sc : scb, l > 2u ? zp : zpb, qlo, qhi);
+                    st.v[u].w = fq_elem<FMT>(st.v[u].w, l > 3u ? sc : scb, l > 3u ? zp : zpb, qlo, qhi);
                 } else {
-                    st.v[u].x = fq_one(st.v[u].x, sc, zp, qlo, qhi);
-                    st.v[u].y = fq_one(st.v[u].y, sc, zp, qlo, qhi);
-                    st.v[u].z = fq_one(st.v[u].z, sc, zp, qlo, qhi);
-                    st.v[u].w = fq_one(st.v[u].w, sc, zp, qlo, qhi);
+                    st.v[u].x = fq_elem<FMT>(st.v[u].x, sc, zp, qlo, qhi);
+                    st.v[u].y = fq_elem<FMT>(st.v[u].y, sc, zp, qlo, qhi);
+                    st.v[u].z = fq_elem<FMT>(st.v[u].z, sc, zp, qlo, qhi);
+                    st.v[u].w = fq_elem<FMT>(st.v[u].w, sc, zp, qlo, qhi);
                 }
                 __builtin_nontemporal_store(st.v[u], yv + i0 + u * kBlock);
             }
@@ -932,13 +964,13 @@ __device__ __forceinline__ void fq_span(const float* __restrict__ x, const float
     const uint32_t t = (nvec << 2) + tid;   // (a chunk that is no multiple of four long: the tensor's last elements)
     if (t < cnt) {
         const uint32_t c = n_channels == 1u ? 0u : (uint32_t)(((e0 + t) / inner) % n_channels);
-        ys[t] = fq_one(fq_pre<PRE>(xs[t], x2s[t]), scale_p[c], (float)zp_p[c], qlo, qhi);
+        ys[t] = fq_elem<FMT>(fq_pre<PRE>(xs[t], x2s[t]), scale_p[c], fq_zp<FMT>(zp_p, c), qlo, qhi);
     }
 }
 
 // one tensor: workgroup b takes elements [b * chunk, (b + 1) * chunk) (chunk a multiple of 1024)
-// (PRE: the producer's ReLU / Add + ReLU on the way in, fq_pre; x2 is read for kFqPreAddRelu only)
-template <int PRE>
+// (PRE: the producer's ReLU / Add + ReLU on the way in, fq_pre; x2 is read for kFqPreAddRelu only.  FMT: the number format, fq_elem)
+template <int PRE, int FMT>
 __global__ __launch_bounds__(kBlock) void k_fake_quant(const float* __restrict__ x, const float* __restrict__ x2, float* __restrict__ y,
                                                         uint64_t n, uint64_t chunk, const float* __restrict__ scale_p,
                                                         const int32_t* __restrict__ zp_p, uint32_t n_channels, uint32_t inner, float qlo,
@@ -946,11 +978,12 @@ __global__ __launch_bounds__(kBlock) void k_fake_quant(const float* __restrict__
     const uint64_t e0 = (uint64_t)blockIdx.x * chunk;
     if (e0 >= n) return;
     const uint64_t cnt = n - e0 < chunk ? n - e0 : chunk;
-    fq_span<PRE>(x, x2, y, e0, (uint32_t)cnt, scale_p, zp_p, n_channels, inner, qlo, qhi);
+    fq_span<PRE, FMT>(x, x2, y, e0, (uint32_t)cnt, scale_p, zp_p, n_channels, inner, qlo, qhi);
 }
 
 // a whole tensor set in ONE launch: the balanced partition's items (item.seg = tensor, item.offset / count = the elements) over
 // the tensors' base pointers and a parameter row per tensor
+template <int FMT>
 __global__ __launch_bounds__(kBlock) void k_fake_quant_items(const dpl_work_item* __restrict__ items, const uint32_t* __restrict__ bb,
                                                               const float* const* __restrict__ seg_x, float* const* __restrict__ seg_y,
                                                               const dpl_fake_quant_params* __restrict__ prm) {
@@ -959,7 +992,7 @@ __global__ __launch_bounds__(kBlock) void k_fake_quant_items(const dpl_work_item
     for (uint32_t k = k0; k < k1; ++k) {
         const dpl_work_item it = items[k];
         const dpl_fake_quant_params p = prm[it.seg];
-        fq_span<kFqPreNone>(seg_x[it.seg], nullptr, seg_y[it.seg], it.offset, it.count, p.d_scale, p.d_zero_point, (uint32_t)p.n_channels, (uint32_t)p.inner,
+        fq_span<kFqPreNone, FMT>(seg_x[it.seg], nullptr, seg_y[it.seg], it.offset, it.count, p.d_scale, p.d_zero_point, (uint32_t)p.n_channels, (uint32_t)p.inner,
                 (float)p.qlo, (float)p.qhi);
     }
 }
@@ -1147,6 +1180,44 @@ __global__ __launch_bounds__(kBlock) void k_cos_items(const dpl_work_item* __res
         }
         __syncthreads();
     }
+}
+
+// one tensor in either number format (FMT: kFqFmtInt / kFqFmtE4M3; `who`: the entry point's name, for the messages)
+template <int FMT>
+int fake_quant_launch(const char* who, int32_t pre, const float* d_x, const float* d_x2, float* d_y, int64_t n, const float* d_scale,
+                      const int32_t* d_zp, int64_t n_channels, int64_t inner, int32_t qlo, int32_t qhi, dpl_stream_t s) {
+    auto bad = [who](const char* what) {
+        char m[192];
+        snprintf(m, sizeof(m), "%s: %s", who, what);
+        return fail_msg(m);
+    };
+    if (pre != DPL_FQ_PRE_NONE && pre != DPL_FQ_PRE_RELU && pre != DPL_FQ_PRE_ADD_RELU)
+        return bad("pre must be DPL_FQ_PRE_NONE, _RELU or _ADD_RELU");
+    if (n <= 0) return 0;
+    if (pre == DPL_FQ_PRE_ADD_RELU && d_x2 == nullptr) return bad("DPL_FQ_PRE_ADD_RELU needs d_x2");
+    if (n_channels < 1 || inner < 1 || n_channels > 0xFFFFFFFFll || inner > 0xFFFFFFFFll)
+        return bad("n_channels and inner must be in [1, 2^32)");
+    // A contiguous chunk of 3072 elements (12 KiB read + 12 KiB written) per workgroup, whatever the tensor's size (a multiple of
+    // 1024 elements: every chunk starts on a 16-byte boundary of an aligned tensor).  Measured on the tensors a fake-quantised
+    // ResNet-50 forward at batch 64 runs this on (26 - 205 MB, distinct buffers in rotation), fraction of
+    // 8 TB/s by chunk: 1024: 0.61 / 0.52 (205 MB / 26 MB), 2048: 0.72 / 0.57, 3072: 0.76 / 0.56, 4096: 0.75 / 0.54, 8192: 0.78 /
+    // 0.54, 12288: 0.72 / 0.43 — and rounds 3 - 4's rule (n / 4096 elements, at least 4096: 50 KB chunks for a 205 MB tensor):
+    // 0.70 / 0.54.  The Q/DQ nodes of that forward: 0.61 -> 0.65 of the roofline (bench.py `fake_quant.product_forward`).
+    constexpr int64_t kFqChunk = 3072;
+    int64_t chunk = kFqChunk;
+    if ((n + chunk - 1) / chunk > 0x40000000ll) chunk = ((n + 0x3FFFFFFFll) / 0x40000000ll + 1023) / 1024 * 1024;
+    if (chunk > 0xFFFFFC00ll) chunk = 0xFFFFFC00ll;
+    const int64_t blocks = (n + chunk - 1) / chunk;
+    if (blocks > 0x7FFFFFFFll) return bad("tensor too large");
+#define DPL_FQ_LAUNCH(PRE)                                                                                                    \
+    hipLaunchKernelGGL((k_fake_quant<PRE, FMT>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)s, d_x, d_x2, d_y, (uint64_t)n,   \
+                       (uint64_t)chunk, d_scale, d_zp, (uint32_t)n_channels, (uint32_t)inner, (float)qlo, (float)qhi)
+    if (pre == DPL_FQ_PRE_ADD_RELU) DPL_FQ_LAUNCH(kFqPreAddRelu);
+    else if (pre == DPL_FQ_PRE_RELU) DPL_FQ_LAUNCH(kFqPreRelu);
+    else DPL_FQ_LAUNCH(kFqPreNone);
+#undef DPL_FQ_LAUNCH
+    DPL_LAUNCH_CHECK("k_fake_quant");
+    return 0;
 }
 
 }  // namespace
@@ -1454,42 +1525,31 @@ int dpl_fake_quant(const float* d_x, float* d_y, int64_t n, const float* d_scale
 
 int dpl_fake_quant_pre(int32_t pre, const float* d_x, const float* d_x2, float* d_y, int64_t n, const float* d_scale,
                        const int32_t* d_zp, int64_t n_channels, int64_t inner, int32_t qlo, int32_t qhi, dpl_stream_t s) {
-    if (pre != DPL_FQ_PRE_NONE && pre != DPL_FQ_PRE_RELU && pre != DPL_FQ_PRE_ADD_RELU)
-        return fail_msg("dpl_fake_quant_pre: pre must be DPL_FQ_PRE_NONE, _RELU or _ADD_RELU");
-    if (n <= 0) return 0;
-    if (pre == DPL_FQ_PRE_ADD_RELU && d_x2 == nullptr) return fail_msg("dpl_fake_quant_pre: DPL_FQ_PRE_ADD_RELU needs d_x2");
-    if (n_channels < 1 || inner < 1 || n_channels > 0xFFFFFFFFll || inner > 0xFFFFFFFFll)
-        return fail_msg("dpl_fake_quant_pre: n_channels and inner must be in [1, 2^32)");
-    // A contiguous chunk of 3072 elements (12 KiB read + 12 KiB written) per workgroup, whatever the tensor's size (a multiple of
-    // 1024 elements: every chunk starts on a 16-byte boundary of an aligned tensor).  Measured on the tensors a fake-quantised
-    // ResNet-50 forward at batch 64 runs this on (26 - 205 MB, distinct buffers in rotation), fraction of
-    // 8 TB/s by chunk: 1024: 0.61 / 0.52 (205 MB / 26 MB), 2048: 0.72 / 0.57, 3072: 0.76 / 0.56, 4096: 0.75 / 0.54, 8192: 0.78 /
-    // 0.54, 12288: 0.72 / 0.43 — and rounds 3 - 4's rule (n / 4096 elements, at least 4096: 50 KB chunks for a 205 MB tensor):
-    // 0.70 / 0.54.  The Q/DQ nodes of that forward: 0.61 -> 0.65 of the roofline (bench.py `fake_quant.product_forward`).
-    constexpr int64_t kFqChunk = 3072;
-    int64_t chunk = kFqChunk;
-    if ((n + chunk - 1) / chunk > 0x40000000ll) chunk = ((n + 0x3FFFFFFFll) / 0x40000000ll + 1023) / 1024 * 1024;
-    if (chunk > 0xFFFFFC00ll) chunk = 0xFFFFFC00ll;
-    const int64_t blocks = (n + chunk - 1) / chunk;
-    if (blocks > 0x7FFFFFFFll) return fail_msg("dpl_fake_quant_pre: tensor too large");
-#define DPL_FQ_LAUNCH(PRE)                                                                                                    \
-    hipLaunchKernelGGL(k_fake_quant<PRE>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)s, d_x, d_x2, d_y, (uint64_t)n,   \
-                       (uint64_t)chunk, d_scale, d_zp, (uint32_t)n_channels, (uint32_t)inner, (float)qlo, (float)qhi)
-    if (pre == DPL_FQ_PRE_ADD_RELU) DPL_FQ_LAUNCH(kFqPreAddRelu);
-    else if (pre == DPL_FQ_PRE_RELU) DPL_FQ_LAUNCH(kFqPreRelu);
-    else DPL_FQ_LAUNCH(kFqPreNone);
-#undef DPL_FQ_LAUNCH
-    DPL_LAUNCH_CHECK("k_fake_quant");
-    return 0;
+    return fake_quant_launch<kFqFmtInt>("dpl_fake_quant_pre", pre, d_x, d_x2, d_y, n, d_scale, d_zp, n_channels, inner, qlo, qhi, s);
+}
+
+int dpl_fake_quant_fp8(int32_t pre, const float* d_x, const float* d_x2, float* d_y, int64_t n, const float* d_scale,
+                       int64_t n_channels, int64_t inner, dpl_stream_t s) {
+    return fake_quant_launch<kFqFmtE4M3>("dpl_fake_quant_fp8", pre, d_x, d_x2, d_y, n, d_scale, nullptr, n_channels, inner, 0, 0, s);
 }
 
 int dpl_fake_quant_items(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin, int64_t n_blocks,
                          const float* const* d_seg_x, float* const* d_seg_y, const dpl_fake_quant_params* d_params, dpl_stream_t s) {
     if (n_items <= 0) return 0;
     if (int e = check_blocks("dpl_fake_quant_items", n_items, d_block_begin, n_blocks)) return e;
-    hipLaunchKernelGGL(k_fake_quant_items, dim3((unsigned)n_blocks), dim3(kBlock), 0, (hipStream_t)s, d_items, d_block_begin, d_seg_x,
-                       d_seg_y, d_params);
+    hipLaunchKernelGGL(k_fake_quant_items<kFqFmtInt>, dim3((unsigned)n_blocks), dim3(kBlock), 0, (hipStream_t)s, d_items, d_block_begin,
+                       d_seg_x, d_seg_y, d_params);
     DPL_LAUNCH_CHECK("k_fake_quant_items");
+    return 0;
+}
+
+int dpl_fake_quant_fp8_items(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin, int64_t n_blocks,
+                             const float* const* d_seg_x, float* const* d_seg_y, const dpl_fake_quant_params* d_params, dpl_stream_t s) {
+    if (n_items <= 0) return 0;
+    if (int e = check_blocks("dpl_fake_quant_fp8_items", n_items, d_block_begin, n_blocks)) return e;
+    hipLaunchKernelGGL(k_fake_quant_items<kFqFmtE4M3>, dim3((unsigned)n_blocks), dim3(kBlock), 0, (hipStream_t)s, d_items, d_block_begin,
+                       d_seg_x, d_seg_y, d_params);
+    DPL_LAUNCH_CHECK("k_fake_quant_fp8_items");
     return 0;
 }
 

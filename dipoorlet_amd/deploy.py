@@ -2,7 +2,8 @@
 
 Pure host-side dict -> file code, no GPU work; kept so a run ends with the same artefacts.  File names,
 JSON structure (indent=4) and value formulas follow the reference emitters cited per function (all eight
-platforms; the rv / stpu tables are checked against files the reference's own emitters wrote).
+platforms; the rv / stpu tables are checked against files the reference's own emitters wrote).  `ocp_fp8` is this project's
+own: the static per-tensor scales of the activations.
 """
 import json
 import os
@@ -92,6 +93,19 @@ def gen_atlas_quant_param(graph, clip_val, args, **kwargs):
                 step = 1.0
             res[t] = {"scale": step, "offset": int(round(-lo / step) - 128)}
     _dump(res, args, "atlas_quant_param.json")
+
+
+@deploy_dispatcher.register("ocp_fp8")
+def gen_ocp_fp8_scales(graph, clip_val, args, **kwargs):
+    """{"format": "float8e4m3fn", "scale": {tensor: s}} -> ocp_fp8_scales.json: the fp32 scale (clip / 448) that the
+    fake-quantised graph used for that tensor, as quantize.get_qnode_by_param derives it from the clip."""
+    from .quantize import get_qnode_by_param
+    qi = platform_setting_table["ocp_fp8"]["qi_params"]
+    scale = {}
+    for k, v in clip_val.items():
+        q, _, _ = get_qnode_by_param(qi, k, None, [v[0], v[1]])       # (a fresh list: the per-tensor collapse is in place)
+        scale[k] = float(q.scale[0])
+    _dump({"format": "float8e4m3fn", "scale": scale}, args, "ocp_fp8_scales.json")
 
 
 def to_deploy(graph, act_clip_val, weight_clip_val, args, **kwargs):

@@ -730,8 +730,8 @@ class GraphSession(ActivationSession):
 
     def _fold_weights(self, nodes):
         """Fake-quantised WEIGHTS are constants: quantised once, here, instead of on every forward — every weight of the graph
-        in ONE launch (dpl_fake_quant_items over the set of weight tensors, per-channel rows along each weight's own axis: 54
-        tensors for ResNet-50) rather than one launch and two parameter uploads per weight (quantize.py:197-239 builds a Q/DQ
+        in ONE launch (dpl_fake_quant_items — dpl_fake_quant_fp8_items for FP8 nodes, quantize.QDQNode.fmt — over the set of
+        weight tensors, per-channel rows along each weight's own axis: 54 tensors for ResNet-50) rather than one launch and two parameter uploads per weight (quantize.py:197-239 builds a Q/DQ
         pair per weight; ONNXRuntime runs each on every inference)."""
         if not nodes:
             return
@@ -741,12 +741,19 @@ class GraphSession(ActivationSession):
                 self.consts[n.output[0]] = _OPS["FakeQuant"](self, n, w) if w.is_cuda else w
             return
         from . import ops
+        from .quantize import FP8_E4M3
+        fp8 = [self.graph._qdq[n.name].fmt == FP8_E4M3 for n in nodes]
+        if any(fp8) and not all(fp8):      # (one platform, one format — a hand-made graph may mix them: a launch per format)
+            self._fold_weights([n for n, f in zip(nodes, fp8) if f])
+            self._fold_weights([n for n, f in zip(nodes, fp8) if not f])
+            return
         plan = ops.TensorSetPlan([w.numel() for w in ws], 1, self.device)
         # all scales / zero points of the set in two transfers
         qs = [self.graph._qdq[n.name] for n in nodes]
         sizes = [q.scale.size for q in qs]
         scale = torch.from_numpy(np.concatenate([q.scale for q in qs]).astype(np.float32)).to(self.device)
-        zp = torch.from_numpy(np.concatenate([np.broadcast_to(q.zero_point_as_stored(), q.scale.shape) for q in qs]).astype(np.int32)).to(self.device)
+        if not fp8[0]:
+            zp = torch.from_numpy(np.concatenate([np.broadcast_to(q.zero_point_as_stored(), q.scale.shape) for q in qs]).astype(np.int32)).to(self.device)
         params, off = [], 0
         for q, w, k in zip(qs, ws, sizes):
             lo, hi = q.saturation()
@@ -755,9 +762,9 @@ class GraphSession(ActivationSession):
                 if w.shape[q.axis] != k:
                     raise ValueError(f"fake-quant of {q.tensor_name}: {k} channel scales for axis {q.axis} of {tuple(w.shape)}")
                 inner = int(np.prod(w.shape[q.axis + 1:])) if q.axis + 1 < w.dim() else 1
-            params.append((scale[off:off + k], zp[off:off + k], inner, lo, hi))
+            params.append((scale[off:off + k], inner) if fp8[0] else (scale[off:off + k], zp[off:off + k], inner, lo, hi))
             off += k
-        outs = ops.FakeQuantSet(plan, params)([w.reshape(1, -1) for w in ws])
+        outs = ops.FakeQuantSet(plan, params, fmt="fp8" if fp8[0] else "int")([w.reshape(1, -1) for w in ws])
         for n, w, y in zip(nodes, ws, outs):
             self.consts[n.output[0]] = y.view(w.shape)
 

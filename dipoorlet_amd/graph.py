@@ -148,6 +148,8 @@ class ONNXGraph:
         self.graph.node.insert(idx, fq)
         self.initializer[q_nodes.scale_name] = q_nodes.scale if q_nodes.scale.size > 1 else q_nodes.scale.reshape(())
         zp = q_nodes.zero_point if q_nodes.symmetric else q_nodes.zero_point.view(np.uint8)
+        if q_nodes.zp_dtype == "float8e4m3fn":     # the zero of the format: one 0x00 byte per element (TensorProto type 17)
+            zp = onnx_io.Float8E4M3FNBytes(np.zeros(q_nodes.scale.shape, np.uint8))
         self.initializer[q_nodes.zero_point_name] = zp if zp.size > 1 else zp.reshape(())
         self.set_index()
 
@@ -222,10 +224,11 @@ class ONNXGraph:
     def to_model(self, expand_fake_quant=True):
         m = onnx_io.Model()
         m.ir_version, m.opset, m.graph_name = self.ir_version, dict(self.opset), self.graph.name
-        nodes = []
+        nodes, float8 = [], False
         for n in self.graph.node:
             if n.op_type == "FakeQuant" and expand_fake_quant:   # emit the reference's 2-node form (quantize.py:208-231)
                 q = self._qdq[n.name]
+                float8 |= q.zp_dtype == "float8e4m3fn"
                 attrs = {"axis": q.axis} if q.per_channel else {}
                 nodes.append(Node("QuantizeLinear", [q.tensor_name, q.scale_name, q.zero_point_name], [q.q_output],
                                   name=q.q_name, attrs=attrs))
@@ -234,6 +237,10 @@ class ONNXGraph:
             else:
                 nodes.append(n)
         m.nodes = nodes
+        if float8:
+            # QuantizeLinear / DequantizeLinear take a float8e4m3fn zero point from opset 19 (IR version 9) on
+            m.opset[""] = max(m.opset.get("", 0), 19)
+            m.ir_version = max(m.ir_version, 9)
         m.initializers = dict(self.initializer)
         m.inputs = [(n, onnx_io.FLOAT, self.tensor_name_shape_map.get(n)) for n in self.network_inputs]
         m.outputs = [(n, onnx_io.FLOAT, self.tensor_name_shape_map.get(n)) for n in self.network_outputs]

@@ -22,6 +22,17 @@ _NP = {FLOAT: np.float32, UINT8: np.uint8, INT8: np.int8, UINT16: np.uint16, INT
        INT64: np.int64, BOOL: np.bool_, FLOAT16: np.float16, DOUBLE: np.float64, UINT32: np.uint32, UINT64: np.uint64}
 _ONNX = {np.dtype(v): k for k, v in _NP.items()}
 
+FLOAT8E4M3FN = 17       # (opset 19 / IR 9) numpy has no such dtype: carried as opaque bytes, Float8E4M3FNBytes
+
+
+class Float8E4M3FNBytes(np.ndarray):
+    """A TensorProto of data type FLOAT8E4M3FN as its raw bytes: a uint8 array (one e4m3fn code per element) that remembers
+    what it is, so that it is written back as type 17.  Nothing here computes with the codes."""
+
+    def __new__(cls, codes):
+        return np.require(codes, np.uint8, "C").view(cls)
+
+
 ATTR_FLOAT, ATTR_INT, ATTR_STRING, ATTR_TENSOR, ATTR_FLOATS, ATTR_INTS, ATTR_STRINGS = 1, 2, 3, 4, 6, 7, 8
 
 
@@ -107,6 +118,9 @@ def _parse_tensor(buf):
             raw = bytes(v)
         elif fno == 10:
             f64 += list(np.frombuffer(bytes(v), "<f8")) if wt == 2 else [struct.unpack("<d", v)[0]]
+    if dtype == FLOAT8E4M3FN:
+        codes = np.frombuffer(raw, np.uint8) if raw is not None else np.array(i32, np.int64).astype(np.uint8)   # (int32_data: a code each)
+        return Tensor(name, Float8E4M3FNBytes(codes.reshape(dims)))
     if dtype not in _NP:
         raise ValueError(f"tensor {name}: unsupported ONNX data type {dtype}")
     npd = np.dtype(_NP[dtype])
@@ -339,11 +353,15 @@ def _int(fno, v):
 
 
 def _enc_tensor(name, arr):
-    arr = np.asarray(arr)
-    if arr.dtype not in _ONNX:
-        raise ValueError(f"cannot encode dtype {arr.dtype}")
+    if isinstance(arr, Float8E4M3FNBytes):
+        dtype = FLOAT8E4M3FN
+    else:
+        arr = np.asarray(arr)
+        if arr.dtype not in _ONNX:
+            raise ValueError(f"cannot encode dtype {arr.dtype}")
+        dtype = _ONNX[arr.dtype]
     out = b"".join(_int(1, d) for d in arr.shape)
-    out += _int(2, _ONNX[arr.dtype]) + _str(8, name)
+    out += _int(2, dtype) + _str(8, name)
     out += _len(9, np.ascontiguousarray(arr).astype(arr.dtype.newbyteorder("<")).tobytes())
     return out
 

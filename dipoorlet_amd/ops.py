@@ -989,15 +989,9 @@ def rowwise_minmax(w2d, out=None):
 FQ_PRE = {None: 0, "none": 0, "relu": 1, "add_relu": 2}     # include/dipoorlet_hip.h DPL_FQ_PRE_*
 
 
-def fake_quant(x, scale, zero_point, qlo, qhi, axis=None, out=None, pre=None, x2=None):
-    """Fused QuantizeLinear -> DequantizeLinear (quantize.py:197-239) on the device.
-
-    scale: fp32 device tensor [1] or [C]; zero_point: int32 device tensor of the same length;
-    axis: channel axis when len(scale) > 1.  y = (clamp(rint(x/scale)+zp, qlo, qhi) - zp) * scale.
-    pre: the producer's activation applied on the way in (dpl_fake_quant_pre) — 'relu': fq(max(x, 0)); 'add_relu':
-    fq(max(x + x2, 0)), x2 of x's shape (the residual Add of a bottleneck and its ReLU) — for a forward that does not expose the
-    producer's output (the merge-ReLU rule, quantize.py:50-55, puts the Q/DQ pair directly behind that ReLU).
-    """
+def _fq_args(x, scale, axis, pre, x2, zero_point=None):
+    """The argument checks the Q/DQ kernels of both number formats share -> (pre code, scale and zero point as the kernel takes
+    them, channels, inner); zero_point: the integer grid's only."""
     _require_cuda(x, "x")
     code = FQ_PRE[pre]
     if code == 2:
@@ -1007,11 +1001,12 @@ def fake_quant(x, scale, zero_point, qlo, qhi, axis=None, out=None, pre=None, x2
     # (a graph walk issues one of these per tensor: no conversion calls when the parameters already are what the kernel takes)
     if not (scale.device == x.device and scale.dtype == torch.float32 and scale.dim() == 1 and scale.is_contiguous()):
         scale = scale.to(device=x.device, dtype=torch.float32).contiguous().reshape(-1)
-    if not (zero_point.device == x.device and zero_point.dtype == torch.int32 and zero_point.dim() == 1 and zero_point.is_contiguous()):
-        zero_point = zero_point.to(device=x.device, dtype=torch.int32).contiguous().reshape(-1)
     nch = scale.numel()
-    if zero_point.numel() != nch:
-        raise _hip.DipoorletHipError("scale and zero_point lengths differ")
+    if zero_point is not None:
+        if not (zero_point.device == x.device and zero_point.dtype == torch.int32 and zero_point.dim() == 1 and zero_point.is_contiguous()):
+            zero_point = zero_point.to(device=x.device, dtype=torch.int32).contiguous().reshape(-1)
+        if zero_point.numel() != nch:
+            raise _hip.DipoorletHipError("scale and zero_point lengths differ")
     inner = 1
     if nch > 1:
         if axis is None:
@@ -1020,9 +1015,33 @@ def fake_quant(x, scale, zero_point, qlo, qhi, axis=None, out=None, pre=None, x2
             raise _hip.DipoorletHipError(f"axis {axis} has {x.shape[axis]} channels, scale has {nch}")
         for d in x.shape[axis + 1:]:
             inner *= int(d)
+    return code, scale, zero_point, nch, inner
+
+
+def fake_quant(x, scale, zero_point, qlo, qhi, axis=None, out=None, pre=None, x2=None):
+    """Fused QuantizeLinear -> DequantizeLinear (quantize.py:197-239) on the device.
+
+    scale: fp32 device tensor [1] or [C]; zero_point: int32 device tensor of the same length;
+    axis: channel axis when len(scale) > 1.  y = (clamp(rint(x/scale)+zp, qlo, qhi) - zp) * scale.
+    pre: the producer's activation applied on the way in (dpl_fake_quant_pre) — 'relu': fq(max(x, 0)); 'add_relu':
+    fq(max(x + x2, 0)), x2 of x's shape (the residual Add of a bottleneck and its ReLU) — for a forward that does not expose the
+    producer's output (the merge-ReLU rule, quantize.py:50-55, puts the Q/DQ pair directly behind that ReLU).
+    """
+    code, scale, zero_point, nch, inner = _fq_args(x, scale, axis, pre, x2, zero_point)
     y = torch.empty_like(x) if out is None else out
     _hip.check(_hip.lib().dpl_fake_quant_pre(code, _ptr(x), _ptr(x2) if code == 2 else None, _ptr(y), x.numel(), _ptr(scale),
                                              _ptr(zero_point), nch, inner, int(qlo), int(qhi), _stream()), "dpl_fake_quant_pre")
+    return y
+
+
+def fake_quant_fp8(x, scale, axis=None, out=None, pre=None, x2=None):
+    """The same pair on the OCP FP8 E4M3 grid (dpl_fake_quant_fp8; quantisation type 'Float8E4M3FN'): y = fl32(e4m3_round(fl32(x /
+    scale)) * scale), the nearest e4m3fn value, ties to even, saturating at +-448, NaN kept (tests/fp8_model.py is the definition).
+    scale: fp32 device tensor [1] or [C]; axis, out, pre, x2: as fake_quant.  No zero point, no integer bounds."""
+    code, scale, _, nch, inner = _fq_args(x, scale, axis, pre, x2)
+    y = torch.empty_like(x) if out is None else out
+    _hip.check(_hip.lib().dpl_fake_quant_fp8(code, _ptr(x), _ptr(x2) if code == 2 else None, _ptr(y), x.numel(), _ptr(scale),
+                                             nch, inner, _stream()), "dpl_fake_quant_fp8")
     return y
 
 
@@ -1035,15 +1054,27 @@ class FakeQuantSet:
         ys = fq(xs)                              # or fq(xs, out=ys); xs[t]: [B, ...] contiguous fp32 as the plan describes
 
     `inner` = elements per channel row of ONE tensor as laid out in memory ([B, C, H, W] with per-channel parameters on axis 1:
-    inner = H * W); ignored for per-tensor parameters."""
+    inner = H * W); ignored for per-tensor parameters.
 
-    def __init__(self, plan, params):
+    fmt='fp8': the OCP FP8 E4M3 grid (dpl_fake_quant_fp8_items, fake_quant_fp8) — params[t] = (scale fp32 [1 | C], inner)."""
+
+    def __init__(self, plan, params, fmt="int"):
+        if fmt not in ("int", "fp8"):
+            raise _hip.DipoorletHipError(f"FakeQuantSet: fmt must be 'int' or 'fp8', got {fmt!r}")
+        self.fmt = fmt
         if len(params) != plan.T:
             raise _hip.DipoorletHipError(f"expected {plan.T} parameter rows, got {len(params)}")
         self.plan = plan
         self.keep = []
         rows = (_hip.FakeQuantParams * plan.T)()
-        for t, (scale, zp, inner, qlo, qhi) in enumerate(params):
+        for t, row in enumerate(params):
+            if fmt == "fp8":
+                scale, inner = row
+                scale = scale.to(device=plan.device, dtype=torch.float32).contiguous().reshape(-1)
+                self.keep.append(scale)
+                rows[t] = _hip.FakeQuantParams(scale.data_ptr(), None, scale.numel(), int(inner) if scale.numel() > 1 else 1, 0, 0)
+                continue
+            scale, zp, inner, qlo, qhi = row
             scale = scale.to(device=plan.device, dtype=torch.float32).contiguous().reshape(-1)
             zp = zp.to(device=plan.device, dtype=torch.int32).contiguous().reshape(-1)
             if scale.numel() != zp.numel():
@@ -1064,8 +1095,8 @@ class FakeQuantSet:
         if out is None:
             out = [torch.empty_like(x) for x in tensors]
         ty = plan.seg_table(out)
-        _hip.check(_hip.lib().dpl_fake_quant_items(*self.work.args(), _ptr(tx), _ptr(ty), _ptr(self.d_params), _stream()),
-                   "dpl_fake_quant_items")
+        entry = "dpl_fake_quant_fp8_items" if self.fmt == "fp8" else "dpl_fake_quant_items"
+        _hip.check(getattr(_hip.lib(), entry)(*self.work.args(), _ptr(tx), _ptr(ty), _ptr(self.d_params), _stream()), entry)
         return out
 
 

@@ -4,6 +4,9 @@ Same keys and values as the reference table (dipoorlet/platform_settings.py:1-18
 calibration hot path reads them verbatim: `'dynamic_sym' in qi_params` decides OCTAV's `unsigned`
 factor (forward_net.py:319) and qi/qw params feed scale / zero-point derivation (quantize.py:111-194).
 Expressed through a small builder instead of eight literal dicts.
+
+`ocp_fp8` is this project's own entry (the reference has no floating-point grid): static per-tensor / per-channel scales for
+OCP FP8 E4M3, type "Float8E4M3FN" — `bit_width` stays 8, the width of the format (quantize.get_qnode_by_param).
 """
 
 LAYER_HAS_WEIGHT = ["Conv", "Gemm", "ConvTranspose", "PRelu", "BatchNormalization"]
@@ -14,6 +17,12 @@ _BASIC = ["Relu", "Eltwise", "MaxPool", "Conv", "Gemm", "ConvTranspose", "PRelu"
 
 def _lin(symmetric, **extra):
     d = {"bit_width": 8, "type": "Linear", "symmetric": symmetric}
+    d.update(extra)
+    return d
+
+
+def _fp8(**extra):
+    d = {"bit_width": 8, "type": "Float8E4M3FN", "symmetric": True}
     d.update(extra)
     return d
 
@@ -41,4 +50,5 @@ platform_setting_table = {
                     _lin(True, dynamic_sym=True, log_scale=True)),
     "imx": _platform(_BASIC, _lin(True, per_channel=True, log_scale=True), _lin(True, log_scale=True),
                      net_out=True, deploy_weight=True),
+    "ocp_fp8": _platform(["Conv", "Gemm", "ConvTranspose", "MatMul"], _fp8(per_channel=True), _fp8()),
 }

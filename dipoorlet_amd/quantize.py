@@ -18,14 +18,17 @@ from .utils import logger
 QTENSORSUFFIX = "_q"
 DQTENSORSUFFIX = "_dq"
 QUANT_NODE_NAME_LIST = ["QuantizeLinear", "DequantizeLinear"]
+FP8_E4M3 = "Float8E4M3FN"      # the quantisation type of OCP FP8 E4M3 (platform `ocp_fp8`); every other platform: "Linear"
+E4M3_MAX = 448
 MERGE_RELU = ["Conv", "Gemm", "Eltwise", "Add"]
 RELU_TYPE = ["Relu", "PRelu", "Mul"]
 
 
 class QDQNode:
-    """The fused fake-quant stand-in for the reference's 2-node `graph_quant` (quantize.py:197-239)."""
+    """The fused fake-quant stand-in for the reference's 2-node `graph_quant` (quantize.py:197-239).  `fmt`: the number format
+    of the grid — "Linear" (an 8-bit integer one) or FP8_E4M3 (scale only: the zero point is 0, written as a float8e4m3fn)."""
 
-    def __init__(self, tensor_name, tensor_shape, scale, zero_point, need_transpose, per_channel, symmetric):
+    def __init__(self, tensor_name, tensor_shape, scale, zero_point, need_transpose, per_channel, symmetric, fmt="Linear"):
         self.tensor_name = tensor_name
         self.tensor_shape = list(tensor_shape) if tensor_shape is not None else None
         self.scale = np.asarray(scale, np.float32).reshape(-1)
@@ -33,7 +36,8 @@ class QDQNode:
         self.per_channel = bool(per_channel)
         self.symmetric = bool(symmetric)
         self.axis = (1 if need_transpose else 0) if per_channel else None  # :214, :220
-        self.zp_dtype = "int8" if symmetric else "uint8"                  # :205-206
+        self.fmt = fmt
+        self.zp_dtype = "float8e4m3fn" if fmt == FP8_E4M3 else "int8" if symmetric else "uint8"      # :205-206
         self.q_name = tensor_name + "_QuantizeLinear"
         self.dq_name = tensor_name + "_DequantizeLinear"
         self.scale_name = tensor_name + "_scale"
@@ -48,7 +52,9 @@ class QDQNode:
 
     def saturation(self):
         """QuantizeLinear saturates to the zero-point dtype's full range (ONNX opset 13) — note: -128,
-        not the q_min = -127 the reference computes at :134 for its torch-side code."""
+        not the q_min = -127 the reference computes at :134 for its torch-side code.  FP8: saturate = 1, the largest finite value."""
+        if self.fmt == FP8_E4M3:
+            return -E4M3_MAX, E4M3_MAX
         return (-128, 127) if self.symmetric else (0, 255)
 
     def apply(self, x, out=None, pre=None, x2=None):
@@ -59,6 +65,8 @@ class QDQNode:
                          torch.from_numpy(self.zero_point_as_stored()).to(x.device))
         lo, hi = self.saturation()
         axis = self.axis if self.scale.size > 1 else None
+        if self.fmt == FP8_E4M3:
+            return ops.fake_quant_fp8(x, self._dev[0], axis=axis, out=out, pre=pre, x2=x2)
         return ops.fake_quant(x, self._dev[0], self._dev[1], lo, hi, axis=axis, out=out, pre=pre, x2=x2)
 
 
@@ -102,11 +110,29 @@ def _affine_grid(bits, lo, hi, tensor_name):
     return [float(scale)], zp, [int(-zp)], [int(levels - zp)]
 
 
+def _e4m3_grid(lo, hi):
+    """scale = max(|lo|, |hi|) / 448 per channel — the clip lands on the format's largest finite value —, computed as
+    _symmetric_grid computes its own; zero point 0, saturation at +-448."""
+    n = lo.size if isinstance(lo, np.ndarray) else 1
+    scale = np.asarray(np.max(np.abs([lo, hi]), axis=0)) / ([E4M3_MAX] * n)
+    scale = np.where(scale == 0, 1.0, scale)
+    return scale.tolist()
+
+
 def get_qnode_by_param(param, in_tensor_name, tensor_shape, range, need_transpose=False):
     """quantize.py:111-194 — returns (QDQNode, q_min, q_max) for the clip range `range` = [lo, hi] (scalars, or
     per-channel arrays for weights).  Kept from the reference because callers rely on it: a per-tensor platform
-    collapses `range` to its overall min / max IN PLACE; `dynamic_sym` platforms switch a non-negative activation
+    collapses `range` to its overall min / max IN PLACE (type "Float8E4M3FN" too: scale = max(|lo|, |hi|) / 448, zero point 0,
+    q_min / q_max = -448 / 448); `dynamic_sym` platforms switch a non-negative activation
     (|lo| < 1e-6) to the asymmetric grid — one more bit; `log_scale` snaps scales to powers of two."""
+    if param["type"] == FP8_E4M3:
+        per_channel = bool(param.get("per_channel", False))
+        if not per_channel:
+            range[0], range[1] = np.min(range[0]), np.max(range[1])
+        scale = np.array(_e4m3_grid(range[0], range[1]), dtype=np.float32).reshape(-1)
+        q_nodes = QDQNode(in_tensor_name, tensor_shape, scale, np.zeros(scale.shape, np.int8), need_transpose, per_channel, True,
+                          fmt=FP8_E4M3)
+        return q_nodes, -E4M3_MAX, E4M3_MAX
     if param["type"] != "Linear":
         return None, None, None
     per_channel = bool(param.get("per_channel", False))

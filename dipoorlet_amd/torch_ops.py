@@ -13,6 +13,7 @@ Per tensor:
     dipoorlet::fake_quant(Tensor x, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor
     dipoorlet::fake_quant_relu(Tensor x, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor          fq(relu(x))
     dipoorlet::fake_quant_add_relu(Tensor x, Tensor x2, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor
+    dipoorlet::fake_quant_fp8(Tensor x, Tensor scale, int axis) -> Tensor      the pair on the OCP FP8 E4M3 grid (ops.fake_quant_fp8)
 Over every tensor of a batch of images in ONE launch — what the reference's loops over `ort_outputs` stand for
 (forward_net.py:220-235, 265-280, 314-340); xs[t] is tensor t of the batch, [B, ...] contiguous fp32:
     dipoorlet::minmax_batched(Tensor[] xs, Tensor(a!) mins, Tensor(b!) maxs) -> ()   running min / max per tensor, [T] fp32
@@ -270,6 +271,16 @@ def fake_quant_add_relu(x: torch.Tensor, x2: torch.Tensor, scale: torch.Tensor, 
 
 @fake_quant_add_relu.register_fake
 def _(x, x2, scale, zero_point, axis, qlo, qhi):
+    return torch.empty_like(x)
+
+
+@torch.library.custom_op("dipoorlet::fake_quant_fp8", mutates_args=(), device_types="cuda")
+def fake_quant_fp8(x: torch.Tensor, scale: torch.Tensor, axis: int) -> torch.Tensor:
+    return ops.fake_quant_fp8(x.contiguous(), scale, axis=axis if scale.numel() > 1 else None)
+
+
+@fake_quant_fp8.register_fake
+def _(x, scale, axis):
     return torch.empty_like(x)
 
 

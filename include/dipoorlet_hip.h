@@ -25,8 +25,9 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 23 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
-                              23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass) */
+#define DPL_ABI_VERSION 24 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+                              23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
+                              24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -365,6 +366,20 @@ typedef struct dpl_fake_quant_params {
 } dpl_fake_quant_params;
 int dpl_fake_quant_items(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin, int64_t n_blocks,
                          const float* const* d_seg_x, float* const* d_seg_y, const dpl_fake_quant_params* d_params, dpl_stream_t s);
+
+/* ---- the same pair on the OCP FP8 E4M3 grid ("float8e4m3fn": bias 7, 3 mantissa bits, subnormal step 2^-9, largest finite
+ *      value 448, no infinities) — ONNX opset 19 QuantizeLinear with a float8e4m3fn zero point and saturate = 1, followed by
+ *      DequantizeLinear:
+ *      y = fl32(e4m3_round(fl32(x / scale[c])) * scale[c])
+ *      e4m3_round: the nearest e4m3fn value, round half to even (in the subnormal range too); |v| > 448 and +-inf give +-448;
+ *      NaN stays NaN; the sign of zero is kept.  The division and the product are single fp32 operations.  No zero point, no
+ *      qlo / qhi.  `pre`, d_x2, n_channels, inner: as dpl_fake_quant_pre. */
+int dpl_fake_quant_fp8(int32_t pre, const float* d_x, const float* d_x2, float* d_y, int64_t n, const float* d_scale,
+                       int64_t n_channels, int64_t inner, dpl_stream_t s);
+/* ... over a whole tensor set in one launch: the arguments of dpl_fake_quant_items; d_zero_point, qlo and qhi of the parameter
+ * rows are ignored (d_zero_point may be null). */
+int dpl_fake_quant_fp8_items(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin, int64_t n_blocks,
+                             const float* const* d_seg_x, float* const* d_seg_y, const dpl_fake_quant_params* d_params, dpl_stream_t s);
 
 /* ---- cosine-similarity partial sums (utils.py:273-278): d_acc[slot*3 + {0,1,2}] += sum(a*b), sum(a*a),
  *      sum(b*b) in fp64. */
