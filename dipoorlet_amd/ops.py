@@ -7,6 +7,7 @@ set into work items once; `CalibAccumulators` holds the persistent device-side s
 (running min/max, uint64 histograms, OCTAV states) that replace the reference's per-image Python
 lists (forward_net.py:204-235, 252-280, 297-340).
 """
+import collections
 import ctypes as C
 import os
 import weakref
@@ -75,7 +76,15 @@ class TensorSetPlan:
         self.total = sum(self.elems) * self.batch
         self.chunk = int(chunk_elems) if chunk_elems else None
         self._work = {}
-        self._seg_cache = {}
+        self._elems_dev = None      # filled by elems_device(): the plan's first range pass
+        self._octav_scratch = None  # ... by octav_scratch()
+        self._octav_lh = None       # ... by octav_loghist_scratch()
+        self._octav_tail = None     # ... by octav_tail(): the OctavTailPlan, or False where the C ABI refuses the set
+        self._octav_rotations = weakref.WeakSet()   # every pipeline's _Rotation on this plan
+        self._seg_cache = {}        # seg_table(): pointer tuple -> slot of the block the first launch allocates:
+        self._seg_dev = self._seg_host = self._seg_np = None    # [slots, T] int64: device, pinned, the pinned one as numpy
+        self._seg_copied = self._seg_keys = None    # per slot: the event behind its last upload, its pointer tuple
+        self._seg_next = 0
 
     @property
     def n_pairs(self):
@@ -106,14 +115,14 @@ class TensorSetPlan:
     def elems_device(self):
         """uint64 [T] on the device: elements of every tensor of a batch (what dpl_hist_spec_accumulate partitions).  Uploaded once
         per plan, synchronously, like the work sets: a plan's first range pass waits for that copy, no later call does."""
-        if getattr(self, "_elems_dev", None) is None:
+        if self._elems_dev is None:
             self._elems_dev = torch.tensor([e * self.batch for e in self.elems], dtype=torch.int64, device=self.device)
         return self._elems_dev
 
     def octav_scratch(self):
         """(pair_spans, pair_base u64 [B*T], pair_order, list0, list1): where each pair's data lives, and two tail lists of
         the batch's size with the pair regions laid out in pair order (32-element aligned: whole 128-byte lines)."""
-        if getattr(self, "_octav_scratch", None) is None:
+        if self._octav_scratch is None:
             # (a region starts on a 128-byte line: the streaming workgroup that walks a pair reads back the list it has just
             # written, and no other workgroup of the launch may have pulled a line of it into the CU's L1 beforehand — which a
             # neighbouring pair's last, straddling line would)
@@ -131,7 +140,7 @@ class TensorSetPlan:
 
     def octav_loghist_scratch(self):
         """(count u32 [B*T, 2048], mantissa-sum u64 [B*T, 2048], bitmap u32 [B*T, 66]) for the bracket form."""
-        if getattr(self, "_octav_lh", None) is None:
+        if self._octav_lh is None:
             n = self.n_pairs
             self._octav_lh = (torch.empty(n, 2048, dtype=torch.int32, device=self.device),
                               torch.empty(n, 2048, dtype=torch.int64, device=self.device),
@@ -141,26 +150,25 @@ class TensorSetPlan:
     def octav_tail(self):
         """The exact-tail form's HOST plan (dpl_octav_plan_*: every buffer size comes from the C ABI), its static tables on the
         device and the threshold history of this tensor set — or None when a pair needs more than 64 slices."""
-        if getattr(self, "_octav_tail", None) is None:
+        if self._octav_tail is None:
             arr, ns = _hip._span_array(self._spans(True))
             L = _hip.lib()
             handle = L.dpl_octav_plan_create(C.addressof(arr), ns, self.T, max(1, min(DEFAULT_BLOCKS["octav"], (self.total + 4095) // 4096)))
-            if not handle:
-                self._octav_tail = False
-            else:
-                self._octav_tail = OctavTailPlan(self, handle)
+            self._octav_tail = OctavTailPlan(self, handle) if handle else False
         return self._octav_tail or None
 
     def octav_reset(self):
         """Cold start of the exact-tail OCTAV form: what the plan learned from earlier batches (the thresholds its tensors' pairs
         asked for) is forgotten — the state of a plan that has never run.  Call between independent calibration runs that share
         a plan (after OctavPipeline.sync())."""
-        tp = getattr(self, "_octav_tail", None)
-        if tp:
-            tp.history.zero_()
-            tp.calls = 0
-        for pipe in list(getattr(self, "_octav_pipes", ())):
-            pipe._forget(self)
+        rotations = list(self._octav_rotations)
+        if any(st.pending for rot in rotations for st in rot.sets):    # (asked of every pipeline before anything changes)
+            raise _hip.DipoorletHipError("octav_reset with batches in flight: call OctavPipeline.sync() first")
+        if self._octav_tail:
+            self._octav_tail.history.zero_()
+            self._octav_tail.calls = 0
+        for rot in rotations:
+            rot.restart()
 
     def _validate(self, tensors):
         if len(tensors) != self.T:
@@ -208,25 +216,21 @@ class TensorSetPlan:
         slot = self._seg_cache.get(key)
         if slot is not None:
             return self._seg_dev[slot]
-        if getattr(self, "_seg_dev", None) is None:
+        if self._seg_dev is None:
             self._seg_host = torch.empty(_SEG_CACHE_MAX, max(self.T, 1), dtype=torch.int64).pin_memory()
             self._seg_np = self._seg_host.numpy()
             self._seg_dev = torch.empty(_SEG_CACHE_MAX, max(self.T, 1), dtype=torch.int64, device=self.device)
-            self._seg_copied = [None] * _SEG_CACHE_MAX      # per slot: the event behind its last host -> device copy
+            self._seg_copied = [None] * _SEG_CACHE_MAX
             self._seg_keys = [None] * _SEG_CACHE_MAX
-            self._seg_next = 0
         slot = self._seg_next % _SEG_CACHE_MAX
         self._seg_next += 1
-        if self._seg_keys[slot] is not None:
-            self._seg_cache.pop(self._seg_keys[slot], None)
+        self._seg_cache.pop(self._seg_keys[slot], None)
         ev = self._seg_copied[slot]
         if ev is not None and not ev.query():       # (the copy that last read this pinned row has not run yet: 64 sets ago)
             ev.synchronize()
         self._seg_np[slot, :len(key)] = key
         self._seg_dev[slot].copy_(self._seg_host[slot], non_blocking=True)
-        if ev is None:
-            ev = self._seg_copied[slot] = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
+        self._seg_copied[slot] = torch.cuda.current_stream(self.device).record_event(ev)
         self._seg_keys[slot] = key
         self._seg_cache[key] = slot
         return self._seg_dev[slot]
@@ -335,6 +339,12 @@ class BoundSet:
         return self.tensors[i]
 
 
+class _LedgerRecord(collections.namedtuple("_LedgerRecord", "ref entry T")):
+    """CalibAccumulators' ledger: a bound set (weakly), its slab entry, the T slots the entry is laid out for (read by name
+    here; still a tuple, because tests/test_hist_spec_gpu.py reads the entry by position)."""
+    __slots__ = ()
+
+
 class CalibAccumulators:
     """Persistent per-tensor statistics on the device.
 
@@ -371,15 +381,14 @@ class CalibAccumulators:
         self.hist = None
         self.ranges = None
         self.speculate = bool(speculate)
-        self._ledger = {}       # id(bound set) -> (weak reference to it, entry, T)
+        self._ledger = {}       # id(bound set) -> _LedgerRecord
         self._slab = []         # entries not in use: held for this object's lifetime, never returned to the allocator in between
         self._spec_stats = torch.zeros(4, dtype=torch.int64, device=self.device) if self.speculate else None
         self.reset_minmax()
 
     def reset_minmax(self):
         """Running min / max back to 'no data'; the ledger of range-pass histograms is emptied (its entries go back to the slab)."""
-        for _, entry, _ in self._ledger.values():
-            self._slab.append(entry)
+        self._slab.extend(rec.entry for rec in self._ledger.values())
         self._ledger.clear()
         _hip.check(_hip.lib().dpl_minmax_init(_ptr(self.min_enc), _ptr(self.max_enc), _ptr(self.nan), self.n,
                                               _stream()), "dpl_minmax_init")
@@ -392,10 +401,14 @@ class CalibAccumulators:
                 and max(plan.elems) * plan.batch < (1 << 32)
                 and plan.T * self.bins * 4 * self.SPEC_MAX_SHARE <= plan.total * 4)
 
-    def _entry_for(self, bound):
+    def _live(self, bound):     # the live record of this bound set, or None (an id may outlive its set)
         rec = self._ledger.get(id(bound))
-        if rec is not None and rec[0]() is bound:
-            return rec[1]
+        return rec if rec is not None and rec.ref() is bound else None
+
+    def _entry_for(self, bound):
+        rec = self._live(bound)
+        if rec is not None:
+            return rec.entry
         # (An entry may be used on another stream than the one current when it was allocated: the CLI's range pass runs on a side
         # stream, its histogram pass on the caller's, ordered by main.wait_stream(side).  That is safe because the slab holds every
         # entry for this object's lifetime — no block goes back to the allocator while work on either stream may still be queued;
@@ -409,19 +422,15 @@ class CalibAccumulators:
 
         def dropped(ref):           # the bound set died: its entry is free again (the ledger never kept the set alive)
             rec = ledger.get(key)
-            if rec is not None and rec[0] is ref:
+            if rec is not None and rec.ref is ref:     # (the set is gone: the record must still be its own)
                 del ledger[key]
-                slab.append(rec[1])
-        self._ledger[key] = (weakref.ref(bound, dropped), entry, bound.plan.T)
+                slab.append(rec.entry)
+        self._ledger[key] = _LedgerRecord(weakref.ref(bound, dropped), entry, bound.plan.T)
         return entry
 
     def _entry_of(self, plan, tensors):
-        if not isinstance(tensors, BoundSet):
-            return None
-        rec = self._ledger.get(id(tensors))
-        if rec is None or rec[0]() is not tensors or rec[2] != plan.T:
-            return None
-        return rec[1]
+        rec = self._live(tensors) if isinstance(tensors, BoundSet) else None
+        return rec.entry if rec is not None and rec.T == plan.T else None
 
     def spec_stats(self, reset=False):
         """HOST (synchronises): what the histogram passes so far skipped — {'pairs', 'pairs_skipped', 'elements',
@@ -434,12 +443,11 @@ class CalibAccumulators:
     def spec_flags(self, tensors):
         """HOST (synchronises): per tensor what the last abs_hist_accumulate over this bound set did — 1: the range pass's row was
         added and the tensor not read, 2: nothing to count (range status != 0), 0: read — or None when the set has no entry."""
-        rec = self._ledger.get(id(tensors))
-        if rec is None or rec[0]() is not tensors:
+        rec = self._live(tensors)
+        if rec is None:
             return None
-        T = rec[2]      # (the entry is laid out for the T slots of the set's plan: dpl_hist_spec_entry_bytes)
-        off = T * C.sizeof(_hip.HistRange)
-        return rec[1][off:off + 4 * T].view(torch.int32).cpu()
+        off = rec.T * C.sizeof(_hip.HistRange)      # (the entry is laid out for the T slots of the set's plan: dpl_hist_spec_entry_bytes)
+        return rec.entry[off:off + 4 * rec.T].view(torch.int32).cpu()
 
     def spec_cuts(self, plan, tensors):
         """HOST (synchronises; a test hook): the n_blocks + 1 cuts the histogram pass's kernel works to for the flags this bound
@@ -470,10 +478,10 @@ class CalibAccumulators:
                        "dpl_minmax_hist_accumulate")
             return
         if isinstance(tensors, BoundSet):       # (a plain range pass over a set that has an entry: the entry no longer describes it)
-            rec = self._ledger.get(id(tensors))
-            if rec is not None and rec[0]() is tensors:
+            rec = self._live(tensors)
+            if rec is not None:
                 del self._ledger[id(tensors)]
-                self._slab.append(rec[1])
+                self._slab.append(rec.entry)
         w = plan.work("minmax", per_image)
         _hip.check(_hip.lib().dpl_minmax_accumulate(*w.args(), _ptr(tab), _ptr(self.min_enc), _ptr(self.max_enc),
                                                     _ptr(self.nan), _stream()), "dpl_minmax_accumulate")
@@ -555,14 +563,14 @@ _ONEREAD_EPOCH = 8      # batches per threshold-history epoch (the C ABI's: dpl_
 
 
 def _default_form():
-    """DPL_OCTAV_FORM, else 'tail' (round 4: exact tail / bounded bulk; csrc/octav_tail.hpp)."""
+    """DPL_OCTAV_FORM, else 'tail' (exact tail / bounded bulk; csrc/octav_tail.hpp)."""
     form = os.environ.get("DPL_OCTAV_FORM", "tail")
     if form not in _OCTAV_MODE:
-        raise _hip.DipoorletHipError(f"DPL_OCTAV_FORM={form}: the forms are {sorted(_OCTAV_MODE)} (round 5 removed 'oneread')")
+        raise _hip.DipoorletHipError(f"DPL_OCTAV_FORM={form}: the forms are {sorted(_OCTAV_MODE)}")
     return form
 
 
-def octav_batch(plan, tensors, dynamic_sym, states=None, compact=None, form=None, inline=False):
+def octav_batch(plan, tensors, dynamic_sym, states=None, form=None, inline=False):
     """OCTAV for every (image, tensor) pair of one batch -> fp32 device tensor [B, T, 3] = (s, min, max).
 
     Forms (all end on the reference's result, forward_net.py:323-330):
@@ -580,7 +588,7 @@ def octav_batch(plan, tensors, dynamic_sym, states=None, compact=None, form=None
                            bins, exact per-pair iteration; pairs it cannot serve finish on the compaction route
       'compact'            evaluation at s_0 + tail compaction, then per-pair iteration over shrinking lists
       'full'               every evaluation re-reads the full data (21 passes)
-    `compact=True/False` is the older spelling of 'compact' / 'full'.  DPL_OCTAV_FORM overrides the default.
+    DPL_OCTAV_FORM overrides the default.
     Tolerance: every form is within 1e-5 * max(1, |ref|) of the reference's optimal_s (the tests' bound; the reference's own stop
     rule is an absolute 1e-6); min / max are exact.  'tail' repeats to about 1e-6 relative from run to run, not bit for bit — the
     threshold history and wave timing decide which early iterates are taken as bounds, and with them the iterate on which
@@ -588,7 +596,7 @@ def octav_batch(plan, tensors, dynamic_sym, states=None, compact=None, form=None
     (the exact fall-back, and the reference point of the golden tests).
     states (optional): a uint8 device buffer of (B * T + 1) * 80 bytes that receives the pairs' states and the control block."""
     if form is None:
-        form = ("compact" if compact else "full") if compact is not None else _default_form()
+        form = _default_form()
     mode = _OCTAV_MODE[form]
     if form == "tail":
         tp = plan.octav_tail()
@@ -702,6 +710,47 @@ def _separate_stream(device, others, tries=6):
     return best
 
 
+class _PipeSet:
+    """One of a rotation's S sets: what a batch in flight holds until the host settles it, S submits later.  Two state blocks,
+    used alternately: call k's must survive until the host has read it; the next call's, k + S, is initialised behind call k."""
+    __slots__ = ("S", "blocks", "rescue", "host_states", "base_host", "done", "refs", "job", "k", "pending")
+
+    def __init__(self, tp, S):
+        self.S, n = S, tp.plan.n_pairs
+        self.blocks = (tp.new("state"), tp.new("state"))
+        self.rescue = tp.new("rescue")
+        # (pinned: what _settle needs of a batch is on the host by the time it looks, and what it uploads leaves without a wait)
+        self.host_states = torch.zeros((n + 1) * C.sizeof(_hip.OctavState), dtype=torch.uint8).pin_memory()
+        self.base_host = torch.zeros(8 * (n + 1), dtype=torch.uint8).pin_memory()
+        # submit fills these: the event behind the batch's side-stream work, (tensors, pointer table, rows) held until sync(),
+        # the bound job, the call number (-1: not used since creation or reset), whether the batch is still to be settled
+        self.done = self.refs = self.job = None
+        self.k, self.pending = -1, False
+
+    def block(self, k):
+        """The state block of call k: the one place that maps a call number to a block."""
+        return self.blocks[(k // self.S) % 2]
+
+
+class _Rotation:
+    """An OctavPipeline's scratch on one plan (every size is the C plan's, dpl_octav_plan_sizes): S sets, one list per stream
+    that carries streaming kernels, one rescue list, the compaction route's arena; the call counter (call k: set k % S)."""
+    __slots__ = ("plan", "tp", "S", "calls", "sets", "list0", "list1", "fallback", "__weakref__")
+
+    def __init__(self, plan, tp, n_lanes):
+        # (_PIPE_SETS is read here alone: a rotation runs on the S it was built with)
+        self.plan, self.tp, self.S, self.calls = plan, tp, _PIPE_SETS, 0
+        self.sets = [_PipeSet(tp, self.S) for _ in range(self.S)]
+        self.list0, self.list1 = [tp.new("list") for _ in range(max(1, n_lanes))], tp.new("list")
+        self.fallback = None    # _settle: the compaction route's arena, from the first batch that asks for it
+        plan._octav_rotations.add(self)
+
+    def restart(self):      # TensorSetPlan.octav_reset(), nothing in flight
+        self.calls = 0
+        for st in self.sets:
+            st.k = -1
+
+
 class OctavPipeline:
     """OCTAV over a RUN of batches in the exact-tail form on streams of its own.  Same kernels, same results as octav_batch.
 
@@ -713,9 +762,8 @@ class OctavPipeline:
     every pair — batch i + 1 starts while batch i drains.  Side stream, behind the streaming kernel of batch i and beside that
     of batch i + 1: the rescue of the pairs a walk could not finish (on the device, no host round trip), the result rows, the
     state and the threshold snapshot for batch i + 3.
-    The pipeline OWNS its rotation per plan (every size is the C plan's, dpl_octav_plan_sizes: 2 S state blocks, S rescue blocks,
-    one list per lane stream, one rescue list, the compaction route's lists once a batch has asked for them; the call counter):
-    two pipelines may run the same plan (they share only what the plan has learned: maxima taken into its threshold history).
+    The pipeline OWNS its rotation per plan (_Rotation): two pipelines may run the same plan (they share only what the plan has
+    learned: maxima taken into its threshold history).
     The control block of a batch (listed values, rescued pairs, pairs left for the compaction route) is copied to pinned memory
     and read when the set comes up for reuse three submits later (or in sync()): statistics, and — only when the count is
     non-zero — the compaction route for that batch.  The activations of a batch, its pointer table and its result stay
@@ -724,6 +772,7 @@ class OctavPipeline:
     octav_batch (the two-read form) on the caller's stream instead."""
 
     def __init__(self, dynamic_sym, device=None, lanes=None):
+        self._side_handle = None        # dpl_stream_create's (DPL_OCTAV_SIDE_PRIO > 0): __del__ destroys it
         self.dyn = 1 if dynamic_sym else 0
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         n_lanes = int(os.environ.get("DPL_OCTAV_LANES", "0")) or (2 if lanes is None else int(lanes))
@@ -735,7 +784,6 @@ class OctavPipeline:
         # in creation order — and then the rescue of batch i and the streaming kernel of batch i + 1 run one after the other (1.17 ms
         # under the profiler on one box, 0.71 on another after a two-lane pipeline had been created first): _separate_stream asks
         # the device.  DPL_OCTAV_SIDE_PRIO = -1 / 0 / 1 (high / normal / low): a fixed priority, no questions asked.
-        self._side_handle = None
         prio = os.environ.get("DPL_OCTAV_SIDE_PRIO")
         if prio in (None, ""):
             self.side = _separate_stream(self.device, [torch.cuda.current_stream(self.device)])
@@ -758,8 +806,7 @@ class OctavPipeline:
         if n_lanes >= 2:       # (each on a queue of its own too: two lanes on one queue would not overlap)
             for _ in range(n_lanes):
                 self.lanes.append(_separate_stream(self.device, [torch.cuda.current_stream(self.device), self.side] + self.lanes))
-        self._plans = {}          # id(plan) -> this pipeline's rotation state for the plan
-        self._touched = []
+        self._plans = {}          # id(plan) -> _Rotation (which keeps the plan alive)
         # record_events = True: per submit a (start, end) pair of timing events around the streaming kernel ON ITS LANE, kept in
         # .events (what --timing_json reports as the statistics' GPU seconds: the caller's stream no longer carries the kernel)
         self.record_events = False
@@ -768,11 +815,10 @@ class OctavPipeline:
         self.reset_stats()
 
     def __del__(self):
-        h = getattr(self, "_side_handle", None)
-        if h:
+        if self._side_handle:
             try:
                 self.side.synchronize()
-                _hip.lib().dpl_stream_destroy(C.c_void_p(h))
+                _hip.lib().dpl_stream_destroy(C.c_void_p(self._side_handle))
             except Exception:   # noqa: BLE001  (interpreter shutdown)
                 pass
 
@@ -781,82 +827,44 @@ class OctavPipeline:
         self.tiles_reread = self.raises = 0
         self.list_share = self.max_share = 0.0    # listed values / elements (running mean / maximum over the settled batches)
 
-    def _state(self, plan, tp):
-        """This pipeline's rotation on `plan`; every buffer's size is the C plan's (dpl_octav_plan_sizes): 2 S state blocks (call k
-        uses k % 2S; the block for call k + S is initialised at the end of call k's side-stream work, the one of call k must
-        survive until the host has read k's control block, S submits later), S rescue blocks, one list per stream that carries
-        streaming kernels, one rescue list (one side stream).  Nothing is shared with another pipeline on the same plan but what
-        the plan has learned (the history's atomic maxima)."""
-        ps = self._plans.get(id(plan))
-        if ps is None:
-            S = _PIPE_SETS
-            csz = C.sizeof(_hip.OctavState)
-            off = plan.n_pairs * csz
-            states = [tp.new("state") for _ in range(2 * S)]
-            ps = dict(plan=plan, tp=tp, calls=0, states=states, failed=[x[off:off + csz] for x in states],
-                      list0=[tp.new("list") for _ in range(max(1, len(self.lanes)))], list1=tp.new("list"), fallback=None, sets=[])
-            for _ in range(S):
-                # (pinned: the control block — statistics —, the whole state block and the compaction route's region table: what
-                # _settle needs of a batch is on the host by the time it looks, and what it uploads leaves without a wait)
-                ps["sets"].append(dict(failed=torch.zeros(csz, dtype=torch.uint8).pin_memory(), rescue=tp.new("rescue"),
-                                       host_states=torch.zeros(off + csz, dtype=torch.uint8).pin_memory(),
-                                       base_host=torch.zeros(8 * (plan.n_pairs + 1), dtype=torch.uint8).pin_memory(),
-                                       done=None, refs=None, pending=False, k=-1, prepared=None))
-            self._plans[id(plan)] = ps
-            if getattr(plan, "_octav_pipes", None) is None:
-                import weakref
-                plan._octav_pipes = weakref.WeakSet()
-            plan._octav_pipes.add(self)
-        return ps
+    def _rotation(self, plan, tp):
+        rot = self._plans.get(id(plan))
+        if rot is None:
+            rot = self._plans[id(plan)] = _Rotation(plan, tp, len(self.lanes))
+        return rot
 
     def scratch_bytes(self, plan):
         """Device bytes of this pipeline's OCTAV scratch on `plan`: tables, history, state / rescue blocks, lists, and the
         compaction route's lists if a batch has asked for them."""
-        ps = self._plans.get(id(plan))
-        if ps is None:
+        rot = self._plans.get(id(plan))
+        if rot is None:
             return None
-        tp = ps["tp"]
-        n = tp.tables.numel() + tp.history.numel() + sum(x.numel() for x in ps["states"]) + sum(x.numel() for x in ps["list0"])
-        n += ps["list1"].numel() + sum(st["rescue"].numel() for st in ps["sets"])
-        return n + (ps["fallback"].numel() if ps["fallback"] is not None else 0)
+        bufs = [rot.tp.tables, rot.tp.history, rot.list1, *rot.list0] + [x for st in rot.sets for x in (*st.blocks, st.rescue)]
+        return sum(x.numel() for x in bufs) + (rot.fallback.numel() if rot.fallback is not None else 0)
 
-    def _forget(self, plan):
-        """plan.octav_reset(): this pipeline's rotation for the plan starts over (nothing may be in flight)."""
-        ps = self._plans.get(id(plan))
-        if ps is None:
-            return
-        for st in ps["sets"]:
-            if st["pending"]:
-                raise _hip.DipoorletHipError("octav_reset with batches in flight: call OctavPipeline.sync() first")
-            st["prepared"] = None
-            st["k"] = -1
-        ps["calls"] = 0
-
-    def _prepare(self, ps, st, k, stream):
+    def _prepare(self, rot, st, k, stream):
         """State block + threshold snapshot for this pipeline's call number k on the plan (set `st` lends its rescue block to the
         job; prepare reads no tensors: the pointer table argument is a stand-in)."""
-        r = k % (2 * _PIPE_SETS)
-        job = ps["tp"].bind(ps["states"][r], st["rescue"], ps["list0"][0], ps["list1"], ps["list1"], k, self.dyn)
+        job = rot.tp.bind(st.block(k), st.rescue, rot.list0[0], rot.list1, rot.list1, k, self.dyn)
         _hip.check(_hip.lib().dpl_octav_oneread_prepare(C.byref(job), C.c_void_p(stream)), "dpl_octav_oneread_prepare")
-        st["prepared"] = k
 
-    def _finish(self, plan, ps, st):
+    def _finish(self, rot, st):
         """Side stream: results of the set's batch -> its output rows, the set made ready for its next use, completion event."""
         side = self.side.cuda_stream
-        _hip.check(_hip.lib().dpl_octav_finalize(_ptr(st["states"]), plan.n_pairs, _ptr(st["refs"][2]), side), "dpl_octav_finalize")
-        self._prepare(ps, st, st["k"] + _PIPE_SETS, side)    # off the caller's stream: the set's next use is S calls away
-        st["done"] = torch.cuda.Event()
-        st["done"].record(self.side)
+        _hip.check(_hip.lib().dpl_octav_finalize(_ptr(st.block(st.k)), rot.plan.n_pairs, _ptr(st.refs[2]), side), "dpl_octav_finalize")
+        self._prepare(rot, st, st.k + rot.S, side)    # off the caller's stream: the set's next use is S calls away
+        st.done = self.side.record_event()
 
-    def _settle(self, plan, ps, st):
+    def _settle(self, rot, st):
         """HOST: read the statistics the set's last batch left in pinned memory (the walk finished long ago: the set comes up
         for reuse S submits later).  Nothing is launched here unless pairs are left for the compaction route: the pairs a walk
         could not finish are rescued on the device, without the host (submit)."""
-        if not st["pending"]:
+        if not st.pending:
             return
-        st["pending"] = False
-        st["done"].synchronize()
-        ctl = _hip.OctavState.from_buffer_copy(st["failed"].numpy().tobytes())
+        st.pending = False
+        st.done.synchronize()
+        plan = rot.plan
+        ctl = _hip.OctavState.from_buffer_copy(st.host_states.numpy(), plan.n_pairs * C.sizeof(_hip.OctavState))    # the control block
         # listed values; pairs rescued by a re-read of the pair + pairs that ended on the compaction route
         listed, failed = float(ctl.sum), int(ctl.len0) + int(ctl.cnt_le)
         self.compaction_pairs += int(ctl.cnt_le)
@@ -873,39 +881,36 @@ class OctavPipeline:
             # what neither the walk nor the rescue could finish (a bracket that cannot be formed: flat distributions, values
             # beyond 2^14, a list beyond its region): the compaction route, launched only now that the count is known — the set's
             # batch is S submits old, its tensors are still referenced — on lists with regions for just the pairs that need them
-            # (the states are read back), its results written over the batch's output rows
-            ps["fallback"] = ps["tp"].compaction(st["job"], st["states"], self.side, ps["fallback"], st["host_states"], st["base_host"])
-            self._finish(plan, ps, st)
+            # (laid out from the states in pinned memory), its results written over the batch's output rows
+            rot.fallback = rot.tp.compaction(st.job, st.block(st.k), self.side, rot.fallback, st.host_states, st.base_host)
+            self._finish(rot, st)
 
     def submit(self, plan, tensors):
         form = _default_form()
         tp = plan.octav_tail() if form == "tail" else None
         if tp is None:      # another form was asked for, or a pair above 64 slices: one batch at a time on the caller's stream
             return octav_batch(plan, tensors, bool(self.dyn), form="bracket" if form == "tail" else form)
-        main = torch.cuda.current_stream(plan.device)
-        ps = self._state(plan, tp)
-        sets = ps["sets"]
-        k = ps["calls"]
-        ps["calls"] = k + 1
-        caller = main
+        main = caller = torch.cuda.current_stream(plan.device)
+        rot = self._rotation(plan, tp)
+        k = rot.calls
         if self.lanes:
             main = self.lanes[k % len(self.lanes)]
-        cur = sets[k % _PIPE_SETS]
-        r = k % (2 * _PIPE_SETS)
-        self._settle(plan, ps, cur)
-        if cur["done"] is not None:
-            main.wait_event(cur["done"])        # everything that last used this set has finished
+        cur = rot.sets[k % rot.S]
+        self._settle(rot, cur)
+        if cur.done is not None:
+            main.wait_event(cur.done)           # everything that last used this set has finished
         tab = plan.seg_table(tensors)
         out = torch.empty(plan.batch, plan.T, 3, dtype=torch.float32, device=plan.device)
+        rot.calls = k + 1                       # (only now: a tensor set that seg_table refuses takes no call number)
         if main is not caller:
             main.wait_stream(caller)            # the batch's activations and its pointer table are the caller's stream's work
-        cur["refs"] = (tensors if isinstance(tensors, BoundSet) else list(tensors), tab, out)
-        cur["k"] = k
-        cur["states"] = ps["states"][r]
+        cur.refs = (tensors if isinstance(tensors, BoundSet) else list(tensors), tab, out)
         L = _hip.lib()
-        if cur.get("prepared") != k:
-            self._prepare(ps, cur, k, main.cuda_stream)
-        job = cur["job"] = tp.bind(cur["states"], cur["rescue"], ps["list0"][k % len(ps["list0"])], ps["list1"], tab, k, self.dyn)
+        if cur.k < 0:       # (a set used before finds its block prepared: its last call, k - S, ended on _finish)
+            self._prepare(rot, cur, k, main.cuda_stream)
+        cur.k = k
+        state = cur.block(k)
+        job = cur.job = tp.bind(state, cur.rescue, rot.list0[k % len(rot.list0)], rot.list1, tab, k, self.dyn)
         if self.record_events:
             began = torch.cuda.Event(enable_timing=True)
             began.record(main)
@@ -918,31 +923,24 @@ class OctavPipeline:
         # the rescue of the pairs a walk could not finish, on the device: no host round trip decides anything
         _hip.check(L.dpl_octav_oneread_finish(C.byref(job), C.c_void_p(self.side.cuda_stream)), "dpl_octav_oneread_finish")
         with torch.cuda.stream(self.side):
-            cur["failed"].copy_(ps["failed"][r], non_blocking=True)    # (statistics, and whether the compaction route is needed: _settle)
-            # ... which lays its lists out from the pairs' states: 80 bytes per pair behind every batch (315 KB for a ResNet-50
-            # batch) instead of a read-back — a host synchronisation with the side stream, 0.3 ms of an idle caller's stream —
-            # when a batch asks for the route
-            cur["host_states"].copy_(cur["states"][:cur["host_states"].numel()], non_blocking=True)
-        self._finish(plan, ps, cur)
-        cur["pending"] = True
-        if all(p is not plan for p in self._touched):
-            self._touched.append(plan)
+            # the pairs' states and the control block behind them — statistics, and whether the compaction route is needed, which
+            # lays its lists out from the states (_settle): 80 bytes per pair behind every batch instead of a read-back
+            cur.host_states.copy_(state[:cur.host_states.numel()], non_blocking=True)
+        self._finish(rot, cur)
+        cur.pending = True
         return out
 
     def sync(self):
         """Settle every outstanding batch (host waits for the walks), order the caller's stream after the side stream and
         let go of the batches' tensors."""
-        for plan in self._touched:
-            ps = self._plans[id(plan)]
-            for st in sorted(ps["sets"], key=lambda q: q["k"]):
-                self._settle(plan, ps, st)
-        torch.cuda.current_stream(self.device).wait_stream(self.side)
-        for lane in self.lanes:
-            torch.cuda.current_stream(self.device).wait_stream(lane)
-        for plan in self._touched:
-            for st in self._plans[id(plan)]["sets"]:
-                st["refs"] = None
-        self._touched = []
+        for rot in self._plans.values():
+            for st in sorted(rot.sets, key=lambda q: q.k):
+                self._settle(rot, st)
+        for stream in [self.side] + self.lanes:
+            torch.cuda.current_stream(self.device).wait_stream(stream)
+        for rot in self._plans.values():
+            for st in rot.sets:
+                st.refs = None
 
 
 # ------------------------------------------------------------------------------- single-tensor conveniences

@@ -31,7 +31,7 @@ def sweep(pipe, plan, pool, tag, reps=3):
 
 if variant == "l1state_l2_l1":
     p1 = ops.OctavPipeline(False, dev, lanes=1)
-    p1._state(plan, plan.octav_tail())
+    p1._rotation(plan, plan.octav_tail())
 if variant != "l1":
     p2 = ops.OctavPipeline(False, dev, lanes=2)
     sweep(p2, plan, pool, "two lanes")

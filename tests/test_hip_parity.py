@@ -919,6 +919,45 @@ def test_two_pipelines_share_a_plan(dev, monkeypatch):
             assert _close(got[..., 0], want[k][..., 0]), k
 
 
+@pytest.mark.parametrize("lanes", [1, 2])
+def test_pipeline_survives_octav_reset(dev, monkeypatch, lanes):
+    """One pipeline reused across TensorSetPlan.octav_reset() — what every timed sweep of the benchmark does: the reset is
+    refused while batches are in flight and leaves them to finish with the right rows; after sync() it zeroes the threshold
+    history, the rotation starts over, and the same batches give the same rows again (a small pair, a one-slice pair and a
+    whole-window pair; five batches: more than S + 1, so every set is reused on both sides of the reset)."""
+    from dipoorlet_amd import _hip, ops
+    monkeypatch.setenv("DPL_OCTAV_FORM", "tail")
+    rng = np.random.default_rng(79)
+    B, sizes = 2, [30000, 200704, 777]
+    batches = [[torch.from_numpy((rng.standard_normal((B, n)) * (1 + t + 0.2 * k)).astype(np.float32)).to(dev) for t, n in enumerate(sizes)]
+               for k in range(5)]
+    want = [ops.octav_batch(ops.TensorSetPlan(sizes, B, dev), x, False, form="bracket").cpu().numpy() for x in batches]
+
+    def same_rows(rows):
+        for k, (o, w) in enumerate(zip(rows, want)):
+            got = o.cpu().numpy()
+            assert np.array_equal(got[..., 1:], w[..., 1:]), k
+            assert _close(got[..., 0], w[..., 0]), k
+    plan = ops.TensorSetPlan(sizes, B, dev)
+    pipe = ops.OctavPipeline(False, dev, lanes=lanes)
+    pipe.record_events = True
+    rows = [pipe.submit(plan, x) for x in batches]
+    with pytest.raises(_hip.DipoorletHipError):
+        plan.octav_reset()                          # batches in flight
+    pipe.sync()
+    torch.cuda.synchronize()
+    same_rows(rows)
+    assert pipe.batches == 5 and len(pipe.events) == 5
+    assert all(began.elapsed_time(streamed) > 0 for began, streamed in pipe.events)
+    plan.octav_reset()
+    pipe.reset_stats()
+    assert not plan.octav_tail().history.any().item()
+    rows = [pipe.submit(plan, x) for x in batches]
+    pipe.sync()
+    same_rows(rows)
+    assert pipe.batches == 5 and pipe.compaction_pairs == 0
+
+
 @pytest.mark.parametrize("hook", ["exact", "rescue"])
 def test_two_pipelines_rescue_at_once(dev, monkeypatch, hook):
     """Two pipelines on ONE plan whose walks are refused for every second pair (the C ABI's test hooks) rescue the same pair
