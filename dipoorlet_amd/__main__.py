@@ -1,5 +1,5 @@
 """`python -m dipoorlet_amd -M model.onnx -I calib_dir -N 1024 -A hist -D trt` — the reference's CLI
-(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, and `-D ocp_fp8`, static OCP FP8 E4M3 scales, are this project's additions).
+(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, and `-D ocp_fp8`, static OCP FP8 E4M3 scales, are this project's additions).
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
@@ -30,12 +30,14 @@ def build_parser():
     for flag in ("--we", "--bc", "--update_bn", "--adaround", "--brecq", "--drop", "--savefp", "--stpu_wg",
                  "--skip_prof_layer", "--slurm", "--mpirun", "--sparse", "--optim_transformer"):
         p.add_argument(flag, default=False, action="store_true")
-    p.add_argument("-A", "--act_quant", choices=["minmax", "hist", "mse", "kl"], default="mse",
+    p.add_argument("-A", "--act_quant", choices=["minmax", "hist", "mse", "kl", "qmse"], default="mse",
                    help="minmax / hist: bit-exact clip ranges; mse (OCTAV): within 1e-5 * max(1, |ref|) of the reference's, repeating "
                         "to about 1e-6 relative from run to run (DPL_OCTAV_FORM=bracket: the bit-stable two-read form); kl: entropy "
-                        "search on the |x| histogram (not in the reference; honours --bins, ignores --threshold)")
+                        "search on the |x| histogram (not in the reference; honours --bins, ignores --threshold); qmse: the clip of least "
+                        "quantisation error of that histogram on the platform's own grid, integer or FP8 (not in the reference; -D trt, "
+                        "stpu, ocp_fp8; honours --bins, ignores --threshold)")
     p.add_argument("-D", "--deploy", choices=["trt", "stpu", "magicmind", "rv", "atlas", "snpe", "ti", "imx", "ocp_fp8"],
-                   required=True, help="ocp_fp8 (not in the reference): static OCP FP8 E4M3 scales, clip / 448; with -A minmax or -A hist")
+                   required=True, help="ocp_fp8 (not in the reference): static OCP FP8 E4M3 scales, clip / 448; with -A minmax, -A hist or -A qmse")
     p.add_argument("--bins", default=2048, type=int)  # the reference omits type= and crashes on a CLI value
     p.add_argument("--threshold", default=0.99999, type=float)
     p.add_argument("--ada_bs", type=int, default=64)
@@ -62,18 +64,28 @@ def build_parser():
 
 
 def check_args(args):
-    """What a platform cannot do, said before any device work.  A floating-point grid (`-D ocp_fp8`) is reached through the
+    """What a platform cannot do, said before any device work.  `-A qmse` models a symmetric grid with a free scale and a fixed
+    sign: the integer grid of `-D trt` / `stpu` and the E4M3 codes of `-D ocp_fp8`.  A floating-point grid (`-D ocp_fp8`) is reached through the
     FakeQuant nodes only: the clip sweeps that know nothing of the grid and the transforms that run the fake-quantised forward
     work unchanged; what assumes or learns an integer grid does not."""
     from .platform_settings import platform_setting_table
-    if not platform_setting_table[args.deploy]["qi_params"]["type"].startswith("Float8"):
+    qi = platform_setting_table[args.deploy]["qi_params"]
+    if args.act_quant == "qmse":
+        # the search models ONE grid per format: symmetric about zero, any real scale, the sign fixed
+        why = ("its activations are asymmetric (a zero point)" if not qi["symmetric"] else
+               "its activation scales are powers of two (log_scale)" if qi.get("log_scale") else
+               "the sign of its activations is decided per tensor (dynamic_sym)" if "dynamic_sym" in qi else None)
+        if why:
+            raise ValueError(f"-A qmse is not supported with -D {args.deploy}: {why}, and the search models a symmetric grid with a "
+                             "free scale.  Supported: -D trt, -D stpu, -D ocp_fp8")
+    if not qi["type"].startswith("Float8"):
         return
     bad = [flag for flag, on in (("-A mse", args.act_quant == "mse"),        # OCTAV's fixed point assumes a uniform grid
                                  ("-A kl", args.act_quant == "kl"),          # its levels are integer levels
                                  ("--adaround", args.adaround), ("--brecq", args.brecq), ("--sparse", args.sparse)) if on]
     if bad:     # (the three transforms learn integer rounding)
         raise ValueError(f"-D {args.deploy} is a floating-point grid: {', '.join(bad)} not supported (they assume or learn an integer "
-                         "grid).  Supported: -A minmax, -A hist, --bc, --we, --update_bn and profiling")
+                         "grid).  Supported: -A minmax, -A hist, -A qmse, --bc, --we, --update_bn and profiling")
 
 
 def main(argv=None):

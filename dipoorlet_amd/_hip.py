@@ -15,8 +15,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPL_LIB: another build of the same sources (the host-sanitizer build of scripts/asan_host_check.sh); never a different code path
 LIB_PATH = os.environ.get("DPL_LIB") or os.path.join(_HERE, "csrc", "libdipoorlet_hip.so")
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 MAX_BINS = 16384
+GRID_UNIFORM, GRID_E4M3 = 0, 1          # DPL_GRID_*: the grids of dpl_hist_qmse
 HIST_SPEC_MAX_TENSORS = 2048
 
 
@@ -101,6 +102,7 @@ SIGNATURES = {
     "dpl_hist_spec_cuts": (C.c_int, [_P, _P, _I64, _I64, _P, _P]),
     "dpl_hist_percentile": (C.c_int, [_P, _P, _P, _I64, C.c_int, _DBL, _P, _P]),
     "dpl_hist_kl": (C.c_int, [_P, _P, _P, _I64, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "dpl_hist_qmse": (C.c_int, [_P, _P, _P, _I64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "dpl_octav_init": (C.c_int, [_P, _I64, C.c_int, _P]),
     "dpl_octav_run_compact": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "dpl_octav_run": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _I64, C.c_int, C.c_int, _P]),

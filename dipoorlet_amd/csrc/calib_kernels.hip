@@ -749,6 +749,89 @@ __global__ __launch_bounds__(kWave) void k_hist_kl_pick(const double* __restrict
     }
 }
 
+// ================================================================ K4c: quantisation-MSE clip — beyond the reference
+// The definition is this project's own (tests/qmse_model.py), in units of half a bin width: bin b's centre is
+// m = 2 b + 1, candidate i in [first, bins] clips at t = 2 i - 1 (the centre of bin i - 1) with scale t / top; u = m top / t,
+// Q = the grid point nearest to min(u, top), and out[i] = sum_b h[b] (u - Q)^2 * (t / (2 top))^2 / N.  The grid is a
+// compile-time parameter: the integers 0 .. top, or the non-negative finite E4M3 codes (top = 448).
+//
+// Geometry of k_hist_kl: grid = (candidate chunk, tensor); the tensor's row staged once in LDS, here as fp64 counts (exact:
+// < 2^53; 8 B per bin, 128 KB at 16384 bins); one wave per candidate at a time, lanes own bins, bins without a count skipped.
+// Per bin everything but the choice of Q is exact in fp64: a = unit m top and Q' t (unit = 1, or 512 on E4M3, whose codes are
+// multiples of 2^-9: Q' = 512 Q) are integers below 2^53, so unit (u - Q) t = a - Q' t carries no rounding, whichever Q was
+// chosen.  The choice itself, from u = a * fl(1 / t) (the reciprocal is wave-uniform and stays out of the loop), is the right
+// one: u is within 3 ulp of the quotient (1e-11 at most, u <= top <= 32767 being all that matters), and no quotient comes
+// nearer to a midpoint of the grid than 1 / (2 t) > 1e-5 (uniform) or 1 / (1024 t) > 1e-8 (E4M3), never onto one
+// (qmse_model.py).  E4M3 in fp64: the
+// exponent field, clamped at the subnormal binade, gives the power-of-two step; rint does the rest.  Saturation (u >= top) is
+// the same formula.  Every candidate costs the same: they are dealt round-robin.  A lane adds its bins in ascending order, the
+// 64 partial sums meet in the fixed wave_sum tree, one lane stores: no floating-point atomics, two calls give the same bits,
+// and a candidate's value does not depend on the launch's geometry.
+constexpr int kGridUniform = DPL_GRID_UNIFORM, kGridE4M3 = DPL_GRID_E4M3;
+
+template <int GRID>
+__global__ __launch_bounds__(kBlock) void k_hist_qmse(const uint64_t* __restrict__ hist, int bins, int first, int top, int n_chunks,
+                                                       double* __restrict__ err) {
+    extern __shared__ __attribute__((aligned(16))) double qm_lds[];
+    double* hd = qm_lds;                                            // [bins] the counts
+    uint64_t* part = reinterpret_cast<uint64_t*>(hd + bins);        // [kBlock / kWave] the waves' totals
+    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const uint32_t slot = blockIdx.x / (uint32_t)n_chunks, chunk = blockIdx.x % (uint32_t)n_chunks;
+    const uint64_t* __restrict__ h = hist + (uint64_t)slot * (uint64_t)bins;
+    double* __restrict__ out = err + (uint64_t)slot * ((uint64_t)bins + 1u);
+    const uint32_t F = (uint32_t)first, C = (uint32_t)n_chunks, nb = (uint32_t)bins;
+
+    uint64_t s = 0;
+    for (uint32_t b = tid; b < nb; b += kBlock) {
+        const uint64_t v = h[b];
+        s += v;
+        hd[b] = (double)(long long)v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);   // (integers: any order)
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    uint64_t N = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / kWave; ++w) N += part[w];
+
+    // ---- candidates below `first` are not searched
+    for (uint32_t i = chunk + tid * C; i < F; i += kBlock * C) out[i] = INFINITY;
+
+    constexpr double unit = GRID == kGridE4M3 ? 512.0 : 1.0;
+    const double dtop = GRID == kGridE4M3 ? 448.0 : (double)top;
+    const double atop = unit * dtop;                                // a = m * atop
+    const double norm = (double)(long long)N * (4.0 * atop * atop);
+    for (uint32_t i = F + chunk + wave * C; i <= nb; i += (kBlock / kWave) * C) {
+        const double t = (double)(2u * i - 1u);
+        const double rt = 1.0 / (unit * t);                         // u = a * rt
+        double acc = 0.0;
+        if (N != 0ull) {
+            for (uint32_t b = lane; b < nb; b += kWave) {
+                const double hb = hd[b];
+                if (hb != 0.0) {
+                    const double a = (double)(2u * b + 1u) * atop;
+                    const double v = fmin(a * rt, dtop);
+                    double q;                                       // unit * Q
+                    if (GRID == kGridE4M3) {
+                        int e = (int)((__double_as_longlong(v) >> 52) & 0x7FF) - 1023;      // v's binade (v > 0)
+                        e = e < -6 ? -6 : e;                        // the subnormal binade's step: 2^-9
+                        const double istep = __longlong_as_double((long long)(1023 + 3 - e) << 52);      // 1 / step = 2^(3 - e)
+                        const double step512 = __longlong_as_double((long long)(1023 + 9 - 3 + e) << 52);  // 512 step
+                        q = rint(v * istep) * step512;
+                    } else {
+                        q = rint(v);
+                    }
+                    const double dt = a - q * t;                    // unit * (u - Q) * t, exact
+                    acc += hb * (dt * dt);
+                }
+            }
+            acc = wave_sum(acc);
+        }
+        if (lane == 0) out[i] = N != 0ull ? acc / norm : INFINITY;
+    }
+}
+
 // ================================================================ K5: per-row min / max of a [rows, cols] matrix
 __global__ __launch_bounds__(kBlock) void k_rowwise_minmax(const float* __restrict__ w, int64_t cols,
                                                             float* __restrict__ omn, float* __restrict__ omx) {
@@ -1504,6 +1587,33 @@ int dpl_hist_kl(const uint64_t* d_hist, const float* d_min, const float* d_max, 
                        (int)chunks, d_div);
     DPL_LAUNCH_CHECK("k_hist_kl");
     hipLaunchKernelGGL(k_hist_kl_pick, dim3((unsigned)n_slots), dim3(kWave), 0, (hipStream_t)s, d_div, d_min, d_max, bins,
+                       d_best, d_clip);
+    DPL_LAUNCH_CHECK("k_hist_kl_pick");
+    return 0;
+}
+
+int dpl_hist_qmse(const uint64_t* d_hist, const float* d_min, const float* d_max, int64_t n_slots, int bins, int first, int grid,
+                  int top, double* d_err, int32_t* d_best, float* d_clip, dpl_stream_t s) {
+    if (bins < 1 || bins > DPL_MAX_BINS) return fail_msg("dpl_hist_qmse: bins must be in [1, 16384]");
+    if (first < 1 || first > bins) return fail_msg("dpl_hist_qmse: first must be in [1, bins]");
+    if (grid != DPL_GRID_UNIFORM && grid != DPL_GRID_E4M3) return fail_msg("dpl_hist_qmse: grid must be DPL_GRID_UNIFORM or DPL_GRID_E4M3");
+    if (grid == DPL_GRID_UNIFORM && (top < 1 || top > 32767)) return fail_msg("dpl_hist_qmse: top must be in [1, 32767] on the uniform grid");
+    if (grid == DPL_GRID_E4M3 && top != 0) return fail_msg("dpl_hist_qmse: top must be 0 on the E4M3 grid (its largest value is 448)");
+    if (n_slots <= 0) return 0;
+    // candidate chunks per tensor: about 1024 workgroups per launch, and no fewer than eight candidates per workgroup
+    const int64_t n_cand = (int64_t)bins - first + 1;
+    int64_t chunks = (1024 + n_slots - 1) / n_slots;
+    if (chunks > n_cand / 8) chunks = n_cand / 8;
+    if (chunks < 1) chunks = 1;
+    if (n_slots * chunks > 0x7FFFFFFFll) return fail_msg("dpl_hist_qmse: too many slots");
+    const size_t lds = (size_t)bins * sizeof(double) + (kBlock / kWave) * sizeof(uint64_t);
+    const dim3 wgs((unsigned)(n_slots * chunks));
+    if (grid == DPL_GRID_E4M3)
+        hipLaunchKernelGGL(k_hist_qmse<kGridE4M3>, wgs, dim3(kBlock), lds, (hipStream_t)s, d_hist, bins, first, top, (int)chunks, d_err);
+    else
+        hipLaunchKernelGGL(k_hist_qmse<kGridUniform>, wgs, dim3(kBlock), lds, (hipStream_t)s, d_hist, bins, first, top, (int)chunks, d_err);
+    DPL_LAUNCH_CHECK("k_hist_qmse");
+    hipLaunchKernelGGL(k_hist_kl_pick, dim3((unsigned)n_slots), dim3(kWave), 0, (hipStream_t)s, d_err, d_min, d_max, bins,
                        d_best, d_clip);
     DPL_LAUNCH_CHECK("k_hist_kl_pick");
     return 0;

@@ -345,6 +345,16 @@ class _LedgerRecord(collections.namedtuple("_LedgerRecord", "ref entry T")):
     __slots__ = ()
 
 
+def qmse_grid(qtype, bit_width=8):
+    """(grid, top) of dpl_hist_qmse for a platform's qi_params["type"]: "Linear" — the integers up to 2 ** (bit_width - 1) - 1,
+    quantize._symmetric_grid's — or "Float8E4M3FN" (the format's own codes: top is not an argument)."""
+    if qtype == "Linear":
+        return _hip.GRID_UNIFORM, 2 ** (int(bit_width) - 1) - 1
+    if qtype == "Float8E4M3FN":
+        return _hip.GRID_E4M3, 0
+    raise _hip.DipoorletHipError(f"hist_qmse: no grid for quantisation type {qtype!r} (Linear or Float8E4M3FN)")
+
+
 class CalibAccumulators:
     """Persistent per-tensor statistics on the device.
 
@@ -552,6 +562,20 @@ class CalibAccumulators:
         _hip.check(_hip.lib().dpl_hist_kl(_ptr(self.hist), _ptr(self.gmin), _ptr(self.gmax), self.n, self.bins, levels,
                                           _ptr(div), _ptr(best), _ptr(clip), _stream()), "dpl_hist_kl")
         return clip, best, div
+
+    def hist_qmse(self, qtype, bit_width=8, first=128):
+        """Quantisation-MSE clip search on the accumulated histograms (k_hist_qmse; the definition: tests/qmse_model.py): the
+        bin centres fake-quantised on the grid of `qtype` (a platform's qi_params["type"]: "Linear" — the integers up to
+        2 ** (bit_width - 1) - 1 — or "Float8E4M3FN") for every candidate "keep `i` bins", i in [first, bins]
+        -> (clip [n, 2] fp32, best [n] int32: the bins kept, -1 for an empty histogram, whose clip is the range,
+        err [n, bins + 1] fp64: every candidate's mean squared error in bin widths^2, +inf below `first`)."""
+        grid, top = qmse_grid(qtype, bit_width)
+        clip = torch.empty(self.n, 2, dtype=torch.float32, device=self.device)
+        best = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        err = torch.empty(self.n, self.bins + 1, dtype=torch.float64, device=self.device)
+        _hip.check(_hip.lib().dpl_hist_qmse(_ptr(self.hist), _ptr(self.gmin), _ptr(self.gmax), self.n, self.bins, int(first), grid, top,
+                                            _ptr(err), _ptr(best), _ptr(clip), _stream()), "dpl_hist_qmse")
+        return clip, best, err
 
 
 _OCTAV_MAX_ITERS = 20  # forward_net.py:325

@@ -1,7 +1,7 @@
 """Activation clip-range search: the three registry algorithms of the reference
 (dipoorlet/tensor_cali/basic_algorithm.py:8-69) plus the per-channel weight ranges (:72-91), computed
-on the MI355X — and, in a registry of its own (tensor_cali_extensions), the entropy search `kl` the reference
-never shipped.
+on the MI355X — and, in registries of their own, the entropy search `kl` the reference never shipped
+(tensor_cali_extensions) and the quantisation-MSE search `qmse` on the platform's own grid (tensor_cali_grid_aware).
 
 Registry keys, call form and return type are the reference's: `tensor_cali_dispatcher(key, graph, args)`
 -> {tensor_name: [lo, hi]} with numpy scalars (they must support .tolist(), utils.py:314-316); an
@@ -32,6 +32,13 @@ def tensor_cali_dispatcher(*args, **kwargs):
 def tensor_cali_extensions(*args, **kwargs):
     """Algorithms beyond the reference's three: same call form as tensor_cali_dispatcher, a registry of its own (the reference
     answers their keys with "Calibration Algorithm Not Found!", and tensor_cali_dispatcher keeps doing so)."""
+    logger.info("Calibration Algorithm Not Found!")
+
+
+@dispatch_functool
+def tensor_cali_grid_aware(*args, **kwargs):
+    """Algorithms whose answer depends on the platform's number format (its qi_params): same call form, a registry of its own —
+    tensor_cali_extensions holds the format-blind additions."""
     logger.info("Calibration Algorithm Not Found!")
 
 
@@ -113,6 +120,23 @@ def find_clip_val_kl(onnx_graph, args, store_stats=None, run=None, **kwargs):
         raise ValueError(f"-A kl needs --bins >= {levels} (the quantisation levels of '{args.deploy}'), got {int(args.bins)}")
     acc, names = _hist_statistics(onnx_graph, args, store_stats, run)
     clip, _, _ = acc.hist_kl(levels)
+    return _as_clip_dict(names, clip[:, 0], clip[:, 1])
+
+
+@tensor_cali_grid_aware.register("qmse")
+def find_clip_val_qmse(onnx_graph, args, store_stats=None, run=None, **kwargs):
+    """Quantisation-MSE calibration — not in the reference, whose `mse` is OCTAV (a per-image fixed point, for a uniform grid):
+    the clip of least mean squared error when the centres of the |x| histogram's bins are fake-quantised on the platform's own
+    activation grid — the integers of its bit width, or the OCP FP8 E4M3 codes of `-D ocp_fp8` — for every candidate bin.  The
+    definition is this project's (tests/qmse_model.py), searched on the device in one launch (k_hist_qmse) over the
+    very histograms `-A hist` accumulates — same sweeps, same merge over ranks, same store_stats hook.
+    args.threshold is not used; the lowest candidate is the platform's level count (128), which args.bins must reach."""
+    first = kl_levels(args.deploy)
+    if int(args.bins) < first:
+        raise ValueError(f"-A qmse needs --bins >= {first} (the quantisation levels of '{args.deploy}'), got {int(args.bins)}")
+    qi = platform_setting_table[args.deploy]["qi_params"]
+    acc, names = _hist_statistics(onnx_graph, args, store_stats, run)
+    clip, _, _ = acc.hist_qmse(qi["type"], qi["bit_width"], first)
     return _as_clip_dict(names, clip[:, 0], clip[:, 1])
 
 

@@ -4,7 +4,7 @@ from . import basic_algorithm as _algo
 
 def tensor_calibration(onnx_graph, args):
     """-> (activation clip ranges from the algorithm registered under args.act_quant — in the reference's registry or, for
-    keys beyond it ('kl'), in tensor_cali_extensions —, per-channel weight ranges).
+    keys beyond it, in tensor_cali_extensions ('kl') or tensor_cali_grid_aware ('qmse') —, per-channel weight ranges).
     Every rank calls this; the activation statistics are merged over ranks inside the algorithm.
 
     The reference walks the initializers for the weight ranges and then lets the algorithm build its ORT session
@@ -14,10 +14,11 @@ def tensor_calibration(onnx_graph, args):
     from ..forward_net import WALL, CalibrationRun, wall
     WALL.clear()      # (the host-wall breakdown --timing_json reports is this calibration's, not the process's)
     run = None
-    # a reference key goes to the reference's registry; any other to the extensions', whose default is the reference's answer
-    registry = _algo.tensor_cali_dispatcher
-    if args.act_quant not in registry.registry:
-        registry = _algo.tensor_cali_extensions
+    # the three registries in turn: the reference's, the extensions', the grid-aware; a key none of them holds gets the last
+    # one's default, which is the reference's answer
+    for registry in (_algo.tensor_cali_dispatcher, _algo.tensor_cali_extensions, _algo.tensor_cali_grid_aware):
+        if args.act_quant in registry.registry:
+            break
     if args.act_quant in registry.registry:
         run = CalibrationRun(onnx_graph, args)
     try:

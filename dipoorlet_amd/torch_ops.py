@@ -8,6 +8,7 @@ Per tensor:
     dipoorlet::abs_hist_(Tensor x, float dmax, int bins, Tensor(a!) hist) -> ()      hist += np.histogram(|x|, bins, (0, dmax))
     dipoorlet::hist_percentile(Tensor hist, float gmin, float gmax, float threshold) -> Tensor   [2] fp32 clip
     dipoorlet::hist_kl(Tensor hist, float gmin, float gmax, int levels) -> Tensor                [2] fp32 clip (entropy search)
+    dipoorlet::hist_qmse(Tensor hist, float gmin, float gmax, str qtype, int bit_width, int first) -> Tensor   [2] fp32 clip (quantisation-MSE search)
     dipoorlet::octav(Tensor x, bool dynamic_sym) -> Tensor     [3] fp32 (s, min, max) (forward_net.py:315-330)
     dipoorlet::rowwise_minmax(Tensor w2d) -> (Tensor, Tensor)
     dipoorlet::fake_quant(Tensor x, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor
@@ -195,6 +196,26 @@ def hist_kl(hist: torch.Tensor, gmin: float, gmax: float, levels: int) -> torch.
 
 @hist_kl.register_fake
 def _(hist, gmin, gmax, levels):
+    return hist.new_empty(2, dtype=torch.float32)
+
+
+@torch.library.custom_op("dipoorlet::hist_qmse", mutates_args=(), device_types="cuda")
+def hist_qmse(hist: torch.Tensor, gmin: float, gmax: float, qtype: str, bit_width: int, first: int) -> torch.Tensor:
+    if hist.dtype != torch.int64 or not hist.is_contiguous():
+        raise ValueError("hist must be a contiguous int64 tensor")
+    bins = hist.numel()
+    grid, top = ops.qmse_grid(qtype, bit_width)
+    rng = _range_of(hist, gmin, gmax)
+    clip = torch.empty(2, dtype=torch.float32, device=hist.device)
+    best = torch.empty(1, dtype=torch.int32, device=hist.device)
+    err = torch.empty(bins + 1, dtype=torch.float64, device=hist.device)      # (the search's workspace: an output of the C ABI)
+    _hip.check(_hip.lib().dpl_hist_qmse(ops._ptr(hist), ops._ptr(rng[0:1]), ops._ptr(rng[1:2]), 1, bins, int(first), grid, top,
+                                        ops._ptr(err), ops._ptr(best), ops._ptr(clip), ops._stream()), "dpl_hist_qmse")
+    return clip
+
+
+@hist_qmse.register_fake
+def _(hist, gmin, gmax, qtype, bit_width, first):
     return hist.new_empty(2, dtype=torch.float32)
 
 

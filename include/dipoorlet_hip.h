@@ -25,9 +25,10 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 24 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 25 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
-                              24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid) */
+                              24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
+                              25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -164,6 +165,21 @@ int dpl_hist_percentile(const uint64_t* d_hist, const float* d_min, const float*
  *      2 <= levels <= bins <= DPL_MAX_BINS.  No floating-point atomics: two calls give the same bits. */
 int dpl_hist_kl(const uint64_t* d_hist, const float* d_min, const float* d_max, int64_t n_slots, int bins,
                 int levels, double* d_div, int32_t* d_best, float* d_clip, dpl_stream_t s);
+
+/* ---- quantisation-MSE clip on the same histogram, on the platform's own grid: beyond the reference, whose "mse" is OCTAV (a
+ *      per-image fixed point).  In units of half a bin width: bin b's centre is m = 2 b + 1, candidate i in [first, bins] clips at
+ *      t = 2 i - 1 (the centre of bin i - 1) with scale t / top; u = m top / t, Q = the grid point nearest to min(u, top), and
+ *      err[i] = (t / (2 top))^2 sum_b h[b] (u - Q)^2 / N: the mean squared error of the fake-quantised bin centres, in bin
+ *      widths^2.  grid = DPL_GRID_UNIFORM: the integers 0 .. top, 1 <= top <= 32767 (127 for 8 bits); DPL_GRID_E4M3: the 127
+ *      non-negative finite OCP FP8 E4M3 codes, largest 448, and `top` must be 0.  The clip is the centre of bin i* - 1 for the
+ *      lowest i* of least error, in fp32 as dpl_hist_percentile ends.  The definition is tests/qmse_model.py.
+ *      d_err fp64 [n_slots, bins + 1] is caller-provided workspace AND output (+inf for i < first, and everywhere for an empty
+ *      histogram); d_best int32 [n_slots] (i*, -1: none -> the clip is [min, max]); d_clip fp32 [n_slots, 2].
+ *      1 <= first <= bins <= DPL_MAX_BINS.  No floating-point atomics: two calls give the same bits. */
+#define DPL_GRID_UNIFORM 0
+#define DPL_GRID_E4M3 1
+int dpl_hist_qmse(const uint64_t* d_hist, const float* d_min, const float* d_max, int64_t n_slots, int bins,
+                  int first, int grid, int top, double* d_err, int32_t* d_best, float* d_clip, dpl_stream_t s);
 
 /* ---- OCTAV ("mse"): replaces forward_net.py:315-330 per (image,tensor) pair (slot = pair).
  *      dpl_octav_run enqueues the first pass plus 20 (pass, update) rounds; converged pairs exit early. */
