@@ -9,6 +9,9 @@ QuantizeLinear -> DequantizeLinear pair, quantize.QDQNode) run on k_fake_quant.
 Batching: the reference feeds one image per forward (model input batch dim 1).  Here B images are
 stacked on dim 0; Reshape targets and dim-0 broadcasts that were constant-folded for batch 1 are
 re-scaled to B.
+
+One dispatcher: GraphSession.schedule() lists the Steps of a pass; a whole-batch forward (GraphSession._forward) and the
+node-major walks of the weight transforms (Frontier) both run them, so a fusion is taught to the schedule alone.
 """
 import atexit
 import os
@@ -651,6 +654,34 @@ def relu_fusion(graph, folded, consts, keep=(), shape1=None):
     return fused, skipped
 
 
+def run_op(s, node, *args):
+    """The executor's op for `node`: the one place the op table is indexed, at each call (entries are replaced on live sessions)."""
+    return _OPS[node.op_type](s, node, *args)
+
+
+class Step:
+    """One node that runs, and how: on its own (`pre` None: it reads node.input, live — --bc appends a bias input in the middle
+    of a walk), or — a FakeQuant node with `pre` 'relu' / 'add_relu' — with its producers' ReLU / Add + ReLU inside its kernel,
+    reading `ins`, their inputs (relu_fusion).  Calling it is the dispatch of GraphSession's forward and of the Frontier's walk:
+    inputs from fetch(name), outputs as a list; the op and fused_fake_quant are looked up at the call (both are replaced on
+    live sessions)."""
+    __slots__ = ("node", "pre", "ins")
+
+    def __init__(self, node, pre=None, ins=None):
+        self.node, self.pre, self.ins = node, pre, ins
+
+    @property
+    def inputs(self):
+        return self.node.input if self.pre is None else self.ins
+
+    def __call__(self, s, fetch):
+        args = [fetch(i) if i != "" else None for i in self.inputs]
+        while args and args[-1] is None:
+            args.pop()
+        out = run_op(s, self.node, *args) if self.pre is None else fused_fake_quant(s, self.node, self.pre, *args)
+        return list(out) if isinstance(out, (list, tuple)) else [out]
+
+
 class GraphSession(ActivationSession):
     """All-outputs session over an ONNXGraph."""
 
@@ -666,6 +697,10 @@ class GraphSession(ActivationSession):
         self.device = torch.device(device)
         self.batch = 1
         self.consts = {}
+        self.shape1, self.tensor_names, self.elems_per_image = None, [], []   # per-image shapes / exposed tensors: _infer
+        self._prewarmed, self._conv_threads = False, None   # prewarm_convs' threads, until the first forward has joined them
+        self._consts_host = self._consts_copied = None      # the pinned source of the initializers until their copy has run
+        self._fusion_cache, self._schedules = {}, {}        # per frozenset(keep) (the schedules: None too)
         if self.device.type == "cuda":
             warm_libraries(self.device, blas=first_batch is None)     # (no-op for what the CLI has started already)
         missing = sorted({n.op_type for n in graph.graph.node if n.op_type not in _OPS})
@@ -674,11 +709,13 @@ class GraphSession(ActivationSession):
         self.expose_fake_quant = expose_fake_quant
         self.input_names = list(graph.network_inputs)
         # fake-quantised WEIGHTS are constants: quantise them once here instead of on every forward
-        self._folded = set()
         self._batched_ok = None   # decided by batched_ok() at the first batched run
         fold = [n for n in graph.graph.node if n.op_type == "FakeQuant" and n.input[0] in graph.initializer]
+        self._folded = {n.name for n in fold}
+        self._folded_by_out = {n.output[0]: n for n in fold}
+        self._folded_by_in = {}
         for node in fold:
-            self._folded.add(node.name)
+            self._folded_by_in.setdefault(node.input[0], []).append(node)
         # shapes first (host rules: no device work), so that the libraries' first calls for THIS graph start before the weights
         # travel; a graph the rules do not cover needs its weights on the device for the batch-1 forward that replaces them
         uploaded = False
@@ -722,9 +759,8 @@ class GraphSession(ActivationSession):
         """Shape of an initializer, of a folded fake-quantised one, or of an activation at `batch` images; None if unknown."""
         if name in self.graph.initializer:
             return tuple(np.asarray(self.graph.initializer[name]).shape)
-        for node in self.graph.graph.node:
-            if node.name in self._folded and node.output[0] == name:
-                return tuple(np.asarray(self.graph.initializer[node.input[0]]).shape)
+        if name in self._folded_by_out:
+            return tuple(np.asarray(self.graph.initializer[self._folded_by_out[name].input[0]]).shape)
         shp = self.shape1.get(name)
         return None if shp is None else (batch * shp[0],) + tuple(shp[1:])
 
@@ -738,7 +774,7 @@ class GraphSession(ActivationSession):
         ws = [self.consts[n.input[0]] for n in nodes]
         if self.device.type != "cuda" or not all(w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.numel() > 0 for w in ws):
             for n, w in zip(nodes, ws):
-                self.consts[n.output[0]] = _OPS["FakeQuant"](self, n, w) if w.is_cuda else w
+                self.consts[n.output[0]] = run_op(self, n, w) if w.is_cuda else w
             return
         from . import ops
         from .quantize import FP8_E4M3
@@ -865,8 +901,7 @@ class GraphSession(ActivationSession):
         resolves a configuration's solver and loads its code object on first use — 2.7 ms per configuration, 63 ms for
         ResNet-50's 23 from one thread, 18 ms from three, and the main thread's own first forward then finds them loaded
         (scripts/miopen_probe.py).  Returns at once; the session's first forward joins the threads."""
-        if self.device.type != "cuda" or batch < 1 or os.environ.get("DPL_PREWARM_CONVS", "1") == "0" \
-                or getattr(self, "_prewarmed", False):
+        if self.device.type != "cuda" or batch < 1 or os.environ.get("DPL_PREWARM_CONVS", "1") == "0" or self._prewarmed:
             return
         self._prewarmed = True
         seen, todo = set(), []
@@ -890,7 +925,7 @@ class GraphSession(ActivationSession):
                 with torch.no_grad(), torch.cuda.stream(torch.cuda.Stream(self.device)):
                     for node, shape, rest in part:      # (zero weights of the right shapes: the solver is chosen by the configuration)
                         args = [torch.zeros(r, device=self.device) for r in rest]
-                        _OPS["Conv"](self, node, torch.zeros(shape, device=self.device), *args)
+                        run_op(self, node, torch.zeros(shape, device=self.device), *args)
                     torch.cuda.current_stream(self.device).synchronize()
             except Exception:   # noqa: BLE001  (best effort)
                 pass
@@ -907,17 +942,26 @@ class GraphSession(ActivationSession):
         """Replace an initializer on the device (a weight updated by a weight transform) and refresh the folded
         fake-quantised copy that depends on it."""
         self.consts[name] = _host_ints(tensor.to(self.device))
-        for node in self.graph.graph.node:
-            if node.name in self._folded and node.input[0] == name:
-                self.consts[node.output[0]] = _OPS["FakeQuant"](self, node, self.consts[name])
+        for node in self._folded_by_in.get(name, ()):
+            self.consts[node.output[0]] = run_op(self, node, self.consts[name])
 
     def fusion(self, keep):
         """relu_fusion for a forward that hands out the tensors `keep` only (cached per set of names)."""
         key = frozenset(keep)
-        cache = self.__dict__.setdefault("_fusion_cache", {})
-        if key not in cache:
-            cache[key] = relu_fusion(self.graph, self._folded, self.consts, key, getattr(self, "shape1", None))
-        return cache[key]
+        if key not in self._fusion_cache:
+            self._fusion_cache[key] = relu_fusion(self.graph, self._folded, self.consts, key, self.shape1)
+        return self._fusion_cache[key]
+
+    def schedule(self, keep=None):
+        """The Steps of one pass over the graph, in graph order (a tuple, cached per set of names).  keep=None: every node but the
+        folded weight FakeQuants, each on its own; a collection of names: what fusion(keep) says — the Relu / Add nodes that run
+        inside a Q/DQ kernel are absent, that FakeQuant node's step carries `pre` and their inputs."""
+        key = None if keep is None else frozenset(keep)
+        if key not in self._schedules:
+            fused, skipped = ({}, ()) if key is None else self.fusion(key)
+            self._schedules[key] = tuple(Step(n, *fused.get(n.name, ())) for n in self.graph.graph.node
+                                         if n.name not in self._folded and n.name not in skipped)
+        return self._schedules[key]
 
     def _forward(self, feeds, batch, keep=None):
         """keep: the tensors the caller will read (None: any of them — every node runs on its own); a fake-quantised graph then
@@ -925,23 +969,9 @@ class GraphSession(ActivationSession):
         self.batch = batch
         env = dict(self.consts)
         env.update(feeds)
-        fused, skipped = self.fusion(keep) if keep is not None and self.device.type == "cuda" else ({}, ())
-        for node in self.graph.graph.node:
-            if node.name in self._folded or node.name in skipped:
-                continue
-            if node.name in fused:
-                pre, ins = fused[node.name]
-                env[node.output[0]] = fused_fake_quant(self, node, pre, *[env[i] for i in ins])
-                continue
-            args = [env[i] if i != "" else None for i in node.input]
-            while args and args[-1] is None:
-                args.pop()
-            out = _OPS[node.op_type](self, node, *args)
-            if isinstance(out, (list, tuple)):
-                for o, v in zip(node.output, out):
-                    env[o] = v
-            else:
-                env[node.output[0]] = out
+        for step in self.schedule(keep if self.device.type == "cuda" else None):
+            for o, v in zip(step.node.output, step(self, env.__getitem__)):
+                env[o] = v
         return env
 
     def _lead(self):
@@ -949,14 +979,14 @@ class GraphSession(ActivationSession):
 
     @torch.no_grad()
     def _run_env(self, inputs, batch, keep=None):
-        if getattr(self, "_conv_threads", None):
+        if self._conv_threads:
             # the first forward WAITS for the convolution threads instead of racing them (two threads resolving the same
             # configuration at the same time both pay for it)
             with _wall("warm_wait_convs_s"):
                 for t in self._conv_threads:
                     t.join()
             self._conv_threads = None
-        if getattr(self, "_consts_host", None) is not None and self._consts_copied.query():
+        if self._consts_host is not None and self._consts_copied.query():
             self._consts_host = None
         mark("first_forward:start")     # (the other helper threads are not waited for: first calls are serialised by the libraries' own locks)
         return self._forward({n: inputs[n].to(self.device, torch.float32) for n in self.input_names}, batch, keep)
@@ -1057,3 +1087,93 @@ class GraphSession(ActivationSession):
         not among `names` (relu_fusion)."""
         names = list(names)
         return self._run_any(inputs, names, keep=names)
+
+
+def _references(steps, consts, outputs):
+    """How many readers every activation has in a walk over `steps` (+ 1 for a network output: it stays)."""
+    ref = {}
+    for step in steps:
+        for i in step.inputs:
+            if i != "" and i not in consts:
+                ref[i] = ref.get(i, 0) + 1
+    for o in outputs:
+        ref[o] = ref.get(o, 0) + 1
+    return ref
+
+
+def _release(ref, live, step):
+    """`step` has run: its inputs lose a reader; what nobody reads any more — an output nobody consumes too — leaves `live`."""
+    for i in step.inputs:
+        if i in ref:
+            ref[i] -= 1
+            if ref[i] == 0:
+                live.pop(i, None)
+    for o in step.node.output:
+        if o not in ref:
+            live.pop(o, None)
+
+
+def frontier_peak_elems(session):
+    """Largest number of live activation elements per image during a node-major walk, every node on its own (the reference
+    counting of Frontier over the per-image tensor sizes the session inferred)."""
+    size = dict(zip(session.tensor_names, session.elems_per_image))
+    steps = session.schedule()
+    ref = _references(steps, session.consts, session.graph.network_outputs)
+    live = {n: size.get(n, 0) for n in session.graph.network_inputs}
+    peak = sum(live.values())
+    for step in steps:
+        for o in step.node.output:
+            if o != "":
+                live[o] = size.get(o, size.get(step.inputs[0], 0) if step.inputs else 0)
+        peak = max(peak, sum(live.values()))
+        _release(ref, live, step)
+    return peak
+
+
+def load_chunks(graph, args, st, ed, device, on_host=False):
+    """Images [st, ed) of the calibration set in chunks of args.calib_batch: (chunk bounds, {input name: [chunk tensors]})."""
+    from .forward_net import load_input_batch
+    chunk = int(getattr(args, "calib_batch", 16) or 16)
+    bounds = [(i, min(i + chunk, ed)) for i in range(st, ed, chunk)]
+    shapes = {n: graph.get_tensor_shape(n) for n in graph.network_inputs}
+    chunks = {n: [load_input_batch(args.input_dir, [n], shapes, i, j, device)[n] for i, j in bounds] for n in graph.network_inputs}
+    return bounds, ({n: [t.cpu() for t in v] for n, v in chunks.items()} if on_host else chunks)
+
+
+class Frontier:
+    """Activations of every live tensor for the whole calibration set, as lists of per-chunk tensors: the node-major walk of
+    --bc, --update_bn, AdaRound, BRECQ and --sparse (each node runs for all images before the next one starts; activations
+    are freed by reference count).  It runs the session's own Steps."""
+
+    def __init__(self, session, bounds, inputs, on_host=False, keep=()):
+        """bounds, inputs: load_chunks'.  keep: tensors the caller reads from `env` by name besides a node's own inputs / outputs
+        while it runs.  On a fake-quantised graph a ReLU (and the residual Add in front of it) whose only reader is a Q/DQ pair
+        runs inside that pair's kernel (relu_fusion): its output is never in `env`."""
+        self.sess, self.sizes = session, [j - i for i, j in bounds]
+        self.env = dict(inputs)
+        self.steps = {step.node.name: step for step in session.schedule(keep)}
+        self.ref = _references(self.steps.values(), session.consts, session.graph.network_outputs)
+        # on_host: the live activations of the whole set do not fit the HBM budget — chunks wait in (pinned) host memory and
+        # come back to the device one at a time when a node consumes them: slower (PCIe both ways), same values
+        self.on_host = on_host
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+
+    def inputs_of(self, node):
+        """The tensors `node` reads: its inputs, or — a Q/DQ pair that runs its producers' Add / ReLU — theirs."""
+        return self.steps[node.name].inputs
+
+    def run(self, node):
+        step = self.steps.get(node.name)
+        if step is None:        # a folded weight FakeQuant; a Relu / Add that runs inside the Q/DQ kernel behind it
+            return
+        consts, env = self.sess.consts, self.env
+        outs = [[] for _ in node.output]
+        for c, size in enumerate(self.sizes):
+            self.sess.batch = size
+            r = step(self.sess, lambda i: consts[i] if i in consts else env[i][c].to(self.dev))
+            for k, v in enumerate(r[:len(outs)]):
+                outs[k].append(v.cpu() if self.on_host else v)
+        for o, v in zip(node.output, outs):
+            if o != "":
+                env[o] = v
+        _release(self.ref, env, step)

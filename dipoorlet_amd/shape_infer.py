@@ -404,7 +404,7 @@ def infer(graph, folded, input_names, batch=1):
             args.pop()
         if all(a is None or _real(a) for a in args) and node.op_type in ex._OPS and args:
             with torch.no_grad():
-                out = ex._OPS[node.op_type](host, node, *args)          # values known: the executor's own op, on the host
+                out = ex.run_op(host, node, *args)          # values known: the executor's own op, on the host
         else:
             fn = _RULES.get(node.op_type)
             if fn is None:

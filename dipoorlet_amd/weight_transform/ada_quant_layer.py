@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from .. import _hip
-from ..executor import _OPS
+from ..executor import run_op
 from ..ops import _ptr, _stream
 
 __all__ = ["quant_acti", "quant_weight", "adaround_reg", "TempDecay", "L2_norm", "RoundingParam", "RoundSchedule",
@@ -272,7 +272,7 @@ class AdaQLayer:
     def __call__(self, x, apply_relu=True):
         qw = self.rp.qw.transpose(0, 1) if self.transposed else self.rp.qw
         args = (x, qw) if self.bias is None else (x, qw, self.bias)
-        x = _OPS[self.type](_OP_CTX, self.node, *args)
+        x = run_op(_OP_CTX, self.node, *args)
         if self.relu_flag and apply_relu:
             x = torch.relu(x)
         if self.acti_quant:

@@ -19,14 +19,13 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from ..executor import GraphSession
-from ..forward_net import ActivationCache, load_input_batch
+from ..executor import Frontier, GraphSession, load_chunks
+from ..forward_net import ActivationCache
 from ..graph import ONNXGraph
 from ..platform_settings import platform_setting_table
 from ..quantize import quant_graph
 from ..utils import logger
 from .ada_quant_layer import AdaQLayer, L2_norm, RoundSchedule, adaround_reg
-from .bias_correction import _Frontier
 from .sparse_quant_layer import SparseQLayer, cosine_lr
 from .weight_equalization import node_has_equalized
 from .utils import (LEARNABLE_LAYER_TYPES, follow_relu, following_relu, get_block_from_first, get_quant_tensor,
@@ -214,31 +213,24 @@ def reconstruct(graph_ori, graph, act_clip_val, weight_clip_val, args, blockwise
         fp_cache = ActivationCache(graph_ori, args, st, ed)
         graph_q, _ = quant_graph(graph_new, {k: [np.copy(v[0]), np.copy(v[1])] for k, v in clip_val.items()}, args)
         s_q = GraphSession(graph_q, device=dev)
-        chunk = int(getattr(args, "calib_batch", 16) or 16)
-        bounds = [(i, min(i + chunk, ed)) for i in range(st, ed, chunk)]
-        sizes = [j - i for i, j in bounds]
-        shapes = {n: graph_ori.get_tensor_shape(n) for n in graph_ori.network_inputs}
-        qf = _Frontier(s_q, graph_q)
-        for name in graph_ori.network_inputs:
-            qf.env[name] = [load_input_batch(args.input_dir, [name], shapes, i, j, dev)[name] for i, j in bounds]
+        bounds, inputs = load_chunks(graph_ori, args, st, ed, dev)
+        qf = Frontier(s_q, bounds, inputs)
     ori_nodes = {n.name: n for n in graph.graph.node}
     learnable = [n.name for n in graph_ori.graph.node if n.op_type in LEARNABLE_LAYER_TYPES and n.name not in skip]
     already = set()
     for node in graph_q.graph.node:
-        if node.name in s_q._folded:
-            continue
         if node.name in learnable and node.name not in already:
             block = get_block_from_first(graph, ori_nodes[node.name], args) if blockwise else [ori_nodes[node.name]]
             if getattr(args, "we", False):      # an equalised layer cannot be mimicked (adaround.py:36-37, brecq.py:39-41)
                 if not blockwise and node_has_equalized(graph, block[0]):
                     with torch.no_grad():
-                        qf.run(node, len(bounds), sizes)
+                        qf.run(node)
                     continue
                 if blockwise and node_has_equalized(graph, block[-1]):
                     block.pop(-1)
                     if not block:           # (the reference would index an empty list here)
                         with torch.no_grad():
-                            qf.run(node, len(bounds), sizes)
+                            qf.run(node)
                         continue
             if rank == 0:
                 logger.info("{} for: {}".format(head, " ".join(b.name for b in block)))
@@ -268,7 +260,7 @@ def reconstruct(graph_ori, graph, act_clip_val, weight_clip_val, args, blockwise
                     s_q.set_const(b.input[1], w_new)
             del layers, q_in, fp_in, fp_out
         with torch.no_grad():
-            qf.run(node, len(bounds), sizes)
+            qf.run(node)
     graph_new.update_model()
     if rank == 0 and getattr(args, "output_dir", None):
         graph_new.output_dir = args.output_dir

@@ -10,7 +10,7 @@ import math
 import torch
 
 from .. import _hip
-from ..executor import _OPS
+from ..executor import run_op
 from ..ops import _ptr, _stream
 from .ada_quant_layer import _OP_CTX, _channel_layout, _require_cuda
 
@@ -104,7 +104,7 @@ class SparseQLayer:
             self._quant(self.qw, self.mask)
         qw = self.qw.transpose(0, 1) if self.transposed else self.qw
         args = (x, qw) if self.bias is None else (x, qw, self.bias)
-        x = _OPS[self.type](_OP_CTX, self.node, *args)
+        x = run_op(_OP_CTX, self.node, *args)
         return torch.relu(x) if (self.relu_flag and apply_relu) else x
 
     def step(self, lr, grad_scale=1.0, grad_out=None):

@@ -10,12 +10,10 @@ input are two torch reductions on the device and the momentum recurrence is eval
 import numpy as np
 import torch
 
-from ..executor import GraphSession
-from ..forward_net import load_input_batch
+from ..executor import Frontier, GraphSession, load_chunks
 from ..graph import ONNXGraph
 from ..quantize import quant_graph
 from ..utils import logger
-from .bias_correction import _Frontier
 
 __all__ = ["update_bn", "update_bn_multipass", "fold_running_stats"]
 
@@ -45,17 +43,10 @@ def update_bn_multipass(graph, act_clip_val, weight_clip_val, args, recalibrate=
     graph_q, _ = quant_graph(graph_bn, clip_val, args)
     dev = torch.device("cuda", torch.cuda.current_device())
     s_q = GraphSession(graph_q, device=dev)
-    chunk = int(getattr(args, "calib_batch", 16) or 16)
-    N = args.data_num            # rank 0 walks all images, like the reference (ActivationCache(graph_q, args))
-    bounds = [(i, min(i + chunk, N)) for i in range(0, N, chunk)]
-    sizes = [j - i for i, j in bounds]
-    shapes = {n: graph.get_tensor_shape(n) for n in graph.network_inputs}
-    qf = _Frontier(s_q, graph_q)
-    for n in graph.network_inputs:
-        qf.env[n] = [load_input_batch(args.input_dir, [n], shapes, i, j, dev)[n] for i, j in bounds]
+    # rank 0 walks all images, like the reference (ActivationCache(graph_q, args))
+    bounds, inputs = load_chunks(graph, args, 0, args.data_num, dev)
+    qf = Frontier(s_q, bounds, inputs)
     for node in graph_q.graph.node:
-        if node.name in s_q._folded:
-            continue
         if node.op_type == "BatchNormalization":
             logger.info("Update BN for node: {}".format(node.name))
             means, stds = [], []
@@ -73,7 +64,7 @@ def update_bn_multipass(graph, act_clip_val, weight_clip_val, args, recalibrate=
                 g.set_initializer(var_name, new_var.astype(np.float32))
             s_q.set_const(mean_name, torch.from_numpy(new_mean.astype(np.float32)))
             s_q.set_const(var_name, torch.from_numpy(new_var.astype(np.float32)))
-        qf.run(node, len(bounds), sizes)
+        qf.run(node)
     graph_bn.update_model()
     if getattr(args, "output_dir", None):
         graph_bn.output_dir = args.output_dir

@@ -591,3 +591,80 @@ def test_relu_and_add_relu_fused_into_the_fake_quant_kernel(workdir, monkeypatch
         if node.op_type in ("Conv", "Gemm"):
             b = next(n for n in g_fused.graph.node if n.name == node.name).input[2]
             assert np.array_equal(g_fused.get_initializer(b), g_plain.get_initializer(b)), node.name
+
+
+@pytest.fixture(scope="module")
+def fq_resnet18():
+    """A fake-quantised ResNet-18 at 32 x 32 (-D trt; activation clips +-3, per-channel weight ranges) with its session, and
+    5 images: (graph, session, output name, {input name: images})."""
+    import types
+
+    from dipoorlet_amd import dist_helper, models
+    from dipoorlet_amd.quantize import quant_graph
+    from dipoorlet_amd.tensor_cali import find_clip_val_minmax_weight
+    dist_helper.init_default()
+    g = models.resnet18(image=32)
+    plain = g.make_session()
+    clip = {n: [-3.0, 3.0] for n in plain.tensor_names}
+    clip.update(find_clip_val_minmax_weight(g, None, session=plain))
+    gq, _ = quant_graph(g, clip, types.SimpleNamespace(deploy="trt", skip_layers=[]))
+    gen = torch.Generator().manual_seed(7)
+    x = {n: torch.randn([5] + [int(d) for d in g.get_tensor_shape(n)[1:]], generator=gen).cuda() for n in plain.input_names}
+    return gq, gq.make_session(), gq.network_outputs[0], x
+
+
+@pytest.mark.two_forwards
+def test_dispatcher_looks_the_op_up_at_each_call(fq_resnet18):
+    """bench.py's fake-quant object runs two forwards of a session, THEN replaces executor._OPS['FakeQuant'] and the module
+    attribute executor.fused_fake_quant by timing wrappers and counts their calls: the schedule's steps must look both up when
+    they run, not when the schedule is built.  After two run_named forwards, one more calls the fused wrapper once per fused
+    chain and the plain one once per activation FakeQuant node that is neither folded nor fused, and returns the same bits."""
+    from dipoorlet_amd import executor
+    gq, sq, out, x = fq_resnet18
+    x2 = {n: v[:2] for n, v in x.items()}
+    fused, _ = sq.fusion([out])
+    alone = [n.name for n in gq.graph.node if n.op_type == "FakeQuant" and n.name not in sq._folded and n.name not in fused]
+    assert fused and alone
+    (y0,) = sq.run_named(x2, [out])
+    (y1,) = sq.run_named(x2, [out])
+    assert torch.equal(y0, y1)
+    calls = {"plain": 0, "fused": 0}
+    orig, orig_fused = executor._OPS["FakeQuant"], executor.fused_fake_quant
+
+    def plain(sess, node, t):
+        calls["plain"] += 1
+        return orig(sess, node, t)
+
+    def fused_(sess, node, pre, *xs):
+        calls["fused"] += 1
+        return orig_fused(sess, node, pre, *xs)
+    try:
+        executor._OPS["FakeQuant"] = plain
+        executor.fused_fake_quant = fused_
+        (y2,) = sq.run_named(x2, [out])
+    finally:
+        executor._OPS["FakeQuant"], executor.fused_fake_quant = orig, orig_fused
+    assert calls == {"plain": len(alone), "fused": len(fused)}
+    assert torch.equal(y2, y0)
+
+
+@pytest.mark.two_forwards
+@pytest.mark.parametrize("on_host", [False, True])
+def test_frontier_walk_is_the_forward_chunk_by_chunk(fq_resnet18, on_host):
+    """executor.Frontier runs the session's own steps node-major: over 5 images in chunks of 2, 2 and 1 (a ragged last chunk) its
+    chunks of the network output are run_named(chunk, [out]) bit for bit, and when every node has run `env` holds the network
+    outputs and nothing else (every other activation was freed by its reference count).  Kept in host memory between nodes
+    (on_host): the same bits."""
+    from dipoorlet_amd import executor
+    gq, sq, out, x = fq_resnet18
+    bounds = [(0, 2), (2, 4), (4, 5)]
+    chunks = {n: [v[i:j].cpu() if on_host else v[i:j] for i, j in bounds] for n, v in x.items()}
+    fr = executor.Frontier(sq, bounds, chunks, on_host)
+    for node in gq.graph.node:
+        fr.run(node)
+    assert set(fr.env) == set(gq.network_outputs)
+    assert len(fr.env[out]) == len(bounds)
+    for (i, j), got in zip(bounds, fr.env[out]):
+        assert got.is_cuda != on_host
+        (want,) = sq.run_named({n: v[i:j] for n, v in x.items()}, [out])
+        assert got.shape == want.shape and torch.equal(got.cuda(), want)

@@ -457,3 +457,42 @@ def test_relu_fusion_plan_follows_the_merge_relu_rule(monkeypatch):
     assert sq.fusion([out])[0].keys() == fused.keys()
     monkeypatch.setenv("DPL_FUSE_RELU", "0")
     assert executor.relu_fusion(gq, sq._folded, sq.consts, [out], sq.shape1) == ({}, set())
+
+
+def test_schedule_lists_the_steps_both_interpreters_run():
+    """GraphSession.schedule on the fake-quantised ResNet-18 of test_relu_fusion_plan_follows_the_merge_relu_rule (-D trt; host
+    only).  schedule(None): one step per node that is not a folded weight FakeQuant, in graph order, nothing fused;
+    schedule([out]): exactly fusion([out]) — the skipped Relu / Add nodes absent, the fused FakeQuant steps carrying `pre` and
+    the chain's inputs; cached per set of names.  frontier_peak_elems (it decides --bc's on_host) counts over the unfused
+    schedule: the two literals are what bias_correction._frontier_peak_elems returned for these graphs before the executor
+    owned the walk."""
+    import types
+
+    from dipoorlet_amd import executor, models
+    from dipoorlet_amd.quantize import quant_graph
+    g = models.resnet18(seed=1, image=32)
+    s = executor.GraphSession(g, device="cpu")
+    clip = {n: [-3.0, 3.0] for n in s.tensor_names}
+    for node in g.graph.node:
+        for i in node.input[1:]:
+            if i in g.initializer:
+                a = np.asarray(g.initializer[i])
+                a2 = a.reshape(a.shape[0], -1)
+                clip[i] = [a2.min(-1), a2.max(-1)]
+    gq, _ = quant_graph(g, clip, types.SimpleNamespace(deploy="trt", skip_layers=[]))
+    sq = executor.GraphSession(gq, device="cpu")
+    out = gq.network_outputs[0]
+    plain = sq.schedule(None)
+    assert isinstance(plain, tuple) and len(sq._folded) > 0
+    assert [st.node.name for st in plain] == [n.name for n in gq.graph.node if n.name not in sq._folded]
+    assert all(st.pre is None and st.inputs is st.node.input for st in plain)
+    fused, skipped = sq.fusion([out])
+    assert fused and skipped
+    steps = sq.schedule([out])
+    assert [st.node.name for st in steps] == [n.name for n in gq.graph.node if n.name not in sq._folded and n.name not in skipped]
+    assert {st.node.name: (st.pre, st.ins) for st in steps if st.pre is not None} == fused
+    assert all(st.inputs == fused[st.node.name][1] for st in steps if st.pre is not None)
+    assert all(st.inputs is st.node.input for st in steps if st.pre is None)
+    assert sq.schedule([out]) is steps and sq.schedule(None) is plain and sq.schedule() is plain
+    assert executor.frontier_peak_elems(s) == 32768
+    assert executor.frontier_peak_elems(sq) == 32768
