@@ -3,7 +3,7 @@
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
-model, optional) -> weight transforms (--bc, --we, --update_bn, --adaround, --brecq [--drop], --sparse) -> platform deploy file.
+model, optional) -> weight transforms (--smooth, --bc, --we, --update_bn, --adaround, --brecq [--drop], --sparse) -> platform deploy file.
 Extra flags: --calib_batch, --resident_gb, --merge {allreduce,reference}, --skip_profiling, --timing_json.
 """
 import argparse
@@ -28,7 +28,7 @@ def build_parser():
     p.add_argument("-O", "--output_dir", help="output data path")
     p.add_argument("-N", "--data_num", help="num of calibration pics", type=int, required=True)
     for flag in ("--we", "--bc", "--update_bn", "--adaround", "--brecq", "--drop", "--savefp", "--stpu_wg",
-                 "--skip_prof_layer", "--slurm", "--mpirun", "--sparse", "--optim_transformer"):
+                 "--skip_prof_layer", "--slurm", "--mpirun", "--sparse", "--optim_transformer", "--smooth"):
         p.add_argument(flag, default=False, action="store_true")
     p.add_argument("-A", "--act_quant", choices=["minmax", "hist", "mse", "kl", "qmse"], default="mse",
                    help="minmax / hist: bit-exact clip ranges; mse (OCTAV): within 1e-5 * max(1, |ref|) of the reference's, repeating "
@@ -44,6 +44,9 @@ def build_parser():
     p.add_argument("--ada_epoch", type=int, default=5000)
     p.add_argument("--skip_layers", default=[], type=str, nargs="+")
     p.add_argument("--sparse_rate", type=float, default=0.5)
+    p.add_argument("--smooth_alpha", type=float, default=0.5,
+                   help="--smooth (not in the reference): fold per-channel scales s = max|x|^alpha / max|w|^(1 - alpha) of every LayerNorm "
+                        "affine that feeds only MatMul / Gemm weights into those weights; alpha in [0, 1]")
     p.add_argument("--pattern", choices=["unstruction", "nv24"], default="unstruction")
     p.add_argument("--model_type", choices=["unet"], default=None)
     p.add_argument("--quant_format", default="QDQ", type=str, choices=["QOP", "QDQ"])
@@ -69,6 +72,9 @@ def check_args(args):
     FakeQuant nodes only: the clip sweeps that know nothing of the grid and the transforms that run the fake-quantised forward
     work unchanged; what assumes or learns an integer grid does not."""
     from .platform_settings import platform_setting_table
+    alpha = getattr(args, "smooth_alpha", 0.5)
+    if not 0.0 <= alpha <= 1.0:      # (a NaN too)
+        raise ValueError(f"--smooth_alpha must lie in [0, 1], got {alpha}")
     qi = platform_setting_table[args.deploy]["qi_params"]
     if args.act_quant == "qmse":
         # the search models ONE grid per format: symmetric about zero, any real scale, the sign fixed

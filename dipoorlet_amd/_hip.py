@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPL_LIB: another build of the same sources (the host-sanitizer build of scripts/asan_host_check.sh); never a different code path
 LIB_PATH = os.environ.get("DPL_LIB") or os.path.join(_HERE, "csrc", "libdipoorlet_hip.so")
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 MAX_BINS = 16384
 GRID_UNIFORM, GRID_E4M3 = 0, 1          # DPL_GRID_*: the grids of dpl_hist_qmse
 HIST_SPEC_MAX_TENSORS = 2048
@@ -127,6 +127,7 @@ SIGNATURES = {
     "dpl_test_hook_rescue_fail_every": (C.c_int, [C.c_int]),
     "dpl_octav_finalize": (C.c_int, [_P, _I64, _P, _P]),
     "dpl_rowwise_minmax": (C.c_int, [_P, _I64, _I64, _P, _P, _P]),
+    "dpl_colwise_absmax": (C.c_int, [_P, _I64, _I64, _P, _P]),
     "dpl_fake_quant": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _I64, _I32, _I32, _P]),
     "dpl_fake_quant_pre": (C.c_int, [_I32, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I32, _I32, _P]),
     "dpl_fake_quant_items": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P]),

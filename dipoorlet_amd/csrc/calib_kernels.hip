@@ -861,6 +861,62 @@ __global__ __launch_bounds__(kBlock) void k_rowwise_minmax(const float* __restri
     }
 }
 
+// ================================================================ K5b: per-column running max |x| of a [rows, cols] matrix
+// acc[c] = max(acc[c], max_r |x[r, c]|) as an UNSIGNED-INTEGER maximum on the bit pattern of |x|: non-negative floats order like
+// their bits and every NaN pattern lies above +inf, so a NaN in a column (or already in acc) stays a NaN, -0.0 counts as +0.0,
+// and the result does not depend on the order in which workgroups arrive (no floating-point atomic).
+// Geometry: a workgroup is tw lanes along the columns (tw = 2^k <= 64; a lane owns T = one float, or four with 16-B loads) by
+// 256 / tw rows; blockIdx.x picks the column tile, blockIdx.y the rows, grid-strided, kColUnroll independent loads in flight per
+// lane.  A lane keeps its columns' maximum in registers over the whole row loop, the 256 / tw lanes that share a column are
+// folded in LDS, and lane row 0 issues at most ONE atomicMax per column and workgroup — none where the running value read
+// beforehand is not below the candidate (acc only grows, so a stale read can only cause a redundant atomic, never a lost one).
+constexpr int kColMaxLanes = 64;     // 64 lanes x 16 B: a wave instruction reads 1 KiB contiguous of one row
+constexpr int kColUnroll = 4;
+constexpr int kColMaxBlocks = 2048;  // 8 workgroups per CU
+using u4 = __attribute__((ext_vector_type(4))) uint32_t;
+
+template <class T>   // uint32_t: one column per lane;  u4: four, cols % 4 == 0 and x 16-byte aligned
+__global__ __launch_bounds__(kBlock) void k_colwise_absmax(const T* __restrict__ x_generic, uint64_t rows, uint64_t cv, uint32_t tw,
+                                                            uint32_t* __restrict__ acc) {
+    __shared__ T s_m[kBlock];
+    const __attribute__((address_space(1))) T* x = (const __attribute__((address_space(1))) T*)x_generic;
+    const uint32_t tid = threadIdx.x, rp = kBlock / tw;
+    const uint64_t c = (uint64_t)blockIdx.x * tw + (tid & (tw - 1));     // this lane's (vector) column; cv of them in a row
+    T m = T(0);
+    if (c < cv) {
+        const uint64_t step = (uint64_t)gridDim.y * rp;
+        for (uint64_t r = (uint64_t)blockIdx.y * rp + tid / tw; r < rows; r += kColUnroll * step) {
+            T v[kColUnroll];
+#pragma unroll
+            for (int u = 0; u < kColUnroll; ++u) {
+                const uint64_t rr = r + u * step;       // past the end: the last row once more (a branch here would serialise the loads)
+                v[u] = __builtin_nontemporal_load(x + (rr < rows ? rr : rows - 1) * cv + c);
+            }
+#pragma unroll
+            for (int u = 0; u < kColUnroll; ++u) m = __builtin_elementwise_max(m, v[u] & T(0x7FFFFFFFu));
+        }
+    }
+    s_m[tid] = m;
+    __syncthreads();
+    for (uint32_t h = kBlock / 2; h >= tw; h >>= 1) {      // tid and tid + h (h a multiple of tw) share a column
+        if (tid < h) s_m[tid] = __builtin_elementwise_max(s_m[tid], s_m[tid + h]);
+        __syncthreads();
+    }
+    if (tid < tw && c < cv) {
+        m = s_m[tid];
+        if constexpr (sizeof(T) == 16) {
+            uint32_t* a = acc + 4 * c;
+            const uint32_t a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];     // (acc is only 4-byte aligned: four loads, issued together)
+            if (m.x > a0) atomicMax(a + 0, m.x);
+            if (m.y > a1) atomicMax(a + 1, m.y);
+            if (m.z > a2) atomicMax(a + 2, m.z);
+            if (m.w > a3) atomicMax(a + 3, m.w);
+        } else {
+            if (m > acc[c]) atomicMax(acc + c, m);
+        }
+    }
+}
+
 // ================================================================ K6: fused quantize -> dequantize
 __device__ __forceinline__ float fq_one(float x, float scale, float zp, float qlo, float qhi) {
     float q = __fadd_rn(rintf(__fdiv_rn(x, scale)), zp);  // round half to even, then zero point
@@ -1625,6 +1681,33 @@ int dpl_rowwise_minmax(const float* d_w, int64_t rows, int64_t cols, float* d_mi
     hipLaunchKernelGGL(k_rowwise_minmax, dim3((unsigned)rows), dim3(kBlock), 0, (hipStream_t)s, d_w, cols, d_min,
                        d_max);
     DPL_LAUNCH_CHECK("k_rowwise_minmax");
+    return 0;
+}
+
+int dpl_colwise_absmax(const float* d_x, int64_t rows, int64_t cols, float* d_acc, dpl_stream_t s) {
+    if (rows < 0 || cols < 1) return fail_msg("dpl_colwise_absmax: rows must be >= 0 and cols >= 1");
+    if (rows == 0) return 0;
+    if (!d_x || !d_acc) return fail_msg("dpl_colwise_absmax: null pointer");
+    if (rows > INT64_MAX / cols) return fail_msg("dpl_colwise_absmax: rows * cols overflows 64 bits");
+    const bool vec = (cols % 4 == 0) && (((uintptr_t)d_x & 15u) == 0);     // every row then starts on 16 bytes
+    const uint64_t cv = (uint64_t)(vec ? cols / 4 : cols);
+    uint32_t tw = 1;
+    while (tw < (uint32_t)kColMaxLanes && tw < cv) tw <<= 1;
+    const uint64_t gx = (cv + tw - 1) / tw;
+    if (gx > 0x7FFFFFFFull) return fail_msg("dpl_colwise_absmax: cols out of range");
+    // rows: every workgroup makes the same number of trips (kColUnroll * 256 / tw rows each), at most kColMaxBlocks workgroups
+    const uint64_t per_trip = (uint64_t)kColUnroll * (kBlock / tw);
+    const uint64_t trips = ((uint64_t)rows + per_trip - 1) / per_trip;
+    const uint64_t cap = gx >= (uint64_t)kColMaxBlocks ? 1 : (uint64_t)kColMaxBlocks / gx;
+    const uint64_t passes = (trips + cap - 1) / cap;
+    const dim3 g((unsigned)gx, (unsigned)((trips + passes - 1) / passes)), b(kBlock);
+    uint32_t* acc = reinterpret_cast<uint32_t*>(d_acc);
+    if (vec)
+        hipLaunchKernelGGL(k_colwise_absmax<u4>, g, b, 0, (hipStream_t)s, reinterpret_cast<const u4*>(d_x), (uint64_t)rows, cv, tw, acc);
+    else
+        hipLaunchKernelGGL(k_colwise_absmax<uint32_t>, g, b, 0, (hipStream_t)s, reinterpret_cast<const uint32_t*>(d_x), (uint64_t)rows, cv,
+                           tw, acc);
+    DPL_LAUNCH_CHECK("k_colwise_absmax");
     return 0;
 }
 

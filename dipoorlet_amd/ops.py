@@ -1008,6 +1008,26 @@ def rowwise_minmax(w2d, out=None):
     return lo, hi
 
 
+def colwise_absmax(x, acc=None):
+    """Running per-channel max |x| of a channels-last fp32 device tensor (dpl_colwise_absmax; the statistic of --smooth): x of any
+    rank >= 1, contiguous (never copied here), seen as [-1, C] with C = x.shape[-1]; acc <- np.maximum(acc, np.abs(x).max(0)), bit for
+    bit (a NaN in a column or already in acc stays NaN).  acc: fp32 [C] on x's device holding non-negative values, zeroed by its
+    owner before the first batch; None: a zeroed one is made.  Runs on the current stream, no host synchronisation.  Returns acc."""
+    _require_cuda(x, "x")
+    if x.dim() < 1:
+        raise _hip.DipoorletHipError("colwise_absmax: x must have at least one axis")
+    cols = int(x.shape[-1])
+    rows = x.numel() // cols if cols else 0
+    if acc is None:
+        acc = torch.zeros(cols, dtype=torch.float32, device=x.device)
+    else:
+        _require_cuda(acc, "acc")
+        if acc.numel() != cols or acc.device != x.device:
+            raise _hip.DipoorletHipError(f"colwise_absmax: acc holds {acc.numel()} values for {cols} channels")
+    _hip.check(_hip.lib().dpl_colwise_absmax(_ptr(x), rows, cols, _ptr(acc), _stream()), "dpl_colwise_absmax")
+    return acc
+
+
 FQ_PRE = {None: 0, "none": 0, "relu": 1, "add_relu": 2}     # include/dipoorlet_hip.h DPL_FQ_PRE_*
 
 

@@ -11,6 +11,7 @@ Per tensor:
     dipoorlet::hist_qmse(Tensor hist, float gmin, float gmax, str qtype, int bit_width, int first) -> Tensor   [2] fp32 clip (quantisation-MSE search)
     dipoorlet::octav(Tensor x, bool dynamic_sym) -> Tensor     [3] fp32 (s, min, max) (forward_net.py:315-330)
     dipoorlet::rowwise_minmax(Tensor w2d) -> (Tensor, Tensor)
+    dipoorlet::colwise_absmax(Tensor x) -> Tensor              [C] fp32: max |x| per channel of a channels-last x (ops.colwise_absmax)
     dipoorlet::fake_quant(Tensor x, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor
     dipoorlet::fake_quant_relu(Tensor x, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor          fq(relu(x))
     dipoorlet::fake_quant_add_relu(Tensor x, Tensor x2, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor
@@ -259,6 +260,16 @@ def rowwise_minmax(w2d: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 @rowwise_minmax.register_fake
 def _(w2d):
     return w2d.new_empty(w2d.shape[0]), w2d.new_empty(w2d.shape[0])
+
+
+@torch.library.custom_op("dipoorlet::colwise_absmax", mutates_args=(), device_types="cuda")
+def colwise_absmax(x: torch.Tensor) -> torch.Tensor:
+    return ops.colwise_absmax(x.contiguous())
+
+
+@colwise_absmax.register_fake
+def _(x):
+    return x.new_empty(x.shape[-1], dtype=torch.float32)
 
 
 @torch.library.custom_op("dipoorlet::fake_quant", mutates_args=(), device_types="cuda")

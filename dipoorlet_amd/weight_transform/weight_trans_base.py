@@ -10,6 +10,7 @@ from ..utils import load_clip_val, logger, reduce_clip_val, save_clip_val
 from .adaround import adaround
 from .bias_correction import bias_correction
 from .brecq import brecq
+from .smooth import smooth_quant
 from .sparse_quant import sparse_quant
 from .update_bn import update_bn
 from .weight_equalization import weight_equalization
@@ -40,6 +41,14 @@ def weight_calibration(onnx_graph, act_clip_val, weight_clip_val, args):
     with the same model and ranges."""
     graph_after_wt = ONNXGraph()
     graph_after_wt.copy_from(onnx_graph)
+    if getattr(args, "smooth", False):   # (not in the reference) first: everything below sees the smoothed model, as after --we
+        if dist.get_rank() == 0:
+            logger.info("Weight transform: smoothing MatMul inputs...")
+        smoothed = smooth_quant(graph_after_wt, args)      # every rank: the statistics are swept in shards; rank 0 writes the model
+        dist.barrier()
+        if smoothed is not graph_after_wt:                  # (a graph without a site is left as it is and nothing is written)
+            graph_after_wt = _reload("smooth_model", args)
+            act_clip_val, weight_clip_val = _recalibrate(graph_after_wt, args)      # activation ranges change with the scales
     if getattr(args, "bc", False):   # :21-29 — the reference: rank 0 corrects, everyone reloads, weight (bias) ranges refreshed
         # here every rank corrects over its shard of the images and the per-channel sums are all-reduced (bias_correction);
         # --merge reference: rank 0 alone, over all images.  Rank 0 writes the model, everyone reloads it, as before.

@@ -25,10 +25,11 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 25 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 26 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
-                              25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid) */
+                              25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
+                              26: dpl_colwise_absmax (per-channel running max |x| of a channels-last activation: --smooth) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -350,6 +351,14 @@ int dpl_octav_finalize(const dpl_octav_state* d_states, int64_t n_pairs, float* 
 /* ---- per-output-channel weight ranges: replaces np.min/np.max(tensor.reshape(C,-1), -1)
  *      (basic_algorithm.py:88-90).  d_w row-major [rows, cols]. */
 int dpl_rowwise_minmax(const float* d_w, int64_t rows, int64_t cols, float* d_min, float* d_max, dpl_stream_t s);
+
+/* ---- per-channel statistics of a channels-last activation (--smooth): acc[c] = max(acc[c], max_r |x[r * cols + c]|), that is
+ *      np.maximum(acc, np.abs(x).max(0)) for d_x row-major [rows, cols].  A RUNNING maximum: zero d_acc ([cols] fp32) once, then
+ *      call batch after batch; d_acc must hold non-negative values or NaN.  Taken as an unsigned-integer maximum on the bits of
+ *      |x| (integer atomics: the result does not depend on order): a NaN in a column or already in acc stays NaN (any NaN
+ *      pattern), +-inf gives inf, -0.0 counts as +0.0.  16-byte loads when cols % 4 == 0 and d_x is 16-byte aligned, else a
+ *      scalar kernel.  rows == 0: nothing is done; rows < 0, cols < 1, a null pointer with rows > 0: refused. */
+int dpl_colwise_absmax(const float* d_x, int64_t rows, int64_t cols, float* d_acc, dpl_stream_t s);
 
 /* ---- fused QuantizeLinear->DequantizeLinear (quantize.py:197-239; ONNX opset-13 semantics) and the
  *      reference-owned torch restatement quant_acti (weight_transform/ada_quant_layer.py:28-36):
