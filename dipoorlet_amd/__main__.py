@@ -1,5 +1,5 @@
 """`python -m dipoorlet_amd -M model.onnx -I calib_dir -N 1024 -A hist -D trt` — the reference's CLI
-(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, and `-D ocp_fp8`, static OCP FP8 E4M3 scales, are this project's additions).
+(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, and `--mx`, OCP Microscaling on MatMul / Gemm operands, are this project's additions).
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
@@ -47,6 +47,10 @@ def build_parser():
     p.add_argument("--smooth_alpha", type=float, default=0.5,
                    help="--smooth (not in the reference): fold per-channel scales s = max|x|^alpha / max|w|^(1 - alpha) of every LayerNorm "
                         "affine that feeds only MatMul / Gemm weights into those weights; alpha in [0, 1]")
+    p.add_argument("--mx", choices=["mxfp8", "mxfp4"], default=None,
+                   help="(not in the reference; with -D ocp_fp8 only) OCP Microscaling on both operands of every MatMul / Gemm, constant "
+                        "ones included: blocks of 32 along the reduction axis share a power-of-two scale taken from the data, the elements "
+                        "are FP8 E4M3 (mxfp8) or FP4 E2M1 (mxfp4); every other node keeps the platform's static E4M3 scales")
     p.add_argument("--pattern", choices=["unstruction", "nv24"], default="unstruction")
     p.add_argument("--model_type", choices=["unet"], default=None)
     p.add_argument("--quant_format", default="QDQ", type=str, choices=["QOP", "QDQ"])
@@ -75,6 +79,9 @@ def check_args(args):
     alpha = getattr(args, "smooth_alpha", 0.5)
     if not 0.0 <= alpha <= 1.0:      # (a NaN too)
         raise ValueError(f"--smooth_alpha must lie in [0, 1], got {alpha}")
+    if getattr(args, "mx", None) and args.deploy != "ocp_fp8":
+        raise ValueError(f"--mx {args.mx} is not supported with -D {args.deploy}: block-scaled MatMul / Gemm operands sit beside static "
+                         "FP8 scales on every other node.  Supported: -D ocp_fp8")
     qi = platform_setting_table[args.deploy]["qi_params"]
     if args.act_quant == "qmse":
         # the search models ONE grid per format: symmetric about zero, any real scale, the sign fixed

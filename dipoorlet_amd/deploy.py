@@ -108,6 +108,19 @@ def gen_ocp_fp8_scales(graph, clip_val, args, **kwargs):
     _dump({"format": "float8e4m3fn", "scale": scale}, args, "ocp_fp8_scales.json")
 
 
+def gen_ocp_mx_blocks(graph, act_clip_val, weight_clip_val, args):
+    """--mx: {"format": "mxfp8" | "mxfp4", "block_size": 32, "tensors": {name: {"axis": k, "constant": bool}}} ->
+    ocp_mx_blocks.json — the operands of MatMul / Gemm that the fake-quantised graph block-scales, and along which axis (an MX
+    node has no static scale to list).  A tensor's first node goes by the tensor's name, a second one along another axis by the
+    name with that node's suffix (`_ax<k>`)."""
+    from .quantize import MX_BLOCK, quant_graph
+    clip = {k: [np.copy(v[0]), np.copy(v[1])] for k, v in {**act_clip_val, **weight_clip_val}.items()}
+    graph_q, _ = quant_graph(graph, clip, args)
+    tensors = {q.tensor_name + q.suffix: {"axis": int(q.block_axis), "constant": q.tensor_name in graph.initializer}
+               for q in graph_q._qdq.values() if q.is_mx}
+    _dump({"format": args.mx, "block_size": MX_BLOCK, "tensors": tensors}, args, "ocp_mx_blocks.json")
+
+
 def to_deploy(graph, act_clip_val, weight_clip_val, args, **kwargs):
     """deploy_base.py:13-19."""
     if platform_setting_table[args.deploy]["deploy_weight"]:
@@ -115,6 +128,8 @@ def to_deploy(graph, act_clip_val, weight_clip_val, args, **kwargs):
         clip_val.update(weight_clip_val)
     else:
         clip_val = act_clip_val
+    if getattr(args, "mx", None):       # (first: an emitter may rewrite clip_val's entries in place)
+        gen_ocp_mx_blocks(graph, act_clip_val, weight_clip_val, args)
     deploy_dispatcher(args.deploy, graph, clip_val, args, **kwargs)
 
 

@@ -639,7 +639,7 @@ def relu_fusion(graph, folded, consts, keep=(), shape1=None):
         return shape_of(p.input[0]) if p is not None and p.op_type == "FakeQuant" else None
 
     for q in nodes:
-        if q.op_type != "FakeQuant" or q.input[0] in consts:
+        if q.op_type != "FakeQuant" or q.input[0] in consts or graph._qdq[q.name].is_mx:     # (the MX kernel has no PRE form)
             continue
         r = producer.get(q.input[0])
         if r is None or r.op_type != "Relu" or len(r.output) != 1 or not sole(r.output[0], q):
@@ -778,6 +778,13 @@ class GraphSession(ActivationSession):
             return
         from . import ops
         from .quantize import FP8_E4M3
+        mx = [self.graph._qdq[n.name].is_mx for n in nodes]
+        if any(mx):      # block-scaled weights (--mx): no parameter rows for the set form — each once through its node's apply()
+            for n, w, f in zip(nodes, ws, mx):
+                if f:
+                    self.consts[n.output[0]] = run_op(self, n, w)
+            self._fold_weights([n for n, f in zip(nodes, mx) if not f])
+            return
         fp8 = [self.graph._qdq[n.name].fmt == FP8_E4M3 for n in nodes]
         if any(fp8) and not all(fp8):      # (one platform, one format — a hand-made graph may mix them: a launch per format)
             self._fold_weights([n for n, f in zip(nodes, fp8) if f])

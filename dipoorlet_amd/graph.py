@@ -20,6 +20,9 @@ from . import onnx_io
 from .onnx_io import Node
 
 
+MX_DOMAIN = "dipoorlet.amd"     # the operator set of MXQuantizeDequantize (an MX FakeQuant node as to_model writes it), version 1
+
+
 class ONNXGraph:
     def __init__(self, model=None, output_dir="", deploy=None, model_type=None):
         self.model = model
@@ -146,6 +149,9 @@ class ONNXGraph:
         fq = Node("FakeQuant", [q_nodes.tensor_name], [q_nodes.output], name=q_nodes.q_name)
         self._qdq[fq.name] = q_nodes
         self.graph.node.insert(idx, fq)
+        if getattr(q_nodes, "is_mx", False):       # block-scaled: the scales are the data's own — no initializers
+            self.set_index()
+            return
         self.initializer[q_nodes.scale_name] = q_nodes.scale if q_nodes.scale.size > 1 else q_nodes.scale.reshape(())
         zp = q_nodes.zero_point if q_nodes.symmetric else q_nodes.zero_point.view(np.uint8)
         if q_nodes.zp_dtype == "float8e4m3fn":     # the zero of the format: one 0x00 byte per element (TensorProto type 17)
@@ -224,9 +230,16 @@ class ONNXGraph:
     def to_model(self, expand_fake_quant=True):
         m = onnx_io.Model()
         m.ir_version, m.opset, m.graph_name = self.ir_version, dict(self.opset), self.graph.name
-        nodes, float8 = [], False
+        nodes, float8, mx_domain = [], False, False
         for n in self.graph.node:
-            if n.op_type == "FakeQuant" and expand_fake_quant:   # emit the reference's 2-node form (quantize.py:208-231)
+            if n.op_type == "FakeQuant" and expand_fake_quant and self._qdq[n.name].is_mx:
+                # ONNX has no dynamic block-scaled Q/DQ pair to expand into: ONE node of this project's own domain
+                from .quantize import MX_BLOCK, MX_TYPES
+                q = self._qdq[n.name]
+                mx_domain = True
+                nodes.append(Node("MXQuantizeDequantize", [q.tensor_name], [q.output], name=q.q_name, domain=MX_DOMAIN,
+                                  attrs={"axis": int(q.block_axis), "block_size": MX_BLOCK, "elem_type": MX_TYPES[q.fmt][1]}))
+            elif n.op_type == "FakeQuant" and expand_fake_quant:   # emit the reference's 2-node form (quantize.py:208-231)
                 q = self._qdq[n.name]
                 float8 |= q.zp_dtype == "float8e4m3fn"
                 attrs = {"axis": q.axis} if q.per_channel else {}
@@ -241,6 +254,8 @@ class ONNXGraph:
             # QuantizeLinear / DequantizeLinear take a float8e4m3fn zero point from opset 19 (IR version 9) on
             m.opset[""] = max(m.opset.get("", 0), 19)
             m.ir_version = max(m.ir_version, 9)
+        if mx_domain:
+            m.opset[MX_DOMAIN] = 1
         m.initializers = dict(self.initializer)
         m.inputs = [(n, onnx_io.FLOAT, self.tensor_name_shape_map.get(n)) for n in self.network_inputs]
         m.outputs = [(n, onnx_io.FLOAT, self.tensor_name_shape_map.get(n)) for n in self.network_outputs]

@@ -240,7 +240,9 @@ class OctavTailPlan:
     """dpl_octav_plan of one TensorSetPlan: sizes, tables, history, and the buffers of the single-stream use (octav_batch)."""
 
     def __init__(self, plan, handle):
-        self.plan, self.handle = plan, handle
+        # (what it needs of the TensorSetPlan that owns it, not the plan itself: a reference back would tie the two into a cycle,
+        # and a dropped plan's workspace — tens of MB per tensor set — would wait for the cycle collector instead of going at once)
+        self.device, self.n_pairs, self.handle = plan.device, plan.n_pairs, handle
         L = _hip.lib()
         self.sizes = _hip.OctavWorkspaceSizes()
         _hip.check(L.dpl_octav_plan_sizes(handle, C.byref(self.sizes)), "dpl_octav_plan_sizes")
@@ -268,7 +270,7 @@ class OctavTailPlan:
     def new(self, what):
         """A device buffer of the workspace part `what` ('state', 'rescue', 'list', 'fallback', 'result')."""
         n = int(getattr(self.sizes, what + "_bytes"))
-        return torch.empty(max(n, 256), dtype=torch.uint8, device=self.plan.device)
+        return torch.empty(max(n, 256), dtype=torch.uint8, device=self.device)
 
     def compaction(self, job, states, stream, arena=None, host_states=None, base_host=None):
         """The compaction route for the pairs of `job`'s batch that neither their walk nor the rescue finished (its control block
@@ -280,7 +282,7 @@ class OctavTailPlan:
         back now (one host synchronisation on `stream`: octav_batch).  base_host: a pinned buffer of 8 (n_pairs + 1) bytes for the
         region table's upload (same rule)."""
         L = _hip.lib()
-        n = self.plan.n_pairs
+        n = self.n_pairs
         if host_states is None:
             with torch.cuda.stream(stream):
                 host_states = states[:(n + 1) * C.sizeof(_hip.OctavState)].cpu()
@@ -296,7 +298,7 @@ class OctavTailPlan:
         with torch.cuda.stream(stream):
             need = 2 * 4 * total + 8 * (n + 1)
             if arena is None or arena.numel() < need:
-                arena = torch.empty(need + need // 2, dtype=torch.uint8, device=self.plan.device)
+                arena = torch.empty(need + need // 2, dtype=torch.uint8, device=self.device)
             tab = arena[2 * 4 * total:2 * 4 * total + 8 * (n + 1)]
             if base_host is None:
                 tab.copy_(torch.from_numpy(base.view(np.uint8)))       # (a blocking copy of 8 (n + 1) bytes)
@@ -740,7 +742,7 @@ class _PipeSet:
     __slots__ = ("S", "blocks", "rescue", "host_states", "base_host", "done", "refs", "job", "k", "pending")
 
     def __init__(self, tp, S):
-        self.S, n = S, tp.plan.n_pairs
+        self.S, n = S, tp.n_pairs
         self.blocks = (tp.new("state"), tp.new("state"))
         self.rescue = tp.new("rescue")
         # (pinned: what _settle needs of a batch is on the host by the time it looks, and what it uploads leaves without a wait)
@@ -1084,6 +1086,46 @@ def fake_quant_fp8(x, scale, axis=None, out=None, pre=None, x2=None):
     y = torch.empty_like(x) if out is None else out
     _hip.check(_hip.lib().dpl_fake_quant_fp8(code, _ptr(x), _ptr(x2) if code == 2 else None, _ptr(y), x.numel(), _ptr(scale),
                                              nch, inner, _stream()), "dpl_fake_quant_fp8")
+    return y
+
+
+MX_ELEM = {"mxfp8": _hip.MX_E4M3, "mxfp4": _hip.MX_E2M1}     # include/dipoorlet_hip.h DPL_MX_*
+MX_BLOCK = 32
+
+
+def fake_quant_mx(x, axis, elem, out=None, scales=None):
+    """The OCP Microscaling Q/DQ pair (dpl_fake_quant_mx; tests/mx_model.py is the definition): every 32 consecutive elements
+    along `axis` (negative: from the end) share a power-of-two scale taken from their largest |v|, and are rounded to FP8 E4M3
+    (elem 'mxfp8') or FP4 E2M1 ('mxfp4') under it.  No parameters: the scales are the data's own.  out: as fake_quant (may be x);
+    scales: an optional uint8 device tensor of [outer, ceil(K / 32), inner] elements that receives the E8M0 codes (0xFF: a block
+    that holds a NaN or an infinity, whose elements all come out NaN)."""
+    _require_cuda(x, "x")
+    if elem not in MX_ELEM:
+        raise _hip.DipoorletHipError(f"fake_quant_mx: elem must be 'mxfp8' or 'mxfp4', got {elem!r}")
+    if not isinstance(axis, int) or not -x.dim() <= axis < x.dim():
+        raise _hip.DipoorletHipError(f"fake_quant_mx: axis {axis!r} out of range for a tensor of {x.dim()} dimension(s)")
+    axis %= x.dim()
+    outer = inner = 1
+    for d in x.shape[:axis]:
+        outer *= int(d)
+    for d in x.shape[axis + 1:]:
+        inner *= int(d)
+    k = int(x.shape[axis])
+    if out is None:
+        y = torch.empty_like(x)
+    else:
+        _require_cuda(out, "out")
+        if out.shape != x.shape or out.device != x.device:
+            raise _hip.DipoorletHipError("fake_quant_mx: out must have x's shape and device")
+        y = out
+    if scales is not None:
+        want = outer * (-(-k // MX_BLOCK)) * inner
+        if not (isinstance(scales, torch.Tensor) and scales.is_cuda and scales.device == x.device and scales.dtype == torch.uint8
+                and scales.is_contiguous() and scales.numel() == want):
+            raise _hip.DipoorletHipError(f"fake_quant_mx: scales must be a contiguous uint8 device tensor of {want} elements "
+                                         f"([outer, ceil(K / {MX_BLOCK}), inner] = [{outer}, {-(-k // MX_BLOCK)}, {inner}])")
+    _hip.check(_hip.lib().dpl_fake_quant_mx(MX_ELEM[elem], _ptr(x), _ptr(y), outer, k, inner, None if scales is None else _ptr(scales),
+                                            _stream()), "dpl_fake_quant_mx")
     return y
 
 

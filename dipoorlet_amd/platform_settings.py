@@ -7,6 +7,8 @@ Expressed through a small builder instead of eight literal dicts.
 
 `ocp_fp8` is this project's own entry (the reference has no floating-point grid): static per-tensor / per-channel scales for
 OCP FP8 E4M3, type "Float8E4M3FN" — `bit_width` stays 8, the width of the format (quantize.get_qnode_by_param).
+`mx_setting_table` (`--mx`, with `-D ocp_fp8` only) is no platform: the OCP Microscaling parameter sets that replace the platform's
+on both operands of MatMul and Gemm — blocks of 32 along the reduction axis with a shared power-of-two scale, no static scale.
 """
 
 LAYER_HAS_WEIGHT = ["Conv", "Gemm", "ConvTranspose", "PRelu", "BatchNormalization"]
@@ -51,4 +53,9 @@ platform_setting_table = {
     "imx": _platform(_BASIC, _lin(True, per_channel=True, log_scale=True), _lin(True, log_scale=True),
                      net_out=True, deploy_weight=True),
     "ocp_fp8": _platform(["Conv", "Gemm", "ConvTranspose", "MatMul"], _fp8(per_channel=True), _fp8()),
+}
+
+mx_setting_table = {
+    "mxfp8": {"bit_width": 8, "type": "MXFP8E4M3", "block_size": 32},
+    "mxfp4": {"bit_width": 4, "type": "MXFP4E2M1", "block_size": 32},
 }

@@ -20,15 +20,24 @@ DQTENSORSUFFIX = "_dq"
 QUANT_NODE_NAME_LIST = ["QuantizeLinear", "DequantizeLinear"]
 FP8_E4M3 = "Float8E4M3FN"      # the quantisation type of OCP FP8 E4M3 (platform `ocp_fp8`); every other platform: "Linear"
 E4M3_MAX = 448
+# OCP Microscaling (`--mx`, platform_settings.mx_setting_table): quantisation type -> (ops.fake_quant_mx's elem, the element type as
+# the emitted node names it, the largest element value).  Blocks of 32 along QDQNode.block_axis share a power-of-two scale taken
+# from the data: such a node has no static scale and no zero point.
+MX_TYPES = {"MXFP8E4M3": ("mxfp8", "float8e4m3fn", 448), "MXFP4E2M1": ("mxfp4", "float4e2m1", 6)}
+MX_BLOCK = ops.MX_BLOCK
+MX_NODES = ["MatMul", "Gemm"]
 MERGE_RELU = ["Conv", "Gemm", "Eltwise", "Add"]
 RELU_TYPE = ["Relu", "PRelu", "Mul"]
 
 
 class QDQNode:
     """The fused fake-quant stand-in for the reference's 2-node `graph_quant` (quantize.py:197-239).  `fmt`: the number format
-    of the grid — "Linear" (an 8-bit integer one) or FP8_E4M3 (scale only: the zero point is 0, written as a float8e4m3fn)."""
+    of the grid — "Linear" (an 8-bit integer one), FP8_E4M3 (scale only: the zero point is 0, written as a float8e4m3fn) or one of
+    MX_TYPES (block-scaled along `block_axis`: scale and zero point carry no meaning and are not emitted).  `suffix`: appended to
+    every name of the node — a tensor that already has a fake-quant node of another kind keeps that one's names for it."""
 
-    def __init__(self, tensor_name, tensor_shape, scale, zero_point, need_transpose, per_channel, symmetric, fmt="Linear"):
+    def __init__(self, tensor_name, tensor_shape, scale, zero_point, need_transpose, per_channel, symmetric, fmt="Linear",
+                 block_axis=None, suffix=""):
         self.tensor_name = tensor_name
         self.tensor_shape = list(tensor_shape) if tensor_shape is not None else None
         self.scale = np.asarray(scale, np.float32).reshape(-1)
@@ -37,14 +46,20 @@ class QDQNode:
         self.symmetric = bool(symmetric)
         self.axis = (1 if need_transpose else 0) if per_channel else None  # :214, :220
         self.fmt = fmt
+        self.block_axis = block_axis
+        self.suffix = suffix
         self.zp_dtype = "float8e4m3fn" if fmt == FP8_E4M3 else "int8" if symmetric else "uint8"      # :205-206
-        self.q_name = tensor_name + "_QuantizeLinear"
-        self.dq_name = tensor_name + "_DequantizeLinear"
-        self.scale_name = tensor_name + "_scale"
-        self.zero_point_name = tensor_name + "_zero_point"
-        self.q_output = tensor_name + QTENSORSUFFIX
-        self.output = tensor_name + DQTENSORSUFFIX
+        self.q_name = tensor_name + "_QuantizeLinear" + suffix
+        self.dq_name = tensor_name + "_DequantizeLinear" + suffix
+        self.scale_name = tensor_name + "_scale" + suffix
+        self.zero_point_name = tensor_name + "_zero_point" + suffix
+        self.q_output = tensor_name + QTENSORSUFFIX + suffix
+        self.output = tensor_name + DQTENSORSUFFIX + suffix
         self._dev = None
+
+    @property
+    def is_mx(self):
+        return self.fmt in MX_TYPES
 
     def zero_point_as_stored(self):
         """The integers an ONNX runtime sees: int8 values, or the same bytes read as uint8."""
@@ -55,11 +70,17 @@ class QDQNode:
         not the q_min = -127 the reference computes at :134 for its torch-side code.  FP8: saturate = 1, the largest finite value."""
         if self.fmt == FP8_E4M3:
             return -E4M3_MAX, E4M3_MAX
+        if self.is_mx:
+            return -MX_TYPES[self.fmt][2], MX_TYPES[self.fmt][2]
         return (-128, 127) if self.symmetric else (0, 255)
 
     def apply(self, x, out=None, pre=None, x2=None):
         """Fake-quantise a device tensor: QuantizeLinear -> DequantizeLinear semantics, one kernel (pre / x2: the producer's
-        ReLU or Add + ReLU fused in, ops.fake_quant)."""
+        ReLU or Add + ReLU fused in, ops.fake_quant).  An MX node: ops.fake_quant_mx along block_axis, which has no `pre` form."""
+        if self.is_mx:
+            if pre is not None:
+                raise ValueError(f"{self.q_name}: a block-scaled ({self.fmt}) fake-quant node takes no fused producer ({pre!r})")
+            return ops.fake_quant_mx(x, self.block_axis, MX_TYPES[self.fmt][0], out=out)
         if self._dev is None or self._dev[0].device != x.device:
             self._dev = (torch.from_numpy(self.scale).to(x.device),
                          torch.from_numpy(self.zero_point_as_stored()).to(x.device))
@@ -119,19 +140,25 @@ def _e4m3_grid(lo, hi):
     return scale.tolist()
 
 
-def get_qnode_by_param(param, in_tensor_name, tensor_shape, range, need_transpose=False):
+def get_qnode_by_param(param, in_tensor_name, tensor_shape, range, need_transpose=False, block_axis=-1, suffix=""):
     """quantize.py:111-194 — returns (QDQNode, q_min, q_max) for the clip range `range` = [lo, hi] (scalars, or
     per-channel arrays for weights).  Kept from the reference because callers rely on it: a per-tensor platform
     collapses `range` to its overall min / max IN PLACE (type "Float8E4M3FN" too: scale = max(|lo|, |hi|) / 448, zero point 0,
     q_min / q_max = -448 / 448); `dynamic_sym` platforms switch a non-negative activation
-    (|lo| < 1e-6) to the asymmetric grid — one more bit; `log_scale` snaps scales to powers of two."""
+    (|lo| < 1e-6) to the asymmetric grid — one more bit; `log_scale` snaps scales to powers of two.  An MX type
+    (mx_setting_table) ignores `range`: its node is block-scaled along `block_axis`, q_min / q_max = the element format's."""
+    if param["type"] in MX_TYPES:
+        top = MX_TYPES[param["type"]][2]
+        q_nodes = QDQNode(in_tensor_name, tensor_shape, np.ones(1, np.float32), np.zeros(1, np.int8), False, False, True,
+                          fmt=param["type"], block_axis=int(block_axis), suffix=suffix)
+        return q_nodes, -top, top
     if param["type"] == FP8_E4M3:
         per_channel = bool(param.get("per_channel", False))
         if not per_channel:
             range[0], range[1] = np.min(range[0]), np.max(range[1])
         scale = np.array(_e4m3_grid(range[0], range[1]), dtype=np.float32).reshape(-1)
         q_nodes = QDQNode(in_tensor_name, tensor_shape, scale, np.zeros(scale.shape, np.int8), need_transpose, per_channel, True,
-                          fmt=FP8_E4M3)
+                          fmt=FP8_E4M3, suffix=suffix)
         return q_nodes, -E4M3_MAX, E4M3_MAX
     if param["type"] != "Linear":
         return None, None, None
@@ -149,7 +176,7 @@ def get_qnode_by_param(param, in_tensor_name, tensor_shape, range, need_transpos
         scale = 2 ** np.round(np.log2(scale))
     scale = np.array(scale, dtype=np.float32)
     q_nodes = QDQNode(in_tensor_name, tensor_shape, scale, _int8_wrap(zero_point, scale.shape), need_transpose, per_channel,
-                      symmetric)
+                      symmetric, suffix=suffix)
     return q_nodes, q_min, q_max
 
 
@@ -211,19 +238,56 @@ class _NodeRules:
         return role
 
 
+def mx_block_axis(node, idx, shape):
+    """The axis of operand `idx` (0 or 1) of a MatMul / Gemm that the product reduces over — the one MX blocks run along: MatMul
+    A -1, B -2 (-1 for a 1-D B), counted from the end as MatMul's own rule is (the same answer whether or not the graph knows an
+    activation's shape yet); Gemm A 0 if transA else 1, B 1 if transB else 0."""
+    if node.op_type == "Gemm":
+        t = int(node.attrs.get("transA" if idx == 0 else "transB", 0) or 0)
+        return (0 if t else 1) if idx == 0 else (1 if t else 0)
+    return -1 if idx == 0 or (shape is not None and len(shape) == 1) else -2
+
+
+def _taken(act_quantized, name):
+    """The entry of the first fake-quant node of tensor `name` — the one that has the usual names — or None: `name` itself for a
+    static node, (name, axis) for an MX one."""
+    for k in act_quantized:
+        if k == name or (isinstance(k, tuple) and k[0] == name):
+            return k
+    return None
+
+
 def insert_fake_quant_node(graph, node, act_quantized, data_range_list, args):
     """quantize.py:40-95 for one node: derive the grid of every input that has a role, re-wire the input to the
-    fake-quantised tensor, and insert the FakeQuant node unless the tensor already has one (`act_quantized`)."""
-    from .platform_settings import platform_setting_table
+    fake-quantised tensor, and insert the FakeQuant node unless the tensor already has one (`act_quantized`).
+    With args.mx ('mxfp8' / 'mxfp4'; -D ocp_fp8) both operands of a MatMul / Gemm — a constant one too, whatever its role — take
+    the MX parameter set instead, blocked along the operand's reduction axis (mx_block_axis); a Gemm bias is left to the platform's
+    rules.  `act_quantized` holds (name, axis) for such a node: a tensor wanted along two axes, or by a static consumer as well,
+    gets one node each — the first has the usual names, a later MX one the suffix `_ax<k>`, a later static one `_static`."""
+    from .platform_settings import mx_setting_table, platform_setting_table
     plat = platform_setting_table[args.deploy]
+    mx = getattr(args, "mx", None) if node.op_type in MX_NODES else None
     rules = _NodeRules(graph, node, plat, args.deploy)
     for idx, name in enumerate(list(node.input)):
         role = rules.role(name)
+        if mx and idx < 2 and name != "":
+            shape = graph.tensor_name_shape_map.get(name)
+            axis = mx_block_axis(node, idx, shape)
+            key = (name, axis)
+            first = _taken(act_quantized, name)
+            q_nodes, _, _ = get_qnode_by_param(mx_setting_table[mx], name, shape, None, block_axis=axis,
+                                               suffix="" if first in (None, key) else f"_ax{axis}")
+            node.input[idx] = q_nodes.output
+            if key not in act_quantized:
+                graph.insert_qnodes_purely(q_nodes=q_nodes, node=node)
+                act_quantized.append(key)
+            continue
         if role is None:
             continue
         transposed = role == "qw_params" and node.op_type == "ConvTranspose"
+        first = _taken(act_quantized, name)
         q_nodes, _, _ = get_qnode_by_param(plat[role], name, graph.tensor_name_shape_map.get(name), data_range_list[name],
-                                           transposed)
+                                           transposed, suffix="" if first in (None, name) else "_static")
         if q_nodes is None:
             continue
         node.input[idx] = q_nodes.output

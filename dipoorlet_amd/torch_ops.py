@@ -16,6 +16,7 @@ Per tensor:
     dipoorlet::fake_quant_relu(Tensor x, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor          fq(relu(x))
     dipoorlet::fake_quant_add_relu(Tensor x, Tensor x2, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor
     dipoorlet::fake_quant_fp8(Tensor x, Tensor scale, int axis) -> Tensor      the pair on the OCP FP8 E4M3 grid (ops.fake_quant_fp8)
+    dipoorlet::fake_quant_mx(Tensor x, int axis, str elem) -> Tensor           the OCP Microscaling pair, 'mxfp8' / 'mxfp4', blocks of 32 along axis (ops.fake_quant_mx)
 Over every tensor of a batch of images in ONE launch — what the reference's loops over `ort_outputs` stand for
 (forward_net.py:220-235, 265-280, 314-340); xs[t] is tensor t of the batch, [B, ...] contiguous fp32:
     dipoorlet::minmax_batched(Tensor[] xs, Tensor(a!) mins, Tensor(b!) maxs) -> ()   running min / max per tensor, [T] fp32
@@ -314,6 +315,16 @@ def fake_quant_fp8(x: torch.Tensor, scale: torch.Tensor, axis: int) -> torch.Ten
 @fake_quant_fp8.register_fake
 def _(x, scale, axis):
     return torch.empty_like(x)
+
+
+@torch.library.custom_op("dipoorlet::fake_quant_mx", mutates_args=(), device_types="cuda")
+def fake_quant_mx(x: torch.Tensor, axis: int, elem: str) -> torch.Tensor:
+    return ops.fake_quant_mx(x.contiguous(), axis, elem)
+
+
+@fake_quant_mx.register_fake
+def _(x, axis, elem):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 
 @torch.library.custom_op("dipoorlet::fake_quant_set", mutates_args=(), device_types="cuda")

@@ -25,11 +25,12 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 26 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 27 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
                               25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
-                              26: dpl_colwise_absmax (per-channel running max |x| of a channels-last activation: --smooth) */
+                              26: dpl_colwise_absmax (per-channel running max |x| of a channels-last activation: --smooth);
+                              27: dpl_fake_quant_mx (the OCP Microscaling Q/DQ pair, MXFP8 / MXFP4: --mx) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -405,6 +406,22 @@ int dpl_fake_quant_fp8(int32_t pre, const float* d_x, const float* d_x2, float* 
  * rows are ignored (d_zero_point may be null). */
 int dpl_fake_quant_fp8_items(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin, int64_t n_blocks,
                              const float* const* d_seg_x, float* const* d_seg_y, const dpl_fake_quant_params* d_params, dpl_stream_t s);
+
+/* ---- the OCP Microscaling (MX) v1.0 Q/DQ pair (beyond the reference; --mx): the tensor is [outer, k, inner]; every 32
+ *      consecutive indices along k, from 0, form a block (the last one holds the k % 32 elements that exist) with one shared
+ *      scale 2^se, an E8M0 code, and elements of type `elem` — DPL_MX_E4M3 (MXFP8: OCP FP8 E4M3, emax 8, largest value 448) or
+ *      DPL_MX_E2M1 (MXFP4: 0, 0.5, 1, 1.5, 2, 3, 4, 6; emax 2).  With a = max |v| of the block:
+ *        a NaN or inf   every element of the block is NaN, scale code 0xFF
+ *        a == 0         se = -127, the zeros keep their signs
+ *        otherwise      se = max(floor(log2 a) - emax, -127)
+ *      and y = round_elem(v / 2^se) * 2^se, round_elem: the nearest value of the format, ties to the even mantissa, saturating.
+ *      Exact (bit operations: fp32 subnormal inputs and outputs are kept whatever the denormal mode); the definition is
+ *      tests/mx_model.py.  d_scales_or_null: uint8 [outer, ceil(k / 32), inner], se + 127 per block.  d_y may equal d_x.
+ *      1 <= k, inner < 2^31; outer * k * inner == 0 is a no-op. */
+#define DPL_MX_E4M3 0
+#define DPL_MX_E2M1 1
+int dpl_fake_quant_mx(int32_t elem, const float* d_x, float* d_y, uint64_t outer, uint64_t k, uint64_t inner,
+                      uint8_t* d_scales_or_null, dpl_stream_t s);
 
 /* ---- cosine-similarity partial sums (utils.py:273-278): d_acc[slot*3 + {0,1,2}] += sum(a*b), sum(a*a),
  *      sum(b*b) in fp64. */
