@@ -200,46 +200,42 @@ def _span_array(spans):
     return arr, len(spans)
 
 
+def _count_then_fill(name, head, extra=(), refusal=None):
+    """The builders' double call: fn(*head, NULL, 0, NULLs) counts the items, the second call fills them (and the `extra` arrays
+    behind them).  -> (WorkItem array, n); (None, refusal) where the count is the builder's `refusal` status, any other
+    failure raises."""
+    fn = getattr(lib(), name)
+    n = int(fn(*head, None, 0, *([None] * len(extra))))
+    if n < 0:
+        if n == refusal:
+            return None, n
+        check(n, name)
+    out = (WorkItem * max(n, 1))()
+    n2 = fn(*head, C.addressof(out), n, *(C.addressof(e) for e in extra))
+    if n2 != n:
+        raise DipoorletHipError(f"{name}: filled {n2} items after counting {n}")
+    return out, n
+
+
 def build_balanced_items(spans, n_blocks):
     """HOST: spans = iterable of (seg, offset, count, slot) -> (WorkItem array, n_items, block_begin array):
     n_blocks contiguous equal shares of the concatenated element stream."""
     arr, ns = _span_array(spans)
-    n = lib().dpl_build_balanced_items(C.addressof(arr), ns, n_blocks, None, 0, None)
-    if n < 0:
-        check(int(n), "dpl_build_balanced_items")
-    out = (WorkItem * max(n, 1))()
     bb = (C.c_uint32 * (n_blocks + 1))()
-    n2 = lib().dpl_build_balanced_items(C.addressof(arr), ns, n_blocks, C.addressof(out), n, C.addressof(bb))
-    assert n2 == n
-    return out, int(n), bb
+    out, n = _count_then_fill("dpl_build_balanced_items", (C.addressof(arr), ns, n_blocks), (bb,))
+    return out, n, bb
 
 
 def build_octav_slices(spans):
     """HOST: spans (one per (image, tensor) pair, slots 0 .. n-1) -> (WorkItem array, n_slices, pair_slice0 uint32 [n, 2]),
     largest pairs first, or None when a pair is too large for the one-read form (more than 64 slices)."""
     arr, ns = _span_array(spans)
-    n = lib().dpl_build_octav_slices(C.addressof(arr), ns, None, 0, None)
-    if n == -3:
-        return None
-    if n < 0:
-        check(int(n), "dpl_build_octav_slices")
-    out = (WorkItem * max(n, 1))()
     ps = (C.c_uint32 * (2 * max(ns, 1)))()
-    n2 = lib().dpl_build_octav_slices(C.addressof(arr), ns, C.addressof(out), n, C.addressof(ps))
-    assert n2 == n
-    return out, int(n), ps
+    out, n = _count_then_fill("dpl_build_octav_slices", (C.addressof(arr), ns), (ps,), refusal=-3)
+    return None if out is None else (out, n, ps)
 
 
 def build_work_items(spans, chunk_elems):
     """HOST: spans = iterable of (seg, offset, count, slot) -> ctypes array of WorkItem."""
-    spans = list(spans)
-    arr = (Span * max(len(spans), 1))()
-    for i, (seg, off, cnt, slot) in enumerate(spans):
-        arr[i] = Span(off, cnt, seg, slot)
-    n = lib().dpl_build_work_items(C.addressof(arr), len(spans), chunk_elems, None, 0)
-    if n < 0:
-        check(int(n), "dpl_build_work_items")
-    out = (WorkItem * max(n, 1))()
-    n2 = lib().dpl_build_work_items(C.addressof(arr), len(spans), chunk_elems, C.addressof(out), n)
-    assert n2 == n
-    return out, int(n)
+    arr, ns = _span_array(spans)
+    return _count_then_fill("dpl_build_work_items", (C.addressof(arr), ns, chunk_elems))

@@ -9,6 +9,7 @@
 //   * histograms privatised in LDS (ds_add_u32), exact zeros counted in registers (ReLU outputs are
 //     ~50 % zeros and would otherwise serialise on one LDS address), one flush per workgroup;
 //   * order-encoded integer atomics for fp32 min/max, so accumulators persist across launches.
+// The tables these kernels index with (work items, block shares) are built on the host by host_plan.hpp.
 #include "common.hpp"
 
 // Bit-exact numpy parity needs every fp32 operation rounded on its own: HIP's default
@@ -1410,94 +1411,12 @@ int dpl_stream_destroy(dpl_stream_t s) {
     return e == hipSuccess ? 0 : fail("hipStreamDestroy", e);
 }
 
-int64_t dpl_build_work_items(const dpl_span* spans, int64_t n_spans, uint64_t chunk_elems, dpl_work_item* out,
-                             int64_t cap) {
-    if (!spans || n_spans < 0 || chunk_elems == 0 || (chunk_elems % 1024) != 0 || chunk_elems > 0xFFFFFC00ull)
-        return fail_msg("dpl_build_work_items: chunk_elems must be a non-zero multiple of 1024 below 2^32");
-    int64_t n = 0;
-    for (int64_t i = 0; i < n_spans; ++i) {
-        uint64_t off = spans[i].offset, left = spans[i].count;
-        while (left) {
-            const uint64_t c = left < chunk_elems ? left : chunk_elems;
-            if (out && n < cap) {
-                out[n].offset = off;
-                out[n].count = (uint32_t)c;
-                out[n].seg = spans[i].seg;
-                out[n].slot = spans[i].slot;
-                out[n].reserved = 0;
-            }
-            ++n;
-            off += c;
-            left -= c;
-        }
-    }
-    return n;
-}
-
 int dpl_minmax_init(uint32_t* d_min_enc, uint32_t* d_max_enc, uint32_t* d_nan, int64_t n_slots, dpl_stream_t s) {
     if (n_slots <= 0) return 0;
     hipLaunchKernelGGL(k_minmax_init, dim3(grid_for(n_slots, 256)), dim3(256), 0, (hipStream_t)s, d_min_enc,
                        d_max_enc, d_nan, n_slots);
     DPL_LAUNCH_CHECK("k_minmax_init");
     return 0;
-}
-
-int64_t dpl_build_balanced_items(const dpl_span* spans, int64_t n_spans, int64_t n_blocks, dpl_work_item* out,
-                                 int64_t cap, uint32_t* block_begin) {
-    if (!spans || n_spans < 0 || n_blocks < 1) return fail_msg("dpl_build_balanced_items: bad arguments");
-    unsigned __int128 total = 0;
-    for (int64_t i = 0; i < n_spans; ++i) total += spans[i].count;
-    int64_t n = 0;
-    int64_t si = 0;
-    uint64_t lo = 0;       // offset inside span si
-    unsigned __int128 g = 0;  // global position of the cursor in the concatenated element stream
-    for (int64_t b = 0; b < n_blocks; ++b) {
-        if (block_begin) block_begin[b] = (uint32_t)n;
-        const unsigned __int128 target = (b + 1 == n_blocks) ? total : (total * (unsigned __int128)(b + 1)) / (unsigned __int128)n_blocks;
-        while (si < n_spans && g < target) {
-            const uint64_t remaining = spans[si].count - lo;
-            if (remaining == 0) {
-                ++si;
-                lo = 0;
-                continue;
-            }
-            const unsigned __int128 want = target - g;
-            uint64_t take;
-            bool span_done;
-            if (want >= remaining) {
-                take = remaining;
-                span_done = true;
-            } else {
-                take = ((uint64_t)want / 1024u) * 1024u;  // cut points stay 4 KiB-aligned inside a span
-                span_done = false;
-                if (take == 0) break;  // less than one aligned piece left for this block: next block takes it
-            }
-            uint64_t off = spans[si].offset + lo, left = take;
-            while (left) {  // a share larger than 2^32-1024 elements is emitted as several items
-                const uint64_t c = left < 0xFFFFFC00ull ? left : 0xFFFFFC00ull;
-                if (out && n < cap) {
-                    out[n].offset = off;
-                    out[n].count = (uint32_t)c;
-                    out[n].seg = spans[si].seg;
-                    out[n].slot = spans[si].slot;
-                    out[n].reserved = 0;
-                }
-                ++n;
-                off += c;
-                left -= c;
-            }
-            g += take;
-            lo += take;
-            if (span_done) {
-                ++si;
-                lo = 0;
-            } else {
-                break;
-            }
-        }
-    }
-    if (block_begin) block_begin[n_blocks] = (uint32_t)n;
-    return n;
 }
 
 // n_blocks = number of workgroups; d_block_begin (n_blocks + 1 entries) may be null, then n_blocks must equal

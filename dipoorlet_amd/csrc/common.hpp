@@ -1,5 +1,6 @@
-// Shared by every translation unit of libdipoorlet_hip.so: error state, launch constants, wave reductions,
-// the order-preserving fp32 <-> u32 encoding, the streaming skeleton and the work-item -> workgroup mapping.
+// Shared by every translation unit of libdipoorlet_hip.so: error state (host_error.hpp, which has no HIP in it, plus the
+// HIP-error form here), launch constants, wave reductions, the order-preserving fp32 <-> u32 encoding, the streaming
+// skeleton and the work-item -> workgroup mapping.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,19 +10,15 @@
 #include <stdlib.h>
 
 #include "../../include/dipoorlet_hip.h"
+#include "host_error.hpp"
 
 // Bit-exact numpy parity needs every fp32 operation rounded on its own: HIP's default
 // -ffp-contract=fast would fuse i*step + first into one FMA (__fmul_rn/__fadd_rn are plain * and +
 // in this toolchain).  Also passed as a flag by csrc/build.py.
 #pragma clang fp contract(off)
 
-namespace dpl {
-inline thread_local char g_err[512] = "";  // one per thread for the whole library (shared by every translation unit)
-}
-
 namespace {
 
-using dpl::g_err;
 constexpr int kBlock = 256;   // 4 waves of 64
 constexpr int kUnroll = 4;    // float4 loads per lane per register set (two sets are in flight)
 constexpr int kWave = 64;
@@ -30,10 +27,6 @@ using f4 = __attribute__((ext_vector_type(4))) float;  // native vector: nontemp
 int fail(const char* what, hipError_t e) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
     return -1;
-}
-int fail_msg(const char* what) {
-    snprintf(g_err, sizeof(g_err), "%s", what);
-    return -2;
 }
 #define DPL_LAUNCH_CHECK(name)                              \
     do {                                                    \

@@ -1,8 +1,10 @@
 // Shared by the OCTAV translation units (octav_kernels.hip: full / compaction / two-read bracket forms and the rescue's
 // gather; octav_tail_host.hip: the one-read exact-tail form and its rescue walk): the fixed-point step, the log-scale
-// histogram geometry and the bracket walk over its bin edges.
+// histogram geometry and the bracket walk over its bin edges.  The numbers the host planning shares with the kernels (bins,
+// slice and list-region sizes: list_cap_of) are in octav_geometry.hpp.
 #pragma once
 #include "common.hpp"
+#include "octav_geometry.hpp"
 
 #pragma clang fp contract(off)
 
@@ -32,30 +34,13 @@ __device__ __forceinline__ OctavStep octav_step(double sum, unsigned long long c
 }
 
 
-constexpr int kLogNB = 2048;
 constexpr int kLogShift = 17;                               // 23 - 6: six mantissa bits per bin
 constexpr uint32_t kLogKey0 = (uint32_t)(127 - 18) << 6;    // key of 2^-18
-constexpr int kLogWords = kLogNB / 32;
 constexpr int kBitmapRow = kLogWords + 2;                   // + the gather range [lo, hi) as float bits
 constexpr int kLogMaxMarked = 256;
 constexpr uint32_t kSmallPair = 16384;                      // pairs this small are gathered whole
 constexpr uint32_t kRescueUnit = 16384;                     // elements of a pair one workgroup of k_octav_rescue_gather re-reads
 constexpr unsigned kRescueGrid = 512;                       // workgroups of the rescue's persistent kernels (gather and walk)
-
-// Capacity (elements, a multiple of 32: whole 128-byte lines) of the LIST REGION of one slice of n elements in the one-read
-// forms' list buffers.  The exact-tail form lists ~0.5 - 1.5 % of a pair (a wave's budget: kTailAllow0 + what it has seen >> 6,
-// + 512 per raise) and the rescue gathers a bracket's bins (~2 %): a region holds n / 16 + 16384 values, never more than the
-// slice itself.  What does not fit — saturating activations with a tenth of their values at the maximum, constant tensors —
-// is not listed: the pair's walk is refused (its list length says so) and it finishes on the compaction route, whose
-// full-size lists the caller provides only when a batch reports such pairs.  Round 4 gave every pair a region of its own
-// size in every list: 4 x the batch's activations in scratch.  (n / 32 + 16384 was too tight for the rescue: the bracket of a
-// cold 802 816-element pair holds 5 - 6 % of it, and 14 pairs of every cold ResNet-50 sweep ended on the compaction route.)
-constexpr uint32_t kListCapShift = 4, kListCapConst = 16384;
-constexpr uint32_t kListWhole = 20480;   // a pair this small lists its whole window (octav_tail_host.hip: kSmallCap): its region holds all of it
-__host__ __device__ inline uint32_t list_cap_of(unsigned long long n) {
-    const unsigned long long whole = (n + 31ull) & ~31ull, part = ((n >> kListCapShift) + kListCapConst + 31ull) & ~31ull;
-    return (uint32_t)((whole < part || n <= kListWhole) ? whole : part);
-}
 
 __device__ __forceinline__ int log_bin(float a) {
     const int b = (int)(__float_as_uint(a) >> kLogShift) - (int)kLogKey0;

@@ -6,6 +6,7 @@ import re
 
 import pytest
 
+import host_plan_checks as K
 from dipoorlet_amd import _hip
 from dipoorlet_amd.csrc import build as hipbuild
 
@@ -42,80 +43,41 @@ def test_build_work_items_host(lib):
     got = [(arr[i].seg, arr[i].offset, arr[i].count, arr[i].slot) for i in range(n)]
     assert got == [(0, 0, 2048, 0), (0, 2048, 2048, 0), (0, 4096, 904, 0), (1, 16, 1024, 1),
                    (3, 7, 2048, 3), (3, 2055, 1, 3)]
-    # every element covered exactly once
-    for seg, off, cnt, slot in spans:
-        cov = sorted((o, c) for s, o, c, sl in got if s == seg)
-        pos = off
-        for o, c in cov:
-            assert o == pos
-            pos += c
-        assert pos == off + cnt
+    K.check_work_items(spans, 2048, got)                      # every element covered exactly once
     with pytest.raises(_hip.DipoorletHipError):
         _hip.build_work_items(spans, 1000)  # not a multiple of 1024
 
 
+def test_builders_fill_with_asserts_stripped(lib):
+    """The filling call of the count-then-fill builders is no assert's operand: `python -O` still fills the tables."""
+    import subprocess
+    import sys
+    code = ("from dipoorlet_amd import _hip\n"
+            "s = [(0, 0, 5000, 0), (1, 16, 1024, 1)]\n"
+            "a, n = _hip.build_work_items(s, 2048); b, m, bb = _hip.build_balanced_items(s, 2); c, k, ps = _hip.build_octav_slices(s)\n"
+            "print(sum(a[i].count for i in range(n)), sum(b[i].count for i in range(m)), list(bb), sum(c[i].count for i in range(k)), list(ps))\n")
+    r = subprocess.run([sys.executable, "-O", "-c", code], cwd=ROOT, check=True, capture_output=True, text=True)
+    assert r.stdout.split("\n")[-2] == "6024 6024 [0, 1, 3] 6024 [0, 1, 1, 2]", r.stdout
+
+
 def test_build_balanced_items_host(lib):
-    import random
-    rnd = random.Random(4)
-    for trial in range(30):
-        spans = [(i, rnd.choice([0, 16, 4096]), rnd.choice([0, 1, 1000, 2048, 25088, 401408, 802816 * 16]), 100 + i)
-                 for i in range(rnd.randint(1, 12))]
-        nb = rnd.choice([1, 2, 7, 64, 512])
+    for spans, nb in K.balanced_sets():
         arr, n, bb = _hip.build_balanced_items(spans, nb)
         items = [(arr[i].seg, arr[i].offset, arr[i].count, arr[i].slot) for i in range(n)]
-        assert bb[0] == 0 and bb[nb] == n and all(bb[i] <= bb[i + 1] for i in range(nb))
-        # every element of every span exactly once, in order, slots preserved
-        for seg, off, cnt, slot in spans:
-            pos = off
-            for s_, o, c, sl in items:
-                if s_ == seg:
-                    assert o == pos and sl == slot and c > 0
-                    pos += c
-            assert pos == off + cnt
-        # shares are balanced to within one aligned piece per span boundary
-        total = sum(c for _, _, c, _ in spans)
-        share = [sum(items[k][2] for k in range(bb[b], bb[b + 1])) for b in range(nb)]
-        assert sum(share) == total
-        if total >= nb * 8192:
-            assert max(share) <= total / nb + 1024 * (len(spans) + 1)
-        # cuts inside a span are 4 KiB aligned relative to the span start
-        for s_, o, c, sl in items:
-            base = [sp for sp in spans if sp[0] == s_][0][1]
-            assert (o - base) % 1024 == 0
+        # every element of every span exactly once, in order, slots preserved; balanced shares; 4 KiB-aligned cuts
+        K.check_balanced(spans, nb, items, list(bb))
 
 
 def test_build_octav_slices_host(lib):
     """HOST side of the one-read OCTAV form: every pair cut into ceil(count / cap) equal slices on multiples of 4 elements,
     largest pairs first, pair_slice0 = the pair's contiguous slice range; a pair beyond 64 slices refuses the form."""
-    import random
-    rnd = random.Random(9)
     cap = _hip.lib().dpl_octav_slice_cap()
     assert cap % 4096 == 0 and _hip.lib().dpl_octav_list_cap(cap) == cap // 16 + 16384 and _hip.lib().dpl_octav_list_cap(20480) >= 20480
     assert _hip.lib().dpl_octav_small_pair() == 20480
-    for trial in range(20):
-        n = rnd.randint(1, 40)
-        spans = [(i % 5, 1000 * i, rnd.choice([0, 1, 3, 777, 20480, 20481, 401408, cap, cap + 1, 802816, 3 * cap + 5]), i)
-                 for i in range(n)]
+    for spans in K.slice_sets(cap):
         arr, ns, ps = _hip.build_octav_slices(spans)
         items = [(arr[i].seg, arr[i].offset, arr[i].count, arr[i].slot, arr[i].reserved) for i in range(ns)]
-        sizes_seen = []
-        for seg, off, cnt, slot in spans:
-            lo, hi = ps[2 * slot], ps[2 * slot + 1]
-            want = 0 if cnt == 0 else -(-cnt // cap)
-            assert hi - lo == want
-            pos = off
-            for k in range(lo, hi):
-                s_, o, c, sl, res = items[k]
-                assert (s_, o, sl, res) == (seg, pos, slot, want) and 0 < c <= cap
-                assert (o - off) % 4 == 0
-                if k + 1 < hi:
-                    assert c % 4 == 0 and c == items[lo][2]          # equal slices; only the last one takes the remainder
-                pos += c
-            assert pos == off + cnt
-            if want:
-                sizes_seen.append((lo, cnt))
-        order = [c for _, c in sorted(sizes_seen)]
-        assert order == sorted(order, reverse=True)                   # largest pairs first
+        K.check_slices(spans, cap, items, list(ps))
     assert _hip.build_octav_slices([(0, 0, 65 * cap, 0)]) is None
 
 
@@ -198,6 +160,7 @@ def test_octav_plan_host_side(tmp_path):
     assert (z.n_pairs, z.n_slices, z.n_multi, z.n_small) == (B * T, B * 5, B, B)
     assert z.history_bytes == 4 * 2 * T * 64 and z.result_bytes == 4 * 3 * B * T
     assert z.rescue_bytes >= 8 * 2048 * (B * 3) + 8 * 3072 * B * T and z.rescue_bytes < 8 * 2048 * (B * 3) + 8 * 3072 * B * T + 4096 + 4 * 67 * B * T
+    K.check_plan_sizes(z, elems * B, T, cap, L.dpl_octav_list_cap)
     # a job bound to fake addresses: the tables' pointers fall inside the tables block, the lists where they were put
     job = _hip.OctavOnereadJob()
     base = 1 << 40
@@ -205,12 +168,11 @@ def test_octav_plan_host_side(tmp_path):
                                base + (6 << 30), 9, 1, 20, C.byref(job))
     assert st == 0 and job.compaction_inline == 0 and job.d_clist0 is None
     assert (job.write_epoch, job.reset_epoch, job.dynamic_sym, job.max_iters) == (1, 0, 1, 20)
-    for f in ("d_slices", "d_pair_slice0", "d_pair_spans", "d_pair_base", "d_pair_base_full", "d_pair_order", "d_items", "d_block_begin"):
-        assert base <= getattr(job, f) < base + z.tables_bytes, f
-    assert job.d_vis == base + (1 << 30) and job.d_states == base + (2 << 30) and job.d_rescue_bm == base + (3 << 30)
-    assert job.d_list0 == base + (4 << 30) and job.d_list1 == base + (5 << 30) and job.d_seg_ptrs == base + (6 << 30)
+    K.check_job(job, z, (base, base + (1 << 30), base + (2 << 30), base + (3 << 30), base + (4 << 30), base + (5 << 30), None, base + (6 << 30)),
+                9, 1, 20)                   # tables inside the tables block, lists where they were put, epoch fields
     assert L.dpl_octav_plan_bind(plan, base, base, base, base, base, base, base + (7 << 30), base, 16, 0, 20, C.byref(job)) == 0
     assert job.compaction_inline == 1 and job.d_clist1 - job.d_clist0 == z.fallback_bytes // 2 and (job.write_epoch, job.reset_epoch) == (0, 1)
+    K.check_job(job, z, (base,) * 6 + (base + (7 << 30), base), 16, 0, 20)
     L.dpl_octav_plan_destroy(plan)
     # more than 64 slices: no plan (the two-read form serves such a set)
     big, _ = _hip._span_array([(0, 0, 65 * cap, 0)])
@@ -238,11 +200,11 @@ def test_octav_fallback_layout_host():
     L = _hip.lib()
     n = 6
     st = (_hip.OctavState * (n + 1))()
-    for i, (mode, done, elems) in enumerate([(2, 1, 1000), (1, 0, 1000), (3, 0, 50), (1, 1, 77), (1, 0, 33), (0, 0, 9)]):
+    for i, (mode, done, elems) in enumerate(K.SIX_STATES):
         st[i].mode, st[i].done, st[i].n_elems = mode, done, elems
     base = np.full(n + 1, 99, np.uint64)
     assert L.dpl_octav_fallback_layout(C.addressof(st), n, base.ctypes.data) == 1024 + 64
-    assert base.tolist() == [0, 0, 1024, 1024, 1024, 1088, 1088]
+    assert base.tolist() == [0, 0, 1024, 1024, 1024, 1088, 1088] == K.fallback_layout(K.SIX_STATES)
     assert L.dpl_octav_fallback_layout(None, n, base.ctypes.data) < 0
 
 
