@@ -1,7 +1,11 @@
-// MI355X (gfx950 / CDNA4) activation-calibration kernels + C ABI (include/dipoorlet_hip.h).
+// MI355X (gfx950 / CDNA4) activation-calibration kernels + their C ABI (include/dipoorlet_hip.h): the statistics chain — running
+// min / max (K1), the |x| histogram and its range-pass speculation (K2, K2s), the clip searches on it (K4, K4b, K4c).  The Q/DQ
+// pair is in fake_quant_kernels.hip, the row / column / cosine / bias-correction sums in side_kernels.hip, the ABI's version,
+// error text, device info and streams in runtime_abi.hip.
 //
-// Everything here but the entropy search (K4b: fp64 arithmetic on an LDS-resident row) is an HBM-bound streaming
-// reduction / scatter-add: no MFMA.  Design rules
+// Everything here but the two searches K4b / K4c (fp64 arithmetic on an LDS-resident row) is an HBM-bound streaming
+// reduction / scatter-add: no MFMA.  A kernel's dynamic-LDS layout is defined ONCE, in a struct of offset functions beside it:
+// the kernel takes its region pointers from it, the launcher its byte count.  Design rules
 // (guides: cdna_hip_programming.md G2/G11/G12/G13, MI355X_MICROARCH.md §LDS/§HBM):
 //   * 16 B per lane coalesced loads (global_load_dwordx4), several independent loads in flight,
 //     one workgroup per work item (a contiguous chunk of ONE tensor), >> 256 workgroups per launch;
@@ -19,17 +23,7 @@
 
 namespace {
 
-// ================================================================ K1: running min / max
-struct MinMaxOp {
-    float mn, mx;
-    uint32_t nan;
-    __device__ __forceinline__ void operator()(float x) {
-        mn = fminf(mn, x);
-        mx = fmaxf(mx, x);
-        nan |= (x != x);
-    }
-};
-
+// ================================================================ K1: running min / max  (MinMaxOp: common.hpp)
 // Workgroup reduction of the lanes' MinMaxOp and the three atomics into the slot's accumulators (s_mn / s_mx / s_nan: one word per wave).
 __device__ __forceinline__ void minmax_commit(const MinMaxOp& op, uint32_t slot, float* s_mn, float* s_mx, uint32_t* s_nan,
                                               uint32_t* __restrict__ min_enc, uint32_t* __restrict__ max_enc,
@@ -184,6 +178,15 @@ __device__ __forceinline__ void hist_op_init(HistOp<kFast>& op, const dpl_hist_r
     op.nonzero = 0u;
 }
 
+// LDS of a histogramming workgroup:  uint32 counters[bins + 1] | uint32 s_nz[waves]
+// (counter `bins`: HistOp's estimates of `bins`; s_nz: hist_flush's non-zero count per wave).  k_abs_hist's whole dynamic LDS,
+// the tail of k_abs_hist_rest's (RestLds) and the head of k_minmax_hist's (MinMaxHistLds).
+struct HistLds {
+    static __host__ __device__ uint32_t* s_nz(uint32_t* counters, int bins) { return counters + bins + 1; }
+    static __host__ __device__ uint32_t* end(uint32_t* counters, int bins) { return s_nz(counters, bins) + kBlock / kWave; }
+    static __host__ __device__ size_t bytes(int bins) { return ((size_t)bins + 1 + kBlock / kWave) * sizeof(uint32_t); }
+};
+
 // The workgroup's LDS counters of one item -> the slot's row of `out` (uint64: the accumulated histogram; uint32: a batch's own
 // counts in the range pass, where a tensor of fewer than 2^32 elements cannot overflow a counter).
 template <class Count>
@@ -229,8 +232,8 @@ __global__ __launch_bounds__(kBlock) void k_abs_hist(const dpl_work_item* __rest
                                                       const float* const* __restrict__ segs,
                                                       const dpl_hist_range* __restrict__ ranges, int bins,
                                                       uint64_t* __restrict__ hist) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];  // bins + 1 counters + one word per wave
-    uint32_t* s_nz = lds + bins + 1;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];  // HistLds
+    uint32_t* s_nz = HistLds::s_nz(lds, bins);
     uint32_t k0, k1;
     block_items(bb, k0, k1);
     for (uint32_t k = k0; k < k1; ++k) {
@@ -308,11 +311,21 @@ __global__ void k_hist_prepare(const float* __restrict__ gmin, const float* __re
 // batch against the range its running min / max give (a SNAPSHOT taken before the launch: other workgroups move the live
 // accumulators during it) into a per-batch ledger entry; the histogram pass compares the snapshot with the final range byte for
 // byte (k_hist_resolve), adds the rows that match and reads only the tensors whose guess was wrong (k_abs_hist_rest).  A wrong
-// guess costs what it always cost, so no count can change.  Ledger entry (dpl_hist_spec_entry_bytes):
-//   dpl_hist_range snap[n_slots] | uint32 flags[n_slots] | (16-byte aligned) uint32 counts[n_slots, bins]
-__host__ __device__ inline uint64_t spec_counts_offset(int64_t n_slots) {
-    return (((uint64_t)n_slots * (sizeof(dpl_hist_range) + sizeof(uint32_t))) + 15ull) & ~15ull;
-}
+// guess costs what it always cost, so no count can change.
+//
+// A ledger entry (device memory, 16-byte aligned; the documented format: callers read the flags at n_slots * sizeof(dpl_hist_range)):
+//   dpl_hist_range snap[n_slots] | uint32 flags[n_slots] | pad to 16 bytes | uint32 counts[n_slots, bins]
+struct SpecEntry {
+    dpl_hist_range* snap;
+    uint32_t* flags;
+    uint32_t* counts;
+    SpecEntry(const void* d_entry, int64_t n_slots)   // (const: dpl_hist_spec_cuts only reads the flags)
+        : snap((dpl_hist_range*)d_entry), flags((uint32_t*)(snap + n_slots)), counts((uint32_t*)((char*)d_entry + counts_offset(n_slots))) {}
+    static uint64_t counts_offset(int64_t n_slots) {
+        return (((uint64_t)n_slots * (sizeof(dpl_hist_range) + sizeof(uint32_t))) + 15ull) & ~15ull;
+    }
+    static uint64_t bytes(int64_t n_slots, int bins) { return counts_offset(n_slots) + (uint64_t)n_slots * (uint64_t)bins * sizeof(uint32_t); }
+};
 
 // Snapshot of the provisional ranges + the entry's counts zeroed.  A slot with no data yet, a NaN flag or a range numpy would
 // refuse comes out with status != 0 ("no guess": the fused kernel takes its min / max only and k_hist_resolve never accepts it).
@@ -354,6 +367,16 @@ __device__ __forceinline__ void minmax_hist_body(const dpl_work_item& it, const 
     hist_flush(op.h.nonzero, it, r, bins, counts, lds, s_nz);
 }
 
+// LDS of k_minmax_hist:  HistLds | float s_mn[waves] | float s_mx[waves] | uint32 s_nan[waves]   (minmax_commit's words)
+struct MinMaxHistLds {
+    static __host__ __device__ float* s_mn(uint32_t* base, int bins) { return reinterpret_cast<float*>(HistLds::end(base, bins)); }
+    static __host__ __device__ float* s_mx(uint32_t* base, int bins) { return s_mn(base, bins) + kBlock / kWave; }
+    static __host__ __device__ uint32_t* s_nan(uint32_t* base, int bins) {
+        return reinterpret_cast<uint32_t*>(s_mx(base, bins) + kBlock / kWave);
+    }
+    static __host__ __device__ size_t bytes(int bins) { return HistLds::bytes(bins) + 3 * (kBlock / kWave) * sizeof(uint32_t); }
+};
+
 // k_minmax and k_abs_hist in one read: min / max / NaN into the accumulators as k_minmax does, counts against snap[slot] into the
 // ledger entry as k_abs_hist does (same HistOp, same flush).
 __global__ __launch_bounds__(kBlock) void k_minmax_hist(const dpl_work_item* __restrict__ items,
@@ -363,11 +386,11 @@ __global__ __launch_bounds__(kBlock) void k_minmax_hist(const dpl_work_item* __r
                                                          uint32_t* __restrict__ nan_flag,
                                                          const dpl_hist_range* __restrict__ snap, int bins,
                                                          uint32_t* __restrict__ counts) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_mh[];  // bins + 1 counters, one word per wave, 3 words per wave
-    uint32_t* s_nz = lds_mh + bins + 1;
-    float* s_mn = reinterpret_cast<float*>(s_nz + kBlock / kWave);
-    float* s_mx = s_mn + kBlock / kWave;
-    uint32_t* s_nan = reinterpret_cast<uint32_t*>(s_mx + kBlock / kWave);
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_mh[];  // MinMaxHistLds
+    uint32_t* s_nz = HistLds::s_nz(lds_mh, bins);
+    float* s_mn = MinMaxHistLds::s_mn(lds_mh, bins);
+    float* s_mx = MinMaxHistLds::s_mx(lds_mh, bins);
+    uint32_t* s_nan = MinMaxHistLds::s_nan(lds_mh, bins);
     uint32_t k0, k1;
     block_items(bb, k0, k1);
     for (uint32_t k = k0; k < k1; ++k) {
@@ -488,16 +511,31 @@ __device__ __forceinline__ void rest_cut(const uint64_t* P, int n_tensors, uint6
     cut = P[lo - 1] + ((target - P[lo - 1]) & ~1023ull);
 }
 
+// LDS of rest_prefix:  uint64 P[n_tensors + 1] | uint64 s_tot[waves]   (the prefix sums; the scan's wave totals).
+// k_hist_spec_cuts's whole dynamic LDS and the head of k_abs_hist_rest's (n_tensors <= DPL_HIST_SPEC_MAX_TENSORS: 16 KiB).
+struct RestPrefixLds {
+    static __host__ __device__ uint64_t* P(uint32_t* base) { return reinterpret_cast<uint64_t*>(base); }
+    static __host__ __device__ uint64_t* s_tot(uint32_t* base, int n_tensors) { return P(base) + n_tensors + 1; }
+    static __host__ __device__ size_t bytes(int64_t n_tensors) { return ((size_t)n_tensors + 1 + kBlock / kWave) * sizeof(uint64_t); }
+};
+
+// LDS of k_abs_hist_rest:  RestPrefixLds | HistLds
+struct RestLds {
+    static __host__ __device__ uint32_t* counters(uint32_t* base, int n_tensors) {
+        return reinterpret_cast<uint32_t*>(RestPrefixLds::s_tot(base, n_tensors) + kBlock / kWave);
+    }
+    static __host__ __device__ size_t bytes(int64_t n_tensors, int bins) { return RestPrefixLds::bytes(n_tensors) + HistLds::bytes(bins); }
+};
+
 __global__ __launch_bounds__(kBlock) void k_abs_hist_rest(const uint64_t* __restrict__ elems, const uint32_t* __restrict__ flags,
                                                            int n_tensors, const float* const* __restrict__ segs,
                                                            const dpl_hist_range* __restrict__ ranges, int bins,
                                                            uint64_t* __restrict__ hist) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_rest[];
-    // layout: uint64 P[n_tensors + 1] | uint64 wave totals [4] | counters [bins + 1] | s_nz [4]
-    uint64_t* P = reinterpret_cast<uint64_t*>(lds_rest);
-    uint64_t* s_tot = P + n_tensors + 1;
-    uint32_t* lds = reinterpret_cast<uint32_t*>(s_tot + kBlock / kWave);
-    uint32_t* s_nz = lds + bins + 1;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_rest[];  // RestLds
+    uint64_t* P = RestPrefixLds::P(lds_rest);
+    uint64_t* s_tot = RestPrefixLds::s_tot(lds_rest, n_tensors);
+    uint32_t* lds = RestLds::counters(lds_rest, n_tensors);
+    uint32_t* s_nz = HistLds::s_nz(lds, bins);
     rest_prefix(elems, flags, n_tensors, P, s_tot);
     if (P[n_tensors] == 0) return;
     uint64_t cut[2];
@@ -531,9 +569,9 @@ __global__ __launch_bounds__(kBlock) void k_abs_hist_rest(const uint64_t* __rest
 // The cuts k_abs_hist_rest works to, written out (dpl_hist_spec_cuts: what tests hold against tests/hist_spec_model.py).
 __global__ __launch_bounds__(kBlock) void k_hist_spec_cuts(const uint64_t* __restrict__ elems, const uint32_t* __restrict__ flags,
                                                             int n_tensors, uint64_t* __restrict__ cuts) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_cuts[];
-    uint64_t* P = reinterpret_cast<uint64_t*>(lds_cuts);
-    uint64_t* s_tot = P + n_tensors + 1;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_cuts[];  // RestPrefixLds
+    uint64_t* P = RestPrefixLds::P(lds_cuts);
+    uint64_t* s_tot = RestPrefixLds::s_tot(lds_cuts, n_tensors);
     rest_prefix(elems, flags, n_tensors, P, s_tot);
     if (threadIdx.x != 0) return;
     uint64_t cut = 0;
@@ -629,14 +667,29 @@ __device__ __forceinline__ uint32_t kl_live_below(const uint64_t* __restrict__ m
     return bcnt[k] + (uint32_t)__popcll(mask[k] & ((1ull << (x & 63u)) - 1ull));
 }
 
+// LDS of k_hist_kl, nblk = ceil(bins / 64):
+//   uint64 cs[bins + 1]    exclusive prefix sum of the counts
+//   uint64 mask[nblk + 1]  bit b & 63 of mask[b >> 6]: count of bin b != 0 (the last entry is 0)
+//   uint64 part[kBlock]    the scan's per-thread sums
+//   uint32 bcnt[nblk + 1]  non-zero bins below bin 64 k
+struct KlLds {
+    static __host__ __device__ uint32_t nblk(int bins) { return ((uint32_t)bins + 63u) >> 6; }
+    static __host__ __device__ uint64_t* mask(uint64_t* cs, int bins) { return cs + bins + 1; }
+    static __host__ __device__ uint64_t* part(uint64_t* cs, int bins) { return mask(cs, bins) + nblk(bins) + 1; }
+    static __host__ __device__ uint32_t* bcnt(uint64_t* cs, int bins) { return reinterpret_cast<uint32_t*>(part(cs, bins) + kBlock); }
+    static __host__ __device__ size_t bytes(int bins) {
+        return ((size_t)bins + 1 + nblk(bins) + 1 + kBlock) * sizeof(uint64_t) + ((size_t)nblk(bins) + 1) * sizeof(uint32_t);
+    }
+};
+
 __global__ __launch_bounds__(kBlock) void k_hist_kl(const uint64_t* __restrict__ hist, int bins, int levels, int n_chunks,
                                                      double* __restrict__ div) {
-    extern __shared__ __attribute__((aligned(16))) uint64_t kl_lds[];
-    const uint32_t nblk = ((uint32_t)bins + 63u) >> 6;
-    uint64_t* cs = kl_lds;                     // [bins + 1] exclusive prefix sum of the counts
-    uint64_t* mask = cs + bins + 1;            // [nblk + 1] bit b & 63 of mask[b >> 6]: count of bin b != 0 (the last entry is 0)
-    uint64_t* part = mask + nblk + 1;          // [kBlock] the scan's per-thread sums
-    uint32_t* bcnt = reinterpret_cast<uint32_t*>(part + kBlock);   // [nblk + 1] non-zero bins below bin 64 k
+    extern __shared__ __attribute__((aligned(16))) uint64_t kl_lds[];  // KlLds
+    const uint32_t nblk = KlLds::nblk(bins);
+    uint64_t* cs = kl_lds;
+    uint64_t* mask = KlLds::mask(kl_lds, bins);
+    uint64_t* part = KlLds::part(kl_lds, bins);
+    uint32_t* bcnt = KlLds::bcnt(kl_lds, bins);
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     const uint32_t slot = blockIdx.x / (uint32_t)n_chunks, chunk = blockIdx.x % (uint32_t)n_chunks;
     const uint64_t* __restrict__ h = hist + (uint64_t)slot * (uint64_t)bins;
@@ -770,12 +823,18 @@ __global__ __launch_bounds__(kWave) void k_hist_kl_pick(const double* __restrict
 // and a candidate's value does not depend on the launch's geometry.
 constexpr int kGridUniform = DPL_GRID_UNIFORM, kGridE4M3 = DPL_GRID_E4M3;
 
+// LDS of k_hist_qmse:  double hd[bins] | uint64 part[waves]   (the counts; the waves' totals)
+struct QmseLds {
+    static __host__ __device__ uint64_t* part(double* hd, int bins) { return reinterpret_cast<uint64_t*>(hd + bins); }
+    static __host__ __device__ size_t bytes(int bins) { return (size_t)bins * sizeof(double) + (kBlock / kWave) * sizeof(uint64_t); }
+};
+
 template <int GRID>
 __global__ __launch_bounds__(kBlock) void k_hist_qmse(const uint64_t* __restrict__ hist, int bins, int first, int top, int n_chunks,
                                                        double* __restrict__ err) {
-    extern __shared__ __attribute__((aligned(16))) double qm_lds[];
-    double* hd = qm_lds;                                            // [bins] the counts
-    uint64_t* part = reinterpret_cast<uint64_t*>(hd + bins);        // [kBlock / kWave] the waves' totals
+    extern __shared__ __attribute__((aligned(16))) double qm_lds[];  // QmseLds
+    double* hd = qm_lds;
+    uint64_t* part = QmseLds::part(qm_lds, bins);
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     const uint32_t slot = blockIdx.x / (uint32_t)n_chunks, chunk = blockIdx.x % (uint32_t)n_chunks;
     const uint64_t* __restrict__ h = hist + (uint64_t)slot * (uint64_t)bins;
@@ -833,530 +892,33 @@ __global__ __launch_bounds__(kBlock) void k_hist_qmse(const uint64_t* __restrict
     }
 }
 
-// ================================================================ K5: per-row min / max of a [rows, cols] matrix
-__global__ __launch_bounds__(kBlock) void k_rowwise_minmax(const float* __restrict__ w, int64_t cols,
-                                                            float* __restrict__ omn, float* __restrict__ omx) {
-    __shared__ float s_mn[kBlock / kWave], s_mx[kBlock / kWave];
-    __shared__ uint32_t s_nan[kBlock / kWave];
-    const float* p = w + (int64_t)blockIdx.x * cols;
-    MinMaxOp op{INFINITY, -INFINITY, 0u};
-    // rows can be longer than 2^32 only in theory; weights are at most a few 10^7 elements
-    stream_span(p, (uint32_t)cols, op);
-    float mn = wave_min(op.mn), mx = wave_max(op.mx);
-    uint32_t nn = __any(op.nan) ? 1u : 0u;
-    const int wv = threadIdx.x / kWave;
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        s_mn[wv] = mn;
-        s_mx[wv] = mx;
-        s_nan[wv] = nn;
+// ================================================================ what the entry points below check alike (as check_blocks)
+inline int check_bins(const char* who, int bins) {
+    if (bins < 1 || bins > DPL_MAX_BINS) {
+        snprintf(g_err, sizeof(g_err), "%s: bins must be in [1, %d]", who, DPL_MAX_BINS);
+        return -2;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < kBlock / kWave; ++k) {
-            mn = fminf(mn, s_mn[k]);
-            mx = fmaxf(mx, s_mx[k]);
-            nn |= s_nan[k];
-        }
-        omn[blockIdx.x] = nn ? NAN : mn;
-        omx[blockIdx.x] = nn ? NAN : mx;
-    }
+    return 0;
 }
 
-// ================================================================ K5b: per-column running max |x| of a [rows, cols] matrix
-// acc[c] = max(acc[c], max_r |x[r, c]|) as an UNSIGNED-INTEGER maximum on the bit pattern of |x|: non-negative floats order like
-// their bits and every NaN pattern lies above +inf, so a NaN in a column (or already in acc) stays a NaN, -0.0 counts as +0.0,
-// and the result does not depend on the order in which workgroups arrive (no floating-point atomic).
-// Geometry: a workgroup is tw lanes along the columns (tw = 2^k <= 64; a lane owns T = one float, or four with 16-B loads) by
-// 256 / tw rows; blockIdx.x picks the column tile, blockIdx.y the rows, grid-strided, kColUnroll independent loads in flight per
-// lane.  A lane keeps its columns' maximum in registers over the whole row loop, the 256 / tw lanes that share a column are
-// folded in LDS, and lane row 0 issues at most ONE atomicMax per column and workgroup — none where the running value read
-// beforehand is not below the candidate (acc only grows, so a stale read can only cause a redundant atomic, never a lost one).
-constexpr int kColMaxLanes = 64;     // 64 lanes x 16 B: a wave instruction reads 1 KiB contiguous of one row
-constexpr int kColUnroll = 4;
-constexpr int kColMaxBlocks = 2048;  // 8 workgroups per CU
-using u4 = __attribute__((ext_vector_type(4))) uint32_t;
-
-template <class T>   // uint32_t: one column per lane;  u4: four, cols % 4 == 0 and x 16-byte aligned
-__global__ __launch_bounds__(kBlock) void k_colwise_absmax(const T* __restrict__ x_generic, uint64_t rows, uint64_t cv, uint32_t tw,
-                                                            uint32_t* __restrict__ acc) {
-    __shared__ T s_m[kBlock];
-    const __attribute__((address_space(1))) T* x = (const __attribute__((address_space(1))) T*)x_generic;
-    const uint32_t tid = threadIdx.x, rp = kBlock / tw;
-    const uint64_t c = (uint64_t)blockIdx.x * tw + (tid & (tw - 1));     // this lane's (vector) column; cv of them in a row
-    T m = T(0);
-    if (c < cv) {
-        const uint64_t step = (uint64_t)gridDim.y * rp;
-        for (uint64_t r = (uint64_t)blockIdx.y * rp + tid / tw; r < rows; r += kColUnroll * step) {
-            T v[kColUnroll];
-#pragma unroll
-            for (int u = 0; u < kColUnroll; ++u) {
-                const uint64_t rr = r + u * step;       // past the end: the last row once more (a branch here would serialise the loads)
-                v[u] = __builtin_nontemporal_load(x + (rr < rows ? rr : rows - 1) * cv + c);
-            }
-#pragma unroll
-            for (int u = 0; u < kColUnroll; ++u) m = __builtin_elementwise_max(m, v[u] & T(0x7FFFFFFFu));
-        }
-    }
-    s_m[tid] = m;
-    __syncthreads();
-    for (uint32_t h = kBlock / 2; h >= tw; h >>= 1) {      // tid and tid + h (h a multiple of tw) share a column
-        if (tid < h) s_m[tid] = __builtin_elementwise_max(s_m[tid], s_m[tid + h]);
-        __syncthreads();
-    }
-    if (tid < tw && c < cv) {
-        m = s_m[tid];
-        if constexpr (sizeof(T) == 16) {
-            uint32_t* a = acc + 4 * c;
-            const uint32_t a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];     // (acc is only 4-byte aligned: four loads, issued together)
-            if (m.x > a0) atomicMax(a + 0, m.x);
-            if (m.y > a1) atomicMax(a + 1, m.y);
-            if (m.z > a2) atomicMax(a + 2, m.z);
-            if (m.w > a3) atomicMax(a + 3, m.w);
-        } else {
-            if (m > acc[c]) atomicMax(acc + c, m);
-        }
-    }
+// dpl_hist_spec_accumulate / dpl_hist_spec_cuts: P[n_slots + 1] must fit k_abs_hist_rest's LDS, n_blocks a grid
+inline int check_spec_geometry(const char* who, int64_t n_slots, int64_t n_blocks) {
+    const bool slots_ok = n_slots > 0 && n_slots <= DPL_HIST_SPEC_MAX_TENSORS;
+    if (slots_ok && n_blocks > 0 && n_blocks <= 0x7FFFFFFFll) return 0;
+    snprintf(g_err, sizeof(g_err), "%s: %s", who, slots_ok ? "n_blocks out of range" : "n_slots must be in [1, DPL_HIST_SPEC_MAX_TENSORS]");
+    return -2;
 }
 
-// ================================================================ K6: fused quantize -> dequantize
-__device__ __forceinline__ float fq_one(float x, float scale, float zp, float qlo, float qhi) {
-    float q = __fadd_rn(rintf(__fdiv_rn(x, scale)), zp);  // round half to even, then zero point
-    q = fminf(fmaxf(q, qlo), qhi);                        // saturate
-    return __fmul_rn(__fsub_rn(q, zp), scale);
-}
-
-// The OCP FP8 E4M3 ("e4m3fn": bias 7, 3 mantissa bits, subnormal step 2^-9, largest finite 448, no infinities) Q/DQ of one value:
-// the nearest e4m3fn value of v as fp32, round half to even (subnormals too), SATURATING (|v| > 448 and +-inf give +-448: ONNX
-// QuantizeLinear, saturate = 1), NaN stays NaN, the sign of zero is kept.  In fp32 arithmetic on the value's own exponent bits: a
-// value of binade e lies on a grid of step 2^(max(e, -6) - 3); |v| times the inverse step is exact (a power of two), v_rndne
-// rounds it half to even, times the step is exact again (a carry into the next binade lands on a value of the format).  Every
-// fp32 subnormal rounds to zero whether or not the multiply flushes it.  gfx950's v_cvt_pk_fp8_f32 / v_cvt_f32_fp8 would do the
-// same in two instructions; how they round subnormals and what they return above 448 and for NaN has not been measured on this
-// hardware (scripts/fp8_cvt_probe.hip measures it), and the kernel is bound by its 8 B per element, not by these
-// eight operations.
-__device__ __forceinline__ float e4m3_round(float v) {
-    const float a = fminf(fabsf(v), 448.f);            // saturate (a NaN comes out finite here: routed below)
-    uint32_t e = __float_as_uint(a) >> 23;             // biased exponent: binade e - 127
-    e = e < 121u ? 121u : e;                           // below 2^-6 the step stays 2^-9
-    const float step = __uint_as_float((e - 3u) << 23), inv = __uint_as_float((257u - e) << 23);      // 2^(e-130), 2^(130-e)
-    const float r = copysignf(__fmul_rn(rintf(__fmul_rn(a, inv)), step), v);
-    return v != v ? v : r;
-}
-
-// The number format of the Q/DQ pair, a compile-time parameter of the streaming skeleton below beside PRE: kFqFmtInt the integer
-// grid of fq_one (scale, zero point, [qlo, qhi]); kFqFmtE4M3 y = fl32(e4m3_round(fl32(x / scale)) * scale) — the same shape, two
-// single fp32 operations around the rounding; zero point / qlo / qhi are not read (zp_p may be null).
-enum { kFqFmtInt = 0, kFqFmtE4M3 = 1 };
-template <int FMT>
-__device__ __forceinline__ float fq_elem(float x, float scale, float zp, float qlo, float qhi) {
-    if (FMT == kFqFmtE4M3) return __fmul_rn(e4m3_round(__fdiv_rn(x, scale)), scale);
-    return fq_one(x, scale, zp, qlo, qhi);
-}
-template <int FMT>
-__device__ __forceinline__ float fq_zp(const int32_t* __restrict__ zp_p, uint32_t c) {
-    return FMT == kFqFmtInt ? (float)zp_p[c] : 0.f;
-}
-
-// What the producer of a fake-quantised tensor would have written, applied on the way in (the reference's merge-ReLU rule puts
-// most activation Q/DQ pairs directly behind a ReLU, quantize.py:50-55): kFqPreNone x; kFqPreRelu torch.relu(x) = np.maximum(x, 0)
-// (NaN stays NaN; -0 and +0 quantise alike on an integer grid, FP8 keeps the zero's sign); kFqPreAddRelu relu(x + x2), the residual Add of a bottleneck and its ReLU (one fp32
-// addition, rounded to nearest, as torch.add).
-enum { kFqPreNone = 0, kFqPreRelu = 1, kFqPreAddRelu = 2 };
-template <int PRE>
-__device__ __forceinline__ float fq_pre(float x, float x2) {
-    if (PRE == kFqPreAddRelu) x = __fadd_rn(x, x2);
-    if (PRE != kFqPreNone) x = x < 0.f ? 0.f : x;
-    return x;
-}
-
-// One workgroup fake-quantises elements [e0, e0 + cnt) of a tensor viewed as [outer, n_channels, inner] (n_channels == 1: per
-// tensor).  A CONTIGUOUS chunk per workgroup (few large equal shares stream faster from HBM than a grid-stride walk), four
-// 16-byte vectors per lane in flight, non-temporal loads and stores (each byte is touched once).  The channel of a vector needs no
-// division in the loop: a lane's (column, channel) advance by a constant per step — 1024 elements = (1024 / inner) rows and
-// (1024 % inner) columns, both computed once per chunk on the scalar unit — with one conditional wrap each.
-template <int PRE, int FMT>
-__device__ __forceinline__ void fq_span(const float* __restrict__ x, const float* __restrict__ x2, float* __restrict__ y, uint64_t e0,
-                                        uint32_t cnt, const float* __restrict__ scale_p, const int32_t* __restrict__ zp_p,
-                                        uint32_t n_channels, uint32_t inner, float qlo, float qhi) {
-    typedef __attribute__((address_space(1))) f4* gptr_f4w;
-    const uint32_t tid = threadIdx.x;
-    const float* xs = x + e0;
-    const float* x2s = PRE == kFqPreAddRelu ? x2 + e0 : xs;
-    float* ys = y + e0;
-    // 16-byte vectors whatever the rows' length: a vector of a row that is no multiple of four long (7 x 7 maps: 49) may straddle two
-    // channels — it carries the parameters of both and picks per element (rows shorter than a vector: element by element)
-    const bool vec = ((((uintptr_t)xs | (uintptr_t)x2s | (uintptr_t)ys) & 15u) == 0u) && (n_channels == 1u || inner >= 4u);
-    if (!vec) {   // unaligned views / rows shorter than a vector: element by element, same bookkeeping
-        const uint64_t e = e0 + tid;
-        uint32_t col = (uint32_t)(e % inner), c = (uint32_t)((e / inner) % n_channels);
-        const uint32_t step_cols = (uint32_t)kBlock % inner, step_ch = ((uint32_t)kBlock / inner) % n_channels;
-        for (uint32_t i = tid; i < cnt; i += kBlock) {
-            ys[i] = fq_elem<FMT>(fq_pre<PRE>(xs[i], x2s[i]), scale_p[c], fq_zp<FMT>(zp_p, c), qlo, qhi);
-            col += step_cols;
-            c += step_ch;
-            if (col >= inner) {
-                col -= inner;
-                c += 1u;
-            }
-            if (c >= n_channels) c -= n_channels;
-        }
-        return;
+// Candidate chunks per tensor of a clip search (k_hist_kl, k_hist_qmse): about 1024 workgroups per launch, and no fewer than
+// eight candidates per workgroup.
+inline int candidate_chunks(const char* who, int64_t n_slots, int64_t n_cand, int64_t& chunks) {
+    chunks = (1024 + n_slots - 1) / n_slots;
+    if (chunks > n_cand / 8) chunks = n_cand / 8;
+    if (chunks < 1) chunks = 1;
+    if (n_slots * chunks > 0x7FFFFFFFll) {
+        snprintf(g_err, sizeof(g_err), "%s: too many slots", who);
+        return -2;
     }
-    const uint32_t nvec = cnt >> 2;
-    gptr_f4 xv = (gptr_f4)xs;
-    gptr_f4 x2v = (gptr_f4)x2s;
-    gptr_f4w yv = (gptr_f4w)ys;
-    // Two register sets in rotation (as stream_span): the NEXT four vectors of a lane — and, per channel, their parameters — are
-    // requested before the current four are computed and stored: eight loads in flight per lane, and a parameter look-up never
-    // sits between a vector's arrival and its use.
-    const bool per_channel = n_channels != 1u;
-    uint32_t col = 0u, c = 0u, step_cols = 0u, step_ch = 0u;
-    if (per_channel) {   // the lane's first vector: one division; then (col, c) advance by the per-step constants
-        const uint64_t e = e0 + 4ull * tid;
-        col = (uint32_t)(e % inner);
-        c = (uint32_t)((e / inner) % n_channels);
-        step_cols = (4u * kBlock) % inner;
-        step_ch = ((4u * kBlock) / inner) % n_channels;
-    }
-    const float sc1 = scale_p[0], zp1 = fq_zp<FMT>(zp_p, 0u);
-    const bool straddle = per_channel && (inner & 3u) != 0u;   // (uniform) a vector may end in the next channel's row
-    struct Set {
-        f4 v[4];
-        f4 w[PRE == kFqPreAddRelu ? 4 : 1];   // the second operand of the residual Add
-        float sc[4], sc2[4];
-        int32_t zp[4], zp2[4];
-        uint32_t left[4];   // elements of the vector that still belong to the first channel's row (>= 4: all of them)
-    };
-    auto load = [&](Set& st, uint32_t i0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            st.v[u] = i0 + u * kBlock < nvec ? __builtin_nontemporal_load(xv + i0 + u * kBlock) : f4{0.f, 0.f, 0.f, 0.f};
-            if (PRE == kFqPreAddRelu)
-                st.w[PRE == kFqPreAddRelu ? u : 0] =
-                    i0 + u * kBlock < nvec ? __builtin_nontemporal_load(x2v + i0 + u * kBlock) : f4{0.f, 0.f, 0.f, 0.f};
-            if (per_channel) {   // (uniform)
-                st.sc[u] = scale_p[c];
-                if (FMT == kFqFmtInt) st.zp[u] = zp_p[c];
-                if (straddle) {
-                    const uint32_t cn = c + 1u < n_channels ? c + 1u : 0u;
-                    st.sc2[u] = scale_p[cn];
-                    if (FMT == kFqFmtInt) st.zp2[u] = zp_p[cn];
-                    st.left[u] = inner - col;
-                }
-                col += step_cols;
-                c += step_ch;
-                if (col >= inner) {
-                    col -= inner;
-                    c += 1u;
-                }
-                if (c >= n_channels) c -= n_channels;
-            }
-        }
-    };
-    auto eat = [&](Set& st, uint32_t i0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (i0 + u * kBlock < nvec) {
-                const float sc = per_channel ? st.sc[u] : sc1, zp = per_channel && FMT == kFqFmtInt ? (float)st.zp[u] : zp1;
-                if (PRE != kFqPreNone) {
-                    const f4 w = st.w[PRE == kFqPreAddRelu ? u : 0];
-                    st.v[u].x = fq_pre<PRE>(st.v[u].x, w.x);
-                    st.v[u].y = fq_pre<PRE>(st.v[u].y, w.y);
-                    st.v[u].z = fq_pre<PRE>(st.v[u].z, w.z);
-                    st.v[u].w = fq_pre<PRE>(st.v[u].w, w.w);
-                }
-                if (straddle) {   // (uniform)
-                    const float scb = st.sc2[u], zpb = FMT == kFqFmtInt ? (float)st.zp2[u] : 0.f;
-                    const uint32_t l = st.left[u];
-                    st.v[u].x = fq_elem<FMT>(st.v[u].x, sc, zp, qlo, qhi);
-                    st.v[u].y = fq_elem<FMT>(st.v[u].y, l > 1u ? sc : scb, l > 1u ? zp : zpb, qlo, qhi);
-                    st.v[u].z = fq_elem<FMT>(st.v[u].z, l > 2u ? sc : scb, l > 2u ? zp : zpb, qlo, qhi);
-                    st.v[u].w = fq_elem<FMT>(st.v[u].w, l > 3u ? sc : scb, l > 3u ? zp : zpb, qlo, qhi);
-                } else {
-                    st.v[u].x = fq_elem<FMT>(st.v[u].x, sc, zp, qlo, qhi);
-                    st.v[u].y = fq_elem<FMT>(st.v[u].y, sc, zp, qlo, qhi);
-                    st.v[u].z = fq_elem<FMT>(st.v[u].z, sc, zp, qlo, qhi);
-                    st.v[u].w = fq_elem<FMT>(st.v[u].w, sc, zp, qlo, qhi);
-                }
-                __builtin_nontemporal_store(st.v[u], yv + i0 + u * kBlock);
-            }
-        }
-    };
-    if (tid < nvec) {
-        Set A, B;
-        uint32_t i0 = tid;
-        load(A, i0);
-        for (;;) {
-            uint32_t nx = i0 + 4 * kBlock;
-            const bool hb = nx < nvec;
-            if (hb) load(B, nx);
-            eat(A, i0);
-            if (!hb) break;
-            i0 = nx;
-            nx = i0 + 4 * kBlock;
-            const bool ha = nx < nvec;
-            if (ha) load(A, nx);
-            eat(B, i0);
-            if (!ha) break;
-            i0 = nx;
-        }
-    }
-    const uint32_t t = (nvec << 2) + tid;   // (a chunk that is no multiple of four long: the tensor's last elements)
-    if (t < cnt) {
-        const uint32_t c = n_channels == 1u ? 0u : (uint32_t)(((e0 + t) / inner) % n_channels);
-        ys[t] = fq_elem<FMT>(fq_pre<PRE>(xs[t], x2s[t]), scale_p[c], fq_zp<FMT>(zp_p, c), qlo, qhi);
-    }
-}
-
-// one tensor: workgroup b takes elements [b * chunk, (b + 1) * chunk) (chunk a multiple of 1024)
-// (PRE: the producer's ReLU / Add + ReLU on the way in, fq_pre; x2 is read for kFqPreAddRelu only.  FMT: the number format, fq_elem)
-template <int PRE, int FMT>
-__global__ __launch_bounds__(kBlock) void k_fake_quant(const float* __restrict__ x, const float* __restrict__ x2, float* __restrict__ y,
-                                                        uint64_t n, uint64_t chunk, const float* __restrict__ scale_p,
-                                                        const int32_t* __restrict__ zp_p, uint32_t n_channels, uint32_t inner, float qlo,
-                                                        float qhi) {
-    const uint64_t e0 = (uint64_t)blockIdx.x * chunk;
-    if (e0 >= n) return;
-    const uint64_t cnt = n - e0 < chunk ? n - e0 : chunk;
-    fq_span<PRE, FMT>(x, x2, y, e0, (uint32_t)cnt, scale_p, zp_p, n_channels, inner, qlo, qhi);
-}
-
-// a whole tensor set in ONE launch: the balanced partition's items (item.seg = tensor, item.offset / count = the elements) over
-// the tensors' base pointers and a parameter row per tensor
-template <int FMT>
-__global__ __launch_bounds__(kBlock) void k_fake_quant_items(const dpl_work_item* __restrict__ items, const uint32_t* __restrict__ bb,
-                                                              const float* const* __restrict__ seg_x, float* const* __restrict__ seg_y,
-                                                              const dpl_fake_quant_params* __restrict__ prm) {
-    uint32_t k0, k1;
-    block_items(bb, k0, k1);
-    for (uint32_t k = k0; k < k1; ++k) {
-        const dpl_work_item it = items[k];
-        const dpl_fake_quant_params p = prm[it.seg];
-        fq_span<kFqPreNone, FMT>(seg_x[it.seg], nullptr, seg_y[it.seg], it.offset, it.count, p.d_scale, p.d_zero_point, (uint32_t)p.n_channels, (uint32_t)p.inner,
-                (float)p.qlo, (float)p.qhi);
-    }
-}
-
-// ================================================================ N1: cosine-similarity partial sums
-__global__ __launch_bounds__(kBlock) void k_cos_acc(const float* __restrict__ a, const float* __restrict__ b,
-                                                     int64_t n, double* __restrict__ acc) {
-    __shared__ double s_r[3][kBlock / kWave];
-    double ab = 0.0, aa = 0.0, bb = 0.0;
-    const int64_t nvec = n >> 2;
-    const f4* av = reinterpret_cast<const f4*>(a);
-    const f4* bv = reinterpret_cast<const f4*>(b);
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t i0 = (int64_t)blockIdx.x * kBlock + threadIdx.x; i0 < nvec; i0 += 4 * stride) {
-        f4 p[4], q[4];   // eight 16-byte loads in flight per lane
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int64_t i = i0 + u * stride;
-            p[u] = i < nvec ? __builtin_nontemporal_load(av + i) : f4{0.f, 0.f, 0.f, 0.f};
-            q[u] = i < nvec ? __builtin_nontemporal_load(bv + i) : f4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            ab += (double)p[u].x * q[u].x + (double)p[u].y * q[u].y + (double)p[u].z * q[u].z + (double)p[u].w * q[u].w;
-            aa += (double)p[u].x * p[u].x + (double)p[u].y * p[u].y + (double)p[u].z * p[u].z + (double)p[u].w * p[u].w;
-            bb += (double)q[u].x * q[u].x + (double)q[u].y * q[u].y + (double)q[u].z * q[u].z + (double)q[u].w * q[u].w;
-        }
-    }
-    const int64_t t = (nvec << 2) + (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t < n) {
-        ab += (double)a[t] * b[t];
-        aa += (double)a[t] * a[t];
-        bb += (double)b[t] * b[t];
-    }
-    ab = wave_sum(ab);
-    aa = wave_sum(aa);
-    bb = wave_sum(bb);
-    const int w = threadIdx.x / kWave;
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        s_r[0][w] = ab;
-        s_r[1][w] = aa;
-        s_r[2][w] = bb;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double v = 0.0;
-        for (int k = 0; k < kBlock / kWave; ++k) v += s_r[threadIdx.x][k];
-        atomicAdd(acc + threadIdx.x, v);
-    }
-}
-
-// ================================================================ N2: per-channel sum of (a - b)  (bias correction)
-// a, b viewed as [outer, C, inner] (Conv output [n, C, H, W]; Gemm output [n, C] with inner = 1):
-// acc[c] += sum over outer and inner of (a - b), in fp64.  One wave per (outer, channel) row, rows round-robin over
-// the waves of the launch; 16-byte loads when the rows allow it.
-__global__ __launch_bounds__(kBlock) void k_channel_diff_sum(const float* __restrict__ a, const float* __restrict__ b,
-                                                              uint64_t rows, uint32_t n_channels, uint32_t inner,
-                                                              int vec_ok, double* __restrict__ acc) {
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-    const uint64_t wave = (uint64_t)blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
-    const uint64_t n_waves = (uint64_t)gridDim.x * (kBlock / kWave);
-    if (inner == 1) {  // [n, C]: lanes over channels, waves over rows of 64 channels
-        const uint64_t chunks = (n_channels + kWave - 1) / kWave;
-        for (uint64_t t = wave; t < chunks; t += n_waves) {
-            const uint32_t c = (uint32_t)t * kWave + lane;
-            if (c >= n_channels) continue;
-            double d = 0.0;
-            for (uint64_t r = 0; r < rows / n_channels; ++r) d += (double)a[r * n_channels + c] - (double)b[r * n_channels + c];
-            atomicAdd(acc + c, d);
-        }
-        return;
-    }
-    for (uint64_t r = wave; r < rows; r += n_waves) {
-        const float* pa = a + r * inner;
-        const float* pb = b + r * inner;
-        double d = 0.0;
-        uint32_t i = 0;
-        if (vec_ok) {  // inner % 4 == 0 and both bases 16-byte aligned: every row starts aligned
-            const f4* va = reinterpret_cast<const f4*>(pa);
-            const f4* vb = reinterpret_cast<const f4*>(pb);
-            const uint32_t nv = inner >> 2;
-            for (uint32_t j = lane; j < nv; j += 2 * kWave) {
-                const f4 p0 = __builtin_nontemporal_load(va + j), q0 = __builtin_nontemporal_load(vb + j);
-                const bool two = j + kWave < nv;
-                const f4 p1 = two ? __builtin_nontemporal_load(va + j + kWave) : f4{0.f, 0.f, 0.f, 0.f};
-                const f4 q1 = two ? __builtin_nontemporal_load(vb + j + kWave) : f4{0.f, 0.f, 0.f, 0.f};
-                d += ((double)p0.x - (double)q0.x) + ((double)p0.y - (double)q0.y) + ((double)p0.z - (double)q0.z) +
-                     ((double)p0.w - (double)q0.w);
-                d += ((double)p1.x - (double)q1.x) + ((double)p1.y - (double)q1.y) + ((double)p1.z - (double)q1.z) +
-                     ((double)p1.w - (double)q1.w);
-            }
-            i = nv << 2;
-        }
-        for (uint32_t j = i + lane; j < inner; j += kWave) d += (double)pa[j] - (double)pb[j];
-        d = wave_sum(d);
-        if (lane == 0) atomicAdd(acc + (uint32_t)(r % n_channels), d);
-    }
-}
-
-// Per-slot cosine partial sums over work items: slot = (image, tensor) pair for the profiling flow
-// (profiling.py:57-64: one cosine per image per quantised layer output).  a and b come from two segment
-// tables with identical geometry (fp model vs fake-quantised model).
-__global__ __launch_bounds__(kBlock) void k_cos_items(const dpl_work_item* __restrict__ items,
-                                                       const uint32_t* __restrict__ bb,
-                                                       const float* const* __restrict__ segs_a,
-                                                       const float* const* __restrict__ segs_b,
-                                                       double* __restrict__ acc) {
-    __shared__ double s_r[3][kBlock / kWave];
-    uint32_t k0, k1;
-    block_items(bb, k0, k1);
-    for (uint32_t k = k0; k < k1; ++k) {
-        const dpl_work_item it = items[k];
-        gptr_f32 a = (gptr_f32)(segs_a[it.seg] + it.offset);
-        gptr_f32 b = (gptr_f32)(segs_b[it.seg] + it.offset);
-        const uint32_t n = it.count;
-        double ab = 0.0, aa = 0.0, bbs = 0.0;
-        const bool vec = ((((uintptr_t)(segs_a[it.seg] + it.offset)) | ((uintptr_t)(segs_b[it.seg] + it.offset))) & 15u) == 0;
-        uint32_t done = 0;
-        if (vec) {
-            const uint32_t nvec = n >> 2;
-            gptr_f4 av = (gptr_f4)a;
-            gptr_f4 bv = (gptr_f4)b;
-            // two streams, software pipelined like stream_span: the next 2 + 2 vectors per lane are in flight while
-            // the current ones are consumed (ping-pong register sets, no register copy between them)
-            constexpr int kU = 2;
-            constexpr uint32_t kStride = kU * kBlock;
-            auto eat1 = [&](const f4& p, const f4& q) {
-                ab += (double)p.x * q.x + (double)p.y * q.y + (double)p.z * q.z + (double)p.w * q.w;
-                aa += (double)p.x * p.x + (double)p.y * p.y + (double)p.z * p.z + (double)p.w * p.w;
-                bbs += (double)q.x * q.x + (double)q.y * q.y + (double)q.z * q.z + (double)q.w * q.w;
-            };
-#define DPL_CLOAD(P, Q, base)                                      \
-    _Pragma("unroll") for (int u = 0; u < kU; ++u) {               \
-        P[u] = __builtin_nontemporal_load(av + (base) + u * kBlock); \
-        Q[u] = __builtin_nontemporal_load(bv + (base) + u * kBlock); \
-    }
-#define DPL_CEAT(P, Q) _Pragma("unroll") for (int u = 0; u < kU; ++u) eat1(P[u], Q[u])
-            uint32_t i = threadIdx.x;
-            if (i + (kU - 1) * kBlock < nvec) {
-                f4 PA[kU], QA[kU], PB[kU], QB[kU];
-                DPL_CLOAD(PA, QA, i);
-                i += kStride;
-                for (;;) {
-                    if (!(i + (kU - 1) * kBlock < nvec)) {
-                        DPL_CEAT(PA, QA);
-                        break;
-                    }
-                    DPL_CLOAD(PB, QB, i);
-                    i += kStride;
-                    DPL_CEAT(PA, QA);
-                    if (!(i + (kU - 1) * kBlock < nvec)) {
-                        DPL_CEAT(PB, QB);
-                        break;
-                    }
-                    DPL_CLOAD(PA, QA, i);
-                    i += kStride;
-                    DPL_CEAT(PB, QB);
-                }
-            }
-#undef DPL_CLOAD
-#undef DPL_CEAT
-            for (; i < nvec; i += kBlock) eat1(__builtin_nontemporal_load(av + i), __builtin_nontemporal_load(bv + i));
-            done = nvec << 2;
-        }
-        for (uint32_t i = done + threadIdx.x; i < n; i += kBlock) {
-            const float p = a[i], q = b[i];
-            ab += (double)p * q;
-            aa += (double)p * p;
-            bbs += (double)q * q;
-        }
-        ab = wave_sum(ab);
-        aa = wave_sum(aa);
-        bbs = wave_sum(bbs);
-        const int w = threadIdx.x / kWave;
-        if ((threadIdx.x & (kWave - 1)) == 0) {
-            s_r[0][w] = ab;
-            s_r[1][w] = aa;
-            s_r[2][w] = bbs;
-        }
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            double v = 0.0;
-            for (int j = 0; j < kBlock / kWave; ++j) v += s_r[threadIdx.x][j];
-            atomicAdd(acc + 3 * (uint64_t)it.slot + threadIdx.x, v);
-        }
-        __syncthreads();
-    }
-}
-
-// one tensor in either number format (FMT: kFqFmtInt / kFqFmtE4M3; `who`: the entry point's name, for the messages)
-template <int FMT>
-int fake_quant_launch(const char* who, int32_t pre, const float* d_x, const float* d_x2, float* d_y, int64_t n, const float* d_scale,
-                      const int32_t* d_zp, int64_t n_channels, int64_t inner, int32_t qlo, int32_t qhi, dpl_stream_t s) {
-    auto bad = [who](const char* what) {
-        char m[192];
-        snprintf(m, sizeof(m), "%s: %s", who, what);
-        return fail_msg(m);
-    };
-    if (pre != DPL_FQ_PRE_NONE && pre != DPL_FQ_PRE_RELU && pre != DPL_FQ_PRE_ADD_RELU)
-        return bad("pre must be DPL_FQ_PRE_NONE, _RELU or _ADD_RELU");
-    if (n <= 0) return 0;
-    if (pre == DPL_FQ_PRE_ADD_RELU && d_x2 == nullptr) return bad("DPL_FQ_PRE_ADD_RELU needs d_x2");
-    if (n_channels < 1 || inner < 1 || n_channels > 0xFFFFFFFFll || inner > 0xFFFFFFFFll)
-        return bad("n_channels and inner must be in [1, 2^32)");
-    // A contiguous chunk of 3072 elements (12 KiB read + 12 KiB written) per workgroup, whatever the tensor's size (a multiple of
-    // 1024 elements: every chunk starts on a 16-byte boundary of an aligned tensor).  Measured on the tensors a fake-quantised
-    // ResNet-50 forward at batch 64 runs this on (26 - 205 MB, distinct buffers in rotation), fraction of
-    // 8 TB/s by chunk: 1024: 0.61 / 0.52 (205 MB / 26 MB), 2048: 0.72 / 0.57, 3072: 0.76 / 0.56, 4096: 0.75 / 0.54, 8192: 0.78 /
-    // 0.54, 12288: 0.72 / 0.43 — and rounds 3 - 4's rule (n / 4096 elements, at least 4096: 50 KB chunks for a 205 MB tensor):
-    // 0.70 / 0.54.  The Q/DQ nodes of that forward: 0.61 -> 0.65 of the roofline (bench.py `fake_quant.product_forward`).
-    constexpr int64_t kFqChunk = 3072;
-    int64_t chunk = kFqChunk;
-    if ((n + chunk - 1) / chunk > 0x40000000ll) chunk = ((n + 0x3FFFFFFFll) / 0x40000000ll + 1023) / 1024 * 1024;
-    if (chunk > 0xFFFFFC00ll) chunk = 0xFFFFFC00ll;
-    const int64_t blocks = (n + chunk - 1) / chunk;
-    if (blocks > 0x7FFFFFFFll) return bad("tensor too large");
-#define DPL_FQ_LAUNCH(PRE)                                                                                                    \
-    hipLaunchKernelGGL((k_fake_quant<PRE, FMT>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)s, d_x, d_x2, d_y, (uint64_t)n,   \
-                       (uint64_t)chunk, d_scale, d_zp, (uint32_t)n_channels, (uint32_t)inner, (float)qlo, (float)qhi)
-    if (pre == DPL_FQ_PRE_ADD_RELU) DPL_FQ_LAUNCH(kFqPreAddRelu);
-    else if (pre == DPL_FQ_PRE_RELU) DPL_FQ_LAUNCH(kFqPreRelu);
-    else DPL_FQ_LAUNCH(kFqPreNone);
-#undef DPL_FQ_LAUNCH
-    DPL_LAUNCH_CHECK("k_fake_quant");
     return 0;
 }
 
@@ -1364,52 +926,6 @@ int fake_quant_launch(const char* who, int32_t pre, const float* d_x, const floa
 
 // =================================================================================== C ABI
 extern "C" {
-
-int dpl_abi_version(void) { return DPL_ABI_VERSION; }
-const char* dpl_last_error(void) { return g_err; }
-
-int dpl_device_info(char* name, int name_cap, int* compute_units, uint64_t* hbm_bytes) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return fail("hipGetDevice", e);
-    hipDeviceProp_t p;
-    e = hipGetDeviceProperties(&p, dev);
-    if (e != hipSuccess) return fail("hipGetDeviceProperties", e);
-    if (name && name_cap > 0) snprintf(name, name_cap, "%s (%s)", p.name, p.gcnArchName);
-    if (compute_units) *compute_units = p.multiProcessorCount;
-    if (hbm_bytes) *hbm_bytes = (uint64_t)p.totalGlobalMem;
-    if (strncmp(p.gcnArchName, "gfx950", 6) != 0) return fail_msg("current HIP device is not gfx950");
-    return 0;
-}
-
-int dpl_stream_priority_range(int* least, int* greatest) {
-    int lo = 0, hi = 0;
-    hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (e != hipSuccess) return fail("hipDeviceGetStreamPriorityRange", e);
-    if (least) *least = lo;
-    if (greatest) *greatest = hi;
-    return 0;
-}
-
-int dpl_stream_create(int priority, dpl_stream_t* out) {
-    if (!out) return fail_msg("dpl_stream_create: null out");
-    int lo = 0, hi = 0;
-    hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);   // (lo: the numerically largest = least urgent)
-    if (e != hipSuccess) return fail("hipDeviceGetStreamPriorityRange", e);
-    if (priority > lo) priority = lo;
-    if (priority < hi) priority = hi;
-    hipStream_t s = nullptr;
-    e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority);
-    if (e != hipSuccess) return fail("hipStreamCreateWithPriority", e);
-    *out = (dpl_stream_t)s;
-    return 0;
-}
-
-int dpl_stream_destroy(dpl_stream_t s) {
-    if (!s) return 0;
-    hipError_t e = hipStreamDestroy((hipStream_t)s);
-    return e == hipSuccess ? 0 : fail("hipStreamDestroy", e);
-}
 
 int dpl_minmax_init(uint32_t* d_min_enc, uint32_t* d_max_enc, uint32_t* d_nan, int64_t n_slots, dpl_stream_t s) {
     if (n_slots <= 0) return 0;
@@ -1452,7 +968,7 @@ int dpl_minmax_encode(const float* d_min, const float* d_max, int64_t n_slots, u
 
 int dpl_hist_prepare(const float* d_min, const float* d_max, int64_t n_slots, int bins, dpl_hist_range* d_ranges,
                      dpl_stream_t s) {
-    if (bins < 1 || bins > DPL_MAX_BINS) return fail_msg("dpl_hist_prepare: bins must be in [1, 16384]");
+    if (int e = check_bins("dpl_hist_prepare", bins)) return e;
     if (n_slots <= 0) return 0;
     hipLaunchKernelGGL(k_hist_prepare, dim3(grid_for(n_slots, 64)), dim3(64), 0, (hipStream_t)s, d_min, d_max,
                        n_slots, bins, d_ranges);
@@ -1463,41 +979,37 @@ int dpl_hist_prepare(const float* d_min, const float* d_max, int64_t n_slots, in
 int dpl_abs_hist_accumulate(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin,
                             int64_t n_blocks, const float* const* d_seg_ptrs, const dpl_hist_range* d_ranges,
                             int bins, uint64_t* d_hist, dpl_stream_t s) {
-    if (bins < 1 || bins > DPL_MAX_BINS) return fail_msg("dpl_abs_hist_accumulate: bins must be in [1, 16384]");
+    if (int e = check_bins("dpl_abs_hist_accumulate", bins)) return e;
     if (n_items <= 0) return 0;
     if (int e = check_blocks("dpl_abs_hist_accumulate", n_items, d_block_begin, n_blocks)) return e;
-    hipLaunchKernelGGL(k_abs_hist, dim3((unsigned)n_blocks), dim3(kBlock),
-                       ((size_t)bins + 1 + kBlock / kWave) * sizeof(uint32_t), (hipStream_t)s, d_items, d_block_begin,
-                       d_seg_ptrs, d_ranges, bins, d_hist);
+    hipLaunchKernelGGL(k_abs_hist, dim3((unsigned)n_blocks), dim3(kBlock), HistLds::bytes(bins), (hipStream_t)s, d_items,
+                       d_block_begin, d_seg_ptrs, d_ranges, bins, d_hist);
     DPL_LAUNCH_CHECK("k_abs_hist");
     return 0;
 }
 
 uint64_t dpl_hist_spec_entry_bytes(int64_t n_slots, int bins) {
     if (n_slots < 0 || bins < 1 || bins > DPL_MAX_BINS) return 0;
-    return spec_counts_offset(n_slots) + (uint64_t)n_slots * (uint64_t)bins * sizeof(uint32_t);
+    return SpecEntry::bytes(n_slots, bins);
 }
 
 int dpl_minmax_hist_accumulate(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin,
                                int64_t n_blocks, const float* const* d_seg_ptrs, uint32_t* d_min_enc, uint32_t* d_max_enc,
                                uint32_t* d_nan, int64_t n_slots, int bins, void* d_entry, dpl_stream_t s) {
-    if (bins < 1 || bins > DPL_MAX_BINS) return fail_msg("dpl_minmax_hist_accumulate: bins must be in [1, 16384]");
+    if (int e = check_bins("dpl_minmax_hist_accumulate", bins)) return e;
     if (!d_entry || ((uintptr_t)d_entry & 15u)) return fail_msg("dpl_minmax_hist_accumulate: d_entry must be 16-byte aligned");
     if (n_slots <= 0 || n_slots > 0x7FFFFFFFll) return fail_msg("dpl_minmax_hist_accumulate: n_slots out of range");
     if (n_items <= 0) return 0;
     if (int e = check_blocks("dpl_minmax_hist_accumulate", n_items, d_block_begin, n_blocks)) return e;
-    dpl_hist_range* snap = (dpl_hist_range*)d_entry;
-    uint32_t* flags = (uint32_t*)(snap + n_slots);
-    uint32_t* counts = (uint32_t*)((char*)d_entry + spec_counts_offset(n_slots));
+    const SpecEntry entry(d_entry, n_slots);
     int64_t zb = grid_for(n_slots * (int64_t)bins, kBlock * 8);
     if (zb < grid_for(n_slots, kBlock)) zb = grid_for(n_slots, kBlock);
     if (zb > 1024) zb = 1024;
     hipLaunchKernelGGL(k_hist_snapshot, dim3((unsigned)zb), dim3(kBlock), 0, (hipStream_t)s, d_min_enc, d_max_enc, d_nan,
-                       n_slots, bins, snap, flags, counts);
+                       n_slots, bins, entry.snap, entry.flags, entry.counts);
     DPL_LAUNCH_CHECK("k_hist_snapshot");
-    hipLaunchKernelGGL(k_minmax_hist, dim3((unsigned)n_blocks), dim3(kBlock),
-                       ((size_t)bins + 1 + 4 * (kBlock / kWave)) * sizeof(uint32_t), (hipStream_t)s, d_items, d_block_begin,
-                       d_seg_ptrs, d_min_enc, d_max_enc, d_nan, snap, bins, counts);
+    hipLaunchKernelGGL(k_minmax_hist, dim3((unsigned)n_blocks), dim3(kBlock), MinMaxHistLds::bytes(bins), (hipStream_t)s, d_items,
+                       d_block_begin, d_seg_ptrs, d_min_enc, d_max_enc, d_nan, entry.snap, bins, entry.counts);
     DPL_LAUNCH_CHECK("k_minmax_hist");
     return 0;
 }
@@ -1505,20 +1017,15 @@ int dpl_minmax_hist_accumulate(const dpl_work_item* d_items, int64_t n_items, co
 int dpl_hist_spec_accumulate(void* d_entry, const uint64_t* d_elems, int64_t n_slots, int64_t n_blocks,
                              const float* const* d_seg_ptrs, const dpl_hist_range* d_ranges, int bins, uint64_t* d_hist,
                              uint64_t* d_stats, dpl_stream_t s) {
-    if (bins < 1 || bins > DPL_MAX_BINS) return fail_msg("dpl_hist_spec_accumulate: bins must be in [1, 16384]");
+    if (int e = check_bins("dpl_hist_spec_accumulate", bins)) return e;
     if (!d_entry || ((uintptr_t)d_entry & 15u)) return fail_msg("dpl_hist_spec_accumulate: d_entry must be 16-byte aligned");
-    if (n_slots <= 0 || n_slots > DPL_HIST_SPEC_MAX_TENSORS)
-        return fail_msg("dpl_hist_spec_accumulate: n_slots must be in [1, DPL_HIST_SPEC_MAX_TENSORS]");
-    if (n_blocks <= 0 || n_blocks > 0x7FFFFFFFll) return fail_msg("dpl_hist_spec_accumulate: n_blocks out of range");
-    dpl_hist_range* snap = (dpl_hist_range*)d_entry;
-    uint32_t* flags = (uint32_t*)(snap + n_slots);
-    const uint32_t* counts = (const uint32_t*)((char*)d_entry + spec_counts_offset(n_slots));
-    hipLaunchKernelGGL(k_hist_resolve, dim3((unsigned)n_slots), dim3(kBlock), 0, (hipStream_t)s, snap, d_ranges, counts, d_elems,
-                       bins, d_hist, flags, (unsigned long long*)d_stats);
+    if (int e = check_spec_geometry("dpl_hist_spec_accumulate", n_slots, n_blocks)) return e;
+    const SpecEntry entry(d_entry, n_slots);
+    hipLaunchKernelGGL(k_hist_resolve, dim3((unsigned)n_slots), dim3(kBlock), 0, (hipStream_t)s, entry.snap, d_ranges, entry.counts,
+                       d_elems, bins, d_hist, entry.flags, (unsigned long long*)d_stats);
     DPL_LAUNCH_CHECK("k_hist_resolve");
-    const size_t lds = ((size_t)n_slots + 1 + kBlock / kWave) * sizeof(uint64_t) + ((size_t)bins + 1 + kBlock / kWave) * sizeof(uint32_t);
-    hipLaunchKernelGGL(k_abs_hist_rest, dim3((unsigned)n_blocks), dim3(kBlock), lds, (hipStream_t)s, d_elems, flags, (int)n_slots,
-                       d_seg_ptrs, d_ranges, bins, d_hist);
+    hipLaunchKernelGGL(k_abs_hist_rest, dim3((unsigned)n_blocks), dim3(kBlock), RestLds::bytes(n_slots, bins), (hipStream_t)s, d_elems,
+                       entry.flags, (int)n_slots, d_seg_ptrs, d_ranges, bins, d_hist);
     DPL_LAUNCH_CHECK("k_abs_hist_rest");
     return 0;
 }
@@ -1526,12 +1033,9 @@ int dpl_hist_spec_accumulate(void* d_entry, const uint64_t* d_elems, int64_t n_s
 int dpl_hist_spec_cuts(const void* d_entry, const uint64_t* d_elems, int64_t n_slots, int64_t n_blocks, uint64_t* d_cuts,
                        dpl_stream_t s) {
     if (!d_entry || !d_cuts) return fail_msg("dpl_hist_spec_cuts: null argument");
-    if (n_slots <= 0 || n_slots > DPL_HIST_SPEC_MAX_TENSORS)
-        return fail_msg("dpl_hist_spec_cuts: n_slots must be in [1, DPL_HIST_SPEC_MAX_TENSORS]");
-    if (n_blocks <= 0 || n_blocks > 0x7FFFFFFFll) return fail_msg("dpl_hist_spec_cuts: n_blocks out of range");
-    const uint32_t* flags = (const uint32_t*)((const dpl_hist_range*)d_entry + n_slots);
-    hipLaunchKernelGGL(k_hist_spec_cuts, dim3((unsigned)n_blocks), dim3(kBlock),
-                       ((size_t)n_slots + 1 + kBlock / kWave) * sizeof(uint64_t), (hipStream_t)s, d_elems, flags, (int)n_slots, d_cuts);
+    if (int e = check_spec_geometry("dpl_hist_spec_cuts", n_slots, n_blocks)) return e;
+    hipLaunchKernelGGL(k_hist_spec_cuts, dim3((unsigned)n_blocks), dim3(kBlock), RestPrefixLds::bytes(n_slots), (hipStream_t)s, d_elems,
+                       SpecEntry(d_entry, n_slots).flags, (int)n_slots, d_cuts);
     DPL_LAUNCH_CHECK("k_hist_spec_cuts");
     return 0;
 }
@@ -1547,19 +1051,13 @@ int dpl_hist_percentile(const uint64_t* d_hist, const float* d_min, const float*
 
 int dpl_hist_kl(const uint64_t* d_hist, const float* d_min, const float* d_max, int64_t n_slots, int bins, int levels,
                 double* d_div, int32_t* d_best, float* d_clip, dpl_stream_t s) {
-    if (bins < 1 || bins > DPL_MAX_BINS) return fail_msg("dpl_hist_kl: bins must be in [1, 16384]");
+    if (int e = check_bins("dpl_hist_kl", bins)) return e;
     if (levels < 2 || levels > bins) return fail_msg("dpl_hist_kl: levels must be in [2, bins]");
     if (n_slots <= 0) return 0;
-    // candidate chunks per tensor: about 1024 workgroups per launch, and no fewer than eight candidates per workgroup
-    const int64_t n_cand = (int64_t)bins - levels + 1;
-    int64_t chunks = (1024 + n_slots - 1) / n_slots;
-    if (chunks > n_cand / 8) chunks = n_cand / 8;
-    if (chunks < 1) chunks = 1;
-    if (n_slots * chunks > 0x7FFFFFFFll) return fail_msg("dpl_hist_kl: too many slots");
-    const size_t nblk = ((size_t)bins + 63) / 64;
-    const size_t lds = ((size_t)bins + 1 + nblk + 1 + kBlock) * sizeof(uint64_t) + (nblk + 1) * sizeof(uint32_t);
-    hipLaunchKernelGGL(k_hist_kl, dim3((unsigned)(n_slots * chunks)), dim3(kBlock), lds, (hipStream_t)s, d_hist, bins, levels,
-                       (int)chunks, d_div);
+    int64_t chunks;
+    if (int e = candidate_chunks("dpl_hist_kl", n_slots, (int64_t)bins - levels + 1, chunks)) return e;
+    hipLaunchKernelGGL(k_hist_kl, dim3((unsigned)(n_slots * chunks)), dim3(kBlock), KlLds::bytes(bins), (hipStream_t)s, d_hist, bins,
+                       levels, (int)chunks, d_div);
     DPL_LAUNCH_CHECK("k_hist_kl");
     hipLaunchKernelGGL(k_hist_kl_pick, dim3((unsigned)n_slots), dim3(kWave), 0, (hipStream_t)s, d_div, d_min, d_max, bins,
                        d_best, d_clip);
@@ -1569,19 +1067,15 @@ int dpl_hist_kl(const uint64_t* d_hist, const float* d_min, const float* d_max, 
 
 int dpl_hist_qmse(const uint64_t* d_hist, const float* d_min, const float* d_max, int64_t n_slots, int bins, int first, int grid,
                   int top, double* d_err, int32_t* d_best, float* d_clip, dpl_stream_t s) {
-    if (bins < 1 || bins > DPL_MAX_BINS) return fail_msg("dpl_hist_qmse: bins must be in [1, 16384]");
+    if (int e = check_bins("dpl_hist_qmse", bins)) return e;
     if (first < 1 || first > bins) return fail_msg("dpl_hist_qmse: first must be in [1, bins]");
     if (grid != DPL_GRID_UNIFORM && grid != DPL_GRID_E4M3) return fail_msg("dpl_hist_qmse: grid must be DPL_GRID_UNIFORM or DPL_GRID_E4M3");
     if (grid == DPL_GRID_UNIFORM && (top < 1 || top > 32767)) return fail_msg("dpl_hist_qmse: top must be in [1, 32767] on the uniform grid");
     if (grid == DPL_GRID_E4M3 && top != 0) return fail_msg("dpl_hist_qmse: top must be 0 on the E4M3 grid (its largest value is 448)");
     if (n_slots <= 0) return 0;
-    // candidate chunks per tensor: about 1024 workgroups per launch, and no fewer than eight candidates per workgroup
-    const int64_t n_cand = (int64_t)bins - first + 1;
-    int64_t chunks = (1024 + n_slots - 1) / n_slots;
-    if (chunks > n_cand / 8) chunks = n_cand / 8;
-    if (chunks < 1) chunks = 1;
-    if (n_slots * chunks > 0x7FFFFFFFll) return fail_msg("dpl_hist_qmse: too many slots");
-    const size_t lds = (size_t)bins * sizeof(double) + (kBlock / kWave) * sizeof(uint64_t);
+    int64_t chunks;
+    if (int e = candidate_chunks("dpl_hist_qmse", n_slots, (int64_t)bins - first + 1, chunks)) return e;
+    const size_t lds = QmseLds::bytes(bins);
     const dim3 wgs((unsigned)(n_slots * chunks));
     if (grid == DPL_GRID_E4M3)
         hipLaunchKernelGGL(k_hist_qmse<kGridE4M3>, wgs, dim3(kBlock), lds, (hipStream_t)s, d_hist, bins, first, top, (int)chunks, d_err);
@@ -1591,116 +1085,6 @@ int dpl_hist_qmse(const uint64_t* d_hist, const float* d_min, const float* d_max
     hipLaunchKernelGGL(k_hist_kl_pick, dim3((unsigned)n_slots), dim3(kWave), 0, (hipStream_t)s, d_err, d_min, d_max, bins,
                        d_best, d_clip);
     DPL_LAUNCH_CHECK("k_hist_kl_pick");
-    return 0;
-}
-
-int dpl_rowwise_minmax(const float* d_w, int64_t rows, int64_t cols, float* d_min, float* d_max, dpl_stream_t s) {
-    if (rows <= 0) return 0;
-    if (cols <= 0 || cols > 0xFFFFFFFFll) return fail_msg("dpl_rowwise_minmax: cols out of range");
-    hipLaunchKernelGGL(k_rowwise_minmax, dim3((unsigned)rows), dim3(kBlock), 0, (hipStream_t)s, d_w, cols, d_min,
-                       d_max);
-    DPL_LAUNCH_CHECK("k_rowwise_minmax");
-    return 0;
-}
-
-int dpl_colwise_absmax(const float* d_x, int64_t rows, int64_t cols, float* d_acc, dpl_stream_t s) {
-    if (rows < 0 || cols < 1) return fail_msg("dpl_colwise_absmax: rows must be >= 0 and cols >= 1");
-    if (rows == 0) return 0;
-    if (!d_x || !d_acc) return fail_msg("dpl_colwise_absmax: null pointer");
-    if (rows > INT64_MAX / cols) return fail_msg("dpl_colwise_absmax: rows * cols overflows 64 bits");
-    const bool vec = (cols % 4 == 0) && (((uintptr_t)d_x & 15u) == 0);     // every row then starts on 16 bytes
-    const uint64_t cv = (uint64_t)(vec ? cols / 4 : cols);
-    uint32_t tw = 1;
-    while (tw < (uint32_t)kColMaxLanes && tw < cv) tw <<= 1;
-    const uint64_t gx = (cv + tw - 1) / tw;
-    if (gx > 0x7FFFFFFFull) return fail_msg("dpl_colwise_absmax: cols out of range");
-    // rows: every workgroup makes the same number of trips (kColUnroll * 256 / tw rows each), at most kColMaxBlocks workgroups
-    const uint64_t per_trip = (uint64_t)kColUnroll * (kBlock / tw);
-    const uint64_t trips = ((uint64_t)rows + per_trip - 1) / per_trip;
-    const uint64_t cap = gx >= (uint64_t)kColMaxBlocks ? 1 : (uint64_t)kColMaxBlocks / gx;
-    const uint64_t passes = (trips + cap - 1) / cap;
-    const dim3 g((unsigned)gx, (unsigned)((trips + passes - 1) / passes)), b(kBlock);
-    uint32_t* acc = reinterpret_cast<uint32_t*>(d_acc);
-    if (vec)
-        hipLaunchKernelGGL(k_colwise_absmax<u4>, g, b, 0, (hipStream_t)s, reinterpret_cast<const u4*>(d_x), (uint64_t)rows, cv, tw, acc);
-    else
-        hipLaunchKernelGGL(k_colwise_absmax<uint32_t>, g, b, 0, (hipStream_t)s, reinterpret_cast<const uint32_t*>(d_x), (uint64_t)rows, cv,
-                           tw, acc);
-    DPL_LAUNCH_CHECK("k_colwise_absmax");
-    return 0;
-}
-
-int dpl_fake_quant(const float* d_x, float* d_y, int64_t n, const float* d_scale, const int32_t* d_zp,
-                   int64_t n_channels, int64_t inner, int32_t qlo, int32_t qhi, dpl_stream_t s) {
-    return dpl_fake_quant_pre(DPL_FQ_PRE_NONE, d_x, nullptr, d_y, n, d_scale, d_zp, n_channels, inner, qlo, qhi, s);
-}
-
-int dpl_fake_quant_pre(int32_t pre, const float* d_x, const float* d_x2, float* d_y, int64_t n, const float* d_scale,
-                       const int32_t* d_zp, int64_t n_channels, int64_t inner, int32_t qlo, int32_t qhi, dpl_stream_t s) {
-    return fake_quant_launch<kFqFmtInt>("dpl_fake_quant_pre", pre, d_x, d_x2, d_y, n, d_scale, d_zp, n_channels, inner, qlo, qhi, s);
-}
-
-int dpl_fake_quant_fp8(int32_t pre, const float* d_x, const float* d_x2, float* d_y, int64_t n, const float* d_scale,
-                       int64_t n_channels, int64_t inner, dpl_stream_t s) {
-    return fake_quant_launch<kFqFmtE4M3>("dpl_fake_quant_fp8", pre, d_x, d_x2, d_y, n, d_scale, nullptr, n_channels, inner, 0, 0, s);
-}
-
-int dpl_fake_quant_items(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin, int64_t n_blocks,
-                         const float* const* d_seg_x, float* const* d_seg_y, const dpl_fake_quant_params* d_params, dpl_stream_t s) {
-    if (n_items <= 0) return 0;
-    if (int e = check_blocks("dpl_fake_quant_items", n_items, d_block_begin, n_blocks)) return e;
-    hipLaunchKernelGGL(k_fake_quant_items<kFqFmtInt>, dim3((unsigned)n_blocks), dim3(kBlock), 0, (hipStream_t)s, d_items, d_block_begin,
-                       d_seg_x, d_seg_y, d_params);
-    DPL_LAUNCH_CHECK("k_fake_quant_items");
-    return 0;
-}
-
-int dpl_fake_quant_fp8_items(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin, int64_t n_blocks,
-                             const float* const* d_seg_x, float* const* d_seg_y, const dpl_fake_quant_params* d_params, dpl_stream_t s) {
-    if (n_items <= 0) return 0;
-    if (int e = check_blocks("dpl_fake_quant_fp8_items", n_items, d_block_begin, n_blocks)) return e;
-    hipLaunchKernelGGL(k_fake_quant_items<kFqFmtE4M3>, dim3((unsigned)n_blocks), dim3(kBlock), 0, (hipStream_t)s, d_items, d_block_begin,
-                       d_seg_x, d_seg_y, d_params);
-    DPL_LAUNCH_CHECK("k_fake_quant_fp8_items");
-    return 0;
-}
-
-int dpl_cos_accumulate(const float* d_a, const float* d_b, int64_t n, double* d_acc, int64_t slot, dpl_stream_t s) {
-    if (n <= 0) return 0;
-    if (((uintptr_t)d_a | (uintptr_t)d_b) & 15u) return fail_msg("dpl_cos_accumulate: buffers must be 16-B aligned");
-    int64_t blocks = (n / 4 + kBlock * 8 - 1) / (kBlock * 8);
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_cos_acc, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)s, d_a, d_b, n,
-                       d_acc + 3 * slot);
-    DPL_LAUNCH_CHECK("k_cos_acc");
-    return 0;
-}
-
-int dpl_channel_diff_sum(const float* d_a, const float* d_b, int64_t outer, int64_t n_channels, int64_t inner,
-                         double* d_acc, dpl_stream_t s) {
-    if (outer <= 0 || n_channels <= 0 || inner <= 0) return 0;
-    if (n_channels > 0xFFFFFFFFll || inner > 0xFFFFFFFFll) return fail_msg("dpl_channel_diff_sum: extent out of range");
-    const uint64_t rows = (uint64_t)outer * (uint64_t)n_channels;
-    const int vec_ok = ((inner & 3) == 0) && ((((uintptr_t)d_a | (uintptr_t)d_b) & 15u) == 0);
-    uint64_t work = inner == 1 ? (uint64_t)(n_channels + kWave - 1) / kWave : rows;
-    uint64_t blocks = (work + kBlock / kWave - 1) / (kBlock / kWave);
-    if (blocks < 1) blocks = 1;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(k_channel_diff_sum, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)s, d_a, d_b, rows,
-                       (uint32_t)n_channels, (uint32_t)inner, vec_ok, d_acc);
-    DPL_LAUNCH_CHECK("k_channel_diff_sum");
-    return 0;
-}
-
-int dpl_cos_items_accumulate(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin,
-                             int64_t n_blocks, const float* const* d_seg_a, const float* const* d_seg_b,
-                             double* d_acc, dpl_stream_t s) {
-    if (n_items <= 0) return 0;
-    if (int e = check_blocks("dpl_cos_items_accumulate", n_items, d_block_begin, n_blocks)) return e;
-    hipLaunchKernelGGL(k_cos_items, dim3((unsigned)n_blocks), dim3(kBlock), 0, (hipStream_t)s, d_items,
-                       d_block_begin, d_seg_a, d_seg_b, d_acc);
-    DPL_LAUNCH_CHECK("k_cos_items");
     return 0;
 }
 

@@ -138,6 +138,18 @@ __device__ __forceinline__ void stream_span(const float* __restrict__ p_generic,
     if (t < n) op(p[t]);
 }
 
+// A lane's running min / max / "saw a NaN" over a span: the Op of k_minmax, k_minmax_hist (calib_kernels.hip) and
+// k_rowwise_minmax (side_kernels.hip).
+struct MinMaxOp {
+    float mn, mx;
+    uint32_t nan;
+    __device__ __forceinline__ void operator()(float x) {
+        mn = fminf(mn, x);
+        mx = fmaxf(mx, x);
+        nan |= (x != x);
+    }
+};
+
 // Work distribution shared by the streaming kernels: block b owns items [bb[b], bb[b+1]) (a balanced,
 // contiguous share of the launch's elements, dpl_build_balanced_items) or, when bb is null, item b alone.
 __device__ __forceinline__ void block_items(const uint32_t* __restrict__ bb, uint32_t& k0, uint32_t& k1) {

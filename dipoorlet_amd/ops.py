@@ -1,5 +1,5 @@
 """Torch-facing operators over the C ABI: device memory and streams come from PyTorch-ROCm, the
-arithmetic runs in the hand-written gfx950 kernels (csrc/calib_kernels.hip).
+arithmetic runs in the hand-written gfx950 kernels (csrc/*.hip; the statistics chain: csrc/calib_kernels.hip).
 
 Vocabulary: a *tensor set* is the list of activation tensors one forward of the network yields for a
 batch of B calibration images (each tensor is [B, ...] contiguous fp32).  A `TensorSetPlan` cuts the

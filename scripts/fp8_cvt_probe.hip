@@ -1,6 +1,6 @@
 // What gfx950's v_cvt_pk_fp8_f32 / v_cvt_f32_fp8 do, over ALL 2^32 fp32 bit patterns, against the definition of the Float8E4M3FN
 // quantisation type (tests/fp8_model.py, restated here in fp32 arithmetic — the form the kernel's e4m3_round uses,
-// csrc/calib_kernels.hip).  It answers whether the two instructions could replace that arithmetic:
+// csrc/fake_quant_kernels.hip).  It answers whether the two instructions could replace that arithmetic:
 //   hipcc --offload-arch=gfx950 -O2 -ffp-contract=off -o fp8_cvt_probe scripts/fp8_cvt_probe.hip && ./fp8_cvt_probe
 // Counts: `raw` = the two instructions alone; `guarded` = with an fp32 clamp to +-448 in front and NaN routed around them.  A
 // result counts as equal when its 32 bits are (NaN: when both are NaN).  Exit status 0: guarded == definition everywhere.

@@ -11,7 +11,7 @@ OCP FP8 E4M3 ("e4m3fn"): 1 sign bit, 4 exponent bits with bias 7, 3 mantissa bit
 
 These are ONNX opset 19 semantics: QuantizeLinear with a float8e4m3fn zero point and saturate = 1, then DequantizeLinear.
 tests/test_fp8_model.py holds `e4m3_round` to torch's CPU cast (an independent implementation, which does not saturate: the
-comparison covers |v| <= 464); tests/test_fp8_gpu.py holds the kernel (fq_elem<kFqFmtE4M3>, csrc/calib_kernels.hip) to this file,
+comparison covers |v| <= 464); tests/test_fp8_gpu.py holds the kernel (fq_elem<kFqFmtE4M3>, csrc/fake_quant_kernels.hip) to this file,
 bit for bit.
 """
 import numpy as np

@@ -1,7 +1,7 @@
 """The definition of `--smooth` (per-channel activation scales folded into MatMul weights), as a numpy model.
 
 The reference has no such transform: this is SmoothQuant's rescaling (Xiao et al., 2023) as THIS project defines it, and
-dipoorlet_amd/weight_transform/smooth.py and its kernel (`k_colwise_absmax`, csrc/calib_kernels.hip) are held to it.
+dipoorlet_amd/weight_transform/smooth.py and its kernel (`k_colwise_absmax`, csrc/side_kernels.hip) are held to it.
 
   * statistic: for a channels-last activation x seen as [rows, C], the running a <- np.maximum(a, np.abs(x).max(0)), started at
     zero, over every batch of the calibration set.  NaN propagates (a NaN in a column, or already in a, stays), +-inf gives inf,

@@ -290,7 +290,7 @@ def test_fake_quant_per_channel_vectorised_kernel_vs_oracle(dev, shape, axis):
     rng = np.random.default_rng(sum(shape) + axis)
     C_ = shape[axis]
     inner = int(np.prod(shape[axis + 1:]))
-    assert inner % 4 == 0                                   # -> the vectorised variant (calib_kernels.hip dpl_fake_quant)
+    assert inner % 4 == 0                                   # -> the vectorised variant (fake_quant_kernels.hip dpl_fake_quant)
     scale = rng.uniform(0.01, 0.1, C_).astype(np.float32)
     scale[::3] = np.float32(2.0) ** rng.integers(-6, -2, scale[::3].size)          # power-of-two scales: exact ties
     x = rng.standard_normal(shape).astype(np.float32) * 4

@@ -206,6 +206,52 @@ def test_flags_equal_the_model_and_results_equal_the_plain_path(dev, bins):
     assert cuts == M.cuts(e_batch.tolist(), (flags[-1] != 0).tolist(), plan.work("hist").n_blocks)
 
 
+@pytest.mark.parametrize("n_tensors", [2048, 2049])
+def test_the_largest_set_that_speculates_and_the_first_that_does_not(dev, n_tensors):
+    """_hip.HIST_SPEC_MAX_TENSORS = 2048 tensors: the largest P[n_tensors + 1] k_abs_hist_rest and k_hist_spec_cuts keep in LDS.
+    Per-image sizes 1024 + (t mod 7), B = 2, three batches, 16 bins: a batch is 16.8 MB, an entry's T * bins * 4 * 64 = 8.4 MB stays
+    below it, so the set speculates; extremes planted in batch t mod 3, so a third of the tensors is still read in the last batch and
+    the rest skipped.  One tensor more does not speculate.  Both: the BoundSet sweep == the plain-list sweep == numpy."""
+    from dipoorlet_amd import _hip, ops
+    assert _hip.HIST_SPEC_MAX_TENSORS == 2048
+    bins, n_batches = 16, 3
+    kinds = ("relu", "signed", "signed_min")
+    spec = [("t%d" % t, 1024 + t % 7, kinds[t % 5 % 3], 1.0 + 0.125 * (t % 11), (t % 3,)) for t in range(n_tensors)]
+    batches = _make_batches(spec, 17, k_batches=n_batches)
+    elems = [e for _, e, _, _, _ in spec]
+    plan = ops.TensorSetPlan(elems, B, dev)
+    acc = ops.CalibAccumulators(n_tensors, dev, bins)
+    dmax = _batch_dmax(batches)
+    fin = dmax.max(0)
+    ok = _range_ok(fin, bins)
+    assert all(ok)
+    valid = M.valid_table(dmax, fin, ok)
+    assert [int(valid[:, t].sum()) for t in range(6)] == [2, 1, 0, 2, 1, 0], "extremes in batch t mod 3"
+    xs = _upload(batches, dev)
+    bound = [plan.bind(row) for row in xs]
+    speculates = n_tensors <= 2048
+    assert n_tensors * bins * 4 * acc.SPEC_MAX_SHARE <= plan.total * 4
+    assert all(acc.will_speculate(plan, x) == speculates for x in bound)
+    got = _sweep(acc, [(plan, x) for x in bound])
+    st = acc.spec_stats()
+    if speculates:
+        flags = np.stack(_flags(acc, bound))
+        assert np.array_equal(flags == 1, valid), "the device's skip flags differ from the model's table"
+        assert not (flags == 2).any()
+        assert st["pairs"] == n_batches * n_tensors and st["pairs_skipped"] == int(valid.sum())
+        e_batch = np.array(elems, np.int64) * B
+        assert st["elements_skipped"] == int((valid * e_batch[None, :]).sum())
+        cuts = acc.spec_cuts(plan, bound[-1]).numpy().tolist()
+        assert cuts == M.cuts(e_batch.tolist(), (flags[-1] != 0).tolist(), plan.work("hist").n_blocks)
+    else:
+        assert st["pairs"] == 0 and not acc._ledger and acc.spec_flags(bound[0]) is None and acc.spec_cuts(plan, bound[-1]) is None
+    ref_acc = ops.CalibAccumulators(n_tensors, dev, bins)
+    ref = _sweep(ref_acc, [(plan, row) for row in xs])
+    assert ref_acc.spec_stats()["pairs"] == 0
+    _assert_same_results(got, ref)
+    _assert_oracle(got["hist"], batches, bins, fin, list(range(0, n_tensors, 97)) + [2046, 2047, n_tensors - 1])
+
+
 @pytest.mark.parametrize("when", [0, 2, K - 1])
 def test_nan_in_the_first_a_middle_and_the_last_batch(dev, when):
     """A NaN makes the tensor's range NaN (status 1: numpy raises): nothing of it is counted on either path, and from the batch
