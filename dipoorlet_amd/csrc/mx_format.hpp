@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
+#include <hip/hip_runtime.h>   // __forceinline__, __clz
 #define DPL_MX_HD __host__ __device__ __forceinline__
 #else
 #define DPL_MX_HD inline

@@ -1,7 +1,9 @@
 // Shared by the OCTAV translation units (octav_kernels.hip: full / compaction / two-read bracket forms and the rescue's
-// gather; octav_tail_host.hip: the one-read exact-tail form and its rescue walk): the fixed-point step, the log-scale
-// histogram geometry and the bracket walk over its bin edges.  The numbers the host planning shares with the kernels (bins,
-// slice and list-region sizes: list_cap_of) are in octav_geometry.hpp.
+// gather; octav_tail_host.hip: the launchers of the one-read exact-tail form, whose kernels are in octav_tail.hpp and
+// octav_rescue.hpp): the fixed-point step, the states a pair is initialised and restarted in, the log-scale histogram
+// geometry, the bracket walk over its bin edges, the tile walker, and what the two translation units call of each other.
+// The numbers the host planning shares with the kernels (bins, slice and list-region sizes: list_cap_of) are in
+// octav_geometry.hpp.
 #pragma once
 #include "common.hpp"
 #include "octav_geometry.hpp"
@@ -33,6 +35,50 @@ __device__ __forceinline__ OctavStep octav_step(double sum, unsigned long long c
     return r;
 }
 
+// The two states every form writes, each in ONE place.  (Macros over a state `z`, not functions: a local state handed to a
+// function by reference stays in memory until the call is inlined, which is after the compiler's first scalarisation, and the
+// streaming kernel's last block then comes out in another order than the one it has been measured in.)
+//
+// The state of a pair (or the control block) no kernel has touched yet, in the histogram forms' mode: what k_octav_init (with
+// the mode of the form it serves) and k_octav_tail_init store, and what the one-read walk fills its result into.
+#define DPL_OCTAV_FRESH(z)                                                                                           \
+    do {                                                                                                             \
+        (z).sum = 0.0;                                                                                               \
+        (z).cnt_gt = 0;                                                                                              \
+        (z).cnt_le = 0;                                                                                              \
+        (z).min_enc = 0xFFFFFFFFu; /* (the empty range) */                                                           \
+        (z).max_enc = 0u;                                                                                            \
+        (z).nan_seen = 0u;                                                                                           \
+        (z).done = 0u;                                                                                               \
+        (z).s = 0.0f;                                                                                                \
+        (z).unsigned_div = 1.0f;                                                                                     \
+        (z).iters = 0u;                                                                                              \
+        (z).mode = 2u;                                                                                               \
+        (z).n_elems = 0ull;                                                                                          \
+        (z).len[0] = 0u;                                                                                             \
+        (z).len[1] = 0u;                                                                                             \
+        (z).cur = 2u; /* (no list yet) */                                                                            \
+        (z).reserved = 0u;                                                                                           \
+    } while (0)
+
+// A pair that a histogram form could not finish RESTARTS ON THE COMPACTION ROUTE from s_0: list mode, and one more pair in the
+// control block's cnt_le (what the route's kernels look at before they do anything).  k_octav_compact_full expects the state
+// that k_octav_update<true> leaves: s = s_0, done = iters = 0, both lists empty (len = {0, 0}, cur = 2), the three accumulators
+// zero.  `dirty` (a constant): the fields of that state the caller's form has written since — only they are stored, the others
+// still hold it.
+enum : uint32_t { kDirtyIters = 1u, kDirtyDone = 2u, kDirtyList0 = 4u, kDirtyList1 = 8u };
+#define DPL_OCTAV_RESTART_COMPACTION(z, ctl, dirty)                                                                  \
+    do {                                                                                                             \
+        (z).mode = 1u;                                                                                               \
+        if ((dirty) & kDirtyIters) (z).iters = 0u;                                                                   \
+        if ((dirty) & kDirtyDone) (z).done = 0u;                                                                     \
+        if ((dirty) & kDirtyList0) (z).len[0] = 0u;                                                                  \
+        if ((dirty) & kDirtyList1) {                                                                                 \
+            (z).len[1] = 0u;                                                                                         \
+            (z).cur = 2u;                                                                                            \
+        }                                                                                                            \
+        atomicAdd(reinterpret_cast<unsigned long long*>(&(ctl)->cnt_le), 1ull);                                      \
+    } while (0)
 
 constexpr int kLogShift = 17;                               // 23 - 6: six mantissa bits per bin
 constexpr uint32_t kLogKey0 = (uint32_t)(127 - 18) << 6;    // key of 2^-18
@@ -227,5 +273,16 @@ __device__ __forceinline__ void for_each_tile(const float* __restrict__ p, uint3
     }
 }
 
-
 }  // namespace
+
+// ---- what octav_kernels.hip defines and octav_tail_host.hip launches as well
+extern int g_exact_fail_every, g_rescue_fail_every;   // dpl_test_hook_exact_fail_every / _rescue_fail_every
+// the gather pass of the one-read form's rescue (k_octav_rescue_gather)
+int dpl_octav_rescue_gather_launch(const uint32_t* d_missed, dpl_octav_state* d_states, int64_t n_pairs, const dpl_span* d_pair_spans,
+                                   const float* const* d_seg_ptrs, const uint32_t* d_bm_rows, const uint64_t* d_pair_base,
+                                   float* d_list1, hipStream_t st);
+// the compaction route on its own, for the pairs whose state says mode 1
+int dpl_octav_fallback_route(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin, int64_t n_blocks,
+                             const float* const* d_seg_ptrs, dpl_octav_state* d_states, int64_t n_pairs,
+                             const dpl_span* d_pair_spans, const uint64_t* d_pair_base, const uint32_t* d_pair_order,
+                             float* d_list0, float* d_list1, int dynamic_sym, int max_iters, hipStream_t st);

@@ -1,5 +1,5 @@
-// The numbers the OCTAV kernels (octav_common.hpp, octav_tail.hpp, octav_tail_host.hip) and the host planning of their tables
-// (host_plan.hpp) must agree on: one definition each.  Plain constexpr, no HIP: usable from device code, from the library's
+// The numbers the OCTAV kernels (octav_common.hpp, octav_wave.hpp, octav_tail.hpp, octav_rescue.hpp), their launchers
+// (octav_kernels.hip, octav_tail_host.hip) and the host planning of their tables (host_plan.hpp) must agree on: one definition each.  Plain constexpr, no HIP: usable from device code, from the library's
 // host code and from a program a plain C++ compiler builds.
 #pragma once
 #include <stdint.h>

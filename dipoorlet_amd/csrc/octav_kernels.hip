@@ -1,6 +1,9 @@
 // OCTAV ('-A mse', forward_net.py:284-342) on MI355X: kernels + their C ABI entry points (include/dipoorlet_hip.h).
 // Three forms of the same iterate sequence: full re-reads, tail compaction, and the two-read bracket form over an
-// exact log-scale histogram (the default).  Shared helpers: common.hpp.
+// exact log-scale histogram; and, for the one-read exact-tail form (octav_tail_host.hip, the default), the gather pass of
+// its rescue and the compaction route behind it.  Shared helpers: common.hpp, octav_common.hpp.  Each kernel with dynamic
+// LDS has its layout in a struct beside it (StageLds, LogHistLds, QueueLds): the kernel takes its pointers from it, the
+// launcher the byte count.
 #include "common.hpp"
 #include "octav_common.hpp"
 
@@ -167,6 +170,14 @@ __global__ void k_octav_update(dpl_octav_state* __restrict__ st, int64_t n, int 
 // iterate sequence as the full-pass form; a pair whose iterate ever decreases drops back to full passes.
 constexpr int kStageCap = 2048;  // floats of LDS staging per wave
 
+// Dynamic LDS of a compacting kernel of kThreadsT threads:  float stage[waves][kCap]   (tail_tile's staging, one area per wave)
+template <int kThreadsT, int kCap>
+struct StageLds {
+    static __device__ __forceinline__ float* stage(float* base, int w) { return base + w * kCap; }
+    static constexpr size_t bytes() { return (size_t)(kThreadsT / kWave) * kCap * sizeof(float); }
+};
+using CompactFullLds = StageLds<kBlock, kStageCap>;   // k_octav_compact_full
+
 struct TailAcc {
     uint32_t gt;  // wave-uniform: survivors this wave has seen
     double sum;   // per lane
@@ -212,12 +223,12 @@ __global__ __launch_bounds__(kBlock) void k_octav_compact_full(const dpl_work_it
                                                                 const dpl_octav_state* __restrict__ ctl,
                                                                 const uint64_t* __restrict__ pair_base,
                                                                 float* __restrict__ list0) {
-    extern __shared__ __attribute__((aligned(16))) float stage_all[];
+    extern __shared__ __attribute__((aligned(16))) float stage_all[];  // CompactFullLds
     __shared__ double s_sum[kBlock / kWave];
     __shared__ uint32_t s_gt[kBlock / kWave];
     const int w = threadIdx.x / kWave;
     const uint32_t lane = threadIdx.x & (kWave - 1);
-    float* stage = stage_all + w * kStageCap;
+    float* stage = CompactFullLds::stage(stage_all, w);
     if (ctl && ctl->cnt_le == 0ull) return;  // no pair on the compaction route
     uint32_t k0, k1;
     block_items(bb, k0, k1);
@@ -267,6 +278,7 @@ __global__ __launch_bounds__(kBlock) void k_octav_compact_full(const dpl_work_it
 // kernel boundary in between (the lists shrink ~2.5x per step and stay in this XCD's L2).
 constexpr int kIterBlock = 512;      // 8 waves per pair; 64 KiB of LDS staging -> 2 workgroups per CU
 constexpr int kIterStageCap = 2048;  // floats of LDS staging per wave (two full tiles)
+using IterListsLds = StageLds<kIterBlock, kIterStageCap>;   // k_octav_iterate_lists
 
 __global__ __launch_bounds__(kIterBlock) void k_octav_iterate_lists(dpl_octav_state* __restrict__ st,
                                                                      dpl_octav_state* __restrict__ ctl,
@@ -274,7 +286,7 @@ __global__ __launch_bounds__(kIterBlock) void k_octav_iterate_lists(dpl_octav_st
                                                                      const uint64_t* __restrict__ pair_base,
                                                                      float* __restrict__ list0,
                                                                      float* __restrict__ list1, int max_iters) {
-    extern __shared__ __attribute__((aligned(16))) float stage_all[];
+    extern __shared__ __attribute__((aligned(16))) float stage_all[];  // IterListsLds
     constexpr int kWaves = kIterBlock / kWave;
     __shared__ double s_sum[kWaves];
     __shared__ uint32_t s_gt[kWaves];
@@ -288,7 +300,7 @@ __global__ __launch_bounds__(kIterBlock) void k_octav_iterate_lists(dpl_octav_st
     if (me->done || me->mode != 1u || me->cur > 1u) return;  // uniform per workgroup
     const int w = threadIdx.x / kWave;
     const uint32_t lane = threadIdx.x & (kWave - 1);
-    float* stage = stage_all + w * kIterStageCap;
+    float* stage = IterListsLds::stage(stage_all, w);
     const uint64_t base_off = pair_base[pair];
     const unsigned long long n_elems = me->n_elems;
     const float unsigned_div = me->unsigned_div;
@@ -465,22 +477,8 @@ __global__ void k_octav_init(dpl_octav_state* st, int64_t n, uint32_t mode) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i > n) return;  // slot n is the control block
     dpl_octav_state z;
-    z.sum = 0.0;
-    z.cnt_gt = 0;
-    z.cnt_le = 0;
-    z.min_enc = 0xFFFFFFFFu;
-    z.max_enc = 0u;
-    z.nan_seen = 0u;
-    z.done = 0u;
-    z.s = 0.0f;
-    z.unsigned_div = 1.0f;
-    z.iters = 0u;
+    DPL_OCTAV_FRESH(z);
     z.mode = mode;
-    z.n_elems = 0ull;
-    z.len[0] = 0u;
-    z.len[1] = 0u;
-    z.cur = 2u;
-    z.reserved = 0u;
     if (i == n) {  // control block: cnt_gt = pairs in full-pass mode, cnt_le = pairs on the compaction route
         z.cnt_gt = mode == 0u ? (unsigned long long)n : 0ull;
         z.cnt_le = mode == 1u ? (unsigned long long)n : 0ull;
@@ -538,13 +536,19 @@ struct LogHistOp {
     }
 };
 
+// Dynamic LDS of k_octav_loghist:  u64 packed[kLogNB]   (a bin's word: kPackShift)
+struct LogHistLds {
+    static constexpr int kWords = kLogNB;
+    static constexpr size_t bytes() { return (size_t)kWords * sizeof(unsigned long long); }
+};
+
 __global__ __launch_bounds__(kBlock) void k_octav_loghist(const dpl_work_item* __restrict__ items,
                                                            const uint32_t* __restrict__ bb,
                                                            const float* const* __restrict__ segs,
                                                            dpl_octav_state* __restrict__ st,
                                                            uint32_t* __restrict__ lh_cnt,
                                                            unsigned long long* __restrict__ lh_sum) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long l_packed[];  // kLogNB packed bins
+    extern __shared__ __attribute__((aligned(16))) unsigned long long l_packed[];  // LogHistLds
     __shared__ double s_sum[kBlock / kWave];
     __shared__ uint32_t s_a[kBlock / kWave], s_b[kBlock / kWave];
     __shared__ float s_mn[kBlock / kWave], s_mx[kBlock / kWave];
@@ -555,7 +559,7 @@ __global__ __launch_bounds__(kBlock) void k_octav_loghist(const dpl_work_item* _
     for (uint32_t k = k0; k < k1; ++k) {
         const dpl_work_item it = items[k];
         dpl_octav_state* me = st + it.slot;
-        for (int b = threadIdx.x; b < kLogNB; b += kBlock) l_packed[b] = 0ull;
+        for (int b = threadIdx.x; b < LogHistLds::kWords; b += kBlock) l_packed[b] = 0ull;
         __syncthreads();
         LogHistOp op{l_packed, INFINITY, -INFINITY, 0u, 0u, 0.0};  // mn, mx, nan, nz_out, sum_out
         uint32_t* gc = lh_cnt + (uint64_t)it.slot * kLogNB;
@@ -565,7 +569,7 @@ __global__ __launch_bounds__(kBlock) void k_octav_loghist(const dpl_work_item* _
         for (uint32_t s0 = 0; s0 < it.count; s0 += kSub) {
             stream_span(segs[it.seg] + it.offset + s0, min(kSub, it.count - s0), op);
             __syncthreads();
-            for (int b = threadIdx.x; b < kLogNB; b += kBlock) {
+            for (int b = threadIdx.x; b < LogHistLds::kWords; b += kBlock) {
                 const unsigned long long v = l_packed[b];
                 if (v) {
                     const unsigned long long c = v >> kPackShift;
@@ -754,6 +758,16 @@ constexpr int kKeyWords = (1 << (31 - kLogShift)) / 32;   // 512
 constexpr int kKeyWord0 = (int)(kLogKey0 >> 5);           // word of the window's first bin (kLogKey0 is a multiple of 32)
 static_assert((kLogKey0 & 31u) == 0u, "the window must start on a bitmap word");
 
+// Dynamic LDS of k_octav_gather / k_octav_rescue_gather:  u32 queues[waves][kQueueStride][kWave]   — entry j of lane l of a wave
+// sits at [j][l], so the bank of every queue access depends on the lane alone (no conflicts whatever the fills).  entry: a
+// lane's entry j, from the pointer to its entry 0 — which is DPL_LANE_QUEUE (a macro: a function is simplified on its own before
+// it is inlined, and its product of constants then folds otherwise than the kernels' code has it).
+#define DPL_LANE_QUEUE(queues, w, lane) ((queues) + (size_t)(w) * kWave * kQueueStride + (lane))
+struct QueueLds {
+    static __device__ __forceinline__ uint32_t& entry(uint32_t* q, uint32_t j) { return q[j * kWave]; }
+    static constexpr size_t bytes() { return (size_t)kBlock * kQueueStride * sizeof(uint32_t); }
+};
+
 // One span of one pair: the values of the marked bins (bm: the bitmap over the whole key space, in LDS) -> per-lane queues
 // -> the pair's list (cursor: me->len[0], a returning global atomic per wave flush).
 // cap: values the destination region holds — a flush that would pass it is dropped while the cursor keeps counting, so a
@@ -775,7 +789,7 @@ __device__ __forceinline__ void gather_span(const float* __restrict__ p, uint32_
         const uint32_t first = __shfl(base, kWave - 1, kWave);
         base = first + inc - cnt;
         if (first + total <= cap)
-            for (uint32_t j = 0; j < cnt; ++j) dst[base + j] = q[j * kWave];
+            for (uint32_t j = 0; j < cnt; ++j) dst[base + j] = QueueLds::entry(q, j);
         cnt = 0;
     };
     for_each_tile<kBlock>(p, count, [&](const f4 (&v)[4], uint32_t, bool) {
@@ -800,7 +814,7 @@ __device__ __forceinline__ void gather_span(const float* __restrict__ p, uint32_
         if (__any(any != 0u)) {
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
-                q[cnt * kWave] = u[j];
+                QueueLds::entry(q, cnt) = u[j];
                 cnt += hit[j];
             }
         }
@@ -816,12 +830,11 @@ __global__ __launch_bounds__(kBlock) void k_octav_gather(const dpl_work_item* __
                                                           const uint32_t* __restrict__ bitmap,
                                                           const uint64_t* __restrict__ pair_base,
                                                           float* __restrict__ list0) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t queues[];  // [waves][kQueueStride][64]: entry j of lane l
-    // sits at [j][l], so the bank of every queue access depends on the lane alone (no conflicts whatever the fills)
+    extern __shared__ __attribute__((aligned(16))) uint32_t queues[];  // QueueLds
     __shared__ uint32_t bm[kKeyWords];
     const int w = threadIdx.x / kWave;
     const uint32_t lane = threadIdx.x & (kWave - 1);
-    uint32_t* q = queues + (size_t)w * kWave * kQueueStride + lane;
+    uint32_t* q = DPL_LANE_QUEUE(queues, w, lane);
     uint32_t k0, k1;
     block_items(bb, k0, k1);
     for (uint32_t k = k0; k < k1; ++k) {
@@ -852,14 +865,14 @@ __global__ __launch_bounds__(kBlock) void k_octav_rescue_gather(const uint32_t* 
                                                                  const uint32_t* __restrict__ bm_rows,
                                                                  const uint64_t* __restrict__ pair_base,
                                                                  float* __restrict__ list1) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t queues[];
+    extern __shared__ __attribute__((aligned(16))) uint32_t queues[];  // QueueLds
     __shared__ uint32_t bm[kKeyWords];
     __shared__ uint32_t found[3];
     const uint32_t n_missed = ctl->len[0], n_units = ctl->len[1];
     if (n_missed == 0u) return;
     const int w = threadIdx.x / kWave;
     const uint32_t lane = threadIdx.x & (kWave - 1);
-    uint32_t* q = queues + (size_t)w * kWave * kQueueStride + lane;
+    uint32_t* q = DPL_LANE_QUEUE(queues, w, lane);
     uint32_t held = 0xFFFFFFFFu;   // the pair whose bitmap sits in bm
     for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
         __syncthreads();
@@ -1089,14 +1102,9 @@ __global__ __launch_bounds__(kExactBlock, kExactWaves) void k_octav_exact(dpl_oc
         jb = s_jb;
     }
     if (threadIdx.x == 0) {
-        if (bad) {  // restart this pair on the compaction route from s_0 (state as k_octav_update<true> leaves it;
-                    // s_0 is still in me->s: this kernel only writes it back on success)
-            me->mode = 1u;
-            me->iters = 0u;
-            me->len[0] = 0u;
-            me->len[1] = 0u;
-            me->cur = 2u;
-            atomicAdd(reinterpret_cast<unsigned long long*>(&ctl->cnt_le), 1ull);
+        if (bad) {  // s_0 is still in me->s (this kernel only writes it back on success); of the restart state the bracket form
+                    // has written the two lists (k_octav_gather, the bucket pass above), and iters is reset with them
+            DPL_OCTAV_RESTART_COMPACTION(*me, ctl, kDirtyIters | kDirtyList0 | kDirtyList1);
         } else {
             me->s = s;
             me->iters = iters;
@@ -1113,29 +1121,38 @@ int g_rescue_fail_every = 0;  // dpl_test_hook_rescue_fail_every
 int dpl_octav_rescue_gather_launch(const uint32_t* d_missed, dpl_octav_state* d_states, int64_t n_pairs, const dpl_span* d_pair_spans,
                                    const float* const* d_seg_ptrs, const uint32_t* d_bm_rows, const uint64_t* d_pair_base,
                                    float* d_list1, hipStream_t st) {
-    hipLaunchKernelGGL(k_octav_rescue_gather, dim3(kRescueGrid), dim3(kBlock), (size_t)kBlock * kQueueStride * sizeof(uint32_t), st,
+    hipLaunchKernelGGL(k_octav_rescue_gather, dim3(kRescueGrid), dim3(kBlock), QueueLds::bytes(), st,
                        d_missed, d_states + n_pairs, d_states, d_pair_spans, d_seg_ptrs, d_bm_rows, d_pair_base, d_list1);
     DPL_LAUNCH_CHECK("k_octav_rescue_gather");
     return 0;
 }
 
-// The compaction route on its own, for the pairs a histogram form marked mode 1 (shared with octav_tail_host.hip).
+// The compaction route on its own, for the pairs whose state says mode 1 (dpl_octav_run_compact: all of them; the histogram
+// forms, and octav_tail_host.hip: those they could not finish).  `who`: the name a failed launch is reported under.
+static int launch_compaction_route(const char* who, const dpl_work_item* d_items, const uint32_t* d_block_begin, int64_t n_blocks,
+                                   const float* const* d_seg_ptrs, dpl_octav_state* d_states, int64_t n_pairs,
+                                   const dpl_span* d_pair_spans, const uint64_t* d_pair_base, const uint32_t* d_pair_order,
+                                   float* d_list0, float* d_list1, int dynamic_sym, int max_iters, hipStream_t st) {
+    const dim3 ug(grid_for(n_pairs, 256)), ub(256), pg((unsigned)n_blocks), pb(kBlock), pairs((unsigned)n_pairs);
+    dpl_octav_state* ctl = d_states + n_pairs;
+    // evaluate at s_0 over the full data, keep the values above s_0 ...
+    hipLaunchKernelGGL(k_octav_compact_full, pg, pb, CompactFullLds::bytes(), st, d_items, d_block_begin, d_seg_ptrs, d_states,
+                       ctl, d_pair_base, d_list0);
+    hipLaunchKernelGGL(k_octav_update<false>, ug, ub, 0, st, d_states, n_pairs, dynamic_sym, max_iters, ctl);
+    // ... every remaining iteration of every pair inside one launch; degenerate pairs on the full data
+    hipLaunchKernelGGL(k_octav_iterate_lists, pairs, dim3(kIterBlock), IterListsLds::bytes(), st, d_states, ctl, d_pair_order,
+                       d_pair_base, d_list0, d_list1, max_iters);
+    hipLaunchKernelGGL(k_octav_iterate_full, pairs, pb, 0, st, d_states, ctl, d_pair_spans, d_seg_ptrs, max_iters);
+    DPL_LAUNCH_CHECK(who);
+    return 0;
+}
 int dpl_octav_fallback_route(const dpl_work_item* d_items, int64_t n_items, const uint32_t* d_block_begin, int64_t n_blocks,
                              const float* const* d_seg_ptrs, dpl_octav_state* d_states, int64_t n_pairs,
                              const dpl_span* d_pair_spans, const uint64_t* d_pair_base, const uint32_t* d_pair_order,
                              float* d_list0, float* d_list1, int dynamic_sym, int max_iters, hipStream_t st) {
-    const dim3 ug(grid_for(n_pairs, 256)), ub(256), pg((unsigned)n_blocks), pb(kBlock), pairs((unsigned)n_pairs);
-    dpl_octav_state* ctl = d_states + n_pairs;
-    const size_t stage_bytes = (size_t)(kBlock / kWave) * kStageCap * sizeof(float);
-    hipLaunchKernelGGL(k_octav_compact_full, pg, pb, stage_bytes, st, d_items, d_block_begin, d_seg_ptrs, d_states,
-                       ctl, d_pair_base, d_list0);
-    hipLaunchKernelGGL(k_octav_update<false>, ug, ub, 0, st, d_states, n_pairs, dynamic_sym, max_iters, ctl);
-    hipLaunchKernelGGL(k_octav_iterate_lists, pairs, dim3(kIterBlock),
-                       (size_t)(kIterBlock / kWave) * kIterStageCap * sizeof(float), st, d_states, ctl, d_pair_order,
-                       d_pair_base, d_list0, d_list1, max_iters);
-    hipLaunchKernelGGL(k_octav_iterate_full, pairs, pb, 0, st, d_states, ctl, d_pair_spans, d_seg_ptrs, max_iters);
-    DPL_LAUNCH_CHECK("k_octav_fallback_route");
-    return 0;
+    (void)n_items;
+    return launch_compaction_route("k_octav_fallback_route", d_items, d_block_begin, n_blocks, d_seg_ptrs, d_states, n_pairs,
+                                   d_pair_spans, d_pair_base, d_pair_order, d_list0, d_list1, dynamic_sym, max_iters, st);
 }
 
 extern "C" {
@@ -1189,20 +1206,12 @@ int dpl_octav_run_compact(const dpl_work_item* d_items, int64_t n_items, const u
     hipStream_t st = (hipStream_t)s;
     const dim3 ug(grid_for(n_pairs, 256)), ub(256), pg((unsigned)n_blocks), pb(kBlock);
     dpl_octav_state* ctl = d_states + n_pairs;
-    // 1. statistics + s_0             2. evaluate at s_0 over the full data, keep the values above s_0
+    // 1. statistics + s_0             2. - 4. the compaction route, every pair on it (dpl_octav_init: mode 1)
     hipLaunchKernelGGL(k_octav_pass<true>, pg, pb, 0, st, d_items, d_block_begin, d_seg_ptrs, d_states, ctl);
     hipLaunchKernelGGL(k_octav_update<true>, ug, ub, 0, st, d_states, n_pairs, dynamic_sym, max_iters, ctl);
-    if (max_iters > 0) {
-        hipLaunchKernelGGL(k_octav_compact_full, pg, pb, (size_t)(kBlock / kWave) * kStageCap * sizeof(float), st,
-                           d_items, d_block_begin, d_seg_ptrs, d_states, ctl, d_pair_base, d_list0);
-        hipLaunchKernelGGL(k_octav_update<false>, ug, ub, 0, st, d_states, n_pairs, dynamic_sym, max_iters, ctl);
-        // 3. every remaining iteration of every pair inside one launch    4. degenerate pairs on the full data
-        hipLaunchKernelGGL(k_octav_iterate_lists, dim3((unsigned)n_pairs), dim3(kIterBlock),
-                           (size_t)(kIterBlock / kWave) * kIterStageCap * sizeof(float), st, d_states, ctl, d_pair_order,
-                           d_pair_base, d_list0, d_list1, max_iters);
-        hipLaunchKernelGGL(k_octav_iterate_full, dim3((unsigned)n_pairs), pb, 0, st, d_states, ctl, d_pair_spans,
-                           d_seg_ptrs, max_iters);
-    }
+    if (max_iters > 0)
+        return launch_compaction_route("k_octav_compact", d_items, d_block_begin, n_blocks, d_seg_ptrs, d_states, n_pairs, d_pair_spans,
+                                       d_pair_base, d_pair_order, d_list0, d_list1, dynamic_sym, max_iters, st);
     DPL_LAUNCH_CHECK("k_octav_compact");
     return 0;
 }
@@ -1221,12 +1230,12 @@ int dpl_octav_run_bracket(const dpl_work_item* d_items, int64_t n_items, const u
     hipError_t e2 = hipMemsetAsync(d_lh_sum, 0, (size_t)n_pairs * kLogNB * sizeof(uint64_t), st);
     if (e1 != hipSuccess || e2 != hipSuccess) return fail("hipMemsetAsync", e1 != hipSuccess ? e1 : e2);
     // 1. statistics + log-scale histogram   2. s_0 and the bracket walk   3. gather the marked bins   4. exact walk
-    hipLaunchKernelGGL(k_octav_loghist, pg, pb, (size_t)kLogNB * 8, st, d_items, d_block_begin, d_seg_ptrs, d_states,
+    hipLaunchKernelGGL(k_octav_loghist, pg, pb, LogHistLds::bytes(), st, d_items, d_block_begin, d_seg_ptrs, d_states,
                        d_lh_cnt, reinterpret_cast<unsigned long long*>(d_lh_sum));
     hipLaunchKernelGGL(k_octav_bracket, pairs, pb, 0, st, d_states, ctl, d_lh_cnt,
                        reinterpret_cast<unsigned long long*>(d_lh_sum), d_bitmap, dynamic_sym, max_iters);
     if (max_iters > 0) {
-        hipLaunchKernelGGL(k_octav_gather, pg, pb, (size_t)kBlock * kQueueStride * sizeof(uint32_t), st, d_items,
+        hipLaunchKernelGGL(k_octav_gather, pg, pb, QueueLds::bytes(), st, d_items,
                            d_block_begin, d_seg_ptrs, d_states, d_bitmap, d_pair_base, d_list0);
         hipLaunchKernelGGL(k_octav_exact, pairs, dim3(kExactBlock), 0, st, d_states, ctl, d_pair_order,
                            d_lh_cnt, reinterpret_cast<const unsigned long long*>(d_lh_sum), d_bitmap, d_pair_base,

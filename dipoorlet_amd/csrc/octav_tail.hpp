@@ -1,5 +1,6 @@
-// OCTAV ('-A mse', forward_net.py:323-330) in one read: EXACT TAIL, BOUNDED BULK (round 4).  Included by octav_tail_host.hip
-// (shares its LDS layout, scans, the walk's counting idiom and the rescue of pairs a walk cannot finish).
+// OCTAV ('-A mse', forward_net.py:323-330) in one read: EXACT TAIL, BOUNDED BULK (round 4) — the streaming kernel, its walk and
+// their dynamic LDS (TailLds).  The wave primitives and the static LDS block are in octav_wave.hpp, the rescue of pairs a walk
+// cannot finish in octav_rescue.hpp, the launchers in octav_tail_host.hip.
 //
 // The reference's loop s' = sum_{|x|>s} |x| / (c #{|x|<=s} + #{|x|>s}) climbs from s_0 = mean of the non-zero |x| to the
 // LEAST fixed point of a step function F, and that fixed point is carried by the top few dozen ... few thousand values of
@@ -27,6 +28,13 @@
 // histogram so far and publishes the new bin in LDS.  theta only ever rises inside a pair, so the list holds every value
 // >= the final theta; a theta that ends up too high costs a rescue, never a wrong result.
 #pragma once
+#include "common.hpp"
+#include "octav_common.hpp"
+#include "octav_wave.hpp"
+
+#pragma clang fp contract(off)
+
+namespace {
 
 constexpr int kTailTauShift = 8;        // a pair asks for the bin above which n >> 8 of its n elements lie (measured: 7 -> 8 -2 %, 9 the same with four times the rescues at +-30 %)
 constexpr int kTailBudgetShift = 6;     // a wave may list kTailAllow0 + (elements it has seen >> 6) values before it raises theta
@@ -34,8 +42,43 @@ constexpr uint32_t kTailAllow0 = 2048;
 constexpr int kTailOcc = 4;             // waves per SIMD the streaming kernels are bounded for
 constexpr int kTailQueueCap = 512;      // entries of a wave's survivor queue (flushed above 256): 8 KiB per workgroup, which the walk's suffix counts reuse
 constexpr int kTailVec = 12;            // 16-byte vectors per thread the walk keeps the list in (1024 values each); longer lists are streamed from L2
-constexpr int kTailLdsB = kWaves * kTailQueueCap * 4;
-static_assert(kTailQueueCap >= 512 && kTailLdsB >= kLogNB * 4, "a vector may add 256 survivors past the flush mark; the walk keeps its suffix counts in the queues' space");
+static_assert(kTailQueueCap >= 512, "a vector may add 256 survivors past the flush mark");
+constexpr int kSurvVec = 5;                          // 16-byte vectors per lane a wave holds the surviving values in (walk_tail)
+constexpr uint32_t kFitCap = kSurvVec * 4 * kWave;   // values one wave's registers hold (a list this short is loaded there whole)
+
+// The DYNAMIC LDS of k_octav_tail / k_octav_tail_merge: one block of two regions, read as three things over a pair's life.
+//                region A                                            region B
+//   streaming    u64 packed[kLogNB] | u64 dummy[kWave]               u32 queue[kWaves][kTailQueueCap]
+//                (the histogram; one word per lane for what no bin counts)   (the waves' survivor queues: stream_tail)
+//   walk         packed, intact to the end                           u32 tn[kThreads] | f64 ts[kThreads] | u32 surv[kSurvRoom]
+//                                                                    (counts / sums above a group of 8 bins; survivors' staging)
+//   rescue       f64 s_ge[kLogNB], over packed                       u32 n_ge[kLogNB], over the whole of B
+//                (walk_tail's refused branch: the suffix totals of every bin, once every look at packed / tn / ts is behind it)
+struct TailLds {
+    static constexpr uint32_t kHistWords = kLogNB + kWave;                                    // packed + dummy
+    static constexpr uint32_t kB = kHistWords * sizeof(unsigned long long);                   // byte offset of region B
+    static constexpr uint32_t kBBytes = kWaves * kTailQueueCap * sizeof(uint32_t);
+    static constexpr uint32_t kTs = kB + kThreads * sizeof(uint32_t);                         // byte offsets of the walk's view of B
+    static constexpr uint32_t kSurv = kTs + kThreads * sizeof(double);
+    static constexpr uint32_t kSurvRoom = (kB + kBBytes - kSurv) / sizeof(uint32_t);          // values the staging area holds
+    static constexpr size_t bytes() { return (size_t)kB + kBBytes; }
+
+    static __device__ __forceinline__ unsigned long long* packed(unsigned char* lds) { return reinterpret_cast<unsigned long long*>(lds); }
+    static __device__ __forceinline__ unsigned long long* dummy(unsigned char* lds) { return packed(lds) + kLogNB; }
+    static __device__ __forceinline__ uint32_t* queue(unsigned char* lds, int w) {
+        return reinterpret_cast<uint32_t*>(lds + kB) + (uint32_t)w * kTailQueueCap;
+    }
+    static __device__ __forceinline__ uint32_t* tn(unsigned char* lds) { return reinterpret_cast<uint32_t*>(lds + kB); }
+    static __device__ __forceinline__ double* ts(unsigned char* lds) { return reinterpret_cast<double*>(lds + kTs); }
+    static __device__ __forceinline__ uint32_t* surv(unsigned char* lds) { return reinterpret_cast<uint32_t*>(lds + kSurv); }
+    static __device__ __forceinline__ double* s_ge(unsigned char* lds) { return reinterpret_cast<double*>(lds); }
+    static __device__ __forceinline__ uint32_t* n_ge(unsigned char* lds) { return reinterpret_cast<uint32_t*>(lds + kB); }
+};
+static_assert(kLogNB * sizeof(double) <= TailLds::kB && kLogNB * sizeof(uint32_t) <= TailLds::kBBytes,
+              "the rescue's suffix totals: the sums over the histogram, the counts in the queues' space");
+static_assert(TailLds::kSurv < TailLds::kB + TailLds::kBBytes, "the group totals leave room for the staging area");
+// what the walk compacts through the staging area: a wave's registers full, or what the area holds
+constexpr uint32_t kSurvCap = kFitCap <= TailLds::kSurvRoom ? kFitCap : TailLds::kSurvRoom;
 
 struct TailArgs {
     uint32_t* vis_w;             // [T, kLogWords]: word 0 of a tensor's row = kLogNB - (lowest bin its pairs asked for this epoch); 0: none
@@ -54,12 +97,12 @@ struct TailArgs {
 __device__ __forceinline__ void stream_tail(const float* __restrict__ pg, uint32_t cnt, uint32_t* __restrict__ dst,
                                             Shared& sh, dpl_octav_state* __restrict__ ctl, const bool adaptive) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const lptr_u64 l_packed = (lptr_u64)(lds_raw);
+    const lptr_u64 l_packed = (lptr_u64)TailLds::packed(lds_raw);
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & (kWave - 1);
     const int w = tid / kWave;
     float mn = INFINITY, mx = -INFINITY;
-    const lptr_u32 wq = (lptr_u32)(lds_raw + kLdsA) + (uint32_t)w * kTailQueueCap;
+    const lptr_u32 wq = (lptr_u32)TailLds::queue(lds_raw, w);
     uint32_t tail = 0u;          // entries in the wave's queue
     uint32_t mine = 0u;          // values this wave has listed
     uint32_t seen = 0u;          // elements this wave has consumed
@@ -118,7 +161,7 @@ __device__ __forceinline__ void stream_tail(const float* __restrict__ pg, uint32
     };
     uint32_t rare = 0u;
     constexpr uint32_t kWin = (uint32_t)(kLogNB - 1);
-    const lptr_u64 dummy = l_packed + kLogNB + lane;
+    const lptr_u64 dummy = (lptr_u64)TailLds::dummy(lds_raw) + lane;
     // per element: the bin key (14 bits of exponent and top mantissa, relative to the window), ONE LDS add {count += 1, mantissa
     // sum += 23 explicit bits} on the bin's word (zeros and values outside the window: the lane's dummy word), and the threshold
     // test on the key itself (signed: below the window is negative; above it — values >= 2^14, inf, NaN — passes and is harmless:
@@ -235,11 +278,6 @@ __device__ __forceinline__ void stream_tail(const float* __restrict__ pg, uint32
 //     per lane and a DPP sum, no exchange, no barrier;
 //   * lists beyond that (a cold start, a pair much brighter than its tensor's history) take the round-3 shape: rows spread over
 //     the workgroup, partial sums exchanged through LDS.
-constexpr int kSurvVec = 5;                          // 16-byte vectors per lane a wave holds the surviving values in
-constexpr uint32_t kFitCap = kSurvVec * 4 * kWave;   // values one wave's registers hold (a list this short is loaded there whole)
-// ... and what the compaction's staging area holds (group totals, 3 KiB, + the staging area share the queues' space)
-constexpr uint32_t kSurvCap = kFitCap * 4 <= (uint32_t)(kTailLdsB - 3072) ? kFitCap : (uint32_t)(kTailLdsB - 3072) / 4;
-
 template <int kVecT>
 __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t tensor, unsigned char* lds_raw, Shared& sh,
                                           dpl_octav_state* __restrict__ st, dpl_octav_state* __restrict__ ctl,
@@ -251,10 +289,10 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
     dpl_octav_state* me = st + pair;
     const unsigned long long n_pair = n_merged ? n_merged : (unsigned long long)cnt;   // (n_merged: a pair of several slices, k_octav_tail_merge)
     const bool small = !n_merged && cnt <= kSmallCap;
-    const unsigned long long* packed = reinterpret_cast<const unsigned long long*>(lds_raw);   // the histogram: intact to the end
-    uint32_t* tn = reinterpret_cast<uint32_t*>(lds_raw + kLdsA);                                // [256] counts above a group
-    double* ts = reinterpret_cast<double*>(lds_raw + kLdsA + 1024);                             // [256] sums above a group
-    uint32_t* surv = reinterpret_cast<uint32_t*>(lds_raw + kLdsA + 3072);                       // [kSurvCap] survivors' staging
+    const unsigned long long* packed = TailLds::packed(lds_raw);   // the histogram: intact to the end
+    uint32_t* tn = TailLds::tn(lds_raw);                           // counts above a group
+    double* ts = TailLds::ts(lds_raw);                             // sums above a group
+    uint32_t* surv = TailLds::surv(lds_raw);                       // [kSurvCap] survivors' staging
     // the list: this workgroup's own global stores (one CU, one L1), requested before anything else
     const float* lp = list0 + pair_base[pair];
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -268,17 +306,6 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
     // kSurvVec vectors, wave 0 only — all surviving values (entry (u * 64 + lane) * 4 ...)
     f4 v[kVecT];
     static_assert(kVecT >= kSurvVec, "the survivors live in the rows' registers");
-    auto load_rows = [&](auto& dst, auto count, uint32_t row0) {
-        constexpr int kN = decltype(count)::value;
-        const uint32_t voff = tid << 4;
-#pragma unroll
-        for (int u = 0; u < kN; ++u) {
-            const uint32_t e0 = (row0 + (uint32_t)u) << 10;
-            const int nbytes = e0 < L ? (int)(min(L - e0, 1024u) << 2) : 0;   // buffer loads: zero fill past the list's end
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(lp + (e0 < L ? e0 : 0u)), 0, nbytes, 0x00020000);
-            dst[u] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
-        }
-    };
     if (fits) {
         if (w == 0) {
             const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)lp, 0, (int)(L << 2), 0x00020000);
@@ -287,7 +314,7 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
                 v[u] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, ((uint32_t)u * kWave + lane) << 4, 0, 0));
         }
     } else {
-        load_rows(v, std::integral_constant<int, kVecT>{}, 0u);
+        load_rows(v, lp, 0u, L);
     }
     // ---- totals above every group of 8 bins (thread t: bins 2040 - 8 t .. 2047 - 8 t, one exponent: integer sums, ONE conversion)
     constexpr int kPerT = kLogNB / kThreads;
@@ -427,8 +454,8 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
     };
     if (w == 0) {
         // ---- the pair's statistics (stream_tail left them per wave), s_0, the route
-        const float gmn = fminf(fminf(sh.red_mn[0], sh.red_mn[1]), fminf(sh.red_mn[2], sh.red_mn[3]));
-        const float gmx = fmaxf(fmaxf(sh.red_mx[0], sh.red_mx[1]), fmaxf(sh.red_mx[2], sh.red_mx[3]));
+        const WgRange g = wg_range(sh);
+        const float gmn = g.mn, gmx = g.mx;
         const bool nanseen = sh.low_nan != 0u;
         // forward_net.py:319 — np.abs(data_min - 0) < 1e-6 (float32 compare) and 'dynamic_sym' in qi_params
         ud = (fa.dynamic_sym && fabsf(gmn) < 1e-6f && !nanseen) ? 4.0f : 1.0f;
@@ -575,7 +602,7 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
                 cc += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(in));
                 ds += in ? d : 0u;
             };
-            if (n_rows > (uint32_t)kVecT) load_rows(ov, std::integral_constant<int, kOver>{}, (uint32_t)kVecT);
+            if (n_rows > (uint32_t)kVecT) load_rows(ov, lp, (uint32_t)kVecT, L);
             {
                 const uint32_t rows = min(n_rows, (uint32_t)kVecT);
 #pragma unroll
@@ -598,7 +625,7 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
                     in1(ov[u].z);
                     in1(ov[u].w);
                 }
-                if (r0 + (uint32_t)kOver < n_rows) load_rows(ov, std::integral_constant<int, kOver>{}, r0 + (uint32_t)kOver);
+                if (r0 + (uint32_t)kOver < n_rows) load_rows(ov, lp, r0 + (uint32_t)kOver, L);
                 dsum += (unsigned long long)wave_sum_dpp(ds);
                 ds = 0u;
             }
@@ -642,8 +669,8 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
     // walk.  The bracket walk wants the suffix totals of every bin: only now are they written out (over the packed histogram)
     bool rescued = false;
     if (bad && !small && route == 2u) {
-        double* s_ge = reinterpret_cast<double*>(lds_raw);
-        uint32_t* n_ge = reinterpret_cast<uint32_t*>(lds_raw + kLdsA);
+        double* s_ge = TailLds::s_ge(lds_raw);
+        uint32_t* n_ge = TailLds::n_ge(lds_raw);
         {
             uint32_t c8[kPerT];
             unsigned long long m8[kPerT];
@@ -687,8 +714,8 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
         rescued = sh.route == 2u;
         if (rescued) {
             if (tid < (uint32_t)kLogWords) fa.rescue_bm[(uint64_t)pair * kLogWords + tid] = sh.pub[tid];
-            double* rs = reinterpret_cast<double*>(fa.resc + (uint64_t)pair * kRescRow);
-            uint32_t* rn = reinterpret_cast<uint32_t*>(fa.resc + (uint64_t)pair * kRescRow + kLogNB);
+            double* rs = RescRow::s_ge(fa.resc, pair);
+            uint32_t* rn = RescRow::n_ge(fa.resc, pair);
             for (int b = tid; b < kLogNB; b += kThreads) {
                 rs[b] = s_ge[b];
                 rn[b] = n_ge[b];
@@ -697,25 +724,16 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
     }
     if (tid == 0) {
         // the pair's state: its statistics (what the rescue / the compaction route / dpl_octav_finalize read), and what became of it
-        const float gmn = fminf(fminf(sh.red_mn[0], sh.red_mn[1]), fminf(sh.red_mn[2], sh.red_mn[3]));
-        const float gmx = fmaxf(fmaxf(sh.red_mx[0], sh.red_mx[1]), fmaxf(sh.red_mx[2], sh.red_mx[3]));
+        const WgRange g = wg_range(sh);
+        const float gmn = g.mn, gmx = g.mx;
         dpl_octav_state z;
-        z.sum = 0.0;
-        z.cnt_gt = 0ull;
-        z.cnt_le = 0ull;
+        DPL_OCTAV_FRESH(z);
         z.min_enc = gmn <= gmx ? enc_f32(gmn) : 0xFFFFFFFFu;
         z.max_enc = gmn <= gmx ? enc_f32(gmx) : 0u;
         z.nan_seen = sh.low_nan != 0u ? 1u : 0u;
         z.unsigned_div = ud;
         z.n_elems = n_pair;
-        z.len[0] = 0u;
-        z.len[1] = 0u;
-        z.cur = 2u;
-        z.reserved = 0u;
         z.s = s0;          // (a restart begins at s_0)
-        z.iters = 0u;
-        z.done = 0u;
-        z.mode = 2u;
         if (route == 0u) {
             z.done = 1u;
         } else if (bad && rescued) {
@@ -726,8 +744,7 @@ __device__ __forceinline__ void walk_tail(const uint32_t pair, const uint32_t te
             fa.missed[3 * e + 1] = u0;
             fa.missed[3 * e + 2] = nu;
         } else if (bad) {
-            z.mode = 1u;   // restart from s_0 on the compaction route: state as k_octav_update<true> leaves it
-            atomicAdd(reinterpret_cast<unsigned long long*>(&ctl->cnt_le), 1ull);
+            DPL_OCTAV_RESTART_COMPACTION(z, ctl, 0u);   // (z is the fresh state but for the statistics and s_0)
         } else {
             z.s = s;
             z.iters = evals;
@@ -746,7 +763,7 @@ __global__ __launch_bounds__(kThreads, kTailOcc) void k_octav_tail(
     uint32_t n_tensors, const uint64_t* __restrict__ pair_base, float* __restrict__ list0, dpl_octav_state* __restrict__ ctl,
     const dpl_span* __restrict__ spans, unsigned long long* __restrict__ rows, const TailArgs fa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    unsigned long long* l_packed = reinterpret_cast<unsigned long long*>(lds_raw);
+    unsigned long long* l_packed = TailLds::packed(lds_raw);
     __shared__ Shared sh;
     const uint32_t tid = threadIdx.x;
     const dpl_work_item it = slices[blockIdx.x];
@@ -767,7 +784,7 @@ __global__ __launch_bounds__(kThreads, kTailOcc) void k_octav_tail(
         cap = (uint32_t)((region / (uint32_t)c) & ~31u);
         list_at = region0 + ((it.offset - spans[pair].offset) / per) * (unsigned long long)cap;
     }
-    for (int b = tid; b < kLogNB + kWave; b += kThreads) l_packed[b] = 0ull;
+    for (int b = tid; b < (int)TailLds::kHistWords; b += kThreads) l_packed[b] = 0ull;
     if (tid == 0) {
         sh.list_cap = cap;
         sh.region_cap = region;
@@ -789,8 +806,8 @@ __global__ __launch_bounds__(kThreads, kTailOcc) void k_octav_tail(
             row[b] = b == 0 ? ((unsigned long long)sh.tail_j << 32) | (unsigned long long)sh.cursor : l_packed[b];
         if (tid == 0) {
             dpl_octav_state* me = st + pair;
-            const float gmn = fminf(fminf(sh.red_mn[0], sh.red_mn[1]), fminf(sh.red_mn[2], sh.red_mn[3]));
-            const float gmx = fmaxf(fmaxf(sh.red_mx[0], sh.red_mx[1]), fmaxf(sh.red_mx[2], sh.red_mx[3]));
+            const WgRange g = wg_range(sh);
+            const float gmn = g.mn, gmx = g.mx;
             if (gmn <= gmx) {
                 atomicMin(&me->min_enc, enc_f32(gmn));
                 atomicMax(&me->max_enc, enc_f32(gmx));
@@ -819,7 +836,7 @@ __global__ __launch_bounds__(kThreads, kTailOcc) void k_octav_tail_merge(
     const dpl_span* __restrict__ spans, const unsigned long long* __restrict__ rows, const uint32_t* __restrict__ pair_order,
     const uint32_t* __restrict__ pair_slice0, const TailArgs fa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    unsigned long long* l_packed = reinterpret_cast<unsigned long long*>(lds_raw);
+    unsigned long long* l_packed = TailLds::packed(lds_raw);
     __shared__ Shared sh;
     const uint32_t tid = threadIdx.x;
     const uint32_t pair = pair_order[blockIdx.x];           // largest first: the pairs of more than one slice come first
@@ -848,7 +865,7 @@ __global__ __launch_bounds__(kThreads, kTailOcc) void k_octav_tail_merge(
     }
 #pragma unroll
     for (int q = 0; q < kPer; ++q) l_packed[(int)tid + q * kThreads] = acc[q];
-    for (int b = kLogNB + (int)tid; b < kLogNB + kWave; b += kThreads) l_packed[b] = 0ull;
+    for (int b = kLogNB + (int)tid; b < (int)TailLds::kHistWords; b += kThreads) l_packed[b] = 0ull;   // the lanes' dummy words
     // ---- the slices' lists: lengths, thresholds, where each goes
     const uint32_t region = (uint32_t)(pair_base[pair + 1] - pair_base[pair]);
     const uint32_t part_cap = (region / (sl1 - sl0)) & ~31u;          // (as k_octav_tail cut the region)
@@ -897,7 +914,8 @@ __global__ __launch_bounds__(kThreads, kTailOcc) void k_octav_tail_merge(
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // (no line of the region read above may answer the walk's loads from this CU's L1)
     __syncthreads();
-    if (sh.bad) {   // a bin of 2^20 values or more: the compaction route (the state as walk_tail leaves it for that route)
+    if (sh.bad) {   // a bin of 2^20 values or more: the compaction route (the state as walk_tail leaves it for that route, with
+                    // s_0 from the slices' own words)
         const double wd = wave_sum(dsum);
         const uint32_t wn = wave_sum(nsum);
         if ((tid & (kWave - 1)) == 0) {
@@ -907,26 +925,24 @@ __global__ __launch_bounds__(kThreads, kTailOcc) void k_octav_tail_merge(
         __syncthreads();
         if (tid == 0) {
             dpl_octav_state* me = st + pair;
-            dpl_octav_state z = *me;
             const float gmn = sh.red_mn[0], gmx = sh.red_mx[0];
-            const bool nanseen = z.nan_seen != 0u;
+            const bool nanseen = me->nan_seen != 0u;
             double tot = sh.low_sum;
             unsigned long long nz = sh.low_cnt;
             for (int q = 0; q < kWaves; ++q) tot += sh.red_d[q], nz += sh.red_a[q];
             // forward_net.py:324 — sum(|x|) / count(|x| > 0)
             const float s0 = nanseen ? __uint_as_float(0x7FC00000u) : __fdiv_rn((float)tot, (float)(long long)nz);
-            z.sum = 0.0;
-            z.cnt_gt = 0ull;
-            z.cnt_le = 0ull;
+            dpl_octav_state z;
+            DPL_OCTAV_FRESH(z);
+            z.min_enc = me->min_enc;     // (the slices' atomics on the pair's state)
+            z.max_enc = me->max_enc;
+            z.nan_seen = me->nan_seen;
             z.unsigned_div = (fa.dynamic_sym && fabsf(gmn) < 1e-6f && !nanseen) ? 4.0f : 1.0f;
             z.n_elems = n_pair;
-            z.len[0] = 0u;
-            z.len[1] = 0u;
-            z.cur = 2u;
-            z.reserved = 0u;
             z.s = s0;
-            z.iters = 0u;
             z.done = (s0 != s0 || fa.max_iters <= 0) ? 1u : 0u;     // (NaN is a fixed point: finished)
+            // (DPL_OCTAV_RESTART_COMPACTION's two steps, kept apart here: a pair that is finished at s_0 stays in mode 2 and is
+            // not counted, and the count follows the state's store)
             z.mode = z.done ? 2u : 1u;
             *me = z;
             if (!z.done) atomicAdd(reinterpret_cast<unsigned long long*>(&ctl->cnt_le), 1ull);
@@ -948,21 +964,8 @@ __global__ void k_octav_tail_init(dpl_octav_state* st, int64_t n_pairs, uint32_t
     }
     if (i > n_pairs) return;  // slot n_pairs is the control block
     dpl_octav_state z;
-    z.sum = 0.0;
-    z.cnt_gt = 0;
-    z.cnt_le = 0;
-    z.min_enc = 0xFFFFFFFFu;
-    z.max_enc = 0u;
-    z.nan_seen = 0u;
-    z.done = 0u;
-    z.s = 0.0f;
-    z.unsigned_div = 1.0f;
-    z.iters = 0u;
-    z.mode = 2u;
-    z.n_elems = 0ull;
-    z.len[0] = 0u;
-    z.len[1] = 0u;
-    z.cur = 2u;
-    z.reserved = 0u;
+    DPL_OCTAV_FRESH(z);
     st[i] = z;
 }
+
+}  // namespace

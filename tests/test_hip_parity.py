@@ -857,6 +857,57 @@ def test_octav_tail_randomised_shapes_and_distributions(dev):
                 assert g[1] == x.min() and g[2] == x.max()
 
 
+WALK_EDGE_SIZES = [1279, 1280, 1281, 12287, 12288, 12289, 16384, 16385, 20480]
+
+
+def _walk_edge_inputs():
+    """-> (signed, unsigned): per size of WALK_EDGE_SIZES a [2, n] float32 array, |x| uniform in [0.05, 4) — every value non-zero
+    and inside the histogram window — with random signs; `unsigned` is |x| with one element of every pair set to 1e-7 (below the
+    window: |min| < 1e-6, what `dynamic_sym` looks for)."""
+    rng = np.random.default_rng(12288)
+    signed, unsigned = [], []
+    for n in WALK_EDGE_SIZES:
+        a = rng.uniform(0.05, 4.0, (2, n)).astype(np.float32)
+        a = np.clip(a, np.float32(0.05), np.nextafter(np.float32(4.0), np.float32(0.0)))    # (the float32 rounding of the draw)
+        signed.append(a * rng.choice(np.array([-1.0, 1.0], np.float32), (2, n)))
+        u = a.copy()
+        u[np.arange(2), rng.integers(0, n, 2)] = np.float32(1e-7)
+        unsigned.append(u)
+    return signed, unsigned
+
+
+def test_octav_tail_list_lengths_at_the_walk_paths_edges(dev):
+    """The exact-tail form with a list exactly as long as the sizes at which its walk takes another path: kFitCap = kSurvCap =
+    1280 values (a list that one wave's registers hold; the staging area of the compaction through LDS) and kTailVec x 1024 =
+    12288 (the rows resident in the workgroup's registers: beyond them kOver = 4 rows are streamed at a time) — one less, equal,
+    one more; 16384 / 16385 (the first streamed group full / a second one begun) and kSmallCap = 20480.  A pair of at most
+    kSmallCap elements lists its whole window, so a pair whose values are all non-zero and inside the window has a list as long
+    as itself; with `dynamic_sym` one value per pair lies below the window (what makes the minimum count as zero) and the list
+    is one shorter.  Cold and warm, against the numpy oracle; the control block says that exactly those values were listed and
+    that no pair left for the rescue or the compaction route: the walks under test produced the results."""
+    from dipoorlet_amd import _hip, ops
+    B, sizes = 2, WALK_EDGE_SIZES
+    signed, unsigned = _walk_edge_inputs()
+    for dyn, raw in ((False, signed), (True, unsigned)):
+        tensors = [torch.from_numpy(x).to(dev) for x in raw]
+        want = np.array([[O.octav_scale(x[b], O.octav_unsigned(x[b].min(), dyn)) for x in raw] for b in range(B)], np.float64)
+        assert np.isfinite(want).all()
+        listed = sum(int(np.count_nonzero(np.abs(x) >= np.float32(2.0 ** -18))) for x in raw)
+        assert listed == B * sum(sizes) - (B * len(sizes) if dyn else 0)
+        plan = ops.TensorSetPlan(sizes, B, dev)
+        states = torch.empty((plan.n_pairs + 1) * 80, dtype=torch.uint8, device=dev)
+        for call in ("cold", "warm"):
+            got = ops.octav_batch(plan, tensors, dyn, states, form="tail").cpu().numpy()
+            ctl = _hip.OctavState.from_buffer_copy(states.cpu().numpy()[-80:].tobytes())
+            assert ctl.sum == float(listed), (dyn, call, ctl.sum, listed)                   # every pair listed its whole window
+            assert int(ctl.len0) == 0 and int(ctl.cnt_le) == 0, (dyn, call, int(ctl.len0), int(ctl.cnt_le))
+            for t, n in enumerate(sizes):
+                for b in range(B):
+                    x = raw[t][b]
+                    assert _close(got[b, t, 0], want[b, t]), (dyn, call, n, b, got[b, t], want[b, t])
+                    assert got[b, t, 1] == x.min() and got[b, t, 2] == x.max(), (dyn, call, n, b)
+
+
 def test_octav_tail_thresholds_follow_the_images(dev, monkeypatch):
     """What the exact-tail form lists and how often it has to be rescued, over a run of batches through the pipeline: images
     alike (thresholds from the earlier batches: ~1 % listed, next to no rescues), then images that differ in scale by +-30 %
