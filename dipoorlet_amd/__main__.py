@@ -1,9 +1,9 @@
 """`python -m dipoorlet_amd -M model.onnx -I calib_dir -N 1024 -A hist -D trt` — the reference's CLI
-(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, and `--mx`, OCP Microscaling on MatMul / Gemm operands, are this project's additions).
+(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, and `--gptq`, Hessian-compensated weight rounding, are this project's additions).
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
-model, optional) -> weight transforms (--smooth, --bc, --we, --update_bn, --adaround, --brecq [--drop], --sparse) -> platform deploy file.
+model, optional) -> weight transforms (--smooth, --bc, --we, --update_bn, --adaround, --brecq [--drop], --sparse, --gptq) -> platform deploy file.
 Extra flags: --calib_batch, --resident_gb, --merge {allreduce,reference}, --skip_profiling, --timing_json.
 """
 import argparse
@@ -28,7 +28,7 @@ def build_parser():
     p.add_argument("-O", "--output_dir", help="output data path")
     p.add_argument("-N", "--data_num", help="num of calibration pics", type=int, required=True)
     for flag in ("--we", "--bc", "--update_bn", "--adaround", "--brecq", "--drop", "--savefp", "--stpu_wg",
-                 "--skip_prof_layer", "--slurm", "--mpirun", "--sparse", "--optim_transformer", "--smooth"):
+                 "--skip_prof_layer", "--slurm", "--mpirun", "--sparse", "--optim_transformer", "--smooth", "--gptq"):
         p.add_argument(flag, default=False, action="store_true")
     p.add_argument("-A", "--act_quant", choices=["minmax", "hist", "mse", "kl", "qmse"], default="mse",
                    help="minmax / hist: bit-exact clip ranges; mse (OCTAV): within 1e-5 * max(1, |ref|) of the reference's, repeating "
@@ -51,6 +51,13 @@ def build_parser():
                    help="(not in the reference; with -D ocp_fp8 only) OCP Microscaling on both operands of every MatMul / Gemm, constant "
                         "ones included: blocks of 32 along the reduction axis share a power-of-two scale taken from the data, the elements "
                         "are FP8 E4M3 (mxfp8) or FP4 E2M1 (mxfp4); every other node keeps the platform's static E4M3 scales")
+    p.add_argument("--gptq_block", type=int, default=128,
+                   help="--gptq (not in the reference; every platform, -D ocp_fp8 included): round every Conv (group 1) / Gemm weight column "
+                        "by column onto the platform's weight grid, pushing each column's rounding error onto the columns not yet rounded "
+                        "along the inverse Hessian of the layer's fake-quantised inputs (GPTQ); writes gptq.onnx.  --gptq_block: columns "
+                        "per kernel call, 1 .. 128")
+    p.add_argument("--gptq_damp", type=float, default=0.01,
+                   help="--gptq: damp * mean(diag H) is added to the Hessian's diagonal before it is factorised; > 0")
     p.add_argument("--pattern", choices=["unstruction", "nv24"], default="unstruction")
     p.add_argument("--model_type", choices=["unet"], default=None)
     p.add_argument("--quant_format", default="QDQ", type=str, choices=["QOP", "QDQ"])
@@ -79,6 +86,17 @@ def check_args(args):
     alpha = getattr(args, "smooth_alpha", 0.5)
     if not 0.0 <= alpha <= 1.0:      # (a NaN too)
         raise ValueError(f"--smooth_alpha must lie in [0, 1], got {alpha}")
+    if getattr(args, "gptq", False):
+        for flag in ("adaround", "brecq", "sparse"):
+            if getattr(args, flag, False):
+                raise ValueError(f"--gptq and --{flag} cannot be combined: two transforms would each decide how the weights are rounded")
+        if getattr(args, "mx", None):
+            raise ValueError(f"--gptq and --mx {args.mx} cannot be combined: block-scaled operands are not on a static grid (GPTQ on MX "
+                             "grids is not built)")
+        if not 1 <= getattr(args, "gptq_block", 128) <= 128:
+            raise ValueError(f"--gptq_block must lie in [1, 128], got {args.gptq_block}")
+        if not getattr(args, "gptq_damp", 0.01) > 0.0:      # (a NaN too)
+            raise ValueError(f"--gptq_damp must be positive, got {args.gptq_damp}")
     if getattr(args, "mx", None) and args.deploy != "ocp_fp8":
         raise ValueError(f"--mx {args.mx} is not supported with -D {args.deploy}: block-scaled MatMul / Gemm operands sit beside static "
                          "FP8 scales on every other node.  Supported: -D ocp_fp8")

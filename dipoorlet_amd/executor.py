@@ -211,6 +211,13 @@ def _auto_pad(node, x, kernel, strides, dilations):
     return beg + end
 
 
+def conv_padding(node, x, kernel, strides, dilations):
+    """What a Conv applies around x: (the symmetric per-axis padding, or None when begin and end differ; the F.pad list that applies
+    the ONNX pads — `pads`, or what `auto_pad` stands for — explicitly).  For callers that rebuild a convolution's input patches
+    (weight_transform/gptq.py)."""
+    return _pads_nd(_auto_pad(node, x, list(kernel), list(strides), list(dilations)), len(kernel))
+
+
 @op("Conv")
 def _conv(s, node, x, w, b=None):
     nd = w.dim() - 2

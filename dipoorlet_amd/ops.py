@@ -1129,6 +1129,71 @@ def fake_quant_mx(x, axis, elem, out=None, scales=None):
     return y
 
 
+GPTQ_FMT = {"int": _hip.GRID_UNIFORM, "e4m3": _hip.GRID_E4M3}     # include/dipoorlet_hip.h DPL_GRID_*
+GPTQ_MAX_BLOCK = _hip.GPTQ_MAX_BLOCK
+GptqGrid = collections.namedtuple("GptqGrid", "fmt scale zero_point qlo qhi", defaults=(None, 0, 0))
+GptqGrid.__doc__ = """The grid GPTQ rounds onto: fmt 'int' (scale fp32 [1] or [rows], zero_point int32 of the same length, qlo < qhi: the
+Q/DQ pair of fake_quant) or 'e4m3' (scale only: fake_quant_fp8)."""
+
+
+def gptq_block(w, c0, nb, u, grid, err=None):
+    """One block of GPTQ's column recursion, in place (dpl_gptq_block; tests/gptq_model.py gptq_block is the definition, matched
+    bit for bit): columns [c0, c0 + nb) of w (fp32 [rows, K], one output channel per row) are rounded onto `grid` one after the
+    other, each column's error e = (w - q) / u[c, c] going onto the block's later columns as w[:, k] -= e * u[c, k].  u: fp32
+    [K', K'] (K' >= c0 + nb), the upper Cholesky factor of the inverse Hessian.  -> err fp32 [rows, nb].  1 <= nb <= 128."""
+    _require_cuda(w, "w")
+    _require_cuda(u, "u")
+    if w.dim() != 2 or u.dim() != 2 or u.device != w.device:
+        raise _hip.DipoorletHipError("gptq_block: w and u must be matrices on one device")
+    if grid.fmt not in GPTQ_FMT:
+        raise _hip.DipoorletHipError(f"gptq_block: grid.fmt must be 'int' or 'e4m3', got {grid.fmt!r}")
+    rows = int(w.shape[0])
+    if int(c0) < 0 or int(c0) + int(nb) > int(u.shape[0]):       # (the C ABI checks the columns of w and u; it cannot see u's rows)
+        raise _hip.DipoorletHipError(f"gptq_block: rows [{c0}, {int(c0) + int(nb)}) lie outside u ({u.shape[0]} rows)")
+    scale = grid.scale.to(device=w.device, dtype=torch.float32).contiguous().reshape(-1)
+    zp = None
+    if grid.fmt == "int":
+        if grid.zero_point is None:
+            raise _hip.DipoorletHipError("gptq_block: the integer grid needs a zero point")
+        zp = grid.zero_point.to(device=w.device, dtype=torch.int32).contiguous().reshape(-1)
+        if zp.numel() != scale.numel():
+            raise _hip.DipoorletHipError("scale and zero_point lengths differ")
+    if err is None:
+        err = torch.empty((rows, max(int(nb), 0)), dtype=torch.float32, device=w.device)
+    else:
+        _require_cuda(err, "err")
+        if err.device != w.device or err.numel() != rows * int(nb):
+            raise _hip.DipoorletHipError("gptq_block: err must hold [rows, nb] elements on w's device")
+    _hip.check(_hip.lib().dpl_gptq_block(_ptr(w), rows, int(w.shape[1]), int(c0), int(nb), _ptr(u), int(u.shape[1]), _ptr(scale),
+                                         None if zp is None else _ptr(zp), scale.numel(), int(grid.qlo), int(grid.qhi),
+                                         GPTQ_FMT[grid.fmt], _ptr(err), _stream()), "dpl_gptq_block")
+    return err
+
+
+def gptq_quantize(w, u, grid, block=GPTQ_MAX_BLOCK):
+    """GPTQ over a whole layer (tests/gptq_model.py gptq_layer32): the blocks left to right through gptq_block, and between them
+    W[:, c0 + nb:] -= Err @ U[c0:c0 + nb, c0 + nb:], one fp32 GEMM of the BLAS library (the only step whose summation order is not
+    this library's).  w: fp32 [rows, K] (not modified), u: fp32 [K, K].  -> (the rounded weight, Err [rows, K])."""
+    _require_cuda(w, "w")
+    _require_cuda(u, "u")
+    if w.dim() != 2 or tuple(u.shape) != (w.shape[1], w.shape[1]):
+        raise _hip.DipoorletHipError("gptq_quantize: w must be [rows, K] and u [K, K]")
+    if not 1 <= int(block) <= GPTQ_MAX_BLOCK:
+        raise _hip.DipoorletHipError(f"gptq_quantize: block must be in [1, {GPTQ_MAX_BLOCK}]")
+    grid = grid._replace(scale=grid.scale.to(device=w.device, dtype=torch.float32),
+                         zero_point=None if grid.zero_point is None else grid.zero_point.to(device=w.device, dtype=torch.int32))
+    wq = w.clone()
+    K = int(w.shape[1])
+    err = torch.empty_like(wq)
+    for c0 in range(0, K, int(block)):
+        nb = min(int(block), K - c0)
+        e = gptq_block(wq, c0, nb, u, grid)
+        err[:, c0:c0 + nb] = e
+        if c0 + nb < K:
+            wq[:, c0 + nb:].addmm_(e, u[c0:c0 + nb, c0 + nb:], alpha=-1.0)
+    return wq, err
+
+
 class FakeQuantSet:
     """Fused QuantizeLinear -> DequantizeLinear over a WHOLE tensor set in one launch (dpl_fake_quant_items): for a caller that
     holds every tensor of a forward (the profiling flow's fp-vs-quantised comparison, quant_acti over a set) — one launch

@@ -17,6 +17,8 @@ Per tensor:
     dipoorlet::fake_quant_add_relu(Tensor x, Tensor x2, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor
     dipoorlet::fake_quant_fp8(Tensor x, Tensor scale, int axis) -> Tensor      the pair on the OCP FP8 E4M3 grid (ops.fake_quant_fp8)
     dipoorlet::fake_quant_mx(Tensor x, int axis, str elem) -> Tensor           the OCP Microscaling pair, 'mxfp8' / 'mxfp4', blocks of 32 along axis (ops.fake_quant_mx)
+    dipoorlet::gptq_block(Tensor(a!) w, int c0, int nb, Tensor u, Tensor scale, Tensor zero_point, int qlo, int qhi, str fmt) -> Tensor
+                                                               one block of GPTQ's column recursion in place on w; -> Err [rows, nb] (ops.gptq_block)
 Over every tensor of a batch of images in ONE launch — what the reference's loops over `ort_outputs` stand for
 (forward_net.py:220-235, 265-280, 314-340); xs[t] is tensor t of the batch, [B, ...] contiguous fp32:
     dipoorlet::minmax_batched(Tensor[] xs, Tensor(a!) mins, Tensor(b!) maxs) -> ()   running min / max per tensor, [T] fp32
@@ -325,6 +327,18 @@ def fake_quant_mx(x: torch.Tensor, axis: int, elem: str) -> torch.Tensor:
 @fake_quant_mx.register_fake
 def _(x, axis, elem):
     return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op("dipoorlet::gptq_block", mutates_args=("w",), device_types="cuda")
+def gptq_block(w: torch.Tensor, c0: int, nb: int, u: torch.Tensor, scale: torch.Tensor, zero_point: torch.Tensor, qlo: int, qhi: int,
+               fmt: str) -> torch.Tensor:
+    """fmt 'int' or 'e4m3' (zero_point, qlo, qhi are not read for 'e4m3'); w, u: contiguous fp32 matrices."""
+    return ops.gptq_block(w, c0, nb, u, ops.GptqGrid(fmt, scale, zero_point, qlo, qhi))
+
+
+@gptq_block.register_fake
+def _(w, c0, nb, u, scale, zero_point, qlo, qhi, fmt):
+    return w.new_empty((w.shape[0], nb), dtype=torch.float32)
 
 
 @torch.library.custom_op("dipoorlet::fake_quant_set", mutates_args=(), device_types="cuda")

@@ -1,0 +1,216 @@
+"""--gptq (not in the reference): GPTQ (Frantar et al., 2022) — Hessian-compensated weight rounding, one pass per layer, on whatever
+grid the platform's fake-quant nodes round weights to (an integer grid or OCP FP8 E4M3).  tests/gptq_model.py is the definition.
+
+The fake-quantised network is walked once, node-major, exactly as AdaRound's driver walks it (reconstruction.QuantWalk).  For every
+Conv (group 1, two spatial axes) and Gemm whose weight the graph fake-quantises:
+  * H = sum X^T X / rows over the node's fake-quantised input — a Gemm's input rows, a Conv's unfolded patches (pads applied
+    explicitly, so asymmetric ONNX pads are right) — fp32 GEMMs per slab summed in fp64, one fp64 SUM all-reduce per node;
+  * U = the upper Cholesky factor of (H + damp * mean(diag H) * I)^-1, on the host in fp64 (factor(): every rank computes the same
+    matrix, whatever device solver the torch build ships);
+  * ops.gptq_quantize rounds the weight column by column (csrc/gptq_kernels.hip) under the grid of the very get_qnode_by_param call
+    insert_fake_quant_node makes for that initializer: the graph's own Q/DQ node leaves the result unchanged;
+  * the new weight goes into the result, the fake-quantised graph and its session before the node runs, so everything downstream is
+    rounded against GPTQ's weights upstream.
+Profiling and deployment go on with the ORIGINAL ranges, as after AdaRound."""
+import json
+import os
+
+import numpy as np
+import torch
+import torch.distributed as dist
+import torch.nn.functional as F
+
+from .. import ops
+from ..executor import conv_padding
+from ..platform_settings import platform_setting_table
+from ..quantize import FP8_E4M3, get_qnode_by_param
+from ..utils import logger
+from .reconstruction import QuantWalk
+
+__all__ = ["gptq", "factor", "layer_grid"]
+
+GPTQ_NODE_TYPES = ("Conv", "Gemm")
+LEFT_NODE_TYPES = ("ConvTranspose",)       # counted in the log, left as they are
+_SLAB_BYTES = 256 << 20                    # bytes of X (fp32 rows) per GEMM; unfold holds a second copy of a slab while it is reshaped
+_SLAB_ROWS = 1 << 16                       # ... and rows of X per fp32 GEMM at the most: longer sums are split and added in fp64
+_DAMP_RETRIES = 3
+
+
+def factor(H, damp=0.01):
+    """H: fp64 CPU tensor [K, K] (not modified) -> (U fp64 [K, K] upper with (H')^-1 = U^T U, the damping used), H' = H with dead
+    columns' (H[j, j] == 0) diagonal set to 1 plus damp * mean(diag H') * I — or (None, damp) when the factorisation still fails
+    after the damping has been multiplied by 10 three times."""
+    H = H.detach().to(device="cpu", dtype=torch.float64).clone()
+    d = H.diagonal()
+    d[d == 0] = 1.0
+    mean_diag = float(d.mean())
+    for _ in range(_DAMP_RETRIES + 1):
+        Hd = H.clone()
+        Hd.diagonal().add_(damp * mean_diag)
+        L, info = torch.linalg.cholesky_ex(Hd)
+        if int(info) == 0 and bool(torch.isfinite(L).all()):
+            U, info = torch.linalg.cholesky_ex(torch.cholesky_inverse(L), upper=True)
+            if int(info) == 0 and bool(torch.isfinite(U).all()):
+                return U, damp
+        damp *= 10.0
+    return None, damp
+
+
+def layer_grid(graph, node, clip_val, args, dev):
+    """The grid the fake-quantised graph rounds `node`'s weight to -> (ops.GptqGrid, None) or (None, why not).  From the same
+    get_qnode_by_param call as quantize.insert_fake_quant_node's; qlo / qhi: the platform's bit width (what AdaRound clamps to)
+    inside the Q/DQ node's own saturation, so a weight on this grid passes the graph's node unchanged."""
+    name = node.input[1]
+    param = platform_setting_table[args.deploy]["qw_params"]
+    rng = [np.copy(clip_val[name][0]), np.copy(clip_val[name][1])]
+    qnode, q_min, q_max = get_qnode_by_param(param, name, graph.tensor_name_shape_map.get(name), rng, False)
+    if qnode is None or qnode.is_mx:
+        return None, "its weight has no static grid"
+    scale = torch.from_numpy(qnode.scale.copy()).to(dev)
+    if qnode.fmt == FP8_E4M3:
+        return ops.GptqGrid("e4m3", scale), None
+    zp = qnode.zero_point_as_stored()
+    lo, hi = np.asarray(q_min, np.int64).reshape(-1) + zp, np.asarray(q_max, np.int64).reshape(-1) + zp
+    if not (np.all(lo == lo[0]) and np.all(hi == hi[0])):
+        return None, "its channels do not share one integer range"
+    sat_lo, sat_hi = qnode.saturation()
+    return ops.GptqGrid("int", scale, torch.from_numpy(zp.astype(np.int32)).to(dev), max(int(lo[0]), sat_lo), min(int(hi[0]), sat_hi)), None
+
+
+def _why_left(node, weight):
+    """Why GPTQ does not touch `node` (None: it does)."""
+    if node.op_type == "Conv":
+        if int(node.attrs.get("group", 1)) != 1:
+            return "a grouped convolution"
+        if weight.ndim != 4:
+            return "not a convolution over two spatial axes"
+    elif node.attrs.get("transA", 0):
+        return "a Gemm with transA"
+    return None
+
+
+def input_rows(node, x, weight_shape):
+    """The rows X [n, K] of the product the node computes as X @ W^T, W = weight.reshape(C_out, K): a Gemm's input, a Conv's patches
+    in (C_in, kh, kw) order."""
+    if node.op_type == "Gemm":
+        return x.reshape(x.shape[0], -1)
+    kernel = list(weight_shape[2:])
+    strides = node.attrs.get("strides", [1, 1])
+    dil = node.attrs.get("dilations", [1, 1])
+    _, fpad = conv_padding(node, x, kernel, strides, dil)
+    if any(fpad):
+        x = F.pad(x, fpad)
+    cols = F.unfold(x, tuple(kernel), dilation=tuple(dil), padding=0, stride=tuple(strides))     # [B, K, L]
+    return cols.transpose(1, 2).reshape(-1, cols.shape[1])
+
+
+def rows_per_image(node, x, weight_shape):
+    """Rows of input_rows() one image contributes, from the shapes alone: 1 for a Gemm, the output positions of a Conv."""
+    if node.op_type == "Gemm":
+        return 1
+    kernel = list(weight_shape[2:])
+    strides = node.attrs.get("strides", [1, 1])
+    dil = node.attrs.get("dilations", [1, 1])
+    _, fpad = conv_padding(node, x, kernel, strides, dil)       # F.pad order: last axis first, (begin, end) per axis
+    n = 1
+    for ax in range(2):
+        size = x.shape[2 + ax] + fpad[2 * (1 - ax)] + fpad[2 * (1 - ax) + 1]
+        n *= (size - dil[ax] * (kernel[ax] - 1) - 1) // strides[ax] + 1
+    return n
+
+
+def hessian(node, chunks, weight_shape, K, dev):
+    """sum X^T X over this rank's chunks of the node's input, and the number of rows, in ONE fp64 device vector [K * K + 1] (what is
+    all-reduced).  A chunk is taken in slabs of whole images of at most _SLAB_BYTES of fp32 rows (and _SLAB_ROWS rows; one image
+    at the least)."""
+    acc = torch.zeros(K * K + 1, dtype=torch.float64, device=dev)
+    H = acc[:K * K].view(K, K)
+    for x in chunks:
+        per_image = max(1, rows_per_image(node, x, weight_shape))
+        step = max(1, min(_SLAB_ROWS, _SLAB_BYTES // (4 * K)) // per_image)
+        for i in range(0, x.shape[0], step):
+            X = input_rows(node, x[i:i + step], weight_shape)
+            if X.shape[1] != K or X.shape[0] != per_image * min(step, x.shape[0] - i):
+                raise ValueError(f"--gptq: {node.name}: input rows of shape {tuple(X.shape)}, expected {per_image} per image and {K} columns")
+            H += torch.matmul(X.t(), X).double()
+            acc[K * K] += X.shape[0]
+    return acc
+
+
+def _objective(wq, w, H):
+    d = (wq - w).double()
+    return float(((d @ H) * d).sum())
+
+
+def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
+    """-> (the graph with GPTQ's weights — rank 0 saves it as gptq.onnx —, the per-layer report: a list of {node, rows, cols, damp,
+    objective_nearest, objective_gptq, kept}); objective = tr((Wq - W) H (Wq - W)^T) under the layer's own H; `kept`: 'gptq', or
+    'nearest' where the factorisation failed (objective_gptq is None; the weight is left as it is: the graph's Q/DQ node rounds it
+    to nearest).  Rank 0 also writes the report, and the nodes left as they are with the reason, to gptq_report.json."""
+    walk = QuantWalk(graph_ori, graph, act_clip_val, weight_clip_val, args, with_fp=False)
+    graph_new, graph_q, qf, dev, rank = walk.graph_new, walk.graph_q, walk.qf, walk.dev, walk.rank
+    skip = set(getattr(args, "skip_layers", None) or ())
+    block = int(getattr(args, "gptq_block", ops.GPTQ_MAX_BLOCK) or ops.GPTQ_MAX_BLOCK)
+    damp0 = float(getattr(args, "gptq_damp", 0.01) or 0.01)
+    ori_nodes = {n.name: n for n in graph.graph.node}
+    report, left = [], []
+    with torch.no_grad():
+        for node in graph_q.graph.node:
+            ori = ori_nodes.get(node.name)
+            if ori is None or ori.op_type not in GPTQ_NODE_TYPES + LEFT_NODE_TYPES:
+                qf.run(node)
+                continue
+            wname = ori.input[1]
+            weight = graph_new.get_initializer(wname) if len(ori.input) > 1 and wname in graph_new.initializer else None
+            why = ("in --skip_layers" if node.name in skip else "a ConvTranspose" if ori.op_type in LEFT_NODE_TYPES else
+                   "its weight is not a constant" if weight is None else
+                   "the graph does not fake-quantise its weight" if node.input[1] == wname else _why_left(ori, weight))
+            grid = None
+            if why is None:
+                grid, why = layer_grid(graph_new, ori, walk.clip_val, args, dev)
+            rows_first = ori.op_type == "Conv" or bool(ori.attrs.get("transB", 0))
+            if why is None and grid.scale.numel() > 1 and not (rows_first and grid.scale.numel() == weight.shape[0]):
+                why = "its per-channel scales do not run along the output channels"
+            if why is not None:
+                left.append((node.name, why))
+                qf.run(node)
+                continue
+            w_host = np.ascontiguousarray(weight, dtype=np.float32)
+            w2d = torch.from_numpy(w_host.reshape(w_host.shape[0], -1) if rows_first else np.ascontiguousarray(w_host.T)).to(dev)
+            R, K = w2d.shape
+            acc = hessian(ori, qf.env[node.input[0]], w_host.shape, K, dev)
+            if walk.world > 1:
+                dist.all_reduce(acc)
+            H = acc[:K * K].view(K, K) / acc[K * K]
+            U, damp = factor(H.cpu(), damp0)
+            if grid.fmt == "int":
+                w_near = ops.fake_quant(w2d, grid.scale, grid.zero_point, grid.qlo, grid.qhi, axis=0 if grid.scale.numel() > 1 else None)
+            else:
+                w_near = ops.fake_quant_fp8(w2d, grid.scale, axis=0 if grid.scale.numel() > 1 else None)
+            entry = {"node": node.name, "rows": int(R), "cols": int(K), "damp": damp, "kept": "nearest",
+                     "objective_nearest": _objective(w_near, w2d, H), "objective_gptq": None}
+            if U is None:       # the only fall-back: the weight stays as it is, the graph's Q/DQ node rounds it to nearest
+                logger.warning("--gptq: the Hessian of %s could not be factorised (damping up to %g): left at round-to-nearest", node.name, damp)
+            else:
+                wq, _ = ops.gptq_quantize(w2d, U.to(torch.float32).contiguous().to(dev), grid, block)
+                entry.update(objective_gptq=_objective(wq, w2d, H), kept="gptq")
+                if entry["objective_gptq"] > entry["objective_nearest"]:       # (reported, not acted on)
+                    logger.warning("--gptq: %s: the compensated rounding did not lower the objective (%g against %g)", node.name,
+                                   entry["objective_gptq"], entry["objective_nearest"])
+                w_new = wq if rows_first else wq.t().contiguous()
+                walk.set_weight(wname, w_new.reshape(w_host.shape))
+            report.append(entry)
+            if rank == 0:
+                logger.info("GPTQ for: {} [{} x {}] objective nearest {:.6g} -> gptq {} ({})".format(
+                    node.name, R, K, entry["objective_nearest"],
+                    "-" if entry["objective_gptq"] is None else "{:.6g}".format(entry["objective_gptq"]), entry["kept"]))
+            del acc, H, U, w_near
+            qf.run(node)
+    if rank == 0:
+        logger.info("GPTQ: {} layer(s) rounded, {} left as they are{}".format(
+            sum(e["kept"] == "gptq" for e in report), len(left) + sum(e["kept"] != "gptq" for e in report),
+            "".join("\n  {}: {}".format(n, w) for n, w in left)))
+        if getattr(args, "output_dir", None):
+            with open(os.path.join(args.output_dir, "gptq_report.json"), "w") as f:
+                json.dump({"layers": report, "left": [{"node": n, "why": w} for n, w in left]}, f, indent=1)
+    return walk.finish("gptq"), report

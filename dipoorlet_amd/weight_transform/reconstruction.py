@@ -193,28 +193,55 @@ def _build_sparse_layer(graph, graph_new, node, clip_val, args, dev):
     return SparseQLayer(node, weight, bias, qw_tensor, follow_relu(graph, node), sparse_info)
 
 
+class QuantWalk:
+    """The node-major walk of the fake-quantised network that the weight-rounding transforms share (reconstruct() here, gptq() in
+    gptq.py): this rank's shard of the calibration images, a copy of `graph` that receives the new weights (graph_new), its
+    fake-quantised form under the given ranges (graph_q) with a session (s_q) and a Frontier (qf) over the shard, and — with_fp —
+    the full-precision activations of graph_ori (fp_cache).  A transform visits graph_q's nodes in order, writes a node's new
+    weight with set_weight() and runs the node with qf.run(), so everything downstream sees the new weights."""
+
+    def __init__(self, graph_ori, graph, act_clip_val, weight_clip_val, args, with_fp=True):
+        if dist.is_available() and dist.is_initialized():
+            dist.barrier()
+        self.clip_val = {k: [np.copy(v[0]), np.copy(v[1])] for k, v in {**act_clip_val, **weight_clip_val}.items()}
+        self.graph_new = ONNXGraph()
+        self.graph_new.copy_from(graph)
+        self.args = args
+        self.rank, self.world = _rank(), _world()
+        self.num_per_rank = args.data_num // self.world
+        st, ed = self.rank * self.num_per_rank, self.rank * self.num_per_rank + self.num_per_rank
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+        with torch.no_grad():
+            self.fp_cache = ActivationCache(graph_ori, args, st, ed) if with_fp else None
+            self.graph_q, _ = quant_graph(self.graph_new, {k: [np.copy(v[0]), np.copy(v[1])] for k, v in self.clip_val.items()}, args)
+            self.s_q = GraphSession(self.graph_q, device=self.dev)
+            self.bounds, inputs = load_chunks(graph_ori, args, st, ed, self.dev)
+            self.qf = Frontier(self.s_q, self.bounds, inputs)
+
+    def set_weight(self, name, w_new):
+        """w_new (device tensor) becomes initializer `name` of the result, of the fake-quantised graph and of its session."""
+        update_weight(self.graph_new, w_new.cpu().numpy(), name)
+        update_weight(self.graph_q, w_new.cpu().numpy(), name)
+        self.s_q.set_const(name, w_new)
+
+    def finish(self, save_name):
+        """-> the graph with the new weights; rank 0 saves it as <save_name>.onnx."""
+        self.graph_new.update_model()
+        if self.rank == 0 and getattr(self.args, "output_dir", None):
+            self.graph_new.output_dir = self.args.output_dir
+            self.graph_new.save_onnx_model(save_name)
+        return self.graph_new
+
+
 def reconstruct(graph_ori, graph, act_clip_val, weight_clip_val, args, blockwise, save_name, sparse=False):
     """Shared driver of adaround(), brecq() and sparse_quant(): returns the graph with the learned weights."""
-    if dist.is_available() and dist.is_initialized():
-        dist.barrier()
-    clip_val = {k: [np.copy(v[0]), np.copy(v[1])] for k, v in {**act_clip_val, **weight_clip_val}.items()}
-    graph_new = ONNXGraph()
-    graph_new.copy_from(graph)
-    rank, world = _rank(), _world()
-    num_per_rank = args.data_num // world
-    st, ed = rank * num_per_rank, rank * num_per_rank + num_per_rank
-    dev = torch.device("cuda", torch.cuda.current_device())
+    walk = QuantWalk(graph_ori, graph, act_clip_val, weight_clip_val, args)
+    clip_val, graph_new, graph_q, qf, fp_cache = walk.clip_val, walk.graph_new, walk.graph_q, walk.qf, walk.fp_cache
+    rank, num_per_rank, dev = walk.rank, walk.num_per_rank, walk.dev
     skip = getattr(args, "skip_layers", []) or []
     drop = bool(getattr(args, "drop", False)) and blockwise
     with_acti = bool(getattr(args, "acti_quant", False))
     head = "sparse_quant" if sparse else (("Qdrop" if drop else "Brecq") if blockwise else "Adaround")
-
-    with torch.no_grad():
-        fp_cache = ActivationCache(graph_ori, args, st, ed)
-        graph_q, _ = quant_graph(graph_new, {k: [np.copy(v[0]), np.copy(v[1])] for k, v in clip_val.items()}, args)
-        s_q = GraphSession(graph_q, device=dev)
-        bounds, inputs = load_chunks(graph_ori, args, st, ed, dev)
-        qf = Frontier(s_q, bounds, inputs)
     ori_nodes = {n.name: n for n in graph.graph.node}
     learnable = [n.name for n in graph_ori.graph.node if n.op_type in LEARNABLE_LAYER_TYPES and n.name not in skip]
     already = set()
@@ -254,15 +281,8 @@ def reconstruct(graph_ori, graph, act_clip_val, weight_clip_val, args, blockwise
                                log_every=100 if blockwise else 50, log_head="")
             with torch.no_grad():
                 for b, layer in zip(block, layers):
-                    w_new = layer.new_weight()
-                    update_weight(graph_new, w_new.cpu().numpy(), b.input[1])
-                    update_weight(graph_q, w_new.cpu().numpy(), b.input[1])
-                    s_q.set_const(b.input[1], w_new)
+                    walk.set_weight(b.input[1], layer.new_weight())
             del layers, q_in, fp_in, fp_out
         with torch.no_grad():
             qf.run(node)
-    graph_new.update_model()
-    if rank == 0 and getattr(args, "output_dir", None):
-        graph_new.output_dir = args.output_dir
-        graph_new.save_onnx_model(save_name)
-    return graph_new
+    return walk.finish(save_name)

@@ -10,6 +10,7 @@ from ..utils import load_clip_val, logger, reduce_clip_val, save_clip_val
 from .adaround import adaround
 from .bias_correction import bias_correction
 from .brecq import brecq
+from .gptq import gptq
 from .smooth import smooth_quant
 from .sparse_quant import sparse_quant
 from .update_bn import update_bn
@@ -86,4 +87,8 @@ def weight_calibration(onnx_graph, act_clip_val, weight_clip_val, args):
     if getattr(args, "brecq", False):      # :59-64
         args.acti_quant = bool(getattr(args, "drop", False))
         graph_after_wt = brecq(onnx_graph, graph_after_wt, act_clip_val, weight_clip_val, args)
+    if getattr(args, "gptq", False):       # (not in the reference) where AdaRound runs, instead of it; the ORIGINAL ranges stay
+        if dist.get_rank() == 0:
+            logger.info("Weight transform: GPTQ...")
+        graph_after_wt, _ = gptq(onnx_graph, graph_after_wt, act_clip_val, weight_clip_val, args)
     return graph_after_wt, onnx_graph, act_clip_val, weight_clip_val

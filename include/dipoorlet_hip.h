@@ -25,12 +25,13 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 27 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 28 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
                               25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
                               26: dpl_colwise_absmax (per-channel running max |x| of a channels-last activation: --smooth);
-                              27: dpl_fake_quant_mx (the OCP Microscaling Q/DQ pair, MXFP8 / MXFP4: --mx) */
+                              27: dpl_fake_quant_mx (the OCP Microscaling Q/DQ pair, MXFP8 / MXFP4: --mx);
+                              28: dpl_gptq_block (sequential quantise-and-compensate of a block of weight columns: --gptq) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -422,6 +423,22 @@ int dpl_fake_quant_fp8_items(const dpl_work_item* d_items, int64_t n_items, cons
 #define DPL_MX_E2M1 1
 int dpl_fake_quant_mx(int32_t elem, const float* d_x, float* d_y, uint64_t outer, uint64_t k, uint64_t inner,
                       uint8_t* d_scales_or_null, dpl_stream_t s);
+
+/* ---- GPTQ (Frantar et al., 2022; beyond the reference; --gptq): quantise nb consecutive columns of a weight matrix one after
+ *      the other and push each column's rounding error onto the block's columns not yet rounded.  d_w: [rows, ldw] fp32 row-major,
+ *      one output channel per row, updated IN PLACE in columns [c0, c0 + nb) only; d_u: [*, ldu] fp32 row-major, the upper Cholesky
+ *      factor of the inverse Hessian (H^-1 = U^T U), read at rows and columns [c0, c0 + nb) only; d_err: [rows, nb] fp32.
+ *      For j = 0 .. nb - 1, c = c0 + j, every operation a single fp32 operation (no FMA contraction), per row r:
+ *        q = Q(w[r, c]);  e = (w[r, c] - q) / u[c, c];  w[r, c] = q;  err[r, j] = e;
+ *        w[r, c0 + k] = w[r, c0 + k] - e * u[c, c0 + k]      for k = j + 1 .. nb - 1
+ *      Q is the element quantiser of the Q/DQ pair above under scale[ch] (and zero_point[ch], qlo, qhi), ch = r when n_channels ==
+ *      rows, 0 when n_channels == 1: fmt DPL_GRID_UNIFORM the integer grid of dpl_fake_quant (qlo < qhi), DPL_GRID_E4M3 the FP8 grid
+ *      of dpl_fake_quant_fp8 (d_zero_point may be null; qlo, qhi ignored).  No reduction anywhere: the result is bit-exact against
+ *      tests/gptq_model.py gptq_block whatever the launch geometry.  1 <= nb <= DPL_GPTQ_MAX_BLOCK, 0 <= c0, c0 + nb <= ldw and
+ *      <= ldu; rows <= 0 is a no-op.  A refused call (-2) launches nothing. */
+#define DPL_GPTQ_MAX_BLOCK 128
+int dpl_gptq_block(float* d_w, int64_t rows, int64_t ldw, int64_t c0, int64_t nb, const float* d_u, int64_t ldu, const float* d_scale,
+                   const int32_t* d_zero_point, int64_t n_channels, int32_t qlo, int32_t qhi, int32_t fmt, float* d_err, dpl_stream_t s);
 
 /* ---- cosine-similarity partial sums (utils.py:273-278): d_acc[slot*3 + {0,1,2}] += sum(a*b), sum(a*a),
  *      sum(b*b) in fp64. */
