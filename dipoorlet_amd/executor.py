@@ -182,6 +182,23 @@ def _floats(v):
     return list(known) if known is not None else [float(x) for x in v.reshape(-1).tolist()]
 
 
+def _opset(s):
+    """The default-domain opset of the graph a session runs (13 for a bare call without a session)."""
+    graph = getattr(s, "graph", None)
+    return int(getattr(graph, "opset", None).get("", 13)) if graph is not None and getattr(graph, "opset", None) else 13
+
+
+_HOST_VECTORS = {}     # (key, device) -> device tensors built from host arithmetic: Resize / Pad index vectors, pool window counts
+
+
+def _host_vector(key, device, build):
+    """A small device tensor whose values the host knows (build() -> numpy), uploaded once per (key, device)."""
+    t = _HOST_VECTORS.get((key, device))
+    if t is None:
+        t = _HOST_VECTORS[(key, device)] = torch.from_numpy(np.ascontiguousarray(build())).to(device)
+    return t
+
+
 def _pads_nd(pads, nd):
     """ONNX [b1..bn, e1..en] -> (symmetric tuple or None, F.pad list)."""
     pads = list(pads) if pads else [0] * (2 * nd)
@@ -232,17 +249,53 @@ def _conv(s, node, x, w, b=None):
     return fn(x, w, b, tuple(strides), sym, tuple(dil), int(node.attrs.get("group", 1)))
 
 
+def convt_pads(node, size, kernel):
+    """The ONNX [b1..bn, e1..en] crop of a ConvTranspose over spatial input `size`: the `pads` attribute, or what `output_shape` /
+    `auto_pad` = SAME_* stand for — total = full - output_shape per axis (full = stride (in - 1) + output_padding + (k - 1) dil + 1,
+    output_shape = in * stride under SAME_*), begin = total // 2 under SAME_UPPER and total - total // 2 otherwise."""
+    nd = len(kernel)
+    strides = node.attrs.get("strides", [1] * nd)
+    dil = node.attrs.get("dilations", [1] * nd)
+    opad = node.attrs.get("output_padding", [0] * nd)
+    ap = node.attrs.get("auto_pad", "NOTSET")
+    want = node.attrs.get("output_shape")
+    if want:
+        want = list(want)[-nd:]
+    elif ap in ("SAME_UPPER", "SAME_LOWER"):
+        want = [size[i] * strides[i] for i in range(nd)]
+    elif ap == "VALID":
+        return [0] * (2 * nd)
+    else:
+        pads = list(node.attrs.get("pads") or [0] * (2 * nd))
+        if min(pads) < 0:
+            raise NotImplementedError(f"ConvTranspose: negative pads {pads}")
+        return pads
+    beg, end = [], []
+    for i in range(nd):
+        total = strides[i] * (size[i] - 1) + opad[i] + (kernel[i] - 1) * dil[i] + 1 - want[i]
+        if total < 0:
+            raise NotImplementedError(f"ConvTranspose: output_shape {want} is larger than the full output on axis {i}")
+        lo = total // 2 if ap == "SAME_UPPER" else total - total // 2
+        beg.append(lo)
+        end.append(total - lo)
+    return beg + end
+
+
 @op("ConvTranspose")
 def _convt(s, node, x, w, b=None):
     nd = w.dim() - 2
     strides = node.attrs.get("strides", [1] * nd)
     dil = node.attrs.get("dilations", [1] * nd)
-    sym, _ = _pads_nd(node.attrs.get("pads"), nd)
-    if sym is None:
-        raise NotImplementedError("ConvTranspose with asymmetric pads")
+    pads = convt_pads(node, list(x.shape[2:]), list(w.shape[2:]))
+    sym = tuple(min(lo, hi) for lo, hi in zip(pads[:nd], pads[nd:]))       # the library crops this much on both sides
     fn = {1: F.conv_transpose1d, 2: F.conv_transpose2d, 3: F.conv_transpose3d}[nd]
-    return fn(x, w, b, tuple(strides), sym, tuple(node.attrs.get("output_padding", [0] * nd)),
-              int(node.attrs.get("group", 1)), tuple(dil))
+    y = fn(x, w, b, tuple(strides), sym, tuple(node.attrs.get("output_padding", [0] * nd)),
+           int(node.attrs.get("group", 1)), tuple(dil))
+    for i in range(nd):     # asymmetric pads: the rest of the longer side is cropped here
+        lo, hi = pads[i] - sym[i], pads[nd + i] - sym[i]
+        if lo or hi:
+            y = y.narrow(2 + i, lo, y.shape[2 + i] - lo - hi)
+    return y
 
 
 @op("Relu")
@@ -284,6 +337,8 @@ def _hswish(s, node, x):
 def _clip(s, node, x, lo=None, hi=None):
     lo = node.attrs.get("min") if lo is None else _floats(lo)[0]
     hi = node.attrs.get("max") if hi is None else _floats(hi)[0]
+    if lo is None and hi is None:       # (both bounds are optional; torch.clamp wants one)
+        return x
     return torch.clamp(x, min=lo, max=hi)
 
 
@@ -303,7 +358,12 @@ _OPS["Eltwise"] = _OPS["Add"]
 
 @op("Softmax")
 def _softmax(s, node, x):
-    return torch.softmax(x, int(node.attrs.get("axis", -1)))
+    if _opset(s) >= 13:
+        return torch.softmax(x, int(node.attrs.get("axis", -1)))
+    # before opset 13: the tensor is flattened to 2-D at `axis` (default 1) and every row is normalised
+    ax = int(node.attrs.get("axis", 1))
+    ax = ax + x.dim() if ax < 0 else ax
+    return torch.softmax(x.reshape(int(np.prod(x.shape[:ax])) if ax > 0 else 1, -1), 1).reshape(x.shape)
 
 
 def _pool_args(node, x):
@@ -315,29 +375,74 @@ def _pool_args(node, x):
     return k, nd, strides, dil, pads
 
 
+def pool_len(size, k, stride, dil, pb, pe, ceil):
+    """ONNX pooled length of one axis; in ceil mode a last window that starts at or beyond the input and its begin padding
+    does not exist."""
+    num = size + pb + pe - dil * (k - 1) - 1
+    o = (-(-num // stride) if ceil else num // stride) + 1
+    if ceil and (o - 1) * stride >= size + pb:
+        o -= 1
+    return o
+
+
+def _pool_trim(y, x, node, k, nd, strides, dil, pads):
+    """y pooled from an x that was padded explicitly (asymmetric pads): in ceil mode the library, which takes the padding for
+    input, keeps a last window that starts inside the END padding; ONNX has no such window."""
+    if node.attrs.get("ceil_mode", 0):
+        for i in range(nd):
+            o = pool_len(x.shape[2 + i], k[i], strides[i], dil[i], pads[i], pads[nd + i], True)
+            if o != y.shape[2 + i]:
+                y = y.narrow(2 + i, 0, o)
+    return y
+
+
 @op("MaxPool")
 def _maxpool(s, node, x):
     k, nd, strides, dil, pads = _pool_args(node, x)
     sym, fpad = _pads_nd(pads, nd)
-    if sym is None:
-        x = F.pad(x, fpad, value=float("-inf"))
-        sym = (0,) * nd
     fn = {1: F.max_pool1d, 2: F.max_pool2d, 3: F.max_pool3d}[nd]
+    if sym is None:
+        y = fn(F.pad(x, fpad, value=float("-inf")), tuple(k), tuple(strides), (0,) * nd, tuple(dil), bool(node.attrs.get("ceil_mode", 0)))
+        return _pool_trim(y, x, node, k, nd, strides, dil, pads)
     return fn(x, tuple(k), tuple(strides), sym, tuple(dil), bool(node.attrs.get("ceil_mode", 0)))
+
+
+def _window_counts(size, k, stride, pb, pe, ceil):
+    """How many cells of each AveragePool window lie inside the input (count_include_pad = 0), per output position of one axis."""
+    n = pool_len(size, k, stride, 1, pb, pe, ceil)
+    return [min(o * stride - pb + k, size) - max(o * stride - pb, 0) for o in range(n)]
 
 
 @op("AveragePool")
 def _avgpool(s, node, x):
     k, nd, strides, dil, pads = _pool_args(node, x)
+    if any(d != 1 for d in dil):
+        raise NotImplementedError(f"AveragePool: dilations {list(dil)}")
     sym, fpad = _pads_nd(pads, nd)
     cip = bool(node.attrs.get("count_include_pad", 0))
-    if sym is None:
-        if not cip:
-            raise NotImplementedError("AveragePool: asymmetric pads with count_include_pad=0")
-        x = F.pad(x, fpad)
-        sym = (0,) * nd
+    ceil = bool(node.attrs.get("ceil_mode", 0))
     fn = {1: F.avg_pool1d, 2: F.avg_pool2d, 3: F.avg_pool3d}[nd]
-    return fn(x, tuple(k), tuple(strides), sym, bool(node.attrs.get("ceil_mode", 0)), cip)
+    if sym is not None:
+        return fn(x, tuple(k), tuple(strides), sym, ceil, cip)
+    if cip:     # explicit padding counts as input; what ceil mode adds beyond it does not (the library's rule for a padded input)
+        return _pool_trim(fn(F.pad(x, fpad), tuple(k), tuple(strides), (0,) * nd, ceil, True), x, node, k, nd, strides, dil, pads)
+    # asymmetric pads, count_include_pad = 0 (auto_pad = SAME_* on an even size): window SUMS over the zero-padded input, divided
+    # by the number of window cells inside the input (host arithmetic, uploaded once per configuration)
+    xp = F.pad(x, fpad)
+    if nd == 1:     # (avg_pool1d has no divisor_override)
+        y = F.avg_pool2d(xp.unsqueeze(2), (1, k[0]), (1, strides[0]), 0, ceil, True, divisor_override=1).squeeze(2)
+    else:
+        y = fn(xp, tuple(k), tuple(strides), (0,) * nd, ceil, True, divisor_override=1)
+    y = _pool_trim(y, x, node, k, nd, strides, dil, pads)
+    size = tuple(x.shape[2:])
+
+    def counts():
+        c = np.ones((), np.float32)
+        for i in range(nd):
+            c = np.multiply.outer(c, np.asarray(_window_counts(size[i], k[i], strides[i], pads[i], pads[nd + i], ceil), np.float32))
+        return c
+
+    return y / _host_vector(("avg_count", size, tuple(k), tuple(strides), tuple(pads), ceil), x.device, counts)
 
 
 @op("GlobalAveragePool")
@@ -429,13 +534,23 @@ def _concat(s, node, *xs):
     return torch.cat(list(xs), ax)
 
 
+def split_sizes(node, dim):
+    """Split without explicit sizes: `num_outputs` (opset 18; before it, the number of outputs) chunks of ceil(dim / n), the last
+    one smaller when n does not divide dim."""
+    n = int(node.attrs.get("num_outputs", len(node.output)))
+    chunk = -(-dim // n)
+    last = dim - chunk * (n - 1)
+    if last < 0:
+        raise ValueError(f"Split: {n} outputs from an axis of {dim}")
+    return [chunk] * (n - 1) + [last]
+
+
 @op("Split")
 def _split(s, node, x, split=None):
     ax = int(node.attrs.get("axis", 0))
     sizes = _ints(split) if split is not None else node.attrs.get("split")
     if sizes is None:
-        n = len(node.output)
-        sizes = [x.shape[ax] // n] * n
+        sizes = split_sizes(node, x.shape[ax])
     return list(torch.split(x, sizes, ax))
 
 
@@ -463,9 +578,13 @@ def _slice(s, node, x, starts=None, ends=None, axes=None, steps=None):
 @op("Gather")
 def _gather(s, node, x, idx):
     ax = int(node.attrs.get("axis", 0))
+    ax = ax + x.dim() if ax < 0 else ax
     if idx.dim() == 0:
         return x.select(ax, _ints(idx)[0])
+    known = getattr(idx, "_dpl_ints", None)
     idx = idx.long()
+    if known is None or min(known, default=0) < 0:     # ONNX: index i < 0 means i + dim (a device op: no read-back)
+        idx = torch.where(idx < 0, idx + x.shape[ax], idx)
     return torch.index_select(x, ax, idx.reshape(-1)).reshape(x.shape[:ax] + tuple(idx.shape) + x.shape[ax + 1:])
 
 
@@ -498,7 +617,9 @@ def _reduce(fn):
     def run(s, node, x, axes=None):
         ax = _axes(node, axes)
         keep = bool(node.attrs.get("keepdims", 1))
-        if ax is None:
+        if ax is None or len(ax) == 0:      # absent or empty axes: everything, or — noop_with_empty_axes = 1 — nothing
+            if node.attrs.get("noop_with_empty_axes", 0):
+                return x
             ax = list(range(x.dim()))
         return fn(x, tuple(ax), keep)
     return run
@@ -570,25 +691,151 @@ def _equal(s, node, a, b):
     return a == b
 
 
+def pad_amounts(pads, axes, nd):
+    """ONNX pads [b1..bn, e1..en] over the axes `axes` (opset 18; None: every axis; negative axes count from the end) as
+    per-axis (begin, end) lists over all nd axes."""
+    pads = [int(p) for p in pads]
+    axes = list(range(nd)) if axes is None else [a + nd if a < 0 else a for a in axes]
+    if len(pads) != 2 * len(axes):
+        raise ValueError(f"Pad: {len(pads)} pads for {len(axes)} axes")
+    beg, end = [0] * nd, [0] * nd
+    for j, a in enumerate(axes):
+        beg[a], end[a] = pads[j], pads[len(axes) + j]
+    return beg, end
+
+
+def _pad_index(n, b, e, mode):
+    """Source index of every position of an axis of n padded by (b, e) (negative: cropped) in mode 'edge' or 'reflect'."""
+    pos = np.arange(-b, n + e, dtype=np.int64)
+    if mode == "edge":
+        return np.clip(pos, 0, n - 1)
+    if n == 1:
+        raise ValueError("Pad: mode=reflect on an axis of one element")
+    period = 2 * (n - 1)
+    pos = np.mod(pos, period)
+    return np.where(pos >= n, period - pos, pos)
+
+
 @op("Pad")
 def _pad(s, node, x, pads=None, value=None, axes=None):
     pads = _ints(pads) if pads is not None else node.attrs["pads"]
     nd = x.dim()
-    _, fpad = _pads_nd(pads, nd)
+    beg, end = pad_amounts(pads, _ints(axes) if axes is not None else None, nd)
     mode = node.attrs.get("mode", "constant")
-    v = _floats(value)[0] if value is not None else float(node.attrs.get("value", 0.0))
-    return F.pad(x, fpad, mode=mode, value=v) if mode == "constant" else F.pad(x, fpad, mode=mode)
+    if mode == "constant":
+        v = _floats(value)[0] if value is not None else float(node.attrs.get("value", 0.0))
+        first = next((a for a in range(nd) if beg[a] or end[a]), nd)      # (leading axes without pads stay out of the list)
+        fpad = []
+        for a in range(nd - 1, first - 1, -1):
+            fpad += [beg[a], end[a]]
+        return F.pad(x, fpad, value=v) if fpad else x
+    if mode not in ("edge", "reflect"):
+        raise NotImplementedError(f"Pad: mode={mode}")
+    for a in range(nd):     # a selection along each padded axis, on any axis (index vectors from the host, uploaded once)
+        if beg[a] or end[a]:
+            n, b, e = x.shape[a], beg[a], end[a]
+            x = torch.index_select(x, a, _host_vector(("pad", n, b, e, mode), x.device, lambda: _pad_index(n, b, e, mode)))
+    return x
+
+
+def _resize_coords(n_in, n_out, scale, coord):
+    """x_orig (fp64) of every output position of one axis."""
+    x = np.arange(n_out, dtype=np.float64)
+    if coord == "asymmetric":
+        return x / scale
+    if coord == "align_corners":
+        return x * (n_in - 1) / (n_out - 1) if n_out > 1 else np.zeros(n_out)
+    if coord == "pytorch_half_pixel" and n_out == 1:
+        return np.zeros(n_out)
+    return (x + 0.5) / scale - 0.5          # half_pixel
+
+
+def _resize_nearest(n_in, n_out, scale, coord, nearest):
+    xo = _resize_coords(n_in, n_out, scale, coord)
+    i = {"round_prefer_floor": lambda v: np.ceil(v - 0.5), "round_prefer_ceil": lambda v: np.floor(v + 0.5),
+         "floor": np.floor, "ceil": np.ceil}[nearest](xo)
+    return np.clip(i, 0, n_in - 1).astype(np.int64)
+
+
+def _resize_linear(n_in, n_out, scale, coord):
+    xo = np.clip(_resize_coords(n_in, n_out, scale, coord), 0, n_in - 1)
+    i0 = np.floor(xo)
+    return i0.astype(np.int64), np.minimum(i0 + 1, n_in - 1).astype(np.int64), xo - i0
+
+
+_RESIZE_COORDS = ("half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric")
+_RESIZE_NEAREST = ("round_prefer_floor", "round_prefer_ceil", "floor", "ceil")
+
+
+def resize_plan(node, opset, shape, scales, sizes):
+    """(mode, coordinate mode, nearest mode, [(axis, out, scale)] of the axes that change) of a Resize / Upsample node: what its
+    attributes mean at `opset`.  Upsample (7 - 9) and Resize-10 know asymmetric coordinates and floor only; from opset 11 the
+    defaults are half_pixel and round_prefer_floor.  scales / sizes: host values (None when absent or empty)."""
+    mode = node.attrs.get("mode", "nearest")
+    if mode not in ("nearest", "linear"):
+        raise NotImplementedError(f"{node.op_type}: mode={mode}")
+    if node.op_type == "Upsample" or opset < 11:
+        coord, nearest = "asymmetric", "floor"
+    else:
+        coord = node.attrs.get("coordinate_transformation_mode", "half_pixel")
+        nearest = node.attrs.get("nearest_mode", "round_prefer_floor")
+        if coord not in _RESIZE_COORDS:
+            raise NotImplementedError(f"Resize: coordinate_transformation_mode={coord}")
+        if nearest not in _RESIZE_NEAREST:
+            raise NotImplementedError(f"Resize: nearest_mode={nearest}")
+        for name in ("antialias", "exclude_outside", "axes"):
+            if node.attrs.get(name):
+                raise NotImplementedError(f"Resize: {name}={node.attrs[name]}")
+        if node.attrs.get("keep_aspect_ratio_policy", "stretch") != "stretch":
+            raise NotImplementedError(f"Resize: keep_aspect_ratio_policy={node.attrs['keep_aspect_ratio_policy']}")
+    nd = len(shape)
+    if sizes:
+        if len(sizes) != nd:
+            raise ValueError(f"Resize: {len(sizes)} sizes for {nd} axes")
+        if sizes[1] != shape[1]:
+            raise NotImplementedError(f"Resize: sizes {sizes} change the channel axis")
+        # (axis 0 carries the images of a batch: its literal size in a graph exported for one image is not a target)
+        axes = [(a, int(sizes[a]), sizes[a] / shape[a]) for a in range(2, nd) if sizes[a] != shape[a]]
+    elif scales:
+        if len(scales) != nd:
+            raise ValueError(f"{node.op_type}: {len(scales)} scales for {nd} axes")
+        if scales[0] != 1.0 or scales[1] != 1.0:
+            raise NotImplementedError(f"{node.op_type}: scales {scales} on the batch or channel axis")
+        axes = [(a, int(np.floor(shape[a] * scales[a])), scales[a]) for a in range(2, nd) if scales[a] != 1.0]
+    else:
+        raise ValueError(f"{node.op_type}: neither scales nor sizes")
+    return mode, coord, nearest, axes
 
 
 @op("Resize", "Upsample")
 def _resize(s, node, x, roi=None, scales=None, sizes=None):
-    mode = node.attrs.get("mode", "nearest")
-    if node.op_type == "Upsample":
-        scales = roi
-    if sizes is not None and sizes.numel():
-        return F.interpolate(x, size=_ints(sizes)[2:], mode={"linear": "bilinear"}.get(mode, mode))
-    sc = _floats(scales)[2:]
-    return F.interpolate(x, scale_factor=sc, mode={"linear": "bilinear"}.get(mode, mode))
+    opset = _opset(s)
+    if node.op_type == "Upsample" or opset < 11:      # (X, scales); from Resize-11 on (X, roi, scales, sizes)
+        scales, sizes = roi, None
+    sizes = _ints(sizes) if sizes is not None and sizes.numel() else None
+    scales = _floats(scales) if sizes is None and scales is not None and scales.numel() else None
+    mode, coord, nearest, axes = resize_plan(node, opset, tuple(x.shape), scales, sizes)
+    if mode == "nearest" and coord == "asymmetric" and nearest == "floor" and scales is not None and 3 <= x.dim() <= 5 \
+            and all(sc == int(sc) and sc > 0 and not (int(sc) & (int(sc) - 1)) for sc in scales):
+        # what torch's exporter writes for F.interpolate(scale_factor=2): the library's own kernel computes floor(x / scale), exactly
+        # for a power of two
+        return F.interpolate(x, scale_factor=scales[2:], mode="nearest")
+    for a, out, scale in axes:      # separable: one selection (nearest) or one two-tap blend (linear) per axis that changes
+        n = x.shape[a]
+        if mode == "nearest":
+            x = torch.index_select(x, a, _host_vector(("resize", n, out, scale, coord, nearest), x.device,
+                                                      lambda: _resize_nearest(n, out, scale, coord, nearest)))
+            continue
+        i0 = _host_vector(("resize_i0", n, out, scale, coord), x.device, lambda: _resize_linear(n, out, scale, coord)[0])
+        i1 = _host_vector(("resize_i1", n, out, scale, coord), x.device, lambda: _resize_linear(n, out, scale, coord)[1])
+        view = [1] * x.dim()
+        view[a] = out
+        w1 = _host_vector(("resize_w1", n, out, scale, coord), x.device,
+                          lambda: _resize_linear(n, out, scale, coord)[2].astype(np.float32)).view(view)
+        w0 = _host_vector(("resize_w0", n, out, scale, coord), x.device,
+                          lambda: (1.0 - _resize_linear(n, out, scale, coord)[2]).astype(np.float32)).view(view)
+        x = torch.index_select(x, a, i0) * w0 + torch.index_select(x, a, i1) * w1
+    return x
 
 
 @op("FakeQuant")

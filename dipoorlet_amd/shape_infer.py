@@ -131,32 +131,18 @@ def _convt(ex, s, node, x, w, b=None):
     nd = len(w.shape) - 2
     strides = node.attrs.get("strides", [1] * nd)
     dil = node.attrs.get("dilations", [1] * nd)
-    pads = node.attrs.get("pads") or [0] * (2 * nd)
-    if list(pads[:nd]) != list(pads[nd:]):
-        raise NotImplementedError("ConvTranspose with asymmetric pads")
+    pads = ex.convt_pads(node, list(x.shape[2:]), list(w.shape[2:]))
     opad = node.attrs.get("output_padding", [0] * nd)
-    sp = [(x.shape[2 + i] - 1) * strides[i] - 2 * pads[i] + dil[i] * (w.shape[2 + i] - 1) + opad[i] + 1 for i in range(nd)]
+    sp = [(x.shape[2 + i] - 1) * strides[i] - pads[i] - pads[nd + i] + dil[i] * (w.shape[2 + i] - 1) + opad[i] + 1 for i in range(nd)]
     return Spec((x.shape[0], w.shape[1] * int(node.attrs.get("group", 1)), *sp), x.dtype)
 
 
 def _pool(ex, node, x, avg):
     k, nd, strides, dil, pads = ex._pool_args(node, x)
-    if avg:
-        dil = [1] * nd
+    if avg and any(d != 1 for d in dil):
+        raise NotImplementedError(f"AveragePool: dilations {list(dil)}")
     ceil = bool(node.attrs.get("ceil_mode", 0))
-    sym = list(pads[:nd]) == list(pads[nd:])
-    if avg and not sym and not node.attrs.get("count_include_pad", 0):
-        raise NotImplementedError("AveragePool: asymmetric pads with count_include_pad=0")
-    out = []
-    for i in range(nd):
-        size, pb, pe = x.shape[2 + i], pads[i], pads[nd + i]
-        if not sym:               # the executor pads first and pools without padding
-            size, pb, pe = size + pb + pe, 0, 0
-        num = size + pb + pe - dil[i] * (k[i] - 1) - 1
-        o = (-(-num // strides[i]) if ceil else num // strides[i]) + 1
-        if ceil and (o - 1) * strides[i] >= size + pb:      # the last window must start inside the input or the left padding
-            o -= 1
-        out.append(o)
+    out = [ex.pool_len(x.shape[2 + i], k[i], strides[i], dil[i], pads[i], pads[nd + i], ceil) for i in range(nd)]
     return Spec((x.shape[0], x.shape[1], *out), x.dtype)
 
 
@@ -264,8 +250,7 @@ def _split(ex, s, node, x, split=None):
     ax = ax + len(x.shape) if ax < 0 else ax
     sizes = _values(ex, split, "Split") if split is not None else node.attrs.get("split")
     if sizes is None:
-        n = len(node.output)
-        sizes = [x.shape[ax] // n] * n
+        sizes = ex.split_sizes(node, x.shape[ax])
     return [Spec(list(x.shape[:ax]) + [k] + list(x.shape[ax + 1:]), x.dtype) for k in sizes]
 
 
@@ -325,7 +310,11 @@ def _reduce(ex, s, node, x, axes=None):
     ax = _axes_of(ex, node, axes, node.op_type)
     keep = bool(node.attrs.get("keepdims", 1))
     nd = len(x.shape)
-    ax = set(range(nd)) if ax is None else {a + nd if a < 0 else a for a in ax}
+    if ax is None or len(ax) == 0:
+        if node.attrs.get("noop_with_empty_axes", 0):
+            return Spec(x.shape, x.dtype)
+        ax = range(nd)
+    ax = {a + nd if a < 0 else a for a in ax}
     return Spec([1 if i in ax else d for i, d in enumerate(x.shape) if keep or i not in ax], x.dtype)
 
 
@@ -350,19 +339,23 @@ def _expand(ex, s, node, x, shape):
 def _pad(ex, s, node, x, pads=None, value=None, axes=None):
     pads = _values(ex, pads, "Pad") if pads is not None else node.attrs["pads"]
     nd = len(x.shape)
-    return Spec([x.shape[i] + pads[i] + pads[nd + i] for i in range(nd)], x.dtype)
+    beg, end = ex.pad_amounts(pads, _values(ex, axes, "Pad") if axes is not None else None, nd)
+    return Spec([x.shape[i] + beg[i] + end[i] for i in range(nd)], x.dtype)
 
 
 @rule("Resize", "Upsample")
 def _resize(ex, s, node, x, roi=None, scales=None, sizes=None):
-    if node.op_type == "Upsample":
-        scales = roi
-    if sizes is not None and sizes.numel():
-        return Spec(tuple(x.shape[:2]) + tuple(_values(ex, sizes, "Resize")[2:]), x.dtype)
-    if not _real(scales):
+    opset = ex._opset(s)
+    if node.op_type == "Upsample" or opset < 11:
+        scales, sizes = roi, None
+    sizes = _values(ex, sizes, "Resize") if sizes is not None and sizes.numel() else None
+    if sizes is None and (scales is None or not _real(scales)):
         raise Unsupported("Resize: needs the values of its scales")
-    sc = ex._floats(scales)[2:]
-    return Spec(tuple(x.shape[:2]) + tuple(int(np.floor(d * f)) for d, f in zip(x.shape[2:], sc)), x.dtype)
+    scales = ex._floats(scales) if sizes is None and scales.numel() else None
+    out = list(x.shape)
+    for a, n, _ in ex.resize_plan(node, opset, tuple(x.shape), scales, sizes)[3]:
+        out[a] = n
+    return Spec(out, x.dtype)
 
 
 class _HostRun:
@@ -500,13 +493,18 @@ def batch_transparent(graph, folded, input_names, env):
             elif a in batch_axis and nd >= 2 and rank(b) == 2 and k <= nd - 2:
                 out = k
         elif op == "Softmax":
-            out = k if rest_const and ax(int(node.attrs.get("axis", -1)), nd) != k else None
+            if ex._opset(_HostRun(graph, 1)) >= 13:
+                out = k if rest_const and ax(int(node.attrs.get("axis", -1)), nd) != k else None
+            else:       # flattened to 2-D at `axis` (default 1): per-sample when the images are stacked in front of it
+                out = k if rest_const and k < ax(int(node.attrs.get("axis", 1)), nd) else None
         elif op == "LayerNormalization":
             out = k if rest_const and k < ax(int(node.attrs.get("axis", -1)), nd) else None
         elif op in ("ReduceMean", "ReduceSum", "ReduceMax", "ReduceMin", "Squeeze"):
             axes = node.attrs.get("axes") if len(ins) < 2 else values(ins[1])
             if rest_const and axes is not None:
                 axes = [ax(int(a), nd) for a in axes]
+                if not axes and op != "Squeeze" and not node.attrs.get("noop_with_empty_axes", 0):
+                    axes = list(range(nd))      # (empty axes: the reduction takes every axis, the images' too)
                 if k not in axes:
                     gone = op == "Squeeze" or not node.attrs.get("keepdims", 1)
                     out = k - (sum(1 for a in axes if a < k) if gone else 0)
