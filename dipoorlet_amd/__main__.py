@@ -1,9 +1,9 @@
 """`python -m dipoorlet_amd -M model.onnx -I calib_dir -N 1024 -A hist -D trt` — the reference's CLI
-(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, and `--gptq`, Hessian-compensated weight rounding, are this project's additions).
+(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, `--mx_rotate`, a block-Hadamard rotation of those operands, and `--gptq`, Hessian-compensated weight rounding, are this project's additions).
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
-model, optional) -> weight transforms (--smooth, --bc, --we, --update_bn, --adaround, --brecq [--drop], --sparse, --gptq) -> platform deploy file.
+model, optional) -> weight transforms (--smooth, --mx_rotate, --bc, --we, --update_bn, --adaround, --brecq [--drop], --sparse, --gptq) -> platform deploy file.
 Extra flags: --calib_batch, --resident_gb, --merge {allreduce,reference}, --skip_profiling, --timing_json.
 """
 import argparse
@@ -51,6 +51,13 @@ def build_parser():
                    help="(not in the reference; with -D ocp_fp8 only) OCP Microscaling on both operands of every MatMul / Gemm, constant "
                         "ones included: blocks of 32 along the reduction axis share a power-of-two scale taken from the data, the elements "
                         "are FP8 E4M3 (mxfp8) or FP4 E2M1 (mxfp4); every other node keeps the platform's static E4M3 scales")
+    p.add_argument("--mx_rotate", default=False, action="store_true",
+                   help="(not in the reference; with --mx only) rotate every MX block of both operands of every MatMul / Gemm that has a "
+                        "constant 2-D weight and a reduction length K that is a multiple of 32, by the 32-point Hadamard matrix H32: "
+                        "(X . H) . (H . W / 32) = X . W, the same function in real arithmetic, with a large channel spread over its block.  "
+                        "The weight side is folded offline, the activation side is a BlockHadamard node (domain dipoorlet.amd) that a "
+                        "runtime applies in front of its MX quantiser.  Runs after --smooth and before --bc; writes rotate_model.onnx and "
+                        "rotate_report.json, and a \"rotation\" entry in ocp_mx_blocks.json")
     p.add_argument("--gptq_block", type=int, default=128,
                    help="--gptq (not in the reference; every platform, -D ocp_fp8 included): round every Conv (group 1) / Gemm weight column "
                         "by column onto the platform's weight grid, pushing each column's rounding error onto the columns not yet rounded "
@@ -97,6 +104,9 @@ def check_args(args):
             raise ValueError(f"--gptq_block must lie in [1, 128], got {args.gptq_block}")
         if not getattr(args, "gptq_damp", 0.01) > 0.0:      # (a NaN too)
             raise ValueError(f"--gptq_damp must be positive, got {args.gptq_damp}")
+    if getattr(args, "mx_rotate", False) and not getattr(args, "mx", None):
+        raise ValueError("--mx_rotate needs --mx mxfp8 or --mx mxfp4: it rotates the 32-element blocks that --mx scales, and does "
+                         "nothing for a static grid")
     if getattr(args, "mx", None) and args.deploy != "ocp_fp8":
         raise ValueError(f"--mx {args.mx} is not supported with -D {args.deploy}: block-scaled MatMul / Gemm operands sit beside static "
                          "FP8 scales on every other node.  Supported: -D ocp_fp8")

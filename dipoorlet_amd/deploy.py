@@ -112,13 +112,20 @@ def gen_ocp_mx_blocks(graph, act_clip_val, weight_clip_val, args):
     """--mx: {"format": "mxfp8" | "mxfp4", "block_size": 32, "tensors": {name: {"axis": k, "constant": bool}}} ->
     ocp_mx_blocks.json — the operands of MatMul / Gemm that the fake-quantised graph block-scales, and along which axis (an MX
     node has no static scale to list).  A tensor's first node goes by the tensor's name, a second one along another axis by the
-    name with that node's suffix (`_ax<k>`)."""
+    name with that node's suffix (`_ax<k>`).  With --mx_rotate also "rotation": {"block_size": 32, "activations": [...], "weights":
+    [...]} — the activations (keys of "tensors": the outputs of the graph's BlockHadamard nodes) in front of whose MX quantiser a
+    runtime applies H32 per block, and the weights that were folded with H32 / 32 along their block axis."""
     from .quantize import MX_BLOCK, quant_graph
     clip = {k: [np.copy(v[0]), np.copy(v[1])] for k, v in {**act_clip_val, **weight_clip_val}.items()}
     graph_q, _ = quant_graph(graph, clip, args)
     tensors = {q.tensor_name + q.suffix: {"axis": int(q.block_axis), "constant": q.tensor_name in graph.initializer}
                for q in graph_q._qdq.values() if q.is_mx}
-    _dump({"format": args.mx, "block_size": MX_BLOCK, "tensors": tensors}, args, "ocp_mx_blocks.json")
+    res = {"format": args.mx, "block_size": MX_BLOCK, "tensors": tensors}
+    if getattr(args, "mx_rotate", False):
+        acts = [n.output[0] for n in graph.graph.node if n.op_type == "BlockHadamard"]
+        weights = [r.input[1] for a in acts for r in graph.get_tensor_consumer(a) if not isinstance(r, str) and r.op_type in ("MatMul", "Gemm")]
+        res["rotation"] = {"block_size": MX_BLOCK, "activations": acts, "weights": weights}
+    _dump(res, args, "ocp_mx_blocks.json")
 
 
 def to_deploy(graph, act_clip_val, weight_clip_val, args, **kwargs):

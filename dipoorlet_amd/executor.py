@@ -46,7 +46,8 @@ from .forward_net import ActivationSession
 from .forward_net import wall as _wall
 from .utils import logger, mark
 
-_OPS = {}
+_OPS = {}         # the ONNX operators (and the fused FakeQuant pair), each held to its ONNX definition
+_OWN_OPS = {}     # the operators of this project's own operator set (graph.MX_DOMAIN), each held to a model under tests/
 
 _WARM = {}     # "kernels" / "blas": the helper threads (True once joined); "context_s", "kernels_s", "blas_s": their own clocks
 
@@ -151,6 +152,18 @@ def op(*names):
             _OPS[n] = fn
         return fn
     return deco
+
+
+def own_op(*names):
+    def deco(fn):
+        for n in names:
+            _OWN_OPS[n] = fn
+        return fn
+    return deco
+
+
+def has_op(op_type):
+    return op_type in _OPS or op_type in _OWN_OPS
 
 
 def _ints(v):
@@ -846,6 +859,18 @@ def _fake_quant(s, node, x):
     return q.apply(x.contiguous())
 
 
+@own_op("BlockHadamard")
+def _block_hadamard(s, node, x):
+    """`--mx_rotate`: x . blockdiag(H32) along the last axis in front of a rotated MatMul / Gemm (ops.hadamard32; the definition is
+    tests/mx_rotate_model.py fwht32)."""
+    if int(node.attrs.get("block_size", 32)) != 32:
+        raise NotImplementedError(f"BlockHadamard: block_size {node.attrs.get('block_size')} (only 32 is built)")
+    if not x.is_cuda:          # shape-inference pass (host or meta tensors): values are irrelevant there
+        return x
+    from . import ops
+    return ops.hadamard32(x.contiguous())
+
+
 def fused_fake_quant(s, node, pre, *xs):
     """A FakeQuant node with its producer's ReLU / Add + ReLU applied on the way in (relu_fusion): one k_fake_quant<PRE> launch."""
     q = s.graph._qdq[node.name]
@@ -910,7 +935,8 @@ def relu_fusion(graph, folded, consts, keep=(), shape1=None):
 
 def run_op(s, node, *args):
     """The executor's op for `node`: the one place the op table is indexed, at each call (entries are replaced on live sessions)."""
-    return _OPS[node.op_type](s, node, *args)
+    fn = _OPS.get(node.op_type)
+    return (fn if fn is not None else _OWN_OPS[node.op_type])(s, node, *args)
 
 
 class Step:
@@ -957,7 +983,7 @@ class GraphSession(ActivationSession):
         self._fusion_cache, self._schedules = {}, {}        # per frozenset(keep) (the schedules: None too)
         if self.device.type == "cuda":
             warm_libraries(self.device, blas=first_batch is None)     # (no-op for what the CLI has started already)
-        missing = sorted({n.op_type for n in graph.graph.node if n.op_type not in _OPS})
+        missing = sorted({n.op_type for n in graph.graph.node if not has_op(n.op_type)})
         if missing:
             raise NotImplementedError(f"executor: unsupported ONNX ops {missing}")
         self.expose_fake_quant = expose_fake_quant

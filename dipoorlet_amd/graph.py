@@ -20,7 +20,8 @@ from . import onnx_io
 from .onnx_io import Node
 
 
-MX_DOMAIN = "dipoorlet.amd"     # the operator set of MXQuantizeDequantize (an MX FakeQuant node as to_model writes it), version 1
+# the operator set, version 1, of MXQuantizeDequantize (an MX FakeQuant node as to_model writes it) and BlockHadamard (--mx_rotate)
+MX_DOMAIN = "dipoorlet.amd"
 
 
 class ONNXGraph:
@@ -248,6 +249,7 @@ class ONNXGraph:
                 nodes.append(Node("DequantizeLinear", [q.q_output, q.scale_name, q.zero_point_name], [q.output],
                                   name=q.dq_name, attrs=attrs))
             else:
+                mx_domain |= n.domain == MX_DOMAIN
                 nodes.append(n)
         m.nodes = nodes
         if float8:

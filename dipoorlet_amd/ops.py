@@ -1129,6 +1129,26 @@ def fake_quant_mx(x, axis, elem, out=None, scales=None):
     return y
 
 
+def hadamard32(x, out=None):
+    """The block-Hadamard rotation of `--mx_rotate` (dpl_hadamard32; tests/mx_rotate_model.py fwht32 is the definition): every 32
+    consecutive elements along the last axis are multiplied by the symmetric +-1 Sylvester matrix H32 (no normalisation: the
+    constant operand of the product carries the 2^-5).  x: a contiguous fp32 device tensor whose last dimension is a multiple of
+    32; out: as fake_quant (may be x).  One read and one write per element."""
+    _require_cuda(x, "x")
+    if x.dim() < 1 or int(x.shape[-1]) % MX_BLOCK:
+        raise _hip.DipoorletHipError(f"hadamard32: the last dimension must be a multiple of {MX_BLOCK}, got shape {list(x.shape)}")
+    if out is None:
+        y = torch.empty_like(x)
+    else:
+        _require_cuda(out, "out")
+        if out.shape != x.shape or out.device != x.device:
+            raise _hip.DipoorletHipError("hadamard32: out must have x's shape and device")
+        y = out
+    k = int(x.shape[-1])
+    _hip.check(_hip.lib().dpl_hadamard32(_ptr(x), _ptr(y), x.numel() // k if k else 0, k, _stream()), "dpl_hadamard32")
+    return y
+
+
 GPTQ_FMT = {"int": _hip.GRID_UNIFORM, "e4m3": _hip.GRID_E4M3}     # include/dipoorlet_hip.h DPL_GRID_*
 GPTQ_MAX_BLOCK = _hip.GPTQ_MAX_BLOCK
 GptqGrid = collections.namedtuple("GptqGrid", "fmt scale zero_point qlo qhi", defaults=(None, 0, 0))

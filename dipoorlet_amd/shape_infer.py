@@ -84,7 +84,7 @@ def _values(ex, v, what):
 
 @rule("Relu", "LeakyRelu", "Sigmoid", "Tanh", "HardSigmoid", "HardSwish", "Clip", "Gelu", "Erf", "Sqrt", "Exp", "Log", "Abs",
       "Neg", "Reciprocal", "Floor", "Ceil", "Softmax", "BatchNormalization", "LayerNormalization", "InstanceNormalization",
-      "Identity", "Dropout", "FakeQuant")
+      "Identity", "Dropout", "FakeQuant", "BlockHadamard")
 def _same(ex, s, node, x, *rest):
     return Spec(x.shape, x.dtype)
 
@@ -395,7 +395,7 @@ def infer(graph, folded, input_names, batch=1):
         args = [env[i] if i != "" else None for i in node.input]
         while args and args[-1] is None:
             args.pop()
-        if all(a is None or _real(a) for a in args) and node.op_type in ex._OPS and args:
+        if all(a is None or _real(a) for a in args) and ex.has_op(node.op_type) and args:
             with torch.no_grad():
                 out = ex.run_op(host, node, *args)          # values known: the executor's own op, on the host
         else:
@@ -470,6 +470,8 @@ def batch_transparent(graph, folded, input_names, env):
             if rest_const and q is not None and not (q.per_channel and ax(int(q.axis), nd) == k) \
                     and not (q.is_mx and ax(int(q.block_axis), nd) == k):      # (MX blocks along the batch axis mix the samples)
                 out = k
+        elif op == "BlockHadamard":     # blocks along the last axis: per-sample unless that is the images' axis
+            out = k if rest_const and nd >= 2 and k != nd - 1 else None
         elif op in _BINARY:
             a, b = ins
             if a in batch_axis and b in batch_axis:

@@ -17,6 +17,7 @@ Per tensor:
     dipoorlet::fake_quant_add_relu(Tensor x, Tensor x2, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor
     dipoorlet::fake_quant_fp8(Tensor x, Tensor scale, int axis) -> Tensor      the pair on the OCP FP8 E4M3 grid (ops.fake_quant_fp8)
     dipoorlet::fake_quant_mx(Tensor x, int axis, str elem) -> Tensor           the OCP Microscaling pair, 'mxfp8' / 'mxfp4', blocks of 32 along axis (ops.fake_quant_mx)
+    dipoorlet::hadamard32(Tensor x) -> Tensor                                  x . blockdiag(H32) along the last axis, a multiple of 32 (ops.hadamard32: --mx_rotate)
     dipoorlet::gptq_block(Tensor(a!) w, int c0, int nb, Tensor u, Tensor scale, Tensor zero_point, int qlo, int qhi, str fmt) -> Tensor
                                                                one block of GPTQ's column recursion in place on w; -> Err [rows, nb] (ops.gptq_block)
 Over every tensor of a batch of images in ONE launch — what the reference's loops over `ort_outputs` stand for
@@ -326,6 +327,16 @@ def fake_quant_mx(x: torch.Tensor, axis: int, elem: str) -> torch.Tensor:
 
 @fake_quant_mx.register_fake
 def _(x, axis, elem):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op("dipoorlet::hadamard32", mutates_args=(), device_types="cuda")
+def hadamard32(x: torch.Tensor) -> torch.Tensor:
+    return ops.hadamard32(x.contiguous())
+
+
+@hadamard32.register_fake
+def _(x):
     return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 

@@ -11,6 +11,7 @@ from .adaround import adaround
 from .bias_correction import bias_correction
 from .brecq import brecq
 from .gptq import gptq
+from .rotate import mx_rotate
 from .smooth import smooth_quant
 from .sparse_quant import sparse_quant
 from .update_bn import update_bn
@@ -50,6 +51,14 @@ def weight_calibration(onnx_graph, act_clip_val, weight_clip_val, args):
         if smoothed is not graph_after_wt:                  # (a graph without a site is left as it is and nothing is written)
             graph_after_wt = _reload("smooth_model", args)
             act_clip_val, weight_clip_val = _recalibrate(graph_after_wt, args)      # activation ranges change with the scales
+    if getattr(args, "mx_rotate", False):   # (not in the reference) behind --smooth, whose scales it keeps; --bc sees the rotated model
+        if dist.get_rank() == 0:
+            logger.info("Weight transform: rotating MX blocks...")
+        rotated = mx_rotate(graph_after_wt, args)          # every rank: host work only; rank 0 writes the model and the report
+        dist.barrier()
+        if rotated is not graph_after_wt:                   # (a graph without a site is left as it is and nothing is written)
+            graph_after_wt = _reload("rotate_model", args)
+            act_clip_val, weight_clip_val = _recalibrate(graph_after_wt, args)      # the rotated tensors and weights are new
     if getattr(args, "bc", False):   # :21-29 — the reference: rank 0 corrects, everyone reloads, weight (bias) ranges refreshed
         # here every rank corrects over its shard of the images and the per-channel sums are all-reduced (bias_correction);
         # --merge reference: rank 0 alone, over all images.  Rank 0 writes the model, everyone reloads it, as before.

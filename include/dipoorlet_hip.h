@@ -25,13 +25,14 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 28 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 29 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
                               25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
                               26: dpl_colwise_absmax (per-channel running max |x| of a channels-last activation: --smooth);
                               27: dpl_fake_quant_mx (the OCP Microscaling Q/DQ pair, MXFP8 / MXFP4: --mx);
-                              28: dpl_gptq_block (sequential quantise-and-compensate of a block of weight columns: --gptq) */
+                              28: dpl_gptq_block (sequential quantise-and-compensate of a block of weight columns: --gptq);
+                              29: dpl_hadamard32 (32-point Hadamard rotation of every MX block of an activation: --mx_rotate) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -423,6 +424,14 @@ int dpl_fake_quant_fp8_items(const dpl_work_item* d_items, int64_t n_items, cons
 #define DPL_MX_E2M1 1
 int dpl_fake_quant_mx(int32_t elem, const float* d_x, float* d_y, uint64_t outer, uint64_t k, uint64_t inner,
                       uint8_t* d_scales_or_null, dpl_stream_t s);
+
+/* ---- the block-Hadamard rotation of --mx_rotate (beyond the reference): y = x . blockdiag(H32) along the contiguous last axis of
+ *      the [rows, k] tensor, H32[i][j] = (-1)^popcount(i & j) (Sylvester, natural order, symmetric, H32 . H32 = 32 I; NOT
+ *      normalised: the constant operand of the product carries the 2^-5).  Per run of 32 consecutive elements, five stages h = 1, 2,
+ *      4, 8, 16: for every i with (i & h) == 0, (v[i], v[i | h]) <- (v[i] + v[i | h], v[i] - v[i | h]), each a single fp32
+ *      operation — bit-exact against tests/mx_rotate_model.py fwht32 (a NaN or an infinity anywhere in a block spreads over the
+ *      whole block).  d_y may equal d_x.  k must be a multiple of 32 below 2^31; rows * k == 0 is a no-op. */
+int dpl_hadamard32(const float* d_x, float* d_y, uint64_t rows, uint64_t k, dpl_stream_t s);
 
 /* ---- GPTQ (Frantar et al., 2022; beyond the reference; --gptq): quantise nb consecutive columns of a weight matrix one after
  *      the other and push each column's rounding error onto the block's columns not yet rounded.  d_w: [rows, ldw] fp32 row-major,
