@@ -105,15 +105,41 @@ def shard_range(data_num, rank, world_size):
     return rank * rank_num, min((rank + 1) * rank_num, data_num)
 
 
+def balanced_shard(data_num, rank, world_size):
+    """Images [st, ed) of rank `rank` for the walks that must see ALL data_num images (the sharded --bc, forward_net.py:50-52: the
+    reference corrects with every image; --smooth's statistics): a balanced split, where shard_range drops data_num % world_size."""
+    return rank * data_num // world_size, (rank + 1) * data_num // world_size
+
+
+def _group():
+    return dist.is_available() and dist.is_initialized()
+
+
+def rank():
+    """This process' rank in the default group; 0 without one."""
+    return dist.get_rank() if _group() else 0
+
+
+def world():
+    """The default group's size; 1 without one."""
+    return dist.get_world_size() if _group() else 1
+
+
+def barrier():
+    """dist.barrier() on the default group; nothing without one."""
+    if _group():
+        dist.barrier()
+
+
 # ---------------------------------------------------------------------------------- statistic merges
-def _active(world_size):
-    return world_size > 1 and dist.is_available() and dist.is_initialized()
+def active(world_size):
+    return world_size > 1 and _group()
 
 
 def merge_ranges(gmin, gmax, world_size):
     """In place: element-wise MIN of mins and MAX of maxes over ranks.  NaN (a tensor that saw a NaN on
     any rank) must win like it does in numpy: NaN is mapped to -inf / +inf for the collective and back."""
-    if not _active(world_size):
+    if not active(world_size):
         return gmin, gmax
     nan = (torch.isnan(gmin) | torch.isnan(gmax)).to(torch.int32)
     lo = torch.where(nan.bool(), torch.full_like(gmin, float("-inf")), gmin)
@@ -128,14 +154,14 @@ def merge_ranges(gmin, gmax, world_size):
 
 def merge_hist(hist, world_size):
     """In place: SUM of the [T, bins] int64 histograms over ranks (one 2 MB buffer for ResNet-50)."""
-    if _active(world_size):
+    if active(world_size):
         dist.all_reduce(hist, op=dist.ReduceOp.SUM)
     return hist
 
 
 def gather_rows(rows, world_size):
     """[n, T, 3] per-image OCTAV rows of this rank -> [world*n, T, 3] in rank (= image) order."""
-    if not _active(world_size):
+    if not active(world_size):
         return rows
     out = torch.empty((world_size * rows.shape[0],) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
     try:

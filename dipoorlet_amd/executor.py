@@ -1388,13 +1388,18 @@ def _references(steps, consts, outputs):
     return ref
 
 
+def _unread(ref, live, name):
+    """`name` loses a reader; what nobody reads any more leaves `live`.  A name without a count (a constant, "") is left alone."""
+    if name in ref:
+        ref[name] -= 1
+        if ref[name] == 0:
+            live.pop(name, None)
+
+
 def _release(ref, live, step):
-    """`step` has run: its inputs lose a reader; what nobody reads any more — an output nobody consumes too — leaves `live`."""
+    """`step` has run: its inputs lose a reader each; an output nobody consumes leaves `live` at once."""
     for i in step.inputs:
-        if i in ref:
-            ref[i] -= 1
-            if ref[i] == 0:
-                live.pop(i, None)
+        _unread(ref, live, i)
     for o in step.node.output:
         if o not in ref:
             live.pop(o, None)
@@ -1448,6 +1453,16 @@ class Frontier:
     def inputs_of(self, node):
         """The tensors `node` reads: its inputs, or — a Q/DQ pair that runs its producers' Add / ReLU — theirs."""
         return self.steps[node.name].inputs
+
+    def hold(self, name):
+        """One more reader for `name`, until drop(name) — or until a second run() of a node that reads it.  May come before the
+        producer runs (an output nobody consumes would be dropped at once).  A constant of the session is ignored."""
+        if name != "" and name not in self.sess.consts:
+            self.ref[name] = self.ref.get(name, 0) + 1
+
+    def drop(self, name):
+        """Take hold(name)'s reader away again; at zero the tensor leaves `env`."""
+        _unread(self.ref, self.env, name)
 
     def run(self, node):
         step = self.steps.get(node.name)

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import dist_helper, ops
 from .forward_net import load_input_batch
 from .quantize import DQTENSORSUFFIX, quant_graph
 from .utils import logger
@@ -28,16 +28,12 @@ def get_output_single_map(graph):
     return {o: int(np.prod(graph.get_tensor_shape(o)[1:])) <= 10 for o in graph.network_outputs}
 
 
-def _world():
-    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-
-
 def quantize_profiling_multipass(graph_after_wt, graph_ori, act_clip_val, weight_clip_val, args):
     """profiling.py:34-99 -> (layer_cosine_dict, model_cosine_dict, quant_node_list)."""
     clip_val = act_clip_val.copy()
     clip_val.update(weight_clip_val)
     graph_q, quant_node_list = quant_graph(graph_after_wt, clip_val, args)
-    rank = dist.get_rank() if _world() > 1 or (dist.is_available() and dist.is_initialized()) else 0
+    rank = dist_helper.rank()
     if rank == 0 and getattr(args, "output_dir", None):
         graph_q.output_dir = args.output_dir
         graph_q.save_onnx_model(name="quant_model")

@@ -21,10 +21,10 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
-from ..executor import Frontier, GraphSession, frontier_peak_elems, load_chunks
-from ..graph import ONNXGraph
-from ..quantize import quant_graph
+from ..dist_helper import active, balanced_shard as bc_shard
+from ..executor import Frontier, GraphSession, frontier_peak_elems
 from ..utils import logger
+from .walk import QuantWalk
 
 BIAS_CORRECTION_NODE_TYPE = ["Conv", "Gemm"]
 
@@ -74,30 +74,18 @@ def update_conv_node_bias(graph_bc, node, fp_activations, q_activations, world_s
     return diff
 
 
-def bc_shard(data_num, rank, world_size):
-    """Images [st, ed) of rank `rank` for the sharded --bc walk: a balanced split that covers ALL data_num images (the reference
-    corrects with every image, forward_net.py:50-52; the calibration sweeps' floor split would drop data_num % world_size)."""
-    return rank * data_num // world_size, (rank + 1) * data_num // world_size
-
-
 @torch.no_grad()
 def bias_correction(graph, act_clip_val, weight_clip_val, args):
     """bias_correction.py:34-55 -> the bias-corrected graph (also saved as update_bias_model.onnx)."""
-    clip_val = act_clip_val.copy()
-    clip_val.update(weight_clip_val)
-    clip_val = {k: [np.copy(v[0]), np.copy(v[1])] for k, v in clip_val.items()}
-    graph_bc = ONNXGraph()
-    graph_bc.copy_from(graph)
-    graph_q, _ = quant_graph(graph_bc, clip_val, args)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    s_fp = GraphSession(graph, device=dev)
-    s_q = GraphSession(graph_q, device=dev)
+    walk = QuantWalk(graph, act_clip_val, weight_clip_val, args)
+    graph_bc, graph_q, s_q = walk.graph_new, walk.graph_q, walk.s_q
+    s_fp = GraphSession(graph, device=walk.dev)
     # The reference lets rank 0 walk ALL images while the others wait (weight_trans_base.py:21-29, forward_net.py:50-52).  The
     # correction is a per-channel SUM over images, so with several ranks each walks its shard of the images node-major as
     # before and the sums are all-reduced per Conv / Gemm node (RCCL): every rank holds the same corrected biases, and its
     # frontier is 1 / world of the set.  args.merge == 'reference' keeps the reference's schedule.
     world = int(getattr(args, "world_size", 1) or 1)
-    sharded = world > 1 and getattr(args, "merge", "allreduce") != "reference" and dist.is_available() and dist.is_initialized()
+    sharded = getattr(args, "merge", "allreduce") != "reference" and active(world)
     st, ed = bc_shard(args.data_num, int(getattr(args, "rank", 0)), world) if sharded else (0, args.data_num)
     world = world if sharded else 1
     N = ed - st
@@ -110,8 +98,8 @@ def bias_correction(graph, act_clip_val, weight_clip_val, args):
         logger.warning("--bc: the live activations of all %d images of both networks are about %.0f GB at the widest point of "
                        "this graph, over the %.0f GB budget (--resident_gb): keeping them in host memory between nodes",
                        N, need / 1e9, budget / 1e9)
-    bounds, inputs = load_chunks(graph, args, st, ed, dev, on_host)
-    fp, qf = Frontier(s_fp, bounds, inputs, on_host), Frontier(s_q, bounds, inputs, on_host)
+    qf = walk.start(st, ed, on_host)
+    fp = Frontier(s_fp, walk.bounds, qf.env, on_host)       # (the same input chunks)
     fp_nodes = {n.name: n for n in graph.graph.node}
     # DPL_BC_RECOMPUTE=1 (a testing aid): a corrected node's quantised output is computed AGAIN with the corrected bias instead of
     # being fixed up in place (q_out + diff).  The two are the same value up to one fp32 rounding — conv(x, w, b) + d against
@@ -126,12 +114,11 @@ def bias_correction(graph, act_clip_val, weight_clip_val, args):
         corrected = node.op_type in BIAS_CORRECTION_NODE_TYPE
         out = node.output[0]
         if corrected:
-            fp.ref[fp_node.output[0]] = fp.ref.get(fp_node.output[0], 0) + 1  # hold both outputs for the diff BEFORE the nodes
-            qf.ref[out] = qf.ref.get(out, 0) + 1                              # run: an output nobody consumes is dropped at once
-            if recompute:                                                     # (... and the inputs for the second run)
+            fp.hold(fp_node.output[0])      # hold both outputs for the diff BEFORE the nodes run: an output nobody consumes is
+            qf.hold(out)                    # dropped at once
+            if recompute:                   # (... and the inputs for the second run)
                 for i in qf.inputs_of(node):
-                    if i in qf.ref:
-                        qf.ref[i] += 1
+                    qf.hold(i)
         qf.run(node)
         fp.run(fp_node)
         if not corrected:
@@ -143,19 +130,13 @@ def bias_correction(graph, act_clip_val, weight_clip_val, args):
             bname = bc_node.input[2]
             if len(node.input) < 3:       # (a node without a bias has just been given one)
                 node.input.append(bname)
-            s_q.set_const(bname, torch.from_numpy(np.ascontiguousarray(graph_bc.get_initializer(bname), dtype=np.float32)))
+            walk.set_const(bname, torch.from_numpy(np.ascontiguousarray(graph_bc.get_initializer(bname), dtype=np.float32)))
             qf.run(node)
         elif qf.env[out]:
             shape = [1, -1] + [1] * (qf.env[out][0].dim() - 2)
             d_host = diff.reshape(shape).cpu() if on_host else None
             for t in qf.env[out]:  # the bias is additive in the output: fix the computed q output in place
                 t.add_(d_host if on_host else diff.reshape(shape))
-        for env_ref, o in ((fp, fp_node.output[0]), (qf, out)):   # drop the extra hold
-            env_ref.ref[o] -= 1
-            if env_ref.ref[o] == 0:
-                env_ref.env.pop(o, None)
-    graph_bc.update_model()
-    if getattr(args, "output_dir", None) and (not sharded or int(getattr(args, "rank", 0)) == 0):
-        graph_bc.output_dir = args.output_dir
-        graph_bc.save_onnx_model("update_bias_model")
-    return graph_bc
+        fp.drop(fp_node.output[0])
+        qf.drop(out)
+    return walk.finish("update_bias_model")

@@ -1,7 +1,7 @@
 """--gptq (not in the reference): GPTQ (Frantar et al., 2022) — Hessian-compensated weight rounding, one pass per layer, on whatever
 grid the platform's fake-quant nodes round weights to (an integer grid or OCP FP8 E4M3).  tests/gptq_model.py is the definition.
 
-The fake-quantised network is walked once, node-major, exactly as AdaRound's driver walks it (reconstruction.QuantWalk).  For every
+The fake-quantised network is walked once, node-major, exactly as AdaRound's driver walks it (walk.QuantWalk).  For every
 Conv (group 1, two spatial axes) and Gemm whose weight the graph fake-quantises:
   * H = sum X^T X / rows over the node's fake-quantised input — a Gemm's input rows, a Conv's unfolded patches (pads applied
     explicitly, so asymmetric ONNX pads are right) — fp32 GEMMs per slab summed in fp64, one fp64 SUM all-reduce per node;
@@ -21,11 +21,12 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from .. import ops
+from ..dist_helper import barrier, shard_range
 from ..executor import conv_padding
 from ..platform_settings import platform_setting_table
 from ..quantize import FP8_E4M3, get_qnode_by_param
 from ..utils import logger
-from .reconstruction import QuantWalk
+from .walk import QuantWalk
 
 __all__ = ["gptq", "factor", "layer_grid"]
 
@@ -147,8 +148,10 @@ def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
     objective_nearest, objective_gptq, kept}); objective = tr((Wq - W) H (Wq - W)^T) under the layer's own H; `kept`: 'gptq', or
     'nearest' where the factorisation failed (objective_gptq is None; the weight is left as it is: the graph's Q/DQ node rounds it
     to nearest).  Rank 0 also writes the report, and the nodes left as they are with the reason, to gptq_report.json."""
-    walk = QuantWalk(graph_ori, graph, act_clip_val, weight_clip_val, args, with_fp=False)
-    graph_new, graph_q, qf, dev, rank = walk.graph_new, walk.graph_q, walk.qf, walk.dev, walk.rank
+    barrier()
+    walk = QuantWalk(graph, act_clip_val, weight_clip_val, args)
+    graph_new, graph_q, dev, rank = walk.graph_new, walk.graph_q, walk.dev, walk.rank
+    qf = walk.start(*shard_range(args.data_num, rank, walk.world))
     skip = set(getattr(args, "skip_layers", None) or ())
     block = int(getattr(args, "gptq_block", ops.GPTQ_MAX_BLOCK) or ops.GPTQ_MAX_BLOCK)
     damp0 = float(getattr(args, "gptq_damp", 0.01) or 0.01)
@@ -198,7 +201,7 @@ def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
                     logger.warning("--gptq: %s: the compensated rounding did not lower the objective (%g against %g)", node.name,
                                    entry["objective_gptq"], entry["objective_nearest"])
                 w_new = wq if rows_first else wq.t().contiguous()
-                walk.set_weight(wname, w_new.reshape(w_host.shape))
+                walk.set_const(wname, w_new.reshape(w_host.shape))
             report.append(entry)
             if rank == 0:
                 logger.info("GPTQ for: {} [{} x {}] objective nearest {:.6g} -> gptq {} ({})".format(

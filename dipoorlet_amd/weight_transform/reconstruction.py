@@ -19,25 +19,15 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from ..executor import Frontier, GraphSession, load_chunks
+from .. import dist_helper
 from ..forward_net import ActivationCache
-from ..graph import ONNXGraph
 from ..platform_settings import platform_setting_table
-from ..quantize import quant_graph
 from ..utils import logger
 from .ada_quant_layer import AdaQLayer, L2_norm, RoundSchedule, adaround_reg
 from .sparse_quant_layer import SparseQLayer, cosine_lr
 from .weight_equalization import node_has_equalized
-from .utils import (LEARNABLE_LAYER_TYPES, follow_relu, following_relu, get_block_from_first, get_quant_tensor,
-                    update_weight)
-
-
-def _world():
-    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-
-
-def _rank():
-    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+from .utils import LEARNABLE_LAYER_TYPES, follow_relu, following_relu, get_block_from_first, get_quant_tensor
+from .walk import QuantWalk
 
 
 def _use_graph(world):
@@ -57,7 +47,7 @@ def learn_rounding(layers, q_in, fp_in, fp_out, reg, batch_size, max_epoch, drop
     sequence does not depend on the data and the regulariser temperature / Adam bias corrections are advanced on
     the device (RoundSchedule), so with use_graph every batch index gets its iteration captured as a hipGraph after
     the first (eager, library warm-up) epoch and the remaining epochs are graph replays."""
-    world = _world()
+    world = dist_helper.world()
     if use_graph is None:
         use_graph = _use_graph(world)
     n = q_in.shape[0]
@@ -107,12 +97,12 @@ def learn_rounding(layers, q_in, fp_in, fp_out, reg, batch_size, max_epoch, drop
             l2, rg = (float(v) for v in loss.tolist())
             shown = (l2, rg)
             reg.beta = sched.state()[2]
-            if _rank() == 0:
+            if dist_helper.rank() == 0:
                 logger.info("{}Epoch: {:<5} L2 Loss: {:>10.3f} Beta: {:>3.3f}".format(log_head, epoch, l2 + rg, reg.beta))
     reg.beta = sched.state()[2]
     for layer in layers:
         layer.rp.steps = cur_iter
-    if _rank() == 0:
+    if dist_helper.rank() == 0:
         for layer in layers:
             c, f, t = layer.rp.rounding_summary()
             logger.info("Ceil: {:>5} Floor: {:>5} Total: {:>5} Ratio: {:>.3f}".format(c, f, t, (c + f) / t))
@@ -123,7 +113,7 @@ def learn_sparse(layer, q_in, fp_out, batch_size, max_epoch, log_every=50):
     """sparse_quant.py:107-130 — SGD(lr 1e-3, momentum 0.9, weight decay 1e-4) with a per-epoch cosine schedule on
     the layer's weight; one iteration = mask + fused quantiser, conv forward, fused L2 loss + gradient, conv
     backward, fused straight-through gradient + SGD update."""
-    world = _world()
+    world = dist_helper.world()
     n = q_in.shape[0]
     n_batches = math.ceil(n / batch_size)
     loss = torch.zeros(1, dtype=torch.float64, device=q_in.device)
@@ -138,9 +128,9 @@ def learn_sparse(layer, q_in, fp_out, batch_size, max_epoch, log_every=50):
             if world > 1:
                 dist.all_reduce(layer.qw.grad)
             layer.step(lr, 1.0 / world)
-        if epoch % log_every == 0 and _rank() == 0:
+        if epoch % log_every == 0 and dist_helper.rank() == 0:
             logger.info("Epoch: {:<4} L2 Loss: {:>10.6f}, LR: {:>10.6f}".format(epoch, float(loss), lr))
-    if _rank() == 0:
+    if dist_helper.rank() == 0:
         logger.info("Loss: {:>10.6f}".format(float(loss)))
     return float(loss)
 
@@ -193,51 +183,14 @@ def _build_sparse_layer(graph, graph_new, node, clip_val, args, dev):
     return SparseQLayer(node, weight, bias, qw_tensor, follow_relu(graph, node), sparse_info)
 
 
-class QuantWalk:
-    """The node-major walk of the fake-quantised network that the weight-rounding transforms share (reconstruct() here, gptq() in
-    gptq.py): this rank's shard of the calibration images, a copy of `graph` that receives the new weights (graph_new), its
-    fake-quantised form under the given ranges (graph_q) with a session (s_q) and a Frontier (qf) over the shard, and — with_fp —
-    the full-precision activations of graph_ori (fp_cache).  A transform visits graph_q's nodes in order, writes a node's new
-    weight with set_weight() and runs the node with qf.run(), so everything downstream sees the new weights."""
-
-    def __init__(self, graph_ori, graph, act_clip_val, weight_clip_val, args, with_fp=True):
-        if dist.is_available() and dist.is_initialized():
-            dist.barrier()
-        self.clip_val = {k: [np.copy(v[0]), np.copy(v[1])] for k, v in {**act_clip_val, **weight_clip_val}.items()}
-        self.graph_new = ONNXGraph()
-        self.graph_new.copy_from(graph)
-        self.args = args
-        self.rank, self.world = _rank(), _world()
-        self.num_per_rank = args.data_num // self.world
-        st, ed = self.rank * self.num_per_rank, self.rank * self.num_per_rank + self.num_per_rank
-        self.dev = torch.device("cuda", torch.cuda.current_device())
-        with torch.no_grad():
-            self.fp_cache = ActivationCache(graph_ori, args, st, ed) if with_fp else None
-            self.graph_q, _ = quant_graph(self.graph_new, {k: [np.copy(v[0]), np.copy(v[1])] for k, v in self.clip_val.items()}, args)
-            self.s_q = GraphSession(self.graph_q, device=self.dev)
-            self.bounds, inputs = load_chunks(graph_ori, args, st, ed, self.dev)
-            self.qf = Frontier(self.s_q, self.bounds, inputs)
-
-    def set_weight(self, name, w_new):
-        """w_new (device tensor) becomes initializer `name` of the result, of the fake-quantised graph and of its session."""
-        update_weight(self.graph_new, w_new.cpu().numpy(), name)
-        update_weight(self.graph_q, w_new.cpu().numpy(), name)
-        self.s_q.set_const(name, w_new)
-
-    def finish(self, save_name):
-        """-> the graph with the new weights; rank 0 saves it as <save_name>.onnx."""
-        self.graph_new.update_model()
-        if self.rank == 0 and getattr(self.args, "output_dir", None):
-            self.graph_new.output_dir = self.args.output_dir
-            self.graph_new.save_onnx_model(save_name)
-        return self.graph_new
-
-
 def reconstruct(graph_ori, graph, act_clip_val, weight_clip_val, args, blockwise, save_name, sparse=False):
     """Shared driver of adaround(), brecq() and sparse_quant(): returns the graph with the learned weights."""
-    walk = QuantWalk(graph_ori, graph, act_clip_val, weight_clip_val, args)
-    clip_val, graph_new, graph_q, qf, fp_cache = walk.clip_val, walk.graph_new, walk.graph_q, walk.qf, walk.fp_cache
-    rank, num_per_rank, dev = walk.rank, walk.num_per_rank, walk.dev
+    dist_helper.barrier()
+    walk = QuantWalk(graph, act_clip_val, weight_clip_val, args)
+    clip_val, graph_new, graph_q, rank, dev = walk.clip_val, walk.graph_new, walk.graph_q, walk.rank, walk.dev
+    st, ed = dist_helper.shard_range(args.data_num, rank, walk.world)
+    qf = walk.start(st, ed)
+    fp_cache = ActivationCache(graph_ori, args, st, ed)     # (lazy: nothing runs before the first chunks())
     skip = getattr(args, "skip_layers", []) or []
     drop = bool(getattr(args, "drop", False)) and blockwise
     with_acti = bool(getattr(args, "acti_quant", False))
@@ -263,7 +216,7 @@ def reconstruct(graph_ori, graph, act_clip_val, weight_clip_val, args, blockwise
                 logger.info("{} for: {}".format(head, " ".join(b.name for b in block)))
             already.update(b.name for b in block)
             epochs = args.ada_epoch * len(block)
-            reg = adaround_reg(epochs * math.ceil(num_per_rank / args.ada_bs))
+            reg = adaround_reg(epochs * math.ceil((ed - st) / args.ada_bs))
             if sparse:
                 layers = [_build_sparse_layer(graph, graph_new, block[0], clip_val, args, dev)]
             else:
@@ -281,7 +234,7 @@ def reconstruct(graph_ori, graph, act_clip_val, weight_clip_val, args, blockwise
                                log_every=100 if blockwise else 50, log_head="")
             with torch.no_grad():
                 for b, layer in zip(block, layers):
-                    walk.set_weight(b.input[1], layer.new_weight())
+                    walk.set_const(b.input[1], layer.new_weight())
             del layers, q_in, fp_in, fp_out
         with torch.no_grad():
             qf.run(node)

@@ -19,8 +19,7 @@ import json
 import os
 
 import numpy as np
-import torch.distributed as dist
-
+from .. import dist_helper
 from ..graph import MX_DOMAIN, ONNXGraph
 from ..onnx_io import Node
 from ..utils import logger
@@ -133,7 +132,7 @@ def mx_rotate(graph, args):
     """-> the rotated graph (rank 0 saves it as rotate_model.onnx and writes rotate_report.json); `graph` itself, nothing written,
     where it has no site.  Host work only: every rank ends with the same model."""
     sites, left = find_rotate_sites(graph, getattr(args, "skip_layers", None) or ())
-    rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+    rank = dist_helper.rank()
     if not sites:
         if rank == 0:
             logger.info("--mx_rotate: no MatMul / Gemm with a constant weight and K a multiple of {} in this graph: nothing to do{}".format(

@@ -20,11 +20,10 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .. import ops
+from .. import dist_helper, ops
 from ..executor import GraphSession, load_chunks
 from ..graph import ONNXGraph
 from ..utils import logger
-from .bias_correction import bc_shard
 from .utils import update_weight
 
 __all__ = ["SmoothSite", "SmoothReader", "find_smooth_sites", "smooth_scales", "apply_smooth", "smooth_statistics", "smooth_quant"]
@@ -160,8 +159,8 @@ def smooth_statistics(graph, sites, args, session=None):
     returns the same values.  session: a GraphSession of `graph` on the current device to run the forwards on (default: a new one)."""
     dev = torch.device("cuda", torch.cuda.current_device())
     world = int(getattr(args, "world_size", 1) or 1)
-    world = world if world > 1 and dist.is_available() and dist.is_initialized() else 1
-    st, ed = bc_shard(args.data_num, int(getattr(args, "rank", 0)) if world > 1 else 0, world)
+    world = world if dist_helper.active(world) else 1
+    st, ed = dist_helper.balanced_shard(args.data_num, int(getattr(args, "rank", 0)) if world > 1 else 0, world)
     names = [s.tensor for s in sites]
     offs = np.concatenate([[0], np.cumsum([s.channels for s in sites])]).astype(np.int64)
     buf = torch.zeros(int(offs[-1]), dtype=torch.float32, device=dev)
@@ -182,7 +181,7 @@ def smooth_quant(graph, args):
     """-> the smoothed graph (rank 0 saves it as smooth_model.onnx); `graph` itself, nothing written, where it has no site.
     Every rank calls it (the statistics are shared over the process group) and ends with the same model."""
     sites = find_smooth_sites(graph)
-    rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+    rank = dist_helper.rank()
     if not sites:
         if rank == 0:
             logger.info("--smooth: no LayerNorm affine feeding only MatMul / Gemm weights in this graph: nothing to do")

@@ -10,10 +10,8 @@ input are two torch reductions on the device and the momentum recurrence is eval
 import numpy as np
 import torch
 
-from ..executor import Frontier, GraphSession, load_chunks
-from ..graph import ONNXGraph
-from ..quantize import quant_graph
 from ..utils import logger
+from .walk import QuantWalk
 
 __all__ = ["update_bn", "update_bn_multipass", "fold_running_stats"]
 
@@ -37,16 +35,10 @@ def update_bn_multipass(graph, act_clip_val, weight_clip_val, args, recalibrate=
     saved as update_bn_model.onnx.  recalibrate=False (weight_calibration: the re-calibration there is a
     collective over all ranks) returns the graph alone."""
     from ..tensor_cali import tensor_calibration
-    clip_val = {k: [np.copy(v[0]), np.copy(v[1])] for k, v in {**act_clip_val, **weight_clip_val}.items()}
-    graph_bn = ONNXGraph()
-    graph_bn.copy_from(graph)
-    graph_q, _ = quant_graph(graph_bn, clip_val, args)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    s_q = GraphSession(graph_q, device=dev)
-    # rank 0 walks all images, like the reference (ActivationCache(graph_q, args))
-    bounds, inputs = load_chunks(graph, args, 0, args.data_num, dev)
-    qf = Frontier(s_q, bounds, inputs)
-    for node in graph_q.graph.node:
+    walk = QuantWalk(graph, act_clip_val, weight_clip_val, args)
+    graph_bn = walk.graph_new
+    qf = walk.start(0, args.data_num)       # rank 0 walks all images, like the reference (ActivationCache(graph_q, args))
+    for node in walk.graph_q.graph.node:
         if node.op_type == "BatchNormalization":
             logger.info("Update BN for node: {}".format(node.name))
             means, stds = [], []
@@ -59,16 +51,10 @@ def update_bn_multipass(graph, act_clip_val, weight_clip_val, args, recalibrate=
             mean_name, var_name = node.input[3], node.input[4]
             new_mean, new_var = fold_running_stats(graph_bn.get_initializer(mean_name),
                                                    graph_bn.get_initializer(var_name), means, stds)
-            for g in (graph_bn, graph_q):
-                g.set_initializer(mean_name, new_mean.astype(np.float32))
-                g.set_initializer(var_name, new_var.astype(np.float32))
-            s_q.set_const(mean_name, torch.from_numpy(new_mean.astype(np.float32)))
-            s_q.set_const(var_name, torch.from_numpy(new_var.astype(np.float32)))
+            walk.set_const(mean_name, torch.from_numpy(new_mean.astype(np.float32)))
+            walk.set_const(var_name, torch.from_numpy(new_var.astype(np.float32)))
         qf.run(node)
-    graph_bn.update_model()
-    if getattr(args, "output_dir", None):
-        graph_bn.output_dir = args.output_dir
-        graph_bn.save_onnx_model("update_bn_model")
+    walk.finish("update_bn_model")          # (only rank 0 runs this transform)
     if not recalibrate:
         return graph_bn
     act_clip_val, weight_clip_val = tensor_calibration(graph_bn, args)

@@ -18,7 +18,6 @@ from .update_bn import update_bn
 from .weight_equalization import weight_equalization
 
 
-
 def _reload(name, args):
     args.model = os.path.join(args.output_dir, name + ".onnx")        # utils.update_model_path
     return ONNXGraph.load(args.model, args.output_dir, args.deploy, getattr(args, "model_type", None))
@@ -43,49 +42,41 @@ def weight_calibration(onnx_graph, act_clip_val, weight_clip_val, args):
     with the same model and ranges."""
     graph_after_wt = ONNXGraph()
     graph_after_wt.copy_from(onnx_graph)
-    if getattr(args, "smooth", False):   # (not in the reference) first: everything below sees the smoothed model, as after --we
-        if dist.get_rank() == 0:
-            logger.info("Weight transform: smoothing MatMul inputs...")
-        smoothed = smooth_quant(graph_after_wt, args)      # every rank: the statistics are swept in shards; rank 0 writes the model
+    rank = dist.get_rank()
+
+    def stage(flag, message, every_rank, run, saved, rederive, remark=None):
+        """One transform that writes a model every rank goes on with: rank 0 says `message`; every rank — or rank 0 alone — runs
+        `run(graph)`; barrier; everyone reloads <saved>.onnx and re-derives 'all' ranges or the 'weight' ranges (rank 0 says
+        `remark` first).  A transform that hands back the graph it was given wrote nothing: that graph and its ranges stay."""
+        nonlocal graph_after_wt, act_clip_val, weight_clip_val
+        if not getattr(args, flag, False):
+            return
+        if rank == 0:
+            logger.info(message)
+        out = run(graph_after_wt) if every_rank or rank == 0 else None
         dist.barrier()
-        if smoothed is not graph_after_wt:                  # (a graph without a site is left as it is and nothing is written)
-            graph_after_wt = _reload("smooth_model", args)
-            act_clip_val, weight_clip_val = _recalibrate(graph_after_wt, args)      # activation ranges change with the scales
-    if getattr(args, "mx_rotate", False):   # (not in the reference) behind --smooth, whose scales it keeps; --bc sees the rotated model
-        if dist.get_rank() == 0:
-            logger.info("Weight transform: rotating MX blocks...")
-        rotated = mx_rotate(graph_after_wt, args)          # every rank: host work only; rank 0 writes the model and the report
-        dist.barrier()
-        if rotated is not graph_after_wt:                   # (a graph without a site is left as it is and nothing is written)
-            graph_after_wt = _reload("rotate_model", args)
-            act_clip_val, weight_clip_val = _recalibrate(graph_after_wt, args)      # the rotated tensors and weights are new
-    if getattr(args, "bc", False):   # :21-29 — the reference: rank 0 corrects, everyone reloads, weight (bias) ranges refreshed
-        # here every rank corrects over its shard of the images and the per-channel sums are all-reduced (bias_correction);
-        # --merge reference: rank 0 alone, over all images.  Rank 0 writes the model, everyone reloads it, as before.
-        sharded = dist.get_world_size() > 1 and getattr(args, "merge", "allreduce") != "reference"
-        if dist.get_rank() == 0:
-            logger.info("Weight transform: bias correction...")
-        if sharded or dist.get_rank() == 0:
-            bias_correction(graph_after_wt, act_clip_val, weight_clip_val, args)
-        dist.barrier()
-        graph_after_wt = _reload("update_bias_model", args)
-        weight_clip_val = find_clip_val_minmax_weight(graph_after_wt, args)
-    if getattr(args, "we", False):   # :31-38 — equalise on rank 0, everyone reloads and re-calibrates
-        if dist.get_rank() == 0:
-            logger.info("Weight transform: cross-layer equalisation...")
-            weight_equalization(graph_after_wt, args)
-        dist.barrier()
-        graph_after_wt = _reload("weight_equal_model", args)
-        act_clip_val, weight_clip_val = _recalibrate(graph_after_wt, args)
-    if getattr(args, "update_bn", False):   # :40-53
-        if dist.get_rank() == 0:
-            logger.info("Weight transform: BN statistics of the quantised network...")
-            update_bn(graph_after_wt, act_clip_val, weight_clip_val, args, recalibrate=False)
-        dist.barrier()
-        graph_after_wt = _reload("update_bn_model", args)
-        if dist.get_rank() == 0:
-            logger.info("Re calibration...")
-        act_clip_val, weight_clip_val = _recalibrate(graph_after_wt, args)
+        if out is graph_after_wt:
+            return
+        graph_after_wt = _reload(saved, args)
+        if remark and rank == 0:
+            logger.info(remark)
+        if rederive == "all":
+            act_clip_val, weight_clip_val = _recalibrate(graph_after_wt, args)
+        else:
+            weight_clip_val = find_clip_val_minmax_weight(graph_after_wt, args)
+
+    # --smooth, --mx_rotate (not in the reference): first, so that everything below sees their model, as after --we; the rotation
+    # keeps --smooth's scales.  Every rank runs them (--smooth sweeps its statistics in shards; the rotation is host work).
+    # --bc (:21-29): every rank corrects over its shard of the images (bias_correction); --merge reference: rank 0 alone, over all
+    # images, as the reference.  Only biases change: the weight ranges alone are refreshed.  --we (:31-38), --update_bn (:40-53).
+    bc_sharded = dist.get_world_size() > 1 and getattr(args, "merge", "allreduce") != "reference"
+    stage("smooth", "Weight transform: smoothing MatMul inputs...", True, lambda g: smooth_quant(g, args), "smooth_model", "all")
+    stage("mx_rotate", "Weight transform: rotating MX blocks...", True, lambda g: mx_rotate(g, args), "rotate_model", "all")
+    stage("bc", "Weight transform: bias correction...", bc_sharded,
+          lambda g: bias_correction(g, act_clip_val, weight_clip_val, args), "update_bias_model", "weight")
+    stage("we", "Weight transform: cross-layer equalisation...", False, lambda g: weight_equalization(g, args), "weight_equal_model", "all")
+    stage("update_bn", "Weight transform: BN statistics of the quantised network...", False,
+          lambda g: update_bn(g, act_clip_val, weight_clip_val, args, recalibrate=False), "update_bn_model", "all", "Re calibration...")
     if getattr(args, "sparse", False):     # :65-66 — instead of AdaRound / BRECQ
         args.acti_quant = False
         graph_after_wt = sparse_quant(onnx_graph, graph_after_wt, act_clip_val, weight_clip_val, args)

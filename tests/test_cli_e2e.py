@@ -668,3 +668,89 @@ def test_frontier_walk_is_the_forward_chunk_by_chunk(fq_resnet18, on_host):
         assert got.is_cuda != on_host
         (want,) = sq.run_named({n: v[i:j] for n, v in x.items()}, [out])
         assert got.shape == want.shape and torch.equal(got.cuda(), want)
+
+
+_FR_BOUNDS = [(0, 2), (2, 4), (4, 5)]
+
+
+def _frontier(sq, x, on_host):
+    from dipoorlet_amd import executor
+    chunks = {n: [v[i:j].cpu() if on_host else v[i:j] for i, j in _FR_BOUNDS] for n, v in x.items()}
+    return executor.Frontier(sq, _FR_BOUNDS, chunks, on_host)
+
+
+def _assert_chunks_are_run_named(sq, x, name, got):
+    assert len(got) == len(_FR_BOUNDS)
+    for (i, j), t in zip(_FR_BOUNDS, got):
+        (want,) = sq.run_named({n: v[i:j] for n, v in x.items()}, [name])
+        assert t.shape == want.shape and torch.equal(t.cuda(), want)
+
+
+@pytest.mark.two_forwards
+@pytest.mark.parametrize("on_host", [False, True])
+def test_frontier_hold_keeps_a_tensor_until_drop(fq_resnet18, on_host):
+    """Frontier.hold(name) before the producer has run (as --bc holds a node's output): after every node has run the tensor is
+    still in `env`, 3 chunks, run_named(chunk, [name]) bit for bit, beside the network outputs and nothing else; drop(name) takes
+    it out again."""
+    gq, sq, out, x = fq_resnet18
+    convs = [n for n in gq.graph.node if n.op_type == "Conv"]
+    name = convs[len(convs) // 2].output[0]
+    assert name not in gq.network_outputs
+    fr = _frontier(sq, x, on_host)
+    fr.hold(name)
+    for node in gq.graph.node:
+        fr.run(node)
+    assert set(fr.env) == set(gq.network_outputs) | {name}
+    assert all(t.is_cuda != on_host for t in fr.env[name])
+    _assert_chunks_are_run_named(sq, x, name, fr.env[name])
+    fr.drop(name)
+    assert set(fr.env) == set(gq.network_outputs)
+    _assert_chunks_are_run_named(sq, x, out, fr.env[out])
+
+
+@pytest.mark.two_forwards
+@pytest.mark.parametrize("on_host", [False, True])
+def test_frontier_hold_of_inputs_lets_a_node_run_twice(fq_resnet18, on_host):
+    """The inputs of a Conv node held through inputs_of (as --bc's DPL_BC_RECOMPUTE=1 path holds them): the node runs a second
+    time and gives the same bits; that run consumes the hold, so after the walk `env` holds the network outputs only.  The held
+    names include constants (the folded weight, the bias): they are ignored."""
+    gq, sq, out, x = fq_resnet18
+    convs = [n for n in gq.graph.node if n.op_type == "Conv"]
+    conv = convs[len(convs) // 2]
+    fr = _frontier(sq, x, on_host)
+    held = list(fr.inputs_of(conv))
+    assert any(i in sq.consts for i in held) and any(i not in sq.consts for i in held)
+    for node in gq.graph.node:
+        if node is conv:
+            for i in held:
+                fr.hold(i)
+            fr.run(node)
+            first = [t.clone() for t in fr.env[conv.output[0]]]
+        fr.run(node)
+        if node is conv:
+            assert len(first) == len(_FR_BOUNDS) and all(torch.equal(a, b) for a, b in zip(first, fr.env[conv.output[0]]))
+    assert set(fr.env) == set(gq.network_outputs)
+    _assert_chunks_are_run_named(sq, x, out, fr.env[out])
+
+
+@pytest.mark.two_forwards
+@pytest.mark.parametrize("on_host", [False, True])
+def test_frontier_hold_of_a_fused_away_tensor_changes_nothing(fq_resnet18, on_host):
+    """hold() / drop() on a name no step of the schedule produces — the output of the ReLU that runs inside the graph's first
+    fused FakeQuant step — leave `env` and the walk's result as they are: the tensor never exists, and the rule that frees the
+    others is the one rule."""
+    gq, sq, out, x = fq_resnet18
+    first = next(step for step in sq.schedule(()) if step.pre is not None)
+    name = first.node.input[0]
+    assert name not in sq.consts and all(name not in step.node.output for step in sq.schedule(()))
+    fr = _frontier(sq, x, on_host)
+    fr.hold(name)
+    for node in gq.graph.node:
+        fr.run(node)
+        if node is first.node:
+            live = set(fr.env)
+            assert name not in live
+            fr.drop(name)
+            assert set(fr.env) == live
+    assert set(fr.env) == set(gq.network_outputs)
+    _assert_chunks_are_run_named(sq, x, out, fr.env[out])

@@ -325,3 +325,17 @@ def test_bc_shard_is_a_balanced_partition_of_all_images():
             sizes = [b - a for a, b in parts]
             assert max(sizes) - min(sizes) <= 1
             assert sum(b - a for a, b in (shard_range(n, r, w) for r in range(w))) == (n // w) * w
+
+
+def test_rank_world_without_a_group_and_the_balanced_split_has_one_home(monkeypatch):
+    """dist_helper.rank() / world() are 0 / 1 where no process group exists (whatever an earlier test of this process set up:
+    is_initialized is made to say so), and the balanced split of dist_helper is the very function bias_correction.bc_shard names:
+    the same (st, ed) at every (N, rank, W), N in 0..9, W in 1..4."""
+    from dipoorlet_amd import dist_helper
+    from dipoorlet_amd.weight_transform.bias_correction import bc_shard
+    monkeypatch.setattr(dist, "is_initialized", lambda: False)
+    for n in range(10):
+        for w in range(1, 5):
+            assert dist_helper.rank() == 0 and dist_helper.world() == 1
+            for r in range(w):
+                assert dist_helper.balanced_shard(n, r, w) == bc_shard(n, r, w) == (r * n // w, (r + 1) * n // w)
