@@ -294,6 +294,25 @@ def convt_pads(node, size, kernel):
     return beg + end
 
 
+def convt_col2im(x, w, b, strides, pads, opad, group, dil):
+    """F.conv_transpose1d / 2d written as the definition: every input cell times the kernel — one [Cout / g * prod(k), Cin / g] x
+    [Cin / g, cells] product per group — and each product added where it lands (col2im, F.fold).  On the device the library's own
+    transposed convolution picks, by batch and shape, backward-data solvers that spend about five bits of the operands (8 -> 6
+    channels, 2 x 2, stride 2, two images: 12 to 119 units of 2^-24 sum |x w| off, 2.5 on one image — tests/test_qdq_replay_gpu.py);
+    this form stays within 5 units."""
+    nd = w.dim() - 2
+    if nd == 1:     # a leading spatial axis of one cell
+        y = convt_col2im(x.unsqueeze(2), w.unsqueeze(2), b, (1,) + tuple(strides), (0,) + tuple(pads), (0,) + tuple(opad), group, (1,) + tuple(dil))
+        return y.squeeze(2)
+    n, cin = x.shape[0], x.shape[1]
+    k = tuple(w.shape[2:])
+    out = [(x.shape[2 + i] - 1) * strides[i] - 2 * pads[i] + dil[i] * (k[i] - 1) + opad[i] + 1 for i in range(nd)]
+    wait_warm("blas")
+    cols = torch.matmul(w.reshape(group, cin // group, -1).transpose(1, 2), x.reshape(n, group, cin // group, -1))     # [N, g, Cout / g * prod(k), cells]
+    y = F.fold(cols.reshape(n, -1, cols.shape[-1]), out, k, dil, pads, strides)
+    return y if b is None else y + b.reshape(1, -1, 1, 1)
+
+
 @op("ConvTranspose")
 def _convt(s, node, x, w, b=None):
     nd = w.dim() - 2
@@ -301,9 +320,12 @@ def _convt(s, node, x, w, b=None):
     dil = node.attrs.get("dilations", [1] * nd)
     pads = convt_pads(node, list(x.shape[2:]), list(w.shape[2:]))
     sym = tuple(min(lo, hi) for lo, hi in zip(pads[:nd], pads[nd:]))       # the library crops this much on both sides
-    fn = {1: F.conv_transpose1d, 2: F.conv_transpose2d, 3: F.conv_transpose3d}[nd]
-    y = fn(x, w, b, tuple(strides), sym, tuple(node.attrs.get("output_padding", [0] * nd)),
-           int(node.attrs.get("group", 1)), tuple(dil))
+    opad, group = tuple(node.attrs.get("output_padding", [0] * nd)), int(node.attrs.get("group", 1))
+    if x.is_cuda and nd <= 2 and x.dtype == torch.float32 and w.dtype == torch.float32:
+        y = convt_col2im(x, w, b, tuple(strides), sym, opad, group, tuple(dil))
+    else:
+        fn = {1: F.conv_transpose1d, 2: F.conv_transpose2d, 3: F.conv_transpose3d}[nd]
+        y = fn(x, w, b, tuple(strides), sym, opad, group, tuple(dil))
     for i in range(nd):     # asymmetric pads: the rest of the longer side is cropped here
         lo, hi = pads[i] - sym[i], pads[nd + i] - sym[i]
         if lo or hi:

@@ -147,6 +147,7 @@ class ONNXGraph:
         initializers; here the pair is ONE fused 'FakeQuant' node executed by k_fake_quant (quantize.QDQNode)."""
         if node is not None:
             idx = self.index(node)
+        self._check_channel_axis(q_nodes)
         fq = Node("FakeQuant", [q_nodes.tensor_name], [q_nodes.output], name=q_nodes.q_name)
         self._qdq[fq.name] = q_nodes
         self.graph.node.insert(idx, fq)
@@ -159,6 +160,17 @@ class ONNXGraph:
             zp = onnx_io.Float8E4M3FNBytes(np.zeros(q_nodes.scale.shape, np.uint8))
         self.initializer[q_nodes.zero_point_name] = zp if zp.size > 1 else zp.reshape(())
         self.set_index()
+
+    def _check_channel_axis(self, q):
+        """A per-channel pair has one scale per slice of its tensor along `axis` (QuantizeLinear's rule): refuse any other number —
+        e.g. ranges taken along axis 0 of a ConvTranspose weight, whose output channels lie on axis 1 — where the shape is known."""
+        if getattr(q, "is_mx", False) or not q.per_channel or q.scale.size == 1:
+            return
+        shape = self.initializer[q.tensor_name].shape if q.tensor_name in self.initializer else self.tensor_name_shape_map.get(q.tensor_name)
+        if shape is None or len(shape) == 0:
+            return
+        if q.axis >= len(shape) or int(shape[q.axis]) != q.scale.size:
+            raise ValueError(f"fake-quant of {q.tensor_name}: {q.scale.size} channel scales for axis {q.axis} of shape {tuple(shape)}")
 
     def del_network_output(self, out_name):
         self.network_outputs.remove(out_name)
@@ -242,6 +254,7 @@ class ONNXGraph:
                                   attrs={"axis": int(q.block_axis), "block_size": MX_BLOCK, "elem_type": MX_TYPES[q.fmt][1]}))
             elif n.op_type == "FakeQuant" and expand_fake_quant:   # emit the reference's 2-node form (quantize.py:208-231)
                 q = self._qdq[n.name]
+                self._check_channel_axis(q)
                 float8 |= q.zp_dtype == "float8e4m3fn"
                 attrs = {"axis": q.axis} if q.per_channel else {}
                 nodes.append(Node("QuantizeLinear", [q.tensor_name, q.scale_name, q.zero_point_name], [q.q_output],

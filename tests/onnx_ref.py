@@ -8,6 +8,11 @@ for Split; integer / bool tensors keep their type).  aux: None for an operator t
              an average, the interpolation of |x| for a linear Resize): what a rounding-error bound of an fp32 evaluation scales with
   'min_tap'  (convolutions) per output, the smallest |x w| among the products that reach it: what the output would lose at least if a
              kernel position or a row of padding were dropped.
+  'scales'   (MXQuantizeDequantize) the E8M0 scale code of every block.
+
+QuantizeLinear / DequantizeLinear (opset 13 and 19) are defined in fp32 and compared bit for bit: they compute in fp32 and return
+typed tensors (int8 / uint8 / Float8E4M3FN codes; DequantizeLinear fp32) — see that section.  MXQuantizeDequantize and BlockHadamard,
+this project's own domain, defer to tests/mx_model.py and tests/mx_rotate_model.py, the definitions of record.
 """
 import itertools
 import math
@@ -556,3 +561,155 @@ def constant_of_shape(inputs, attrs, opset):
     v = attrs.get("value")
     v = np.asarray(v).reshape(-1)[0] if v is not None else np.float32(0.0)
     return np.full(_ints(inputs[0]), v), None
+
+
+# ------------------------------------------------------------------------------------------------ matrix products
+@ref("MatMul")
+def matmul(inputs, attrs, opset):
+    a, b = _f(inputs[0]), _f(inputs[1])
+    return np.matmul(a, b), {"mag": np.matmul(np.abs(a), np.abs(b))}
+
+
+@ref("Gemm")
+def gemm(inputs, attrs, opset):
+    """Y = alpha A' B' + beta C: A' = A^T if transA, B' = B^T if transB, C broadcast to [M, N]."""
+    a, b = _f(inputs[0]), _f(inputs[1])
+    c = _f(inputs[2]) if len(inputs) > 2 and inputs[2] is not None else None
+    a = a.T if attrs.get("transA", 0) else a
+    b = b.T if attrs.get("transB", 0) else b
+    alpha, beta = float(attrs.get("alpha", 1.0)), float(attrs.get("beta", 1.0))
+    y, mag = alpha * (a @ b), abs(alpha) * (np.abs(a) @ np.abs(b))
+    if c is not None:
+        y, mag = y + beta * c, mag + np.abs(beta * c)
+    return y, {"mag": mag}
+
+
+# ------------------------------------------------------------------------------------------------ QuantizeLinear / DequantizeLinear
+# Written from the operator text (opset 13 and 19).  These two are defined in the operator's own float type, fp32, and their tests
+# are bit for bit: x and the scales are taken as fp32, x / y_scale is ONE fp32 division, (x - zero_point) * x_scale one fp32
+# product, and DequantizeLinear returns fp32 (not the fp64 of the other entries).  A quantised tensor keeps its type: np.int8,
+# np.uint8, or Float8E4M3FN — one e4m3fn code per element.
+class Float8E4M3FN(np.ndarray):
+    """A tensor of ONNX type FLOAT8E4M3FN (17) as its codes: a uint8 array that remembers what it is.  1 sign bit, 4 exponent bits
+    (bias 7), 3 mantissa bits; exponent 0 is subnormal (m 2^-9); no infinities; 0x7f / 0xff are NaN; largest finite 0x7e = 448."""
+
+    def __new__(cls, codes):
+        return np.require(codes, np.uint8, "C").view(cls)
+
+
+def _e4m3fn_values():
+    """The values of the codes 0x00 .. 0x7e, ascending, from the encoding."""
+    code = np.arange(127)
+    e, m = code >> 3, code & 7
+    return np.where(e == 0, m * 2.0 ** -9, (1.0 + m / 8.0) * 2.0 ** (e - 7.0))
+
+
+E4M3FN_VALUES = _e4m3fn_values()
+
+
+def e4m3fn_decode(codes):
+    c = np.asarray(codes).view(np.uint8)
+    mag = np.where((c & 0x7F) == 0x7F, np.nan, E4M3FN_VALUES[np.minimum(c & 0x7F, 126)])
+    return np.where(c & 0x80, -mag, mag).astype(np.float32)
+
+
+def e4m3fn_encode(v, saturate=True):
+    """Cast fp32 -> float8e4m3fn as the Cast / QuantizeLinear text tabulates it: to the nearest value, a tie to the code with the
+    even mantissa; NaN stays NaN; the sign of zero is kept; out of range (beyond the tie with the 480 the format does not have,
+    and +-inf): +-448 with saturate = 1, NaN without."""
+    v = np.asarray(v, np.float32)
+    a = np.abs(v.astype(np.float64))
+    nan = np.isnan(a)
+    over = a > 464.0
+    a = np.where(nan, 0.0, np.minimum(a, 448.0))
+    hi = np.minimum(np.searchsorted(E4M3FN_VALUES, a, "left"), 126)            # the first code whose value is >= a
+    lo = np.maximum(hi - 1, 0)
+    d_lo, d_hi = a - E4M3FN_VALUES[lo], E4M3FN_VALUES[hi] - a
+    code = np.where(d_hi < d_lo, hi, np.where(d_lo < d_hi, lo, np.where(hi % 2 == 0, hi, lo)))      # (the code's lowest bit is the mantissa's)
+    code = np.where(nan | (over & (not saturate)), 0x7F, code)
+    return Float8E4M3FN((code | np.where(np.signbit(v), 0x80, 0)).astype(np.uint8))
+
+
+def _per_axis(p, x, axis, what):
+    """A scale / zero point against x: a scalar (or one element) for the whole tensor, or 1-D along `axis`, one per slice."""
+    p = np.asarray(p)
+    if p.size == 1:
+        return p.reshape(())
+    axis = axis + x.ndim if axis < 0 else axis
+    if p.ndim != 1 or not 0 <= axis < x.ndim or p.shape[0] != x.shape[axis]:
+        raise ValueError(f"{what}: shape {p.shape} against axis {axis} of a tensor of shape {x.shape}")
+    return p.reshape([-1 if d == axis else 1 for d in range(x.ndim)])
+
+
+@ref("QuantizeLinear")
+def quantize_linear(inputs, attrs, opset):
+    """y = saturate(round_half_even(x / y_scale) + y_zero_point), in the type of y_zero_point (absent: uint8 zero): [-128, 127]
+    for int8, [0, 255] for uint8.  float8e4m3fn (opset 19): y = cast(x / y_scale), attribute saturate (default 1); the zero point
+    only names the type.  The text gives a NaN no integer code: here it takes the lower end, as a conversion that saturates does."""
+    x = np.asarray(inputs[0], np.float32)
+    zp = inputs[2] if len(inputs) > 2 and inputs[2] is not None else np.zeros((), np.uint8)
+    axis = int(attrs.get("axis", 1))
+    scale = _per_axis(np.asarray(inputs[1], np.float32), x, axis, "y_scale")
+    with np.errstate(all="ignore"):
+        r = (x / scale).astype(np.float32)                  # the operator's float type: one fp32 division
+    if isinstance(zp, Float8E4M3FN):
+        if opset < 19:
+            raise ValueError(f"QuantizeLinear: a float8e4m3fn zero point at opset {opset} (19 or later)")
+        return e4m3fn_encode(r, bool(attrs.get("saturate", 1))), None
+    zp = np.asarray(zp)
+    if zp.dtype not in (np.int8, np.uint8):
+        raise ValueError(f"QuantizeLinear: zero point of type {zp.dtype}")
+    info = np.iinfo(zp.dtype)
+    with np.errstate(all="ignore"):
+        q = np.rint(r.astype(np.float64)) + _per_axis(zp, x, axis, "y_zero_point").astype(np.float64)
+    q = np.where(np.isnan(q), info.min, np.clip(q, info.min, info.max))
+    return q.astype(zp.dtype), None
+
+
+@ref("DequantizeLinear")
+def dequantize_linear(inputs, attrs, opset):
+    """y = (x - x_zero_point) * x_scale: the difference is exact (integers; a float8e4m3fn against its zero), the product fp32."""
+    x = inputs[0]
+    zp = inputs[2] if len(inputs) > 2 and inputs[2] is not None else None
+    if zp is not None and (type(zp) is not type(x) if isinstance(x, Float8E4M3FN) or isinstance(zp, Float8E4M3FN)
+                           else np.asarray(zp).dtype != np.asarray(x).dtype):
+        raise ValueError("DequantizeLinear: x and x_zero_point differ in type")
+    axis = int(attrs.get("axis", 1))
+    f8 = isinstance(x, Float8E4M3FN)
+    xv = e4m3fn_decode(x) if f8 else np.asarray(x).astype(np.int32)
+    scale = _per_axis(np.asarray(inputs[1], np.float32), xv, axis, "x_scale")
+    if zp is not None:
+        zv = _per_axis(e4m3fn_decode(zp) if f8 else np.asarray(zp).astype(np.int32), xv, axis, "x_zero_point")
+        xv = xv - zv
+    with np.errstate(all="ignore"):
+        return (xv.astype(np.float32) * scale).astype(np.float32), None
+
+
+def qdq_pair(x, scale, zp, attrs, opset):
+    """DequantizeLinear(QuantizeLinear(x)) with the same scale, zero point and attributes -> (y fp32, the codes)."""
+    q, _ = quantize_linear([x, scale, zp], attrs, opset)
+    y, _ = dequantize_linear([q, scale, zp], attrs, opset)
+    return y, q
+
+
+# ------------------------------------------------------------------------------------------------ this project's domain
+_MX_ELEM = {"float8e4m3fn": "mxfp8", "float4e2m1": "mxfp4"}
+
+
+@ref("MXQuantizeDequantize")
+def mx_quantize_dequantize(inputs, attrs, opset):
+    """The block-scaled Q/DQ of --mx: tests/mx_model.py is the definition.  aux: the E8M0 scale codes, [outer, blocks, inner]."""
+    import mx_model
+    if int(attrs.get("block_size", mx_model.BLOCK)) != mx_model.BLOCK:
+        raise ValueError(f"MXQuantizeDequantize: block_size {attrs.get('block_size')}")
+    y, scales = mx_model.fake_quant_mx(np.asarray(inputs[0], np.float32), int(attrs["axis"]), _MX_ELEM[attrs["elem_type"]], return_scales=True)
+    return y, {"scales": scales}
+
+
+@ref("BlockHadamard")
+def block_hadamard(inputs, attrs, opset):
+    """x . blockdiag(H32) along the last axis, fp32, stage by stage: tests/mx_rotate_model.py is the definition."""
+    import mx_rotate_model
+    if int(attrs.get("block_size", mx_rotate_model.BLOCK)) != mx_rotate_model.BLOCK:
+        raise ValueError(f"BlockHadamard: block_size {attrs.get('block_size')}")
+    return mx_rotate_model.fwht32(np.asarray(inputs[0], np.float32)), None

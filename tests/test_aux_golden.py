@@ -75,11 +75,14 @@ def build_aux_graph():
     from dipoorlet_amd.onnx_io import Node
     g = ONNXGraph()
     g.graph.node = [Node(n["op"], list(n["in"]), list(n["out"]), name=n["name"]) for n in AUX_GRAPH["nodes"]]
-    g.initializer = {k: np.zeros((c, 1), np.float32) for k, c in AUX_GRAPH["initializers"].items()}
+    # c output channels each: on axis 1 for the weight of a ConvTranspose ([Cin, Cout / g, ...]), on axis 0 for everything else
+    transposed = {n["in"][1] for n in AUX_GRAPH["nodes"] if n["op"] == "ConvTranspose" and len(n["in"]) > 1}
+    shape = {k: ((1, c) if k in transposed else (c, 1)) for k, c in AUX_GRAPH["initializers"].items()}
+    g.initializer = {k: np.zeros(shape[k], np.float32) for k in shape}
     g.network_inputs, g.network_outputs = list(AUX_GRAPH["inputs"]), list(AUX_GRAPH["outputs"])
     g.input = list(AUX_GRAPH["inputs"]) + list(AUX_GRAPH["initializers"])
     g.tensor_name_shape_map = {t: [1] for t in AUX_GRAPH["tensors"]}
-    g.tensor_name_shape_map.update({k: [c, 1] for k, c in AUX_GRAPH["initializers"].items()})
+    g.tensor_name_shape_map.update({k: list(v) for k, v in shape.items()})
     g.topologize_graph()
     g.set_index()
     return g

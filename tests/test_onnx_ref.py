@@ -200,3 +200,157 @@ def test_small_definitions():
     assert np.isnan(REF["Relu"]([n], {}, 13)[0][0, 0, 0]) and np.isnan(REF["Clip"]([n, np.float32(-1), np.float32(1)], {}, 13)[0][0, 0, 0])
     y = REF["MaxPool"]([n], {"kernel_shape": [2], "strides": [2]}, 13)[0].reshape(-1)
     assert np.isnan(y[0]) and y[1] == 3
+
+
+# ------------------------------------------------------------------------------------------------ QuantizeLinear / DequantizeLinear
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _f8zero(shape=()):
+    return onnx_ref.Float8E4M3FN(np.zeros(shape, np.uint8))
+
+
+def test_quantize_linear_by_hand():
+    # scale 0.5: x / scale = 1, 3, 5, -1, -3 halves -> 0.5 1.5 2.5 -0.5 -1.5: ties go to the even integer: 0 2 2 -0 -2
+    x = np.array([0.25, 0.75, 1.25, -0.25, -0.75, -0.0, 100.0, -100.0], np.float32)
+    s = np.float32(0.5)
+    # int8, zero point -5: 0 2 2 0 -2 0 -> -5 -3 -3 -5 -7 -5; 200 - 5 saturates to 127, -200 - 5 to -128
+    q, _ = REF["QuantizeLinear"]([x, s, np.array(-5, np.int8)], {}, 13)
+    assert q.dtype == np.int8 and q.tolist() == [-5, -3, -3, -5, -7, -5, 127, -128]
+    # back: (q + 5) * 0.5 = 0 1 1 0 -1 0 66 -61.5, and the zero of a -0.0 is +0.0 (an integer difference has no sign)
+    y, _ = REF["DequantizeLinear"]([q, s, np.array(-5, np.int8)], {}, 13)
+    assert y.dtype == np.float32 and y.tolist() == [0, 1, 1, 0, -1, 0, 66, -61.5] and not np.signbit(y[5])
+    # uint8, zero point 200 (above 127): 200 202 202 200 198 200, saturating to 255 and 0; no zero point at all: uint8 zero
+    q, _ = REF["QuantizeLinear"]([x, s, np.array(200, np.uint8)], {}, 13)
+    assert q.dtype == np.uint8 and q.tolist() == [200, 202, 202, 200, 198, 200, 255, 0]
+    assert REF["DequantizeLinear"]([q, s, np.array(200, np.uint8)], {}, 13)[0].tolist() == [0, 1, 1, 0, -1, 0, 27.5, -100]
+    q, _ = REF["QuantizeLinear"]([x, s], {}, 13)
+    assert q.dtype == np.uint8 and q.tolist() == [0, 2, 2, 0, 0, 0, 200, 0]
+    # x / y_scale is an fp32 division: 0.35 / 0.1 is 3.5 in fp32 (a tie -> 4) and 3.4999999 in fp64 (-> 3)
+    assert np.float32(0.35) / np.float32(0.1) == np.float32(3.5) and np.float64(np.float32(0.35)) / np.float64(np.float32(0.1)) < 3.5
+    assert REF["QuantizeLinear"]([np.array([0.35], np.float32), np.float32(0.1), np.array(0, np.int8)], {}, 13)[0].tolist() == [4]
+    # types must match at DequantizeLinear; a NaN has no integer code in the text: the lower end here
+    with pytest.raises(ValueError, match="differ in type"):
+        REF["DequantizeLinear"]([q, s, np.array(0, np.int8)], {}, 13)
+    assert REF["QuantizeLinear"]([np.array([np.nan], np.float32), s, np.array(3, np.int8)], {}, 13)[0].tolist() == [-128]
+
+
+def test_quantize_linear_per_axis():
+    x = np.arange(-6, 6, dtype=np.float32).reshape(2, 3, 2)          # [[-6 -5] [-4 -3] [-2 -1]] [[0 1] [2 3] [4 5]]
+    s3, z3 = np.array([1, 2, 4], np.float32), np.array([0, 10, -10], np.int8)
+    # axis 1 (the default): rows scaled by 1, 2, 4: -6 -5 | -2 -1.5 | -0.5 -0.25 -> -6 -5 | -2 -2 | -0 -0, plus 0, 10, -10
+    q, _ = REF["QuantizeLinear"]([x, s3, z3], {}, 13)
+    assert q[0].tolist() == [[-6, -5], [8, 8], [-10, -10]] and q[1].tolist() == [[0, 1], [11, 12], [-9, -9]]
+    y, _ = REF["DequantizeLinear"]([q, s3, z3], {"axis": 1}, 13)
+    assert y[0].tolist() == [[-6, -5], [-4, -4], [0, 0]] and y[1].tolist() == [[0, 1], [2, 4], [4, 4]]
+    # axis 0 and axis -1, two scales; a number of scales that is not the axis' extent is refused, at either operator
+    s2 = np.array([1, 4], np.float32)
+    q0, _ = REF["QuantizeLinear"]([x, s2, np.zeros(2, np.int8)], {"axis": 0}, 13)
+    assert q0[0].tolist() == [[-6, -5], [-4, -3], [-2, -1]] and q0[1].tolist() == [[0, 0], [0, 1], [1, 1]]
+    assert np.array_equal(REF["QuantizeLinear"]([x, s2, np.zeros(2, np.int8)], {"axis": -1}, 13)[0][1], [[0, 0], [2, 1], [4, 1]])
+    with pytest.raises(ValueError, match="y_scale"):
+        REF["QuantizeLinear"]([x, s2, np.zeros(2, np.int8)], {"axis": 1}, 13)
+    with pytest.raises(ValueError, match="x_scale"):
+        REF["DequantizeLinear"]([q, s2, np.zeros(2, np.int8)], {"axis": 1}, 13)
+    # one element, whatever the axis says: the whole tensor
+    assert np.array_equal(REF["QuantizeLinear"]([x, np.array([2], np.float32), np.array([1], np.int8)], {"axis": 1}, 13)[0][1],
+                          [[1, 1], [2, 3], [3, 3]])
+
+
+def test_float8e4m3fn_codes_by_hand():
+    enc, dec = onnx_ref.e4m3fn_encode, onnx_ref.e4m3fn_decode
+    # 1 = 2^(7 - 7): exponent field 7, mantissa 0: 0x38; 448 = 1.75 * 2^8: 0x7e; the smallest subnormal 2^-9: 0x01; -0.0: 0x80
+    assert enc(np.array([1.0, 448.0, 2.0 ** -9, -0.0, -1.5], np.float32)).tolist() == [0x38, 0x7E, 0x01, 0x80, 0xBC]
+    assert dec(np.array([0x38, 0x7E, 0x01, 0xBC], np.uint8)).tolist() == [1.0, 448.0, 2.0 ** -9, -1.5] and np.isnan(dec(np.array([0x7F, 0xFF], np.uint8))).all()
+    # ties go to the even mantissa: 1.0625 between 1 (0x38) and 1.125 (0x39) -> 0x38; 1.1875 between 0x39 and 1.25 (0x3a) -> 0x3a;
+    # 2^-10, half the smallest subnormal, between 0x00 and 0x01 -> 0x00; 464 between 448 and the 480 the format lacks -> 448
+    assert enc(np.array([1.0625, 1.1875, 2.0 ** -10, 464.0], np.float32)).tolist() == [0x38, 0x3A, 0x00, 0x7E]
+    # out of range: saturate = 1 (the default) gives +-448, saturate = 0 NaN; NaN stays NaN either way
+    big = np.array([465.0, -1e9, np.inf, -np.inf, np.nan], np.float32)
+    assert enc(big).tolist() == [0x7E, 0xFE, 0x7E, 0xFE, 0x7F] and (enc(big, saturate=False) & 0x7F).tolist() == [0x7F] * 5
+    q, _ = REF["QuantizeLinear"]([big, np.float32(1), _f8zero()], {"saturate": 0}, 19)
+    assert isinstance(q, onnx_ref.Float8E4M3FN) and (np.asarray(q) & 0x7F).tolist() == [0x7F] * 5
+    with pytest.raises(ValueError, match="opset 13"):
+        REF["QuantizeLinear"]([big, np.float32(1), _f8zero()], {}, 13)
+    # every code decodes and encodes back to itself
+    codes = np.array([c for c in range(256) if c & 0x7F != 0x7F], np.uint8)
+    assert np.array_equal(np.asarray(enc(dec(codes))), codes)
+
+
+@pytest.mark.parametrize("signed", [True, False], ids=["int8", "uint8"])
+def test_integer_pair_is_the_oracle_bit_for_bit(signed):
+    """DequantizeLinear(QuantizeLinear(x)) against oracle.np_oracle.fake_quant_qdq (the model the k_fake_quant kernels are held to),
+    per tensor and per channel on axes 0 and 1, stored zero points above 127 included: exact .5 ties under power-of-two scales,
+    both saturation ends and one step inside them, -0.0, and random values under arbitrary scales."""
+    from oracle import np_oracle as O
+    rng = np.random.default_rng(7)
+    zps = [0, -128, 127, -65, 5] if signed else [0, 255, 128, 191, 37]                      # (191 is stored as int8 -65)
+    k = np.arange(-300, 301, dtype=np.float32)
+    for zp in zps:
+        stored = np.array(zp, np.int8 if signed else np.uint8)
+        for scale in (0.5, 0.0625, 4.0, 0.1, 0.0371):
+            s = np.float32(scale)
+            x = np.concatenate([(k + 0.5) * s, k * s, np.nextafter((k + 0.5) * s, np.float32(np.inf)), np.array([-0.0, 0.0, 1e30, -1e30, np.inf, -np.inf], np.float32),
+                                (rng.standard_normal(500) * 100 * scale).astype(np.float32)]).astype(np.float32)
+            y, q = onnx_ref.qdq_pair(x, s, stored, {}, 13)
+            want = O.fake_quant_qdq(x, s, stored.view(np.int8), signed=signed)
+            assert np.array_equal(_bits(y), _bits(want)), (zp, scale)
+            info = np.iinfo(stored.dtype)
+            assert (q == info.min).any() and (q == info.max).any()
+    x = (rng.standard_normal((6, 5, 4)) * 40).astype(np.float32)
+    x[0, 0, 0], x[1, 1, 1] = -0.0, 1e9
+    for axis in (0, 1):
+        n = x.shape[axis]
+        s = (2.0 ** rng.integers(-3, 2, n)).astype(np.float32) * np.where(np.arange(n) % 2, np.float32(1), np.float32(0.3))
+        z = rng.integers(-128, 128, n).astype(np.int8) if signed else rng.integers(0, 256, n).astype(np.uint8)
+        y, _ = onnx_ref.qdq_pair(x, s, z, {"axis": axis}, 13)
+        assert np.array_equal(_bits(y), _bits(O.fake_quant_qdq(x, s, z.view(np.int8), axis=axis, signed=signed))), axis
+
+
+def test_fp8_pair_is_the_fp8_model_bit_for_bit():
+    """Opset 19 with a float8e4m3fn zero point against tests/fp8_model.py fake_quant_fp8 (held to torch's cast; the k_fake_quant
+    FP8 kernels are held to it): every boundary point of the format and the special values, per tensor and per channel."""
+    import fp8_model
+    special = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 1e-9, -1e-9, 2.0 ** -10, -2.0 ** -10, 1e30, -1e30, 2.0 ** -149], np.float32)
+    pts = np.concatenate([fp8_model.boundary_points(), special])
+    for scale in (1.0, 0.5, 0.0371, 3.0, 2.0 ** -20):
+        y, q = onnx_ref.qdq_pair((pts.astype(np.float64) * np.float32(scale)).astype(np.float32), np.float32(scale), _f8zero(), {}, 19)
+        want = fp8_model.fake_quant_fp8((pts.astype(np.float64) * np.float32(scale)).astype(np.float32), scale)
+        nan = np.isnan(want)
+        assert np.array_equal(np.isnan(y), nan) and nan.sum() == 1 and np.array_equal(_bits(y)[~nan], _bits(want)[~nan]), scale
+        v = onnx_ref.e4m3fn_decode(q)
+        assert (v == 448).any() and (v == -448).any()
+    x = np.resize(pts, (4, 6, 50)).copy()
+    for axis in (0, 1):
+        s = np.array([1.0, 0.25, 0.0371, 3.0, 0.5, 7.0][:x.shape[axis]], np.float32)
+        y, _ = onnx_ref.qdq_pair(x, s, _f8zero(s.shape), {"axis": axis}, 19)
+        want = fp8_model.fake_quant_fp8(x, s, axis)
+        nan = np.isnan(want)
+        assert np.array_equal(np.isnan(y), nan) and np.array_equal(_bits(y)[~nan], _bits(want)[~nan]), axis
+
+
+def test_project_domain_entries_defer_to_their_models():
+    import mx_model
+    import mx_rotate_model
+    x = (np.random.default_rng(3).standard_normal((3, 48, 2)) * 5).astype(np.float32)
+    for elem, name in (("mxfp8", "float8e4m3fn"), ("mxfp4", "float4e2m1")):
+        y, aux = REF["MXQuantizeDequantize"]([x], {"axis": 1, "block_size": 32, "elem_type": name}, 13)
+        want, scales = mx_model.fake_quant_mx(x, 1, elem, return_scales=True)
+        assert np.array_equal(_bits(y), _bits(want)) and np.array_equal(aux["scales"], scales) and scales.shape == (3, 2, 2)
+    with pytest.raises(ValueError, match="block_size"):
+        REF["MXQuantizeDequantize"]([x], {"axis": 1, "block_size": 16, "elem_type": "float4e2m1"}, 13)
+    x = np.random.default_rng(4).standard_normal((5, 64)).astype(np.float32)
+    assert np.array_equal(_bits(REF["BlockHadamard"]([x], {"block_size": 32}, 13)[0]), _bits(mx_rotate_model.fwht32(x)))
+
+
+def test_gemm_and_matmul_by_hand():
+    a = np.array([[1, -2], [3, 4]], np.float32)
+    b = np.array([[5, 6], [-7, 8]], np.float32)
+    # a b = [[5 + 14, 6 - 16], [15 - 28, 18 + 32]]; the magnitudes add up without signs
+    y, aux = REF["MatMul"]([a, b], {}, 13)
+    assert y.tolist() == [[19, -10], [-13, 50]] and aux["mag"].tolist() == [[19, 22], [43, 50]]
+    # Gemm: 2 a^T b^T + 3 c, c = [10, -20] along N.  a^T = [[1, 3], [-2, 4]], b^T = [[5, -7], [6, 8]]: a^T b^T = [[23, 17], [14, 46]]
+    y, aux = REF["Gemm"]([a, b, np.array([10, -20], np.float32)], {"transA": 1, "transB": 1, "alpha": 2.0, "beta": 3.0}, 13)
+    assert y.tolist() == [[76, -26], [58, 32]] and aux["mag"].tolist() == [[2 * 23 + 30, 2 * 31 + 60], [2 * 34 + 30, 2 * 46 + 60]]
+    assert REF["Gemm"]([a, b], {}, 13)[0].tolist() == [[19, -10], [-13, 50]]
