@@ -90,6 +90,7 @@ def check_args(args):
     FakeQuant nodes only: the clip sweeps that know nothing of the grid and the transforms that run the fake-quantised forward
     work unchanged; what assumes or learns an integer grid does not."""
     from .platform_settings import platform_setting_table
+    from .quantize import FORMATS
     alpha = getattr(args, "smooth_alpha", 0.5)
     if not 0.0 <= alpha <= 1.0:      # (a NaN too)
         raise ValueError(f"--smooth_alpha must lie in [0, 1], got {alpha}")
@@ -119,7 +120,7 @@ def check_args(args):
         if why:
             raise ValueError(f"-A qmse is not supported with -D {args.deploy}: {why}, and the search models a symmetric grid with a "
                              "free scale.  Supported: -D trt, -D stpu, -D ocp_fp8")
-    if not qi["type"].startswith("Float8"):
+    if FORMATS[qi["type"]].integer:
         return
     bad = [flag for flag, on in (("-A mse", args.act_quant == "mse"),        # OCTAV's fixed point assumes a uniform grid
                                  ("-A kl", args.act_quant == "kl"),          # its levels are integer levels

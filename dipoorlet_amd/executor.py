@@ -940,7 +940,7 @@ def relu_fusion(graph, folded, consts, keep=(), shape1=None):
         return shape_of(p.input[0]) if p is not None and p.op_type == "FakeQuant" else None
 
     for q in nodes:
-        if q.op_type != "FakeQuant" or q.input[0] in consts or graph._qdq[q.name].is_mx:     # (the MX kernel has no PRE form)
+        if q.op_type != "FakeQuant" or q.input[0] in consts or not graph._qdq[q.name].format.takes_pre:
             continue
         r = producer.get(q.input[0])
         if r is None or r.op_type != "Relu" or len(r.output) != 1 or not sole(r.output[0], q):
@@ -1068,8 +1068,9 @@ class GraphSession(ActivationSession):
 
     def _fold_weights(self, nodes):
         """Fake-quantised WEIGHTS are constants: quantised once, here, instead of on every forward — every weight of the graph
-        in ONE launch (dpl_fake_quant_items — dpl_fake_quant_fp8_items for FP8 nodes, quantize.QDQNode.fmt — over the set of
-        weight tensors, per-channel rows along each weight's own axis: 54 tensors for ResNet-50) rather than one launch and two parameter uploads per weight (quantize.py:197-239 builds a Q/DQ
+        in ONE launch per static format (ops.FakeQuantSet, its rows from the format's record, quantize.NumberFormat.set_rows — over
+        the set of weight tensors, per-channel rows along each weight's own axis: 54 tensors for ResNet-50) rather than one launch and
+        two parameter uploads per weight (quantize.py:197-239 builds a Q/DQ
         pair per weight; ONNXRuntime runs each on every inference)."""
         if not nodes:
             return
@@ -1079,39 +1080,28 @@ class GraphSession(ActivationSession):
                 self.consts[n.output[0]] = run_op(self, n, w) if w.is_cuda else w
             return
         from . import ops
-        from .quantize import FP8_E4M3
-        mx = [self.graph._qdq[n.name].is_mx for n in nodes]
-        if any(mx):      # block-scaled weights (--mx): no parameter rows for the set form — each once through its node's apply()
-            for n, w, f in zip(nodes, ws, mx):
-                if f:
+        groups = {}     # by the format's whole-set launch (one platform, one format — a hand-made graph, or --mx, may mix them)
+        for n, w in zip(nodes, ws):
+            group = groups.setdefault(self.graph._qdq[n.name].format.set_fmt, ([], []))
+            group[0].append(n)
+            group[1].append(w)
+        for set_fmt, (g_nodes, g_ws) in groups.items():
+            if set_fmt is None:     # (block-scaled weights: no parameter rows for the set form — each once through its node's apply())
+                for n, w in zip(g_nodes, g_ws):
                     self.consts[n.output[0]] = run_op(self, n, w)
-            self._fold_weights([n for n, f in zip(nodes, mx) if not f])
-            return
-        fp8 = [self.graph._qdq[n.name].fmt == FP8_E4M3 for n in nodes]
-        if any(fp8) and not all(fp8):      # (one platform, one format — a hand-made graph may mix them: a launch per format)
-            self._fold_weights([n for n, f in zip(nodes, fp8) if f])
-            self._fold_weights([n for n, f in zip(nodes, fp8) if not f])
-            return
-        plan = ops.TensorSetPlan([w.numel() for w in ws], 1, self.device)
-        # all scales / zero points of the set in two transfers
-        qs = [self.graph._qdq[n.name] for n in nodes]
-        sizes = [q.scale.size for q in qs]
-        scale = torch.from_numpy(np.concatenate([q.scale for q in qs]).astype(np.float32)).to(self.device)
-        if not fp8[0]:
-            zp = torch.from_numpy(np.concatenate([np.broadcast_to(q.zero_point_as_stored(), q.scale.shape) for q in qs]).astype(np.int32)).to(self.device)
-        params, off = [], 0
-        for q, w, k in zip(qs, ws, sizes):
-            lo, hi = q.saturation()
-            inner = 1
-            if k > 1:       # channel c of element i = (i / inner) % n_channels: inner = the elements behind the channel axis
-                if w.shape[q.axis] != k:
-                    raise ValueError(f"fake-quant of {q.tensor_name}: {k} channel scales for axis {q.axis} of {tuple(w.shape)}")
-                inner = int(np.prod(w.shape[q.axis + 1:])) if q.axis + 1 < w.dim() else 1
-            params.append((scale[off:off + k], inner) if fp8[0] else (scale[off:off + k], zp[off:off + k], inner, lo, hi))
-            off += k
-        outs = ops.FakeQuantSet(plan, params, fmt="fp8" if fp8[0] else "int")([w.reshape(1, -1) for w in ws])
-        for n, w, y in zip(nodes, ws, outs):
-            self.consts[n.output[0]] = y.view(w.shape)
+                continue
+            qs, inners = [self.graph._qdq[n.name] for n in g_nodes], []
+            for q, w in zip(qs, g_ws):
+                k, inner = q.scale.size, 1
+                if k > 1:       # channel c of element i = (i / inner) % n_channels: inner = the elements behind the channel axis
+                    if w.shape[q.axis] != k:
+                        raise ValueError(f"fake-quant of {q.tensor_name}: {k} channel scales for axis {q.axis} of {tuple(w.shape)}")
+                    inner = int(np.prod(w.shape[q.axis + 1:])) if q.axis + 1 < w.dim() else 1
+                inners.append(inner)
+            plan = ops.TensorSetPlan([w.numel() for w in g_ws], 1, self.device)
+            outs = ops.FakeQuantSet(plan, qs[0].format.set_rows(qs, inners, self.device), fmt=set_fmt)([w.reshape(1, -1) for w in g_ws])
+            for n, w, y in zip(g_nodes, g_ws, outs):
+                self.consts[n.output[0]] = y.view(w.shape)
 
     def _upload_consts(self):
         """Every initializer to the device ONCE: the fp32 ones (weights, biases: 102 MB for ResNet-50) are packed into one

@@ -151,20 +151,13 @@ class ONNXGraph:
         fq = Node("FakeQuant", [q_nodes.tensor_name], [q_nodes.output], name=q_nodes.q_name)
         self._qdq[fq.name] = q_nodes
         self.graph.node.insert(idx, fq)
-        if getattr(q_nodes, "is_mx", False):       # block-scaled: the scales are the data's own — no initializers
-            self.set_index()
-            return
-        self.initializer[q_nodes.scale_name] = q_nodes.scale if q_nodes.scale.size > 1 else q_nodes.scale.reshape(())
-        zp = q_nodes.zero_point if q_nodes.symmetric else q_nodes.zero_point.view(np.uint8)
-        if q_nodes.zp_dtype == "float8e4m3fn":     # the zero of the format: one 0x00 byte per element (TensorProto type 17)
-            zp = onnx_io.Float8E4M3FNBytes(np.zeros(q_nodes.scale.shape, np.uint8))
-        self.initializer[q_nodes.zero_point_name] = zp if zp.size > 1 else zp.reshape(())
+        self.initializer.update(q_nodes.format.initializers(q_nodes))
         self.set_index()
 
     def _check_channel_axis(self, q):
         """A per-channel pair has one scale per slice of its tensor along `axis` (QuantizeLinear's rule): refuse any other number —
         e.g. ranges taken along axis 0 of a ConvTranspose weight, whose output channels lie on axis 1 — where the shape is known."""
-        if getattr(q, "is_mx", False) or not q.per_channel or q.scale.size == 1:
+        if not q.format.static or not q.per_channel or q.scale.size == 1:
             return
         shape = self.initializer[q.tensor_name].shape if q.tensor_name in self.initializer else self.tensor_name_shape_map.get(q.tensor_name)
         if shape is None or len(shape) == 0:
@@ -243,34 +236,22 @@ class ONNXGraph:
     def to_model(self, expand_fake_quant=True):
         m = onnx_io.Model()
         m.ir_version, m.opset, m.graph_name = self.ir_version, dict(self.opset), self.graph.name
-        nodes, float8, mx_domain = [], False, False
+        nodes, opset, ir_version = [], {}, 0       # ... what the saved FakeQuant nodes require of the file (quantize.NumberFormat)
         for n in self.graph.node:
-            if n.op_type == "FakeQuant" and expand_fake_quant and self._qdq[n.name].is_mx:
-                # ONNX has no dynamic block-scaled Q/DQ pair to expand into: ONE node of this project's own domain
-                from .quantize import MX_BLOCK, MX_TYPES
-                q = self._qdq[n.name]
-                mx_domain = True
-                nodes.append(Node("MXQuantizeDequantize", [q.tensor_name], [q.output], name=q.q_name, domain=MX_DOMAIN,
-                                  attrs={"axis": int(q.block_axis), "block_size": MX_BLOCK, "elem_type": MX_TYPES[q.fmt][1]}))
-            elif n.op_type == "FakeQuant" and expand_fake_quant:   # emit the reference's 2-node form (quantize.py:208-231)
+            if n.op_type == "FakeQuant" and expand_fake_quant:
                 q = self._qdq[n.name]
                 self._check_channel_axis(q)
-                float8 |= q.zp_dtype == "float8e4m3fn"
-                attrs = {"axis": q.axis} if q.per_channel else {}
-                nodes.append(Node("QuantizeLinear", [q.tensor_name, q.scale_name, q.zero_point_name], [q.q_output],
-                                  name=q.q_name, attrs=attrs))
-                nodes.append(Node("DequantizeLinear", [q.q_output, q.scale_name, q.zero_point_name], [q.output],
-                                  name=q.dq_name, attrs=attrs))
+                nodes += q.format.onnx_nodes(q)
+                opset.update(q.format.opset)
+                ir_version = max(ir_version, q.format.ir_version)
             else:
-                mx_domain |= n.domain == MX_DOMAIN
+                if n.domain == MX_DOMAIN:
+                    opset[MX_DOMAIN] = 1
                 nodes.append(n)
         m.nodes = nodes
-        if float8:
-            # QuantizeLinear / DequantizeLinear take a float8e4m3fn zero point from opset 19 (IR version 9) on
-            m.opset[""] = max(m.opset.get("", 0), 19)
-            m.ir_version = max(m.ir_version, 9)
-        if mx_domain:
-            m.opset[MX_DOMAIN] = 1
+        for domain in sorted(opset):
+            m.opset[domain] = max(m.opset.get(domain, 0), opset[domain])
+        m.ir_version = max(m.ir_version, ir_version)
         m.initializers = dict(self.initializer)
         m.inputs = [(n, onnx_io.FLOAT, self.tensor_name_shape_map.get(n)) for n in self.network_inputs]
         m.outputs = [(n, onnx_io.FLOAT, self.tensor_name_shape_map.get(n)) for n in self.network_outputs]

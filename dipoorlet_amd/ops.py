@@ -1190,6 +1190,14 @@ def gptq_block(w, c0, nb, u, grid, err=None):
     return err
 
 
+def gptq_nearest(w, grid):
+    """w (fp32 [rows, K]) rounded to nearest on `grid`, per-row parameters along axis 0: what GPTQ's result is measured against."""
+    axis = 0 if grid.scale.numel() > 1 else None
+    if grid.fmt == "int":
+        return fake_quant(w, grid.scale, grid.zero_point, grid.qlo, grid.qhi, axis=axis)
+    return fake_quant_fp8(w, grid.scale, axis=axis)
+
+
 def gptq_quantize(w, u, grid, block=GPTQ_MAX_BLOCK):
     """GPTQ over a whole layer (tests/gptq_model.py gptq_layer32): the blocks left to right through gptq_block, and between them
     W[:, c0 + nb:] -= Err @ U[c0:c0 + nb, c0 + nb:], one fp32 GEMM of the BLAS library (the only step whose summation order is not

@@ -8,11 +8,16 @@ reference-generated golden rows) and the Q->DQ pair is ONE fused HIP kernel (k_f
 
 Naming follows the reference so the emitted graph / deploy files stay drop-in:
     <t>_scale, <t>_zero_point, <t>_q, <t>_dq, nodes <t>_QuantizeLinear / <t>_DequantizeLinear.
+
+What differs between number formats is in FORMATS, one record per quantisation "type" of platform_settings' tables; a QDQNode
+holds its record (`format`) and every other module asks the node ("Number formats").
 """
 import numpy as np
 import torch
 
-from . import ops
+from . import onnx_io, ops
+from .graph import MX_DOMAIN, ONNXGraph
+from .onnx_io import Node
 from .utils import logger
 
 QTENSORSUFFIX = "_q"
@@ -20,75 +25,10 @@ DQTENSORSUFFIX = "_dq"
 QUANT_NODE_NAME_LIST = ["QuantizeLinear", "DequantizeLinear"]
 FP8_E4M3 = "Float8E4M3FN"      # the quantisation type of OCP FP8 E4M3 (platform `ocp_fp8`); every other platform: "Linear"
 E4M3_MAX = 448
-# OCP Microscaling (`--mx`, platform_settings.mx_setting_table): quantisation type -> (ops.fake_quant_mx's elem, the element type as
-# the emitted node names it, the largest element value).  Blocks of 32 along QDQNode.block_axis share a power-of-two scale taken
-# from the data: such a node has no static scale and no zero point.
-MX_TYPES = {"MXFP8E4M3": ("mxfp8", "float8e4m3fn", 448), "MXFP4E2M1": ("mxfp4", "float4e2m1", 6)}
 MX_BLOCK = ops.MX_BLOCK
 MX_NODES = ["MatMul", "Gemm"]
 MERGE_RELU = ["Conv", "Gemm", "Eltwise", "Add"]
 RELU_TYPE = ["Relu", "PRelu", "Mul"]
-
-
-class QDQNode:
-    """The fused fake-quant stand-in for the reference's 2-node `graph_quant` (quantize.py:197-239).  `fmt`: the number format
-    of the grid — "Linear" (an 8-bit integer one), FP8_E4M3 (scale only: the zero point is 0, written as a float8e4m3fn) or one of
-    MX_TYPES (block-scaled along `block_axis`: scale and zero point carry no meaning and are not emitted).  `suffix`: appended to
-    every name of the node — a tensor that already has a fake-quant node of another kind keeps that one's names for it."""
-
-    def __init__(self, tensor_name, tensor_shape, scale, zero_point, need_transpose, per_channel, symmetric, fmt="Linear",
-                 block_axis=None, suffix=""):
-        self.tensor_name = tensor_name
-        self.tensor_shape = list(tensor_shape) if tensor_shape is not None else None
-        self.scale = np.asarray(scale, np.float32).reshape(-1)
-        self.zero_point = np.asarray(zero_point, np.int8).reshape(-1)  # stored through int8 like :185
-        self.per_channel = bool(per_channel)
-        self.symmetric = bool(symmetric)
-        self.axis = (1 if need_transpose else 0) if per_channel else None  # :214, :220
-        self.fmt = fmt
-        self.block_axis = block_axis
-        self.suffix = suffix
-        self.zp_dtype = "float8e4m3fn" if fmt == FP8_E4M3 else "int8" if symmetric else "uint8"      # :205-206
-        self.q_name = tensor_name + "_QuantizeLinear" + suffix
-        self.dq_name = tensor_name + "_DequantizeLinear" + suffix
-        self.scale_name = tensor_name + "_scale" + suffix
-        self.zero_point_name = tensor_name + "_zero_point" + suffix
-        self.q_output = tensor_name + QTENSORSUFFIX + suffix
-        self.output = tensor_name + DQTENSORSUFFIX + suffix
-        self._dev = None
-
-    @property
-    def is_mx(self):
-        return self.fmt in MX_TYPES
-
-    def zero_point_as_stored(self):
-        """The integers an ONNX runtime sees: int8 values, or the same bytes read as uint8."""
-        return self.zero_point.astype(np.int32) if self.symmetric else self.zero_point.view(np.uint8).astype(np.int32)
-
-    def saturation(self):
-        """QuantizeLinear saturates to the zero-point dtype's full range (ONNX opset 13) — note: -128,
-        not the q_min = -127 the reference computes at :134 for its torch-side code.  FP8: saturate = 1, the largest finite value."""
-        if self.fmt == FP8_E4M3:
-            return -E4M3_MAX, E4M3_MAX
-        if self.is_mx:
-            return -MX_TYPES[self.fmt][2], MX_TYPES[self.fmt][2]
-        return (-128, 127) if self.symmetric else (0, 255)
-
-    def apply(self, x, out=None, pre=None, x2=None):
-        """Fake-quantise a device tensor: QuantizeLinear -> DequantizeLinear semantics, one kernel (pre / x2: the producer's
-        ReLU or Add + ReLU fused in, ops.fake_quant).  An MX node: ops.fake_quant_mx along block_axis, which has no `pre` form."""
-        if self.is_mx:
-            if pre is not None:
-                raise ValueError(f"{self.q_name}: a block-scaled ({self.fmt}) fake-quant node takes no fused producer ({pre!r})")
-            return ops.fake_quant_mx(x, self.block_axis, MX_TYPES[self.fmt][0], out=out)
-        if self._dev is None or self._dev[0].device != x.device:
-            self._dev = (torch.from_numpy(self.scale).to(x.device),
-                         torch.from_numpy(self.zero_point_as_stored()).to(x.device))
-        lo, hi = self.saturation()
-        axis = self.axis if self.scale.size > 1 else None
-        if self.fmt == FP8_E4M3:
-            return ops.fake_quant_fp8(x, self._dev[0], axis=axis, out=out, pre=pre, x2=x2)
-        return ops.fake_quant(x, self._dev[0], self._dev[1], lo, hi, axis=axis, out=out, pre=pre, x2=x2)
 
 
 def _int8_wrap(zero_point, shape):
@@ -99,9 +39,9 @@ def _int8_wrap(zero_point, shape):
     return ((z + 128) % 256 - 128).astype(np.int8)
 
 
-def _symmetric_grid(bits, lo, hi):
-    """scale = max(|lo|, |hi|) / (2^(b-1) - 1) per channel, grid [-(2^(b-1) - 1), 2^(b-1) - 1], zero point 0."""
-    top = 2 ** (bits - 1) - 1
+def _symmetric_grid(top, lo, hi):
+    """scale = max(|lo|, |hi|) / top per channel — the clip lands on the grid's largest value `top` (2^(b-1) - 1; 448 for E4M3) —,
+    grid [-top, top], zero point 0."""
     n = lo.size if isinstance(lo, np.ndarray) else 1
     q_hi = [top] * n
     scale = np.asarray(np.max(np.abs([lo, hi]), axis=0)) / q_hi
@@ -131,53 +71,225 @@ def _affine_grid(bits, lo, hi, tensor_name):
     return [float(scale)], zp, [int(-zp)], [int(levels - zp)]
 
 
-def _e4m3_grid(lo, hi):
-    """scale = max(|lo|, |hi|) / 448 per channel — the clip lands on the format's largest finite value —, computed as
-    _symmetric_grid computes its own; zero point 0, saturation at +-448."""
-    n = lo.size if isinstance(lo, np.ndarray) else 1
-    scale = np.asarray(np.max(np.abs([lo, hi]), axis=0)) / ([E4M3_MAX] * n)
-    scale = np.where(scale == 0, 1.0, scale)
-    return scale.tolist()
+NO_STATIC_GRID = "its weight has no static grid"        # why --gptq leaves a layer whose weight is not on a static grid
+
+
+def _in_one_transfer(arrays, dtype, device):
+    """Host arrays -> their device copies, views of ONE uploaded tensor."""
+    return torch.from_numpy(np.concatenate(arrays).astype(dtype)).to(device).split([a.size for a in arrays])
+
+
+class NumberFormat:
+    """Everything that differs between the number formats a fake-quant node rounds to.  The fields, and below them what the two
+    static formats share: a scale and a zero point per tensor or per channel, saved as a QuantizeLinear -> DequantizeLinear pair."""
+    static = True            # scale / zero-point initializers and, per channel, an axis to check against the tensor's shape
+    takes_pre = True         # apply() has a form with the producer's ReLU / Add + ReLU inside the kernel
+    block_scaled = False     # blocks along QDQNode.block_axis share a scale taken from the data: along the batch axis they mix samples
+    integer = False          # a uniform grid: what -A mse, -A kl, --adaround, --brecq and --sparse assume or learn
+    set_fmt = None           # ops.FakeQuantSet's fmt for a whole-set launch (set_rows); None: node by node through apply()
+    zp_dtype = bounds = None     # by `symmetric` (False, True): the zero point's dtype, the (lowest, highest) value the node saturates to
+    opset, ir_version = {}, 0    # what the saved nodes require of the file: {domain: operator-set version} and the IR version, at least
+
+    def __init__(self, name):
+        self.name = name
+
+    def __deepcopy__(self, memo):       # (a copied graph's nodes share the records)
+        return self
+
+    def initializers(self, q):
+        """{name: array} the node adds to a graph (utils.py:198-206): a single value as a 0-d tensor."""
+        zp = self.zero_point_tensor(q)
+        return {q.scale_name: q.scale if q.scale.size > 1 else q.scale.reshape(()), q.zero_point_name: zp if zp.size > 1 else zp.reshape(())}
+
+    def onnx_nodes(self, q):
+        """The nodes a FakeQuant node is saved as: the reference's 2-node form (quantize.py:208-231)."""
+        attrs = {"axis": q.axis} if q.per_channel else {}
+        return [Node("QuantizeLinear", [q.tensor_name, q.scale_name, q.zero_point_name], [q.q_output], name=q.q_name, attrs=attrs),
+                Node("DequantizeLinear", [q.q_output, q.scale_name, q.zero_point_name], [q.output], name=q.dq_name, attrs=attrs)]
+
+
+class _Linear(NumberFormat):
+    """An 8-bit integer grid (every platform of the reference)."""
+    integer, set_fmt = True, "int"
+    # QuantizeLinear saturates to the zero-point dtype's full range (ONNX opset 13) — note: -128, not the q_min = -127 the
+    # reference computes at :134 for its torch-side code
+    zp_dtype, bounds = ("uint8", "int8"), ((0, 255), (-128, 127))      # :205-206
+
+    def qnode(self, param, name, shape, range, need_transpose, block_axis, suffix):
+        per_channel = bool(param.get("per_channel", False))
+        symmetric = param["symmetric"]
+        if not per_channel:
+            range[0], range[1] = np.min(range[0]), np.max(range[1])
+            if param.get("dynamic_sym", False) and np.abs(range[0] - 0.0) < 1e-6:
+                symmetric = False
+        if symmetric:
+            scale, zero_point, q_min, q_max = _symmetric_grid(2 ** (param["bit_width"] - 1) - 1, range[0], range[1])
+        else:
+            scale, zero_point, q_min, q_max = _affine_grid(param["bit_width"], range[0], range[1], name)
+        if param.get("log_scale", False):
+            scale = 2 ** np.round(np.log2(scale))
+        scale = np.array(scale, dtype=np.float32)
+        return QDQNode(name, shape, scale, _int8_wrap(zero_point, scale.shape), need_transpose, per_channel, symmetric, suffix=suffix), q_min, q_max
+
+    def apply(self, q, x, out, pre, x2):
+        scale, zp = q.on_device(x.device)
+        lo, hi = self.bounds[q.symmetric]
+        return ops.fake_quant(x, scale, zp, lo, hi, axis=q.axis if q.scale.size > 1 else None, out=out, pre=pre, x2=x2)
+
+    def zero_point_tensor(self, q):
+        return q.zero_point if q.symmetric else q.zero_point.view(np.uint8)
+
+    def set_rows(self, qs, inners, device):
+        """ops.FakeQuantSet's parameter rows for the nodes `qs`: all scales / zero points of the set in two transfers."""
+        scales = _in_one_transfer([q.scale for q in qs], np.float32, device)
+        zps = _in_one_transfer([np.broadcast_to(q.zero_point_as_stored(), q.scale.shape) for q in qs], np.int32, device)
+        return [(s, z, inner, *q.saturation()) for q, s, z, inner in zip(qs, scales, zps, inners)]
+
+    def gptq_grid(self, q, q_min, q_max, dev):
+        """-> (ops.GptqGrid, None) or (None, why not).  qlo / qhi: the platform's bit width (what AdaRound clamps to) inside the
+        node's own saturation, so a weight on this grid passes the graph's node unchanged."""
+        zp = q.zero_point_as_stored()
+        lo, hi = np.asarray(q_min, np.int64).reshape(-1) + zp, np.asarray(q_max, np.int64).reshape(-1) + zp
+        if not (np.all(lo == lo[0]) and np.all(hi == hi[0])):
+            return None, "its channels do not share one integer range"
+        sat_lo, sat_hi = q.saturation()
+        return ops.GptqGrid("int", torch.from_numpy(q.scale.copy()).to(dev), torch.from_numpy(zp.astype(np.int32)).to(dev),
+                            max(int(lo[0]), sat_lo), min(int(hi[0]), sat_hi)), None
+
+
+class _FP8(NumberFormat):
+    """OCP FP8 E4M3 (platform `ocp_fp8`): a scale only — the zero point is 0, written as a float8e4m3fn, which QuantizeLinear /
+    DequantizeLinear take from opset 19 (IR version 9) on."""
+    set_fmt, top = "fp8", E4M3_MAX
+    zp_dtype, bounds = ("float8e4m3fn",) * 2, ((-E4M3_MAX, E4M3_MAX),) * 2       # saturate = 1: the largest finite value
+    opset, ir_version = {"": 19}, 9
+
+    def qnode(self, param, name, shape, range, need_transpose, block_axis, suffix):
+        per_channel = bool(param.get("per_channel", False))
+        if not per_channel:
+            range[0], range[1] = np.min(range[0]), np.max(range[1])
+        scale = np.array(_symmetric_grid(self.top, range[0], range[1])[0], dtype=np.float32).reshape(-1)
+        return (QDQNode(name, shape, scale, np.zeros(scale.shape, np.int8), need_transpose, per_channel, True, fmt=self.name, suffix=suffix),
+                -self.top, self.top)
+
+    def apply(self, q, x, out, pre, x2):
+        return ops.fake_quant_fp8(x, q.on_device(x.device)[0], axis=q.axis if q.scale.size > 1 else None, out=out, pre=pre, x2=x2)
+
+    def zero_point_tensor(self, q):     # the zero of the format: one 0x00 byte per element (TensorProto type 17)
+        return onnx_io.Float8E4M3FNBytes(np.zeros(q.scale.shape, np.uint8))
+
+    def set_rows(self, qs, inners, device):
+        return list(zip(_in_one_transfer([q.scale for q in qs], np.float32, device), inners))
+
+    def gptq_grid(self, q, q_min, q_max, dev):
+        return ops.GptqGrid("e4m3", torch.from_numpy(q.scale.copy()).to(dev)), None
+
+
+class _MX(NumberFormat):
+    """OCP Microscaling (`--mx`, platform_settings.mx_setting_table): blocks of MX_BLOCK along QDQNode.block_axis share a
+    power-of-two scale taken from the data — no static scale, no zero point, no initializers; the clip range is ignored.  ONNX has
+    no dynamic block-scaled Q/DQ pair to expand into: the node is saved as ONE node of this project's own domain."""
+    static = takes_pre = False
+    block_scaled = True
+    opset = {MX_DOMAIN: 1}
+    zp_dtype = ("int8",) * 2            # (of the placeholder zero point: never written)
+
+    def __init__(self, name, elem, elem_type, top):
+        """elem: ops.fake_quant_mx's name of the element format; elem_type: as the saved node names it; top: the largest element."""
+        self.name, self.elem, self.elem_type, self.top, self.bounds = name, elem, elem_type, top, ((-top, top),) * 2
+
+    def qnode(self, param, name, shape, range, need_transpose, block_axis, suffix):
+        return (QDQNode(name, shape, np.ones(1, np.float32), np.zeros(1, np.int8), False, False, True, fmt=self.name,
+                        block_axis=int(block_axis), suffix=suffix), -self.top, self.top)
+
+    def apply(self, q, x, out, pre, x2):
+        if pre is not None:
+            raise ValueError(f"{q.q_name}: a block-scaled ({self.name}) fake-quant node takes no fused producer ({pre!r})")
+        return ops.fake_quant_mx(x, q.block_axis, self.elem, out=out)
+
+    def initializers(self, q):
+        return {}
+
+    def onnx_nodes(self, q):
+        return [Node("MXQuantizeDequantize", [q.tensor_name], [q.output], name=q.q_name, domain=MX_DOMAIN,
+                     attrs={"axis": int(q.block_axis), "block_size": MX_BLOCK, "elem_type": self.elem_type})]
+
+    def gptq_grid(self, q, q_min, q_max, dev):
+        return None, NO_STATIC_GRID
+
+
+FORMATS = {f.name: f for f in (_Linear("Linear"), _FP8(FP8_E4M3), _MX("MXFP8E4M3", "mxfp8", "float8e4m3fn", 448),
+                               _MX("MXFP4E2M1", "mxfp4", "float4e2m1", 6))}
+MX_TYPES = {k: f for k, f in FORMATS.items() if f.block_scaled}
+
+
+class QDQNode:
+    """The fused fake-quant stand-in for the reference's 2-node `graph_quant` (quantize.py:197-239).  `fmt`: the number format
+    of the grid, a key of FORMATS (`format`: its record).  `suffix`: appended to every name of the node — a tensor that already
+    has a fake-quant node of another kind keeps that one's names for it."""
+
+    def __init__(self, tensor_name, tensor_shape, scale, zero_point, need_transpose, per_channel, symmetric, fmt="Linear",
+                 block_axis=None, suffix=""):
+        self.tensor_name = tensor_name
+        self.tensor_shape = list(tensor_shape) if tensor_shape is not None else None
+        self.scale = np.asarray(scale, np.float32).reshape(-1)
+        self.zero_point = np.asarray(zero_point, np.int8).reshape(-1)  # stored through int8 like :185
+        self.per_channel = bool(per_channel)
+        self.symmetric = bool(symmetric)
+        self.axis = (1 if need_transpose else 0) if per_channel else None  # :214, :220
+        self.fmt, self.format = fmt, FORMATS[fmt]
+        self.block_axis = block_axis
+        self.suffix = suffix
+        self.zp_dtype = self.format.zp_dtype[self.symmetric]
+        self.q_name = tensor_name + "_QuantizeLinear" + suffix
+        self.dq_name = tensor_name + "_DequantizeLinear" + suffix
+        self.scale_name = tensor_name + "_scale" + suffix
+        self.zero_point_name = tensor_name + "_zero_point" + suffix
+        self.q_output = tensor_name + QTENSORSUFFIX + suffix
+        self.output = tensor_name + DQTENSORSUFFIX + suffix
+        self._dev = None
+
+    @property
+    def is_mx(self):
+        return self.format.block_scaled
+
+    def zero_point_as_stored(self):
+        """The integers an ONNX runtime sees: int8 values, or the same bytes read as uint8."""
+        return self.zero_point.astype(np.int32) if self.symmetric else self.zero_point.view(np.uint8).astype(np.int32)
+
+    def saturation(self):
+        """(lowest, highest) value of the grid the node saturates to."""
+        return self.format.bounds[self.symmetric]
+
+    def on_device(self, device):
+        """(scale, zero point as stored) on `device`: uploaded once."""
+        if self._dev is None or self._dev[0].device != device:
+            self._dev = (torch.from_numpy(self.scale).to(device), torch.from_numpy(self.zero_point_as_stored()).to(device))
+        return self._dev
+
+    def mixes_axis(self, k, nd):
+        """Is axis k of the node's nd-axis tensor one along which elements do not go through the node each on its own with the same
+        parameters: the per-channel axis, or the axis whose blocks share a scale?"""
+        a = self.block_axis if self.format.block_scaled else self.axis
+        return a is not None and (a + nd if a < 0 else a) == k
+
+    def apply(self, x, out=None, pre=None, x2=None):
+        """Fake-quantise a device tensor: QuantizeLinear -> DequantizeLinear semantics, one kernel (pre / x2: the producer's
+        ReLU or Add + ReLU fused in, ops.fake_quant)."""
+        return self.format.apply(self, x, out, pre, x2)
 
 
 def get_qnode_by_param(param, in_tensor_name, tensor_shape, range, need_transpose=False, block_axis=-1, suffix=""):
     """quantize.py:111-194 — returns (QDQNode, q_min, q_max) for the clip range `range` = [lo, hi] (scalars, or
-    per-channel arrays for weights).  Kept from the reference because callers rely on it: a per-tensor platform
-    collapses `range` to its overall min / max IN PLACE (type "Float8E4M3FN" too: scale = max(|lo|, |hi|) / 448, zero point 0,
-    q_min / q_max = -448 / 448); `dynamic_sym` platforms switch a non-negative activation
+    per-channel arrays for weights), (None, None, None) for a type FORMATS does not hold.  Kept from the reference because callers
+    rely on it: a per-tensor platform collapses `range` to its overall min / max IN PLACE (type "Float8E4M3FN" too: scale =
+    max(|lo|, |hi|) / 448, zero point 0, q_min / q_max = -448 / 448); `dynamic_sym` platforms switch a non-negative activation
     (|lo| < 1e-6) to the asymmetric grid — one more bit; `log_scale` snaps scales to powers of two.  An MX type
     (mx_setting_table) ignores `range`: its node is block-scaled along `block_axis`, q_min / q_max = the element format's."""
-    if param["type"] in MX_TYPES:
-        top = MX_TYPES[param["type"]][2]
-        q_nodes = QDQNode(in_tensor_name, tensor_shape, np.ones(1, np.float32), np.zeros(1, np.int8), False, False, True,
-                          fmt=param["type"], block_axis=int(block_axis), suffix=suffix)
-        return q_nodes, -top, top
-    if param["type"] == FP8_E4M3:
-        per_channel = bool(param.get("per_channel", False))
-        if not per_channel:
-            range[0], range[1] = np.min(range[0]), np.max(range[1])
-        scale = np.array(_e4m3_grid(range[0], range[1]), dtype=np.float32).reshape(-1)
-        q_nodes = QDQNode(in_tensor_name, tensor_shape, scale, np.zeros(scale.shape, np.int8), need_transpose, per_channel, True,
-                          fmt=FP8_E4M3, suffix=suffix)
-        return q_nodes, -E4M3_MAX, E4M3_MAX
-    if param["type"] != "Linear":
+    fmt = FORMATS.get(param["type"])
+    if fmt is None:
         return None, None, None
-    per_channel = bool(param.get("per_channel", False))
-    symmetric = param["symmetric"]
-    if not per_channel:
-        range[0], range[1] = np.min(range[0]), np.max(range[1])
-        if param.get("dynamic_sym", False) and np.abs(range[0] - 0.0) < 1e-6:
-            symmetric = False
-    if symmetric:
-        scale, zero_point, q_min, q_max = _symmetric_grid(param["bit_width"], range[0], range[1])
-    else:
-        scale, zero_point, q_min, q_max = _affine_grid(param["bit_width"], range[0], range[1], in_tensor_name)
-    if param.get("log_scale", False):
-        scale = 2 ** np.round(np.log2(scale))
-    scale = np.array(scale, dtype=np.float32)
-    q_nodes = QDQNode(in_tensor_name, tensor_shape, scale, _int8_wrap(zero_point, scale.shape), need_transpose, per_channel,
-                      symmetric, suffix=suffix)
-    return q_nodes, q_min, q_max
+    return fmt.qnode(param, in_tensor_name, tensor_shape, range, need_transpose, block_axis, suffix)
 
 
 def quant_acti(x, scale, q_min, q_max, prob=1.0):
@@ -313,7 +425,6 @@ def quant_graph(onnx_graph, clip_val, args):
     """quantize.py:20-37 -> (fake-quantised copy of the graph, the nodes whose inputs were considered): every node whose
     op type is in the platform's `quant_nodes` and whose name is not in --skip_layers, in graph order; then the network
     outputs where the platform asks for it."""
-    from .graph import ONNXGraph
     from .platform_settings import platform_setting_table
     plat = platform_setting_table[args.deploy]
     skipped = set(getattr(args, "skip_layers", None) or ())

@@ -467,8 +467,7 @@ def batch_transparent(graph, folded, input_names, env):
             out = 0 if rest_const and k == 0 else None
         elif op == "FakeQuant":
             q = graph._qdq.get(node.name)
-            if rest_const and q is not None and not (q.per_channel and ax(int(q.axis), nd) == k) \
-                    and not (q.is_mx and ax(int(q.block_axis), nd) == k):      # (MX blocks along the batch axis mix the samples)
+            if rest_const and q is not None and not q.mixes_axis(k, nd):       # (MX blocks along the batch axis mix the samples)
                 out = k
         elif op == "BlockHadamard":     # blocks along the last axis: per-sample unless that is the images' axis
             out = k if rest_const and nd >= 2 and k != nd - 1 else None

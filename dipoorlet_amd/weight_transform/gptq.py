@@ -24,7 +24,7 @@ from .. import ops
 from ..dist_helper import barrier, shard_range
 from ..executor import conv_padding
 from ..platform_settings import platform_setting_table
-from ..quantize import FP8_E4M3, get_qnode_by_param
+from ..quantize import NO_STATIC_GRID, get_qnode_by_param
 from ..utils import logger
 from .walk import QuantWalk
 
@@ -65,17 +65,7 @@ def layer_grid(graph, node, clip_val, args, dev):
     param = platform_setting_table[args.deploy]["qw_params"]
     rng = [np.copy(clip_val[name][0]), np.copy(clip_val[name][1])]
     qnode, q_min, q_max = get_qnode_by_param(param, name, graph.tensor_name_shape_map.get(name), rng, False)
-    if qnode is None or qnode.is_mx:
-        return None, "its weight has no static grid"
-    scale = torch.from_numpy(qnode.scale.copy()).to(dev)
-    if qnode.fmt == FP8_E4M3:
-        return ops.GptqGrid("e4m3", scale), None
-    zp = qnode.zero_point_as_stored()
-    lo, hi = np.asarray(q_min, np.int64).reshape(-1) + zp, np.asarray(q_max, np.int64).reshape(-1) + zp
-    if not (np.all(lo == lo[0]) and np.all(hi == hi[0])):
-        return None, "its channels do not share one integer range"
-    sat_lo, sat_hi = qnode.saturation()
-    return ops.GptqGrid("int", scale, torch.from_numpy(zp.astype(np.int32)).to(dev), max(int(lo[0]), sat_lo), min(int(hi[0]), sat_hi)), None
+    return (None, NO_STATIC_GRID) if qnode is None else qnode.format.gptq_grid(qnode, q_min, q_max, dev)
 
 
 def _why_left(node, weight):
@@ -186,10 +176,7 @@ def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
                 dist.all_reduce(acc)
             H = acc[:K * K].view(K, K) / acc[K * K]
             U, damp = factor(H.cpu(), damp0)
-            if grid.fmt == "int":
-                w_near = ops.fake_quant(w2d, grid.scale, grid.zero_point, grid.qlo, grid.qhi, axis=0 if grid.scale.numel() > 1 else None)
-            else:
-                w_near = ops.fake_quant_fp8(w2d, grid.scale, axis=0 if grid.scale.numel() > 1 else None)
+            w_near = ops.gptq_nearest(w2d, grid)
             entry = {"node": node.name, "rows": int(R), "cols": int(K), "damp": damp, "kept": "nearest",
                      "objective_nearest": _objective(w_near, w2d, H), "objective_gptq": None}
             if U is None:       # the only fall-back: the weight stays as it is, the graph's Q/DQ node rounds it to nearest

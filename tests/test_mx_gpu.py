@@ -344,3 +344,65 @@ def test_cli(workdir):
     assert {k for k, v in blocks["tensors"].items() if v["constant"]} == {n.input[0] for n in nodes if n.input[0] in m.initializers}
     assert sum(v["constant"] for v in blocks["tensors"].values()) == 9
     assert any(n.op_type == "QuantizeLinear" for n in m.nodes)                        # the Conv's static E4M3 pairs beside them
+
+
+# ------------------------------------------------------------------------------------------------ 9. every format in one fold
+def test_session_folds_weights_of_every_format(dev):
+    """A hand-made graph whose four constant weights get a node of every kind: the session's fold (GraphSession._fold_weights) leaves
+    each equal, bit for bit, to that node's own apply() — one whole-set launch per static format, the MX weight through none.
+    Conv [8, 3, 3, 3] on the integer grid per channel: rows of 27, not a multiple of four (a vector straddles two channels); a
+    second integer weight with a single scale, asymmetric; Gemm [6, 10] on FP8 per channel; MatMul [40, 6] on MXFP4 along axis 0:
+    one full block and a short one of 8 rows, inner = 6 (the unvectorised column kernel)."""
+    from dipoorlet_amd import ops
+    from dipoorlet_amd.executor import GraphSession
+    from dipoorlet_amd.models import _B
+    from dipoorlet_amd.platform_settings import mx_setting_table, platform_setting_table
+    from dipoorlet_amd.quantize import get_qnode_by_param
+    b = _B(31)
+    x = b.conv("input", 3, 8, 3, 1, 1, "c1")                        # c1.weight [8, 3, 3, 3]
+    x = b.conv(x, 8, 10, 1, 1, 0, "c2")                             # c2.weight [10, 8, 1, 1]
+    x = b.node("Flatten", [x], out="flat", axis=1)                  # [1, 10 * 2 * 2]
+    b.w("mm.weight", (40, 6))
+    x = b.node("MatMul", [x, "mm.weight"], out="mm_out")
+    b.w("fc.weight", (6, 10))
+    b.b("fc.bias", 10)
+    x = b.node("Gemm", [x, "fc.weight", "fc.bias"], out="output", alpha=1.0, beta=1.0, transB=0)
+    g = b.finish("input", [1, 3, 2, 2], x)
+    params = {"c1.weight": platform_setting_table["trt"]["qw_params"], "c2.weight": platform_setting_table["snpe"]["qw_params"],
+              "fc.weight": platform_setting_table["ocp_fp8"]["qw_params"], "mm.weight": mx_setting_table["mxfp4"]}
+    for node in list(g.graph.node):
+        name = node.input[1] if len(node.input) > 1 else None
+        if name not in params:
+            continue
+        w2 = np.asarray(g.get_initializer(name), np.float64).reshape(g.get_initializer(name).shape[0], -1)
+        q, _, _ = get_qnode_by_param(params[name], name, list(g.get_initializer(name).shape), [w2.min(axis=1), w2.max(axis=1)], block_axis=0)
+        node.input[1] = q.output
+        g.insert_qnodes_purely(q_nodes=q, node=node)
+        g.topologize_graph()
+    g.update_model()
+    qs = {q.tensor_name: q for q in g._qdq.values()}
+    assert {k: (q.fmt, q.scale.size) for k, q in qs.items()} == {"c1.weight": ("Linear", 8), "c2.weight": ("Linear", 1),
+                                                                 "fc.weight": ("Float8E4M3FN", 6), "mm.weight": ("MXFP4E2M1", 1)}
+    assert not qs["c2.weight"].symmetric and qs["c2.weight"].zero_point_as_stored()[0] > 0
+    launches, call = [], ops.FakeQuantSet.__call__
+
+    def counted(self, tensors, out=None):
+        launches.append((self.fmt, len(tensors)))
+        return call(self, tensors, out)
+    ops.FakeQuantSet.__call__ = counted
+    try:
+        sess = GraphSession(g, device=dev)
+    finally:
+        ops.FakeQuantSet.__call__ = call
+    assert sorted(launches) == [("fp8", 1), ("int", 2)]              # one per static format present; the MX weight in neither
+    assert len(sess._folded) == 4
+    for node in g.graph.node:
+        if node.op_type != "FakeQuant":
+            continue
+        q, w = g._qdq[node.name], sess.consts[node.input[0]]
+        assert node.name in sess._folded and tuple(w.shape) == tuple(g.get_initializer(node.input[0]).shape)
+        one = q.apply(w.contiguous())
+        assert torch.equal(sess.consts[node.output[0]], one), node.name
+        assert not torch.equal(one, w), node.name                      # (the node does round)
+    _same(sess.consts["mm.weight_dq"].cpu().numpy(), M.fake_quant_mx(g.get_initializer("mm.weight"), 0, "mxfp4"), "mm.weight")
+    assert torch.isfinite(sess.run({"input": torch.ones(1, 3, 2, 2, device=dev)})[-1]).all()
