@@ -1,5 +1,5 @@
 """`python -m dipoorlet_amd -M model.onnx -I calib_dir -N 1024 -A hist -D trt` — the reference's CLI
-(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, `--mx_rotate`, a block-Hadamard rotation of those operands, and `--gptq`, Hessian-compensated weight rounding, are this project's additions).
+(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, `--mx_rotate`, a block-Hadamard rotation of those operands, `--mx_pack`, the constant ones as packed element codes and E8M0 scales, and `--gptq`, Hessian-compensated weight rounding, are this project's additions).
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
@@ -58,6 +58,11 @@ def build_parser():
                         "The weight side is folded offline, the activation side is a BlockHadamard node (domain dipoorlet.amd) that a "
                         "runtime applies in front of its MX quantiser.  Runs after --smooth and before --bc; writes rotate_model.onnx and "
                         "rotate_report.json, and a \"rotation\" entry in ocp_mx_blocks.json")
+    p.add_argument("--mx_pack", default=False, action="store_true",
+                   help="(not in the reference; with --mx only) also write the constant MX operands as the bytes a block-scaled GEMM reads: "
+                        "ocp_mx_weights.bin (per tensor its OCP E4M3 bytes or packed E2M1 nibbles, then its E8M0 scale bytes, both "
+                        "K-innermost, every section on a 64-byte boundary) and ocp_mx_weights.json (offsets and shapes, keyed as "
+                        "ocp_mx_blocks.json).  Encoded on the device from the weights as they stand after every weight transform")
     p.add_argument("--gptq_block", type=int, default=128,
                    help="--gptq (not in the reference; every platform, -D ocp_fp8 included): round every Conv (group 1) / Gemm weight column "
                         "by column onto the platform's weight grid, pushing each column's rounding error onto the columns not yet rounded "
@@ -108,6 +113,9 @@ def check_args(args):
     if getattr(args, "mx_rotate", False) and not getattr(args, "mx", None):
         raise ValueError("--mx_rotate needs --mx mxfp8 or --mx mxfp4: it rotates the 32-element blocks that --mx scales, and does "
                          "nothing for a static grid")
+    if getattr(args, "mx_pack", False) and not getattr(args, "mx", None):
+        raise ValueError("--mx_pack needs --mx mxfp8 or --mx mxfp4: it writes the element codes and block scales of the operands that "
+                         "--mx scales, and a static grid has neither")
     if getattr(args, "mx", None) and args.deploy != "ocp_fp8":
         raise ValueError(f"--mx {args.mx} is not supported with -D {args.deploy}: block-scaled MatMul / Gemm operands sit beside static "
                          "FP8 scales on every other node.  Supported: -D ocp_fp8")

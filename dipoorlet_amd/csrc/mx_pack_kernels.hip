@@ -1,0 +1,381 @@
+// K7b: `--mx_pack` — an MX tensor as packed element codes and E8M0 scale bytes, and back (tests/mx_pack_model.py is the definition;
+// mx_format.hpp round_code / decode_bits the arithmetic; mx_block.hpp what is shared with the Q/DQ pair of mx_kernels.hip: the
+// loads, the block maximum, the shared exponent, the decomposition of a launch).  The tensor is fp32 [outer, K, inner], blocks of 32
+// along K.  Codes and scales are K-INNERMOST, the order a block-scaled GEMM reads both operands in: with nblk = ceil(K / 32),
+// codes is [outer, inner, nblk * 32] bytes (E4M3) or [outer, inner, nblk * 16] (E2M1: two to a byte, the even index along K in the
+// low nibble), scales [outer, inner, nblk].  For inner > 1 that is a transpose of the element order, and NOT the order of
+// dpl_fake_quant_mx's scales ([outer, nblk, inner]).  The elements past K of a short last block get code 0.  A block is 32 or 16
+// bytes of codes at a multiple of its size: with a 16-byte aligned base every store and load of codes is 16 bytes wide.
+// No atomics, no LDS, no scratch; 64-bit element indices.
+//   k_mx_encode_rows  inner == 1: the lane groups of k_fake_quant_mx_rows (VEC = 4: 8 lanes a block, 16-byte loads; VEC = 1: 32
+//                     lanes).  A lane's VEC codes are 32, 16, 8 or 4 bits; the lanes of a quad exchange them by DPP quad_perm
+//                     broadcasts, quads by ds_bpermute (__shfl_xor / __shfl_down), and one lane in 4, 8, 16 or 32 stores 16 bytes.
+//   k_mx_encode_cols  inner > 1: a lane owns VEC columns of one block and walks its 32 rows in registers, as k_fake_quant_mx_cols
+//                     does; the 32 codes of a column are 8 or 4 dwords, contiguous in the output, stored as 16-byte vectors.
+//                     The transpose is paid on the code side, 1/4 (1/8) of the bytes; with four columns to a lane a wave is a tile
+//                     of four K-blocks, so that four lanes fill one run of a column (MxPackColsAt).
+//   k_mx_decode_rows, k_mx_decode_cols  the mirrors: codes and scales in, fp32 [outer, K, inner] out, nothing written past K.
+#include "mx_block.hpp"
+
+namespace {
+
+using u4 = __attribute__((ext_vector_type(4))) uint32_t;
+typedef __attribute__((address_space(1))) u4* gptr_u4w;
+typedef const __attribute__((address_space(1))) u4* gptr_u4;
+typedef const __attribute__((address_space(1))) uint32_t* gptr_u32;
+typedef const __attribute__((address_space(1))) uint16_t* gptr_u16;
+typedef const __attribute__((address_space(1))) uint8_t* gptr_u8;
+
+template <int ELEM>
+struct Pack {
+    static constexpr uint32_t bits = ELEM == DPL_MX_E4M3 ? 8u : 4u;      // per element
+    static constexpr uint32_t block_bytes = 4u * bits;                    // 32 elements
+    static constexpr uint32_t nan_code = ELEM == DPL_MX_E4M3 ? 0x7Fu : 0u;  // of every element of a 0xFF block
+};
+
+// The code of element v of a block (se, nan); `exists`: false past K.
+template <int ELEM>
+__device__ __forceinline__ uint32_t mx_code(uint32_t vbits, int se, bool nan, bool exists) {
+    const uint32_t c = ((vbits >> 31) << (dpl_mx::Fmt<ELEM>::ebits + dpl_mx::Fmt<ELEM>::mbits)) | dpl_mx::round_code<ELEM>(vbits & 0x7FFFFFFFu, se);
+    return exists ? (nan ? Pack<ELEM>::nan_code : c) : 0u;
+}
+
+// v of lane J of the caller's quad (lanes 4q .. 4q + 3), in every lane of the quad: one DPP move.  All 64 lanes must be active.
+template <int J>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, J * 0x55, 0xF, 0xF, true);     // quad_perm [J, J, J, J]
+}
+
+// A group of 32 / VEC lanes holds one block's codes, `pay` = the lane's VEC codes in its low VEC * bits bits, lowest index lowest.
+// The group's 32 or 16 bytes go to dst as 16-byte stores.  Called by every lane of the wave (the exchange reads lanes that store
+// nothing); `go`: the group exists.
+template <int ELEM, int VEC>
+__device__ __forceinline__ void mx_store_group_codes(uint8_t* dst, uint32_t pay, uint32_t lane, bool go) {
+    constexpr uint32_t W = VEC * Pack<ELEM>::bits;     // bits a lane holds: 32, 16, 8, 4
+    const uint32_t q0 = quad_bcast<0>(pay), q1 = quad_bcast<1>(pay), q2 = quad_bcast<2>(pay), q3 = quad_bcast<3>(pay);
+    u4 out;
+    uint32_t keep, off = 0u;                           // the lanes with lane % keep == 0 store, at byte `off`
+    if constexpr (W == 32) {                           // a quad is 16 bytes
+        out = u4{q0, q1, q2, q3};
+        keep = 4u;
+        off = (lane >> 2) * 16u;
+    } else if constexpr (W == 16) {                    // a quad is 8 bytes, the group's two quads 16
+        const uint32_t d0 = q0 | (q1 << 16), d1 = q2 | (q3 << 16);
+        out = u4{d0, d1, (uint32_t)__shfl_xor((int)d0, 4, kWave), (uint32_t)__shfl_xor((int)d1, 4, kWave)};
+        keep = 8u;
+    } else if constexpr (W == 8) {                     // a quad is a dword; four quads 16 bytes, the group's eight 32
+        const uint32_t d = q0 | (q1 << 8) | (q2 << 16) | (q3 << 24);
+        out = u4{d, (uint32_t)__shfl_down((int)d, 4, kWave), (uint32_t)__shfl_down((int)d, 8, kWave), (uint32_t)__shfl_down((int)d, 12, kWave)};
+        keep = 16u;
+        off = (lane >> 4) * 16u;
+    } else {                                           // a quad is 16 bits, two quads a dword, the group's eight quads 16 bytes
+        const uint32_t h = q0 | (q1 << 4) | (q2 << 8) | (q3 << 12);
+        const uint32_t d = h | ((uint32_t)__shfl_down((int)h, 4, kWave) << 16);
+        out = u4{d, (uint32_t)__shfl_down((int)d, 8, kWave), (uint32_t)__shfl_down((int)d, 16, kWave), (uint32_t)__shfl_down((int)d, 24, kWave)};
+        keep = 32u;
+    }
+    if (go && lane % keep == 0u) __builtin_nontemporal_store(out, (gptr_u4w)(dst + off));
+}
+
+// Where a lane of a cols kernel works.  One column to a lane (VEC = 1): the slots of k_fake_quant_mx_cols (MxColsAt) — a wave is
+// one K-block of 64 columns.  Four columns to a lane (VEC = 4): a wave is a TILE of four consecutive K-blocks of sixteen column
+// groups, lane = 16 * (K-block in the tile) + column group: an fp32 access of the wave is four runs of 256 contiguous bytes (whole
+// lines, as many as the slot form touches), and the four lanes that hold the four K-blocks of one column access one run of 128
+// (64) contiguous code bytes instead of four runs Kp bytes apart.  Tiles: [outer, ceil(nblk / 4), ceil(cs / 16)].
+template <int VEC>
+struct MxPackColsAt {
+    uint64_t o;
+    uint32_t kb, col;
+    bool live;
+    __device__ __forceinline__ MxPackColsAt(uint64_t n_slots, uint32_t nblk, uint32_t cs) {
+        if constexpr (VEC == 1) {
+            live = (uint64_t)blockIdx.x * kMxColsBlock + threadIdx.x < n_slots;
+            const MxColsAt w(nblk, cs, 1);
+            o = w.o, kb = w.kb, col = w.col;
+        } else {
+            const uint32_t nct = (cs + 15u) / 16u, nkt = (nblk + 3u) / 4u;
+            const uint32_t r = blockIdx.x / nct, ct = blockIdx.x - r * nct;       // (the grid is below 2^31)
+            const uint32_t ob = r / nkt, kt = r - ob * nkt;
+            const uint32_t cg = ct * 16u + (threadIdx.x & 15u);
+            o = ob;
+            kb = kt * 4u + (threadIdx.x >> 4);
+            col = cg * VEC;
+            live = kb < nblk && cg < cs;
+        }
+    }
+};
+
+// ---------------------------------------------------------------------------------------------- encode, inner == 1
+template <int ELEM, int VEC>
+__global__ __launch_bounds__(kBlock) void k_mx_encode_rows(const float* x, uint8_t* codes, uint8_t* scales, uint64_t n_groups, uint32_t K,
+                                                           uint32_t nblk) {
+    const MxRowsAt<VEC> w(nblk);
+    MxVec<VEC> v[kMxRowsIter];
+    bool live[kMxRowsIter];
+#pragma unroll
+    for (int i = 0; i < kMxRowsIter; ++i) {
+        uint64_t row;
+        uint32_t col;
+        w.at(i, nblk, row, col);
+        live[i] = w.group(i) < n_groups && col < K;    // (K % VEC == 0: a vector that starts inside a row ends inside it)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) v[i].b[j] = 0u;
+        if (live[i]) v[i] = mx_load<VEC>(x + row * K + col);
+    }
+#pragma unroll
+    for (int i = 0; i < kMxRowsIter; ++i) {
+        const uint32_t a = mx_group_max<VEC>(v[i]);
+        bool nan;
+        const int se = mx_block_se<ELEM>(a, nan);
+        uint32_t pay = 0u;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) pay |= mx_code<ELEM>(v[i].b[j], se, nan, live[i]) << (Pack<ELEM>::bits * j);
+        const uint64_t g = w.group(i);
+        const bool go = g < n_groups;                  // (the pad lanes of a short last block are part of it: code 0)
+        mx_store_group_codes<ELEM, VEC>(codes + g * Pack<ELEM>::block_bytes, pay, w.lane, go);
+        if (go && w.lane == 0u) ((gptr_u8w)scales)[g] = nan ? 0xFFu : (uint8_t)(se + 127);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- encode, inner > 1
+template <int ELEM, int VEC>
+__global__ __launch_bounds__(kMxColsBlock, 2) void k_mx_encode_cols(const float* x, uint8_t* codes, uint8_t* scales, uint64_t n_slots, uint32_t K,
+                                                                 uint32_t nblk, uint32_t inner, uint32_t cs) {
+    const MxPackColsAt<VEC> w(n_slots, nblk, cs);
+    if (!w.live) return;
+    const uint32_t rows = min(32u, K - w.kb * 32u);
+    const uint64_t base = (w.o * K + (uint64_t)w.kb * 32u) * inner + w.col;
+    MxVec<VEC> v[32];
+#pragma unroll
+    for (int r = 0; r < 32; ++r) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) v[r].b[j] = 0u;
+        if ((uint32_t)r < rows) v[r] = mx_load<VEC>(x + base + (uint64_t)r * inner);
+    }
+    uint32_t a[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) a[j] = 0u;
+#pragma unroll
+    for (int r = 0; r < 32; ++r)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) a[j] = max(a[j], v[r].b[j] & 0x7FFFFFFFu);
+    constexpr uint32_t BITS = Pack<ELEM>::bits, NW = Pack<ELEM>::block_bytes / 4u;      // dwords of one column's block: 8 or 4
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        bool nan;
+        const int se = mx_block_se<ELEM>(a[j], nan);
+        uint32_t wd[NW];
+#pragma unroll
+        for (uint32_t d = 0; d < NW; ++d) wd[d] = 0u;
+#pragma unroll
+        for (int r = 0; r < 32; ++r)
+            wd[(uint32_t)r * BITS / 32u] |= mx_code<ELEM>(v[r].b[j], se, nan, (uint32_t)r < rows) << ((uint32_t)r * BITS % 32u);
+        const uint64_t blk = ((w.o * inner + w.col + (uint32_t)j) * nblk + w.kb);      // of [outer, inner, nblk]
+        uint8_t* dst = codes + blk * Pack<ELEM>::block_bytes;
+#pragma unroll
+        for (uint32_t d = 0; d < NW; d += 4) __builtin_nontemporal_store(u4{wd[d], wd[d + 1], wd[d + 2], wd[d + 3]}, (gptr_u4w)(dst + 4u * d));
+        ((gptr_u8w)scales)[blk] = nan ? 0xFFu : (uint8_t)(se + 127);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- decode
+// Element `i` (0 .. 31) of a block whose codes are the dwords wd[]; scale byte sc.
+template <int ELEM>
+__device__ __forceinline__ uint32_t mx_decode_code(uint32_t code, uint32_t sc) {
+    return sc == 0xFFu ? kQuietNaN : dpl_mx::decode_bits<ELEM>(code, (int)sc - 127);
+}
+
+// inner == 1: the groups of the encoder; a lane reads its VEC codes (32 or 16 bits at once for VEC = 4, the byte that holds it for
+// VEC = 1) and its block's scale byte, and writes VEC floats.
+template <int ELEM, int VEC>
+__global__ __launch_bounds__(kBlock) void k_mx_decode_rows(const uint8_t* codes, const uint8_t* scales, float* y, uint64_t n_groups, uint32_t K,
+                                                           uint32_t nblk) {
+    constexpr uint32_t BITS = Pack<ELEM>::bits;
+    const MxRowsAt<VEC> w(nblk);
+    uint32_t pay[kMxRowsIter], sc[kMxRowsIter];
+    uint64_t at[kMxRowsIter];
+    bool live[kMxRowsIter];
+#pragma unroll
+    for (int i = 0; i < kMxRowsIter; ++i) {
+        uint64_t row;
+        uint32_t col;
+        w.at(i, nblk, row, col);
+        const uint64_t g = w.group(i);
+        live[i] = g < n_groups && col < K;
+        at[i] = row * K + col;
+        pay[i] = sc[i] = 0u;
+        if (live[i]) {
+            const uint8_t* src = codes + g * Pack<ELEM>::block_bytes + w.lane * VEC * BITS / 8u;
+            if constexpr (VEC * BITS == 32)
+                pay[i] = *(gptr_u32)src;
+            else if constexpr (VEC * BITS == 16)
+                pay[i] = *(gptr_u16)src;
+            else
+                pay[i] = (uint32_t)(*(gptr_u8)src) >> (w.lane * BITS % 8u);
+            sc[i] = ((gptr_u8)scales)[g];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < kMxRowsIter; ++i) {
+        if (live[i]) {
+            MxVec<VEC> r;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) r.b[j] = mx_decode_code<ELEM>((pay[i] >> (BITS * j)) & ((1u << BITS) - 1u), sc[i]);
+            mx_store<VEC>(y + at[i], r);
+        }
+    }
+}
+
+// inner > 1: the slots of the encoder; a lane reads the blocks of its VEC columns (16-byte loads) and their scale bytes, and writes
+// the block's rows that exist, each store coalesced across the lanes.
+template <int ELEM, int VEC>
+__global__ __launch_bounds__(kMxColsBlock, 2) void k_mx_decode_cols(const uint8_t* codes, const uint8_t* scales, float* y, uint64_t n_slots,
+                                                                 uint32_t K, uint32_t nblk, uint32_t inner, uint32_t cs) {
+    constexpr uint32_t BITS = Pack<ELEM>::bits, NW = Pack<ELEM>::block_bytes / 4u;
+    const MxPackColsAt<VEC> w(n_slots, nblk, cs);
+    if (!w.live) return;
+    const uint32_t rows = min(32u, K - w.kb * 32u);
+    const uint64_t base = (w.o * K + (uint64_t)w.kb * 32u) * inner + w.col;
+    uint32_t wd[VEC][NW], sc[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        const uint64_t blk = ((w.o * inner + w.col + (uint32_t)j) * nblk + w.kb);
+        const uint8_t* src = codes + blk * Pack<ELEM>::block_bytes;
+#pragma unroll
+        for (uint32_t d = 0; d < NW; d += 4) {
+            const u4 t = __builtin_nontemporal_load((gptr_u4)(src + 4u * d));
+            wd[j][d] = t.x, wd[j][d + 1] = t.y, wd[j][d + 2] = t.z, wd[j][d + 3] = t.w;
+        }
+        sc[j] = ((gptr_u8)scales)[blk];
+    }
+#pragma unroll
+    for (int r = 0; r < 32; ++r) {
+        if ((uint32_t)r < rows) {
+            MxVec<VEC> o;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j)
+                o.b[j] = mx_decode_code<ELEM>((wd[j][(uint32_t)r * BITS / 32u] >> ((uint32_t)r * BITS % 32u)) & ((1u << BITS) - 1u), sc[j]);
+            mx_store<VEC>(y + base + (uint64_t)r * inner, o);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- launches
+struct MxPackPlan {
+    uint32_t K, nblk, cs;
+    bool vec;
+    uint64_t n, blocks;       // groups (inner == 1) or slots, and workgroups
+};
+
+// fp: the fp32 side's base (d_x of encode, d_y of decode) — its alignment decides between 16-byte vectors and single elements
+inline MxPackPlan mx_pack_plan(const void* fp, uint64_t outer, uint64_t k, uint64_t inner) {
+    MxPackPlan p;
+    p.K = (uint32_t)k;
+    p.nblk = (p.K + 31u) / 32u;
+    const bool aligned = ((uintptr_t)fp & 15u) == 0u;
+    if (inner == 1) {
+        p.vec = aligned && (p.K & 3u) == 0u;
+        p.cs = 1;
+        p.n = outer * p.nblk;
+        const uint64_t per_wg = (uint64_t)kMxRowsIter * kBlock * (p.vec ? 4 : 1) / 32;
+        p.blocks = (p.n + per_wg - 1) / per_wg;
+    } else {
+        p.vec = aligned && (inner & 3u) == 0u;
+        p.cs = (uint32_t)(p.vec ? inner / 4 : inner);
+        p.n = outer * p.nblk * p.cs;
+        p.blocks = p.vec ? outer * ((p.nblk + 3u) / 4u) * ((p.cs + 15u) / 16u) : (p.n + kMxColsBlock - 1) / kMxColsBlock;      // tiles : slots
+    }
+    return p;
+}
+
+template <int ELEM>
+int mx_encode_launch(const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, uint8_t* d_codes, uint8_t* d_scales, dpl_stream_t s) {
+    const MxPackPlan p = mx_pack_plan(d_x, outer, k, inner);
+    if (p.blocks > 0x7FFFFFFFull) return fail_msg("dpl_mx_encode: tensor too large");
+    const dim3 grid((unsigned)p.blocks);
+    if (inner == 1) {
+        if (p.vec)
+            hipLaunchKernelGGL((k_mx_encode_rows<ELEM, 4>), grid, dim3(kBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk);
+        else
+            hipLaunchKernelGGL((k_mx_encode_rows<ELEM, 1>), grid, dim3(kBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk);
+        DPL_LAUNCH_CHECK("k_mx_encode_rows");
+        return 0;
+    }
+    if (p.vec)
+        hipLaunchKernelGGL((k_mx_encode_cols<ELEM, 4>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
+                           (uint32_t)inner, p.cs);
+    else
+        hipLaunchKernelGGL((k_mx_encode_cols<ELEM, 1>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
+                           (uint32_t)inner, p.cs);
+    DPL_LAUNCH_CHECK("k_mx_encode_cols");
+    return 0;
+}
+
+template <int ELEM>
+int mx_decode_launch(const uint8_t* d_codes, const uint8_t* d_scales, uint64_t outer, uint64_t k, uint64_t inner, float* d_y, dpl_stream_t s) {
+    const MxPackPlan p = mx_pack_plan(d_y, outer, k, inner);
+    if (p.blocks > 0x7FFFFFFFull) return fail_msg("dpl_mx_decode: tensor too large");
+    const dim3 grid((unsigned)p.blocks);
+    if (inner == 1) {
+        if (p.vec)
+            hipLaunchKernelGGL((k_mx_decode_rows<ELEM, 4>), grid, dim3(kBlock), 0, (hipStream_t)s, d_codes, d_scales, d_y, p.n, p.K, p.nblk);
+        else
+            hipLaunchKernelGGL((k_mx_decode_rows<ELEM, 1>), grid, dim3(kBlock), 0, (hipStream_t)s, d_codes, d_scales, d_y, p.n, p.K, p.nblk);
+        DPL_LAUNCH_CHECK("k_mx_decode_rows");
+        return 0;
+    }
+    if (p.vec)
+        hipLaunchKernelGGL((k_mx_decode_cols<ELEM, 4>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_codes, d_scales, d_y, p.n, p.K, p.nblk,
+                           (uint32_t)inner, p.cs);
+    else
+        hipLaunchKernelGGL((k_mx_decode_cols<ELEM, 1>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_codes, d_scales, d_y, p.n, p.K, p.nblk,
+                           (uint32_t)inner, p.cs);
+    DPL_LAUNCH_CHECK("k_mx_decode_cols");
+    return 0;
+}
+
+// The argument rules both entry points share (those of dpl_fake_quant_mx, plus the codes' alignment).  1: nothing to do.
+int mx_pack_check(const char* who, int32_t elem, const void* fp, const void* codes, const void* scales, uint64_t outer, uint64_t k, uint64_t inner) {
+    char msg[160];
+    if (elem != DPL_MX_E4M3 && elem != DPL_MX_E2M1) {
+        snprintf(msg, sizeof(msg), "%s: elem must be DPL_MX_E4M3 or DPL_MX_E2M1", who);
+        return fail_msg(msg);
+    }
+    if (outer == 0 || k == 0 || inner == 0) return 1;
+    if (fp == nullptr || codes == nullptr || scales == nullptr) {
+        snprintf(msg, sizeof(msg), "%s: the tensor, d_codes and d_scales must not be null", who);
+        return fail_msg(msg);
+    }
+    if (k > 0x7FFFFFFFull || inner > 0x7FFFFFFFull) {
+        snprintf(msg, sizeof(msg), "%s: k and inner must be in [1, 2^31)", who);
+        return fail_msg(msg);
+    }
+    // (the padded tensor, 32 * nblk <= k + 31 along K, must be indexable too)
+    if (outer > (0x7FFFFFFFFFFFFFFFull / (32ull * ((k + 31u) / 32u))) / inner) {
+        snprintf(msg, sizeof(msg), "%s: tensor too large", who);
+        return fail_msg(msg);
+    }
+    if (((uintptr_t)codes & 15u) != 0u) {
+        snprintf(msg, sizeof(msg), "%s: d_codes must be 16-byte aligned (a block's codes are stored and loaded as 16-byte vectors)", who);
+        return fail_msg(msg);
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int dpl_mx_encode(int32_t elem, const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, uint8_t* d_codes, uint8_t* d_scales,
+                             dpl_stream_t s) {
+    const int rc = mx_pack_check("dpl_mx_encode", elem, d_x, d_codes, d_scales, outer, k, inner);
+    if (rc != 0) return rc < 0 ? rc : 0;
+    return elem == DPL_MX_E4M3 ? mx_encode_launch<DPL_MX_E4M3>(d_x, outer, k, inner, d_codes, d_scales, s)
+                               : mx_encode_launch<DPL_MX_E2M1>(d_x, outer, k, inner, d_codes, d_scales, s);
+}
+
+extern "C" int dpl_mx_decode(int32_t elem, const uint8_t* d_codes, const uint8_t* d_scales, uint64_t outer, uint64_t k, uint64_t inner,
+                             float* d_y, dpl_stream_t s) {
+    const int rc = mx_pack_check("dpl_mx_decode", elem, d_y, d_codes, d_scales, outer, k, inner);
+    if (rc != 0) return rc < 0 ? rc : 0;
+    return elem == DPL_MX_E4M3 ? mx_decode_launch<DPL_MX_E4M3>(d_codes, d_scales, outer, k, inner, d_y, s)
+                               : mx_decode_launch<DPL_MX_E2M1>(d_codes, d_scales, outer, k, inner, d_y, s);
+}

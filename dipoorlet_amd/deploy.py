@@ -1,7 +1,7 @@
 """Platform emitters: clip ranges -> the vendor files the reference writes (dipoorlet/deploy/*).
 
-Pure host-side dict -> file code, no GPU work; kept so a run ends with the same artefacts.  File names,
-JSON structure (indent=4) and value formulas follow the reference emitters cited per function (all eight
+Pure host-side dict -> file code, no GPU work (but --mx_pack's, which encodes the MX weights on the device); kept so a
+run ends with the same artefacts.  File names, JSON structure (indent=4) and value formulas follow the reference emitters cited per function (all eight
 platforms; the rv / stpu tables are checked against files the reference's own emitters wrote).  `ocp_fp8` is this project's
 own: the static per-tensor scales of the activations.
 """
@@ -126,6 +126,47 @@ def gen_ocp_mx_blocks(graph, act_clip_val, weight_clip_val, args):
         weights = [r.input[1] for a in acts for r in graph.get_tensor_consumer(a) if not isinstance(r, str) and r.op_type in ("MatMul", "Gemm")]
         res["rotation"] = {"block_size": MX_BLOCK, "activations": acts, "weights": weights}
     _dump(res, args, "ocp_mx_blocks.json")
+    if getattr(args, "mx_pack", False):
+        gen_ocp_mx_weights(graph, [q for q in graph_q._qdq.values() if q.is_mx and q.tensor_name in graph.initializer], args)
+
+
+MX_WEIGHTS_ALIGN = 64     # every section of ocp_mx_weights.bin starts on a multiple of this, zero fill in between
+
+
+def gen_ocp_mx_weights(graph, qnodes, args):
+    """--mx_pack: the constant operands of ocp_mx_blocks.json (its `"constant": true` entries, under the same keys) as the bytes a
+    block-scaled GEMM reads — ops.mx_encode of the initializers as they stand after every weight transform, the ones
+    quant_model.onnx holds (tests/mx_pack_model.py is the definition of the bytes) ->
+      ocp_mx_weights.bin    per tensor its element codes, then its E8M0 scales, back to back, each section on a 64-byte boundary
+      ocp_mx_weights.json   {"format", "block_size": 32, "layout": "k_innermost", "tensors": {key: {"initializer", "shape", "axis",
+                            "k", "k_padded", "codes": {"offset", "nbytes", "shape"}, "scales": {"offset", "nbytes", "shape"}}}}
+    Both arrays are K-innermost: the block axis is moved to the end and padded with code 0 to k_padded = 32 * ceil(k / 32); mxfp4
+    holds two codes to a byte, the even index along k in the low nibble."""
+    import torch
+
+    from . import ops
+    from .quantize import MX_BLOCK
+    dev = torch.device("cuda", torch.cuda.current_device())
+    tensors, offset = {}, 0
+    with open(os.path.join(args.output_dir, "ocp_mx_weights.bin"), "wb") as f:
+        def section(t):
+            nonlocal offset
+            pad = -offset % MX_WEIGHTS_ALIGN
+            f.write(bytes(pad))
+            raw = t.cpu().numpy().tobytes()
+            f.write(raw)
+            entry = {"offset": offset + pad, "nbytes": len(raw), "shape": [int(d) for d in t.shape]}
+            offset += pad + len(raw)
+            return entry
+        for q in qnodes:
+            w = np.ascontiguousarray(graph.get_initializer(q.tensor_name), dtype=np.float32)
+            axis = int(q.block_axis) % w.ndim
+            codes, scales = ops.mx_encode(torch.from_numpy(w).to(dev), axis, args.mx)
+            k = int(w.shape[axis])
+            tensors[q.tensor_name + q.suffix] = {"initializer": q.tensor_name, "shape": [int(d) for d in w.shape], "axis": int(q.block_axis),
+                                                 "k": k, "k_padded": MX_BLOCK * -(-k // MX_BLOCK), "codes": section(codes),
+                                                 "scales": section(scales)}
+    _dump({"format": args.mx, "block_size": MX_BLOCK, "layout": "k_innermost", "tensors": tensors}, args, "ocp_mx_weights.json")
 
 
 def to_deploy(graph, act_clip_val, weight_clip_val, args, **kwargs):

@@ -1100,17 +1100,7 @@ def fake_quant_mx(x, axis, elem, out=None, scales=None):
     scales: an optional uint8 device tensor of [outer, ceil(K / 32), inner] elements that receives the E8M0 codes (0xFF: a block
     that holds a NaN or an infinity, whose elements all come out NaN)."""
     _require_cuda(x, "x")
-    if elem not in MX_ELEM:
-        raise _hip.DipoorletHipError(f"fake_quant_mx: elem must be 'mxfp8' or 'mxfp4', got {elem!r}")
-    if not isinstance(axis, int) or not -x.dim() <= axis < x.dim():
-        raise _hip.DipoorletHipError(f"fake_quant_mx: axis {axis!r} out of range for a tensor of {x.dim()} dimension(s)")
-    axis %= x.dim()
-    outer = inner = 1
-    for d in x.shape[:axis]:
-        outer *= int(d)
-    for d in x.shape[axis + 1:]:
-        inner *= int(d)
-    k = int(x.shape[axis])
+    axis, outer, k, inner = _mx_split("fake_quant_mx", tuple(x.shape), axis, elem)
     if out is None:
         y = torch.empty_like(x)
     else:
@@ -1126,6 +1116,72 @@ def fake_quant_mx(x, axis, elem, out=None, scales=None):
                                          f"([outer, ceil(K / {MX_BLOCK}), inner] = [{outer}, {-(-k // MX_BLOCK)}, {inner}])")
     _hip.check(_hip.lib().dpl_fake_quant_mx(MX_ELEM[elem], _ptr(x), _ptr(y), outer, k, inner, None if scales is None else _ptr(scales),
                                             _stream()), "dpl_fake_quant_mx")
+    return y
+
+
+def _mx_split(who, shape, axis, elem):
+    """The argument checks fake_quant_mx, mx_encode and mx_decode share -> (axis from the front, outer, k, inner)."""
+    if elem not in MX_ELEM:
+        raise _hip.DipoorletHipError(f"{who}: elem must be 'mxfp8' or 'mxfp4', got {elem!r}")
+    nd = len(shape)
+    if not isinstance(axis, int) or not -nd <= axis < nd:
+        raise _hip.DipoorletHipError(f"{who}: axis {axis!r} out of range for a tensor of {nd} dimension(s)")
+    axis %= nd
+    outer = inner = 1
+    for d in shape[:axis]:
+        outer *= int(d)
+    for d in shape[axis + 1:]:
+        inner *= int(d)
+    return axis, outer, int(shape[axis]), inner
+
+
+def mx_packed_shapes(shape, axis, elem):
+    """(codes shape, scales shape) of an MX tensor of `shape` blocked along `axis` as mx_encode writes it: K-innermost, [*outer
+    dims, *inner dims, Kp (mxfp8) or Kp / 2 (mxfp4)] and [..., Kp / 32] with Kp = 32 * ceil(K / 32)."""
+    axis, _, k, _ = _mx_split("mx_packed_shapes", tuple(shape), axis, elem)
+    kp = MX_BLOCK * -(-k // MX_BLOCK)
+    lead = tuple(int(d) for d in shape[:axis]) + tuple(int(d) for d in shape[axis + 1:])
+    return lead + (kp // 2 if elem == "mxfp4" else kp,), lead + (kp // MX_BLOCK,)
+
+
+def mx_encode(x, axis, elem):
+    """`--mx_pack`: what fake_quant_mx(x, axis, elem) computes, as bytes (dpl_mx_encode; tests/mx_pack_model.py is the definition)
+    -> (codes, scales), uint8 device tensors.  scales: the E8M0 byte per block (0xFF: the block holds a NaN or an infinity);
+    codes: OCP FP8 E4M3FN bytes ('mxfp8'; 0x7F in a 0xFF block) or E2M1 nibbles, two to a byte, the even index along `axis` in the
+    low nibble ('mxfp4'; 0 in a 0xFF block).  Both are K-INNERMOST — mx_packed_shapes(x.shape, axis, elem): the block axis moves
+    to the end, padded with code 0 to a multiple of 32 —, which for an axis that is not the last is a transpose of x's element
+    order, and not the order of fake_quant_mx's scales=."""
+    _require_cuda(x, "x")
+    _, outer, k, inner = _mx_split("mx_encode", tuple(x.shape), axis, elem)
+    cs, ss = mx_packed_shapes(x.shape, axis, elem)
+    codes = torch.empty(cs, dtype=torch.uint8, device=x.device)
+    scales = torch.empty(ss, dtype=torch.uint8, device=x.device)
+    _hip.check(_hip.lib().dpl_mx_encode(MX_ELEM[elem], _ptr(x), outer, k, inner, _ptr(codes), _ptr(scales), _stream()), "dpl_mx_encode")
+    return codes, scales
+
+
+def mx_decode(codes, scales, elem, shape, axis, out=None):
+    """The inverse of mx_encode (dpl_mx_decode): codes / scales as mx_packed_shapes(shape, axis, elem) lays them out -> the fp32
+    tensor of `shape`; mx_decode(*mx_encode(x, axis, elem), elem, x.shape, axis) equals fake_quant_mx(x, axis, elem) bit for bit.
+    Defined on every byte pair: scale 0xFF and the E4M3 codes 0x7F / 0xFF give NaN, a product above fp32's range +-inf.  out: an
+    optional contiguous fp32 device tensor of `shape`."""
+    for t, name in ((codes, "codes"), (scales, "scales")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise _hip.DipoorletHipError(f"mx_decode: {name} must be a contiguous uint8 ROCm device tensor; dipoorlet_amd has no CPU path")
+    shape = tuple(int(d) for d in shape)
+    _, outer, k, inner = _mx_split("mx_decode", shape, axis, elem)
+    cs, ss = mx_packed_shapes(shape, axis, elem)
+    if codes.numel() != int(np.prod(cs, dtype=np.int64)) or scales.numel() != int(np.prod(ss, dtype=np.int64)) or scales.device != codes.device:
+        raise _hip.DipoorletHipError(f"mx_decode: a tensor of shape {list(shape)} along axis {axis} has codes {list(cs)} and scales {list(ss)} "
+                                     f"(K-innermost), got {list(codes.shape)} and {list(scales.shape)}")
+    if out is None:
+        y = torch.empty(shape, dtype=torch.float32, device=codes.device)
+    else:
+        _require_cuda(out, "out")
+        if tuple(out.shape) != shape or out.device != codes.device:
+            raise _hip.DipoorletHipError("mx_decode: out must have the given shape and the codes' device")
+        y = out
+    _hip.check(_hip.lib().dpl_mx_decode(MX_ELEM[elem], _ptr(codes), _ptr(scales), outer, k, inner, _ptr(y), _stream()), "dpl_mx_decode")
     return y
 
 

@@ -17,6 +17,8 @@ Per tensor:
     dipoorlet::fake_quant_add_relu(Tensor x, Tensor x2, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor
     dipoorlet::fake_quant_fp8(Tensor x, Tensor scale, int axis) -> Tensor      the pair on the OCP FP8 E4M3 grid (ops.fake_quant_fp8)
     dipoorlet::fake_quant_mx(Tensor x, int axis, str elem) -> Tensor           the OCP Microscaling pair, 'mxfp8' / 'mxfp4', blocks of 32 along axis (ops.fake_quant_mx)
+    dipoorlet::mx_encode(Tensor x, int axis, str elem) -> (Tensor, Tensor)     the same values as bytes: (element codes, E8M0 scales), uint8, K-innermost (ops.mx_encode: --mx_pack)
+    dipoorlet::mx_decode(Tensor codes, Tensor scales, str elem, int[] shape, int axis) -> Tensor   those bytes back to fp32 of `shape` (ops.mx_decode)
     dipoorlet::hadamard32(Tensor x) -> Tensor                                  x . blockdiag(H32) along the last axis, a multiple of 32 (ops.hadamard32: --mx_rotate)
     dipoorlet::gptq_block(Tensor(a!) w, int c0, int nb, Tensor u, Tensor scale, Tensor zero_point, int qlo, int qhi, str fmt) -> Tensor
                                                                one block of GPTQ's column recursion in place on w; -> Err [rows, nb] (ops.gptq_block)
@@ -328,6 +330,27 @@ def fake_quant_mx(x: torch.Tensor, axis: int, elem: str) -> torch.Tensor:
 @fake_quant_mx.register_fake
 def _(x, axis, elem):
     return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op("dipoorlet::mx_encode", mutates_args=(), device_types="cuda")
+def mx_encode(x: torch.Tensor, axis: int, elem: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.mx_encode(x.contiguous(), axis, elem)
+
+
+@mx_encode.register_fake
+def _(x, axis, elem):
+    cs, ss = ops.mx_packed_shapes(x.shape, axis, elem)
+    return x.new_empty(cs, dtype=torch.uint8), x.new_empty(ss, dtype=torch.uint8)
+
+
+@torch.library.custom_op("dipoorlet::mx_decode", mutates_args=(), device_types="cuda")
+def mx_decode(codes: torch.Tensor, scales: torch.Tensor, elem: str, shape: List[int], axis: int) -> torch.Tensor:
+    return ops.mx_decode(codes.contiguous(), scales.contiguous(), elem, shape, axis)
+
+
+@mx_decode.register_fake
+def _(codes, scales, elem, shape, axis):
+    return codes.new_empty(list(shape), dtype=torch.float32)
 
 
 @torch.library.custom_op("dipoorlet::hadamard32", mutates_args=(), device_types="cuda")

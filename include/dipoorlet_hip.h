@@ -25,14 +25,15 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 29 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 30 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
                               25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
                               26: dpl_colwise_absmax (per-channel running max |x| of a channels-last activation: --smooth);
                               27: dpl_fake_quant_mx (the OCP Microscaling Q/DQ pair, MXFP8 / MXFP4: --mx);
                               28: dpl_gptq_block (sequential quantise-and-compensate of a block of weight columns: --gptq);
-                              29: dpl_hadamard32 (32-point Hadamard rotation of every MX block of an activation: --mx_rotate) */
+                              29: dpl_hadamard32 (32-point Hadamard rotation of every MX block of an activation: --mx_rotate);
+                              30: dpl_mx_encode / dpl_mx_decode (an MX tensor as packed element codes and E8M0 scale bytes: --mx_pack) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -424,6 +425,30 @@ int dpl_fake_quant_fp8_items(const dpl_work_item* d_items, int64_t n_items, cons
 #define DPL_MX_E2M1 1
 int dpl_fake_quant_mx(int32_t elem, const float* d_x, float* d_y, uint64_t outer, uint64_t k, uint64_t inner,
                       uint8_t* d_scales_or_null, dpl_stream_t s);
+
+/* ---- the element codes of an MX tensor and back (beyond the reference; --mx_pack; the definition is tests/mx_pack_model.py).
+ *      dpl_mx_encode writes what dpl_fake_quant_mx computes, as bytes: with y its output and se / 0xFF its scale code per block,
+ *        d_scales   the E8M0 byte, se + 127; 0xFF for a block that holds a NaN or an infinity
+ *        E4M3       the OCP FP8 E4M3FN byte S.EEEE.MMM (bias 7) of y / 2^se, the sign bit of a zero kept; 0x7F for every element
+ *                   that exists of a 0xFF block
+ *        E2M1       four bits S.EE.M (bias 1; the magnitude is the index into 0, 0.5, 1, 1.5, 2, 3, 4, 6), two to a byte, the
+ *                   element at the even index along k in the low nibble (ONNX FLOAT4E2M1); 0 in a 0xFF block
+ *      LAYOUT: codes and scales are K-INNERMOST, the order a block-scaled GEMM reads both operands in.  With kp = 32 * ceil(k / 32):
+ *        d_codes    uint8 [outer, inner, kp] (E4M3) or [outer, inner, kp / 2] (E2M1); elements past k of a short last block: code 0
+ *        d_scales   uint8 [outer, inner, kp / 32]
+ *      For inner > 1 this is a TRANSPOSE of the element order of the fp32 tensor [outer, k, inner], and the scales are NOT in the
+ *      order of dpl_fake_quant_mx's d_scales_or_null ([outer, ceil(k / 32), inner]).
+ *      dpl_mx_decode is defined on every byte pair: scale 0xFF -> NaN (0x7FC00000) for the whole block; E4M3 codes 0x7F and 0xFF
+ *      -> NaN; otherwise +-value * 2^(scale - 127) exactly (at least 2^-136: an fp32 subnormal, kept whatever the denormal mode),
+ *      +-inf above fp32's range (never a pair the encoder writes).  It writes the elements that exist, [outer, k, inner], and
+ *      nothing past k.  dpl_mx_decode(dpl_mx_encode(x)) == dpl_fake_quant_mx(x) bit for bit.
+ *      Limits and the no-op rule are dpl_fake_quant_mx's.  d_codes must be 16-byte aligned (refused otherwise: a block's 32 or 16
+ *      bytes move as 16-byte vectors); d_x / d_y of any alignment (not 16-byte aligned, or k resp. inner % 4 != 0: element by
+ *      element); d_scales must not be null. */
+int dpl_mx_encode(int32_t elem, const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, uint8_t* d_codes, uint8_t* d_scales,
+                  dpl_stream_t s);
+int dpl_mx_decode(int32_t elem, const uint8_t* d_codes, const uint8_t* d_scales, uint64_t outer, uint64_t k, uint64_t inner, float* d_y,
+                  dpl_stream_t s);
 
 /* ---- the block-Hadamard rotation of --mx_rotate (beyond the reference): y = x . blockdiag(H32) along the contiguous last axis of
  *      the [rows, k] tensor, H32[i][j] = (-1)^popcount(i & j) (Sylvester, natural order, symmetric, H32 . H32 = 32 I; NOT
