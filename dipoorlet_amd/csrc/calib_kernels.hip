@@ -180,11 +180,11 @@ __device__ __forceinline__ void hist_op_init(HistOp<kFast>& op, const dpl_hist_r
 
 // LDS of a histogramming workgroup:  uint32 counters[bins + 1] | uint32 s_nz[waves]
 // (counter `bins`: HistOp's estimates of `bins`; s_nz: hist_flush's non-zero count per wave).  k_abs_hist's whole dynamic LDS,
-// the tail of k_abs_hist_rest's (RestLds) and the head of k_minmax_hist's (MinMaxHistLds).
+// the tail of k_hist_spec's (RestLds) and the head of k_minmax_hist's (MinMaxHistLds).
 struct HistLds {
     static __host__ __device__ uint32_t* s_nz(uint32_t* counters, int bins) { return counters + bins + 1; }
     static __host__ __device__ uint32_t* end(uint32_t* counters, int bins) { return s_nz(counters, bins) + kBlock / kWave; }
-    static __host__ __device__ size_t bytes(int bins) { return ((size_t)bins + 1 + kBlock / kWave) * sizeof(uint32_t); }
+    static __host__ __device__ constexpr size_t bytes(int bins) { return ((size_t)bins + 1 + kBlock / kWave) * sizeof(uint32_t); }
 };
 
 // The workgroup's LDS counters of one item -> the slot's row of `out` (uint64: the accumulated histogram; uint32: a batch's own
@@ -255,7 +255,7 @@ __device__ __forceinline__ float py_min(float a, float b) { return (b < a) ? b :
 
 // The histogram range of a slot from its fp32 min / max.  A histogram depends on the range through this struct alone, so two
 // ranges that agree byte for byte bin every value alike: what the range pass's speculation rests on (k_hist_snapshot,
-// k_hist_resolve).
+// k_hist_spec).
 __device__ __forceinline__ dpl_hist_range hist_range_of(float gmin, float gmax, int bins) {
     dpl_hist_range r;
     // forward_net.py:266 — data_max = max(np.max(maxlist), -np.min(minlist))
@@ -310,7 +310,7 @@ __global__ void k_hist_prepare(const float* __restrict__ gmin, const float* __re
 // dmax of a tensor stops moving once the batch that holds its extreme has passed.  The range pass therefore histograms every
 // batch against the range its running min / max give (a SNAPSHOT taken before the launch: other workgroups move the live
 // accumulators during it) into a per-batch ledger entry; the histogram pass compares the snapshot with the final range byte for
-// byte (k_hist_resolve), adds the rows that match and reads only the tensors whose guess was wrong (k_abs_hist_rest).  A wrong
+// byte, adds the rows that match and reads only the tensors whose guess was wrong (k_hist_spec: one launch).  A wrong
 // guess costs what it always cost, so no count can change.
 //
 // A ledger entry (device memory, 16-byte aligned; the documented format: callers read the flags at n_slots * sizeof(dpl_hist_range)):
@@ -328,7 +328,7 @@ struct SpecEntry {
 };
 
 // Snapshot of the provisional ranges + the entry's counts zeroed.  A slot with no data yet, a NaN flag or a range numpy would
-// refuse comes out with status != 0 ("no guess": the fused kernel takes its min / max only and k_hist_resolve never accepts it).
+// refuse comes out with status != 0 ("no guess": the fused kernel takes its min / max only and k_hist_spec never accepts it).
 __global__ __launch_bounds__(kBlock) void k_hist_snapshot(const uint32_t* __restrict__ mn, const uint32_t* __restrict__ mx,
                                                            const uint32_t* __restrict__ nan, int64_t n, int bins,
                                                            dpl_hist_range* __restrict__ snap, uint32_t* __restrict__ flags,
@@ -411,65 +411,76 @@ __global__ __launch_bounds__(kBlock) void k_minmax_hist(const dpl_work_item* __r
     }
 }
 
-// One workgroup per slot: the guess was right iff the snapshot equals the final range in all 32 bytes (a sign-of-zero or NaN
-// difference falls to the safe side) and numpy accepts the range.  flags[t]: 1 = the entry's row is this batch's histogram and
-// has been added; 2 = nothing to count (status != 0: k_abs_hist skips such a tensor too); 0 = to be read.
-// stats (may be null) += {pairs, pairs added, elements, elements added}.
-__global__ __launch_bounds__(kBlock) void k_hist_resolve(const dpl_hist_range* __restrict__ snap,
-                                                          const dpl_hist_range* __restrict__ fin,
-                                                          const uint32_t* __restrict__ counts, const uint64_t* __restrict__ elems,
-                                                          int bins, uint64_t* __restrict__ hist, uint32_t* __restrict__ flags,
-                                                          unsigned long long* __restrict__ stats) {
-    const uint32_t t = blockIdx.x;
-    const uint32_t* a = reinterpret_cast<const uint32_t*>(snap + t);
-    const uint32_t* b = reinterpret_cast<const uint32_t*>(fin + t);
-    bool same = true;
+// What the histogram pass does with tensor t, the value of flags[t]: 1 = the entry's row is this batch's histogram and is added
+// (the guess was right: the snapshot equals the final range in all 32 bytes — a sign-of-zero or NaN difference falls to the safe
+// side — and numpy accepts the range); 2 = nothing to count (status != 0: k_abs_hist skips such a tensor too); 0 = to be read.
+// A pure function of snap and fin, which no kernel writes during the histogram pass: every workgroup of k_hist_spec evaluates
+// it for itself and gets the same answer.
+struct SpecVerdict {
+    const dpl_hist_range* __restrict__ snap;
+    const dpl_hist_range* __restrict__ fin;
+    __device__ __forceinline__ uint32_t operator()(int t) const {
+        const uint32_t* a = reinterpret_cast<const uint32_t*>(snap + t);
+        const uint32_t* b = reinterpret_cast<const uint32_t*>(fin + t);
+        bool same = true;
 #pragma unroll
-    for (int w = 0; w < (int)(sizeof(dpl_hist_range) / 4); ++w) same = same && (a[w] == b[w]);
-    const uint32_t status = fin[t].status;
-    const bool valid = same && status == 0u;
-    if (threadIdx.x == 0) {
-        flags[t] = valid ? 1u : (status != 0u ? 2u : 0u);
-        if (stats) {
-            const unsigned long long e = elems[t];
-            atomicAdd(stats + 0, 1ull);
-            atomicAdd(stats + 2, e);
-            if (valid) {
-                atomicAdd(stats + 1, 1ull);
-                atomicAdd(stats + 3, e);
-            }
-        }
+        for (int w = 0; w < (int)(sizeof(dpl_hist_range) / 4); ++w) same = same && (a[w] == b[w]);
+        return fin[t].status != 0u ? 2u : (same ? 1u : 0u);
     }
-    if (!valid) return;
-    const uint32_t* __restrict__ row = counts + (uint64_t)t * (uint64_t)bins;
-    uint64_t* __restrict__ out = hist + (uint64_t)t * (uint64_t)bins;
-    for (int j = threadIdx.x; j < bins; j += kBlock) {
-        const uint32_t c = row[j];
-        if (c) out[j] += (uint64_t)c;  // (this workgroup alone touches row t during the launch)
+};
+
+// The verdicts the last histogram pass over the entry left in memory (the test hook k_hist_spec_cuts).
+struct StoredVerdict {
+    const uint32_t* __restrict__ flags;
+    __device__ __forceinline__ uint32_t operator()(int t) const { return flags[t]; }
+};
+
+// rest_prefix's tally: a thread's share of {pairs added, elements, elements added} (k_hist_spec's statistics), or nothing.
+struct SpecTally {
+    unsigned long long n_add = 0, e_all = 0, e_add = 0;
+    __device__ __forceinline__ void operator()(uint32_t f, uint64_t e) {
+        e_all += e;
+        n_add += f == 1u ? 1ull : 0ull;
+        e_add += f == 1u ? e : 0ull;
     }
-}
+};
+struct NoTally {
+    __device__ __forceinline__ void operator()(uint32_t, uint64_t) {}
+};
 
 __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
     const uint32_t lo = __shfl_up((uint32_t)v, d, kWave), hi = __shfl_up((uint32_t)(v >> 32), d, kWave);
     return ((uint64_t)hi << 32) | lo;
 }
 
-// k_abs_hist over the tensors k_hist_resolve left (flags[t] == 0), BALANCED: the remaining tensors' elements form one stream,
+// k_abs_hist over the tensors whose verdict is 0, BALANCED: the remaining tensors' elements form one stream,
 // workgroup b of G owns [cut(b), cut(b + 1)) of it, cut(b) = floor(total * b / G) rounded down to a multiple of 1024 elements
 // from the start of the tensor it falls in — the cuts dpl_build_balanced_items makes, in closed form, so every workgroup derives
 // its own share from the prefix sums (taken by each workgroup into LDS: T additions) with no list built and no host in between.
 // Tensor t is segment t, slot t, offset 0 (the per-tensor spans of a TensorSetPlan); elems[t] < 2^32.
-// (k_abs_hist_rest below; rest_prefix and rest_cut are its two steps, shared with the test hook k_hist_spec_cuts.)
+// (k_hist_spec below; rest_prefix and rest_cut are its two steps, shared with the test hook k_hist_spec_cuts.)
 //
-// Exclusive prefix sums of the remaining tensors' element counts into P[0 .. n_tensors] (LDS), by the whole workgroup.
-__device__ __forceinline__ void rest_prefix(const uint64_t* __restrict__ elems, const uint32_t* __restrict__ flags, int n_tensors,
-                                            uint64_t* P, uint64_t* s_tot) {
+// Every tensor's verdict into v[0 .. n_tensors) and the exclusive prefix sums of the remaining tensors' element counts into
+// P[0 .. n_tensors] (both LDS), by the whole workgroup.  A thread's loads (verdict's and elems') depend on nothing but t: one
+// round trip.  (P[t] holds tensor t's remaining count between the two loops: a thread reads back only what it wrote itself.)
+// tally(verdict, elements) sees every tensor once, spread over the workgroup's threads.
+template <class Verdict, class Tally>
+__device__ __forceinline__ void rest_prefix(const uint64_t* __restrict__ elems, const Verdict& verdict, int n_tensors,
+                                            uint64_t* P, uint64_t* s_tot, uint32_t* v, Tally& tally) {
     const int per = (n_tensors + kBlock - 1) / kBlock;  // consecutive tensors per thread
     const int t0 = (int)threadIdx.x * per;
     uint64_t mine = 0;
     for (int j = 0; j < per; ++j) {
         const int t = t0 + j;
-        if (t < n_tensors && flags[t] == 0u) mine += elems[t];
+        if (t < n_tensors) {
+            const uint32_t f = verdict(t);
+            const uint64_t e = elems[t];
+            const uint64_t rem = f == 0u ? e : 0ull;
+            v[t] = f;
+            P[t] = rem;
+            mine += rem;
+            tally(f, e);
+        }
     }
     uint64_t incl = mine;
     const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
@@ -485,8 +496,9 @@ __device__ __forceinline__ void rest_prefix(const uint64_t* __restrict__ elems, 
     for (int j = 0; j < per; ++j) {
         const int t = t0 + j;
         if (t < n_tensors) {
+            const uint64_t rem = P[t];
             P[t] = run;
-            if (flags[t] == 0u) run += elems[t];
+            run += rem;
         }
     }
     if (threadIdx.x == kBlock - 1) P[n_tensors] = run;
@@ -511,33 +523,112 @@ __device__ __forceinline__ void rest_cut(const uint64_t* P, int n_tensors, uint6
     cut = P[lo - 1] + ((target - P[lo - 1]) & ~1023ull);
 }
 
-// LDS of rest_prefix:  uint64 P[n_tensors + 1] | uint64 s_tot[waves]   (the prefix sums; the scan's wave totals).
-// k_hist_spec_cuts's whole dynamic LDS and the head of k_abs_hist_rest's (n_tensors <= DPL_HIST_SPEC_MAX_TENSORS: 16 KiB).
+// LDS of rest_prefix:  uint64 P[n_tensors + 1] | uint64 s_tot[3 * waves] | uint32 v[n_tensors]
+// (the prefix sums; the scan's wave totals, afterwards the wave totals of k_hist_spec's three statistics; the verdicts).
+// k_hist_spec_cuts's whole dynamic LDS and the head of k_hist_spec's (n_tensors <= DPL_HIST_SPEC_MAX_TENSORS: 24 KiB).
 struct RestPrefixLds {
+    static constexpr int kTotals = 3 * (kBlock / kWave);
     static __host__ __device__ uint64_t* P(uint32_t* base) { return reinterpret_cast<uint64_t*>(base); }
     static __host__ __device__ uint64_t* s_tot(uint32_t* base, int n_tensors) { return P(base) + n_tensors + 1; }
-    static __host__ __device__ size_t bytes(int64_t n_tensors) { return ((size_t)n_tensors + 1 + kBlock / kWave) * sizeof(uint64_t); }
-};
-
-// LDS of k_abs_hist_rest:  RestPrefixLds | HistLds
-struct RestLds {
-    static __host__ __device__ uint32_t* counters(uint32_t* base, int n_tensors) {
-        return reinterpret_cast<uint32_t*>(RestPrefixLds::s_tot(base, n_tensors) + kBlock / kWave);
+    static __host__ __device__ uint32_t* v(uint32_t* base, int n_tensors) {
+        return reinterpret_cast<uint32_t*>(s_tot(base, n_tensors) + kTotals);
     }
-    static __host__ __device__ size_t bytes(int64_t n_tensors, int bins) { return RestPrefixLds::bytes(n_tensors) + HistLds::bytes(bins); }
+    static __host__ __device__ uint32_t* end(uint32_t* base, int n_tensors) { return v(base, n_tensors) + n_tensors; }
+    static __host__ __device__ constexpr size_t bytes(int64_t n_tensors) {
+        return ((size_t)n_tensors + 1 + kTotals) * sizeof(uint64_t) + (size_t)n_tensors * sizeof(uint32_t);
+    }
 };
 
-__global__ __launch_bounds__(kBlock) void k_abs_hist_rest(const uint64_t* __restrict__ elems, const uint32_t* __restrict__ flags,
-                                                           int n_tensors, const float* const* __restrict__ segs,
-                                                           const dpl_hist_range* __restrict__ ranges, int bins,
-                                                           uint64_t* __restrict__ hist) {
+// LDS of k_hist_spec:  RestPrefixLds | HistLds
+struct RestLds {
+    static __host__ __device__ uint32_t* counters(uint32_t* base, int n_tensors) { return RestPrefixLds::end(base, n_tensors); }
+    static __host__ __device__ constexpr size_t bytes(int64_t n_tensors, int bins) {
+        return RestPrefixLds::bytes(n_tensors) + HistLds::bytes(bins);
+    }
+};
+static_assert(RestLds::bytes(DPL_HIST_SPEC_MAX_TENSORS, DPL_MAX_BINS) <= 160 * 1024, "k_hist_spec's largest layout must fit a CU's LDS");
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, kWave);
+    return x;
+}
+
+// The whole histogram-pass call over a bound set in ONE launch.  No workgroup waits for, or reads, anything another workgroup
+// of the launch writes: each takes every tensor's verdict for itself (rest_prefix over SpecVerdict), so all agree on which rows
+// are added and where the remaining stream is cut.
+//   * Slot t has exactly one resolver, workgroup t mod G: it writes flags[t] and, where the verdict is 1, adds the entry's row
+//     into hist[t, :].  Valid rows of hist are touched only by their resolver; invalid rows are touched only by the streaming
+//     workgroups' atomics: the two sets are disjoint by construction.  The resolver adds with atomics that return nothing all
+//     the same, as hist_flush does: they need no load of hist in front of them, so a resolver goes on to its share of the
+//     stream at once.  The row of its first slot it requests BEFORE the verdicts (kAhead counts per thread, in flight beside
+//     rest_prefix's loads: one round trip for both; unused where the verdict is not 1).
+//   * Workgroup 0 adds the launch's totals to stats (may be null) += {pairs, pairs added, elements, elements added}: four
+//     atomics per launch.
+//   * Every workgroup then streams its share [cut(b), cut(b + 1)) of the tensors to be read, as k_abs_hist does.
+// snap and counts are only read: an entry may be consumed by any number of histogram passes.
+__global__ __launch_bounds__(kBlock) void k_hist_spec(const dpl_hist_range* __restrict__ snap, const uint32_t* __restrict__ counts,
+                                                       uint32_t* __restrict__ flags, const uint64_t* __restrict__ elems,
+                                                       int n_tensors, const float* const* __restrict__ segs,
+                                                       const dpl_hist_range* __restrict__ ranges, int bins,
+                                                       uint64_t* __restrict__ hist, unsigned long long* __restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_rest[];  // RestLds
     uint64_t* P = RestPrefixLds::P(lds_rest);
     uint64_t* s_tot = RestPrefixLds::s_tot(lds_rest, n_tensors);
+    uint32_t* v = RestPrefixLds::v(lds_rest, n_tensors);
     uint32_t* lds = RestLds::counters(lds_rest, n_tensors);
     uint32_t* s_nz = HistLds::s_nz(lds, bins);
-    rest_prefix(elems, flags, n_tensors, P, s_tot);
-    if (P[n_tensors] == 0) return;
+    constexpr int kAhead = 8;  // (2048 bins: the whole row)
+    uint32_t ahead[kAhead];
+#pragma unroll
+    for (int u = 0; u < kAhead; ++u) {
+        const int j = (int)threadIdx.x + u * kBlock;
+        ahead[u] = (blockIdx.x < (uint32_t)n_tensors && j < bins) ? counts[(uint64_t)blockIdx.x * (uint64_t)bins + j] : 0u;
+    }
+    SpecTally tally;
+    rest_prefix(elems, SpecVerdict{snap, ranges}, n_tensors, P, s_tot, v, tally);
+    for (uint32_t t = blockIdx.x; t < (uint32_t)n_tensors; t += gridDim.x) {  // (no barrier inside: the trip count differs between workgroups only)
+        const uint32_t f = v[t];
+        if (threadIdx.x == 0) flags[t] = f;
+        if (f != 1u) continue;
+        const uint32_t* __restrict__ row = counts + (uint64_t)t * (uint64_t)bins;
+        unsigned long long* __restrict__ out = reinterpret_cast<unsigned long long*>(hist + (uint64_t)t * (uint64_t)bins);
+        int j = threadIdx.x;
+        if (t == blockIdx.x) {
+#pragma unroll
+            for (int u = 0; u < kAhead; ++u)
+                if (ahead[u]) atomicAdd(out + j + u * kBlock, (unsigned long long)ahead[u]);  // (ahead[u] == 0 beyond the row)
+            j += kAhead * kBlock;
+        }
+        for (; j < bins; j += kBlock) {
+            const uint32_t c = row[j];
+            if (c) atomicAdd(out + j, (unsigned long long)c);
+        }
+    }
+    if (blockIdx.x == 0 && stats) {  // (uniform over the workgroup, as is the barrier inside)
+        unsigned long long n_add = wave_sum_u64(tally.n_add), e_all = wave_sum_u64(tally.e_all), e_add = wave_sum_u64(tally.e_add);
+        constexpr int kWaves = kBlock / kWave;
+        if ((threadIdx.x & (kWave - 1)) == 0) {  // (s_tot is free: rest_prefix ended in a barrier)
+            const int wv = threadIdx.x / kWave;
+            s_tot[wv] = n_add;
+            s_tot[kWaves + wv] = e_all;
+            s_tot[2 * kWaves + wv] = e_add;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            n_add = e_all = e_add = 0;
+            for (int w = 0; w < kWaves; ++w) {
+                n_add += s_tot[w];
+                e_all += s_tot[kWaves + w];
+                e_add += s_tot[2 * kWaves + w];
+            }
+            atomicAdd(stats + 0, (unsigned long long)n_tensors);
+            atomicAdd(stats + 1, n_add);
+            atomicAdd(stats + 2, e_all);
+            atomicAdd(stats + 3, e_add);
+        }
+    }
+    if (P[n_tensors] == 0) return;  // (uniform; nothing to read: the steady state of a sweep over few distinct sets)
     uint64_t cut[2];
     int at[2];
     rest_cut(P, n_tensors, gridDim.x, blockIdx.x, cut[0], at[0]);
@@ -554,7 +645,7 @@ __global__ __launch_bounds__(kBlock) void k_abs_hist_rest(const uint64_t* __rest
         it.seg = (uint32_t)t;
         it.slot = (uint32_t)t;
         it.reserved = 0u;
-        const dpl_hist_range r = ranges[t];  // (status == 0: k_hist_resolve flagged every other tensor)
+        const dpl_hist_range r = ranges[t];  // (status == 0 and a wrong guess: every other tensor adds nothing to P)
         for (int b = threadIdx.x; b <= bins; b += kBlock) lds[b] = 0u;
         __syncthreads();
         if (r.exact_div)
@@ -566,13 +657,14 @@ __global__ __launch_bounds__(kBlock) void k_abs_hist_rest(const uint64_t* __rest
     }
 }
 
-// The cuts k_abs_hist_rest works to, written out (dpl_hist_spec_cuts: what tests hold against tests/hist_spec_model.py).
+// The cuts k_hist_spec works to for the verdicts it left in flags, written out (dpl_hist_spec_cuts: what tests hold against
+// tests/hist_spec_model.py).  flags[t] is SpecVerdict's value, so these are the cuts that launch worked to.
 __global__ __launch_bounds__(kBlock) void k_hist_spec_cuts(const uint64_t* __restrict__ elems, const uint32_t* __restrict__ flags,
                                                             int n_tensors, uint64_t* __restrict__ cuts) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_cuts[];  // RestPrefixLds
     uint64_t* P = RestPrefixLds::P(lds_cuts);
-    uint64_t* s_tot = RestPrefixLds::s_tot(lds_cuts, n_tensors);
-    rest_prefix(elems, flags, n_tensors, P, s_tot);
+    NoTally none;
+    rest_prefix(elems, StoredVerdict{flags}, n_tensors, P, RestPrefixLds::s_tot(lds_cuts, n_tensors), RestPrefixLds::v(lds_cuts, n_tensors), none);
     if (threadIdx.x != 0) return;
     uint64_t cut = 0;
     int at = 0;
@@ -901,7 +993,7 @@ inline int check_bins(const char* who, int bins) {
     return 0;
 }
 
-// dpl_hist_spec_accumulate / dpl_hist_spec_cuts: P[n_slots + 1] must fit k_abs_hist_rest's LDS, n_blocks a grid
+// dpl_hist_spec_accumulate / dpl_hist_spec_cuts: P[n_slots + 1] must fit k_hist_spec's LDS, n_blocks a grid
 inline int check_spec_geometry(const char* who, int64_t n_slots, int64_t n_blocks) {
     const bool slots_ok = n_slots > 0 && n_slots <= DPL_HIST_SPEC_MAX_TENSORS;
     if (slots_ok && n_blocks > 0 && n_blocks <= 0x7FFFFFFFll) return 0;
@@ -1021,12 +1113,9 @@ int dpl_hist_spec_accumulate(void* d_entry, const uint64_t* d_elems, int64_t n_s
     if (!d_entry || ((uintptr_t)d_entry & 15u)) return fail_msg("dpl_hist_spec_accumulate: d_entry must be 16-byte aligned");
     if (int e = check_spec_geometry("dpl_hist_spec_accumulate", n_slots, n_blocks)) return e;
     const SpecEntry entry(d_entry, n_slots);
-    hipLaunchKernelGGL(k_hist_resolve, dim3((unsigned)n_slots), dim3(kBlock), 0, (hipStream_t)s, entry.snap, d_ranges, entry.counts,
-                       d_elems, bins, d_hist, entry.flags, (unsigned long long*)d_stats);
-    DPL_LAUNCH_CHECK("k_hist_resolve");
-    hipLaunchKernelGGL(k_abs_hist_rest, dim3((unsigned)n_blocks), dim3(kBlock), RestLds::bytes(n_slots, bins), (hipStream_t)s, d_elems,
-                       entry.flags, (int)n_slots, d_seg_ptrs, d_ranges, bins, d_hist);
-    DPL_LAUNCH_CHECK("k_abs_hist_rest");
+    hipLaunchKernelGGL(k_hist_spec, dim3((unsigned)n_blocks), dim3(kBlock), RestLds::bytes(n_slots, bins), (hipStream_t)s, entry.snap,
+                       entry.counts, entry.flags, d_elems, (int)n_slots, d_seg_ptrs, d_ranges, bins, d_hist, (unsigned long long*)d_stats);
+    DPL_LAUNCH_CHECK("k_hist_spec");
     return 0;
 }
 
