@@ -1,5 +1,5 @@
 """`python -m dipoorlet_amd -M model.onnx -I calib_dir -N 1024 -A hist -D trt` — the reference's CLI
-(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, `--mx_rotate`, a block-Hadamard rotation of those operands, `--mx_pack`, the constant ones as packed element codes and E8M0 scales, and `--gptq`, Hessian-compensated weight rounding, are this project's additions).
+(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, `--mx_rotate`, a block-Hadamard rotation of those operands, `--mx_pack`, the constant ones as packed element codes and E8M0 scales, `--mx_verify`, those bytes multiplied on the block-scaled matrix instruction and compared with the fake-quantised graph, and `--gptq`, Hessian-compensated weight rounding, are this project's additions).
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
@@ -63,6 +63,12 @@ def build_parser():
                         "ocp_mx_weights.bin (per tensor its OCP E4M3 bytes or packed E2M1 nibbles, then its E8M0 scale bytes, both "
                         "K-innermost, every section on a 64-byte boundary) and ocp_mx_weights.json (offsets and shapes, keyed as "
                         "ocp_mx_blocks.json).  Encoded on the device from the weights as they stand after every weight transform")
+    p.add_argument("--mx_verify", default=False, action="store_true",
+                   help="(not in the reference; with --mx_pack only) after the deploy files are written, read ocp_mx_weights.bin back and "
+                        "run every MatMul / Gemm whose two operands are block-scaled on CDNA4's block-scaled matrix instruction "
+                        "(ops.mx_gemm) — the activation operand encoded on the device, the constant one from the file's bytes — over the "
+                        "first --calib_batch images, and compare with that node's output in the fake-quantised graph: writes "
+                        "mx_verify_report.json, changes no other file")
     p.add_argument("--gptq_block", type=int, default=128,
                    help="--gptq (not in the reference; every platform, -D ocp_fp8 included): round every Conv (group 1) / Gemm weight column "
                         "by column onto the platform's weight grid, pushing each column's rounding error onto the columns not yet rounded "
@@ -116,6 +122,9 @@ def check_args(args):
     if getattr(args, "mx_pack", False) and not getattr(args, "mx", None):
         raise ValueError("--mx_pack needs --mx mxfp8 or --mx mxfp4: it writes the element codes and block scales of the operands that "
                          "--mx scales, and a static grid has neither")
+    if getattr(args, "mx_verify", False) and not getattr(args, "mx_pack", False):
+        raise ValueError("--mx_verify needs --mx_pack: it reads ocp_mx_weights.bin back and multiplies those bytes on the block-scaled "
+                         "matrix instruction, and without --mx_pack there is no such file")
     if getattr(args, "mx", None) and args.deploy != "ocp_fp8":
         raise ValueError(f"--mx {args.mx} is not supported with -D {args.deploy}: block-scaled MatMul / Gemm operands sit beside static "
                          "FP8 scales on every other node.  Supported: -D ocp_fp8")
@@ -301,6 +310,10 @@ def _main(argv=None):
     if rank == 0:
         logger.info("Deploy to " + args.deploy + "...")
         to_deploy(graph_after_wt, act_clip_val, weight_clip_val, args)
+        if getattr(args, "mx_verify", False):
+            from .mx_verify import mx_verify
+            logger.info("Verifying the packed MX operands on the block-scaled matrix instruction...")
+            mx_verify(graph_after_wt, act_clip_val, weight_clip_val, args)
         logger.info("Total time cost: {} seconds.".format(int(time.time() - start)))
     dist.barrier()
     _ = tensor_range

@@ -1,0 +1,139 @@
+"""`--mx_verify` — the packed MX files checked by the hardware that reads them (not in the reference; with `--mx_pack` only).
+
+ocp_mx_weights.bin holds "the bytes a block-scaled GEMM reads"; this runs that GEMM.  After deploy has written the files, rank 0
+takes the first --calib_batch images through the fake-quantised graph and, for every MatMul / Gemm whose two operands carry MX
+nodes, multiplies the operands as BYTES on CDNA4's block-scaled matrix instruction (ops.mx_gemm):
+  the activation operand   the tensor its MX node reads (under --mx_rotate the BlockHadamard output), encoded on the device along
+                           its block axis (ops.mx_encode) — the same values the graph's MX node produces, as codes and scales;
+  the constant operand     its codes and scales READ BACK from ocp_mx_weights.bin by the offsets of ocp_mx_weights.json — the file
+                           has to be sufficient on its own; an operand that is itself an activation (Q . K^T, attention . V) is
+                           encoded on the fly;
+then alpha / beta / bias as the node defines them, in torch, and compares with the node's own output in the same forward: an fp32
+product of dequantised values.  The bound is that of ops.mx_gemm against its definition, BOUND_FACTOR[format] * Kp * 2^-23 * S
+(S = |A^| . |B^|, computed in the run from the decoded bytes), taken twice because the node's side carries an fp32 summation too —
+plus, for a Gemm with a bias, the same factor on |beta . C|.  The factor is 1 for mxfp4, where the instruction adds exact products
+(measured: no error).  For mxfp8 it is twice the worst ratio measured on random data (tests/test_mx_gemm_gpu.py test 4): the
+instruction truncates the E4M3 products of every run of 8 consecutive k to 2^-14 of the run's largest before it adds them, which
+loses up to 7 * 2^-14 * S whatever Kp is.  -> mx_verify_report.json; no other file changes.
+"""
+import json
+import os
+
+import numpy as np
+import torch
+
+from .utils import logger
+
+REPORT = "mx_verify_report.json"
+BOUND_FACTOR = {"mxfp4": 1.0, "mxfp8": 2 * 19.51}      # on Kp * 2^-23 * S; mxfp8: twice the worst measured ratio, 19.51
+
+
+def _packed_from_file(entry, blob, dev):
+    out = []
+    for part in ("codes", "scales"):
+        sec = entry[part]
+        raw = blob[sec["offset"]:sec["offset"] + sec["nbytes"]]
+        if raw.size != sec["nbytes"]:
+            raise ValueError(f"ocp_mx_weights.bin ends inside a section ({part} at {sec['offset']}, {sec['nbytes']} bytes)")
+        out.append(torch.from_numpy(np.ascontiguousarray(raw).reshape(sec["shape"])).to(dev))
+    return out
+
+
+def mx_verify(graph, act_clip_val, weight_clip_val, args):
+    """-> the report (also written to mx_verify_report.json in args.output_dir)."""
+    from . import ops
+    from .forward_net import ActivationCache
+    from .quantize import MX_BLOCK, quant_graph
+    clip = {k: [np.copy(v[0]), np.copy(v[1])] for k, v in {**act_clip_val, **weight_clip_val}.items()}
+    graph_q, _ = quant_graph(graph, clip, args)
+    with open(os.path.join(args.output_dir, "ocp_mx_weights.json")) as f:
+        meta = json.load(f)
+    blob = np.fromfile(os.path.join(args.output_dir, "ocp_mx_weights.bin"), dtype=np.uint8)
+    elem = meta["format"]
+    images = max(1, min(int(args.data_num), int(getattr(args, "calib_batch", None) or 16)))
+    cache = ActivationCache(graph_q, args, 0, images)
+    sess = cache._session()
+    dev = sess.device
+    by_out = {q.output: q for q in graph_q._qdq.values() if q.is_mx}
+    nodes, skipped = {}, {}
+
+    def activation(name):
+        return torch.cat(list(cache.chunks(name))).contiguous()
+
+    def operand(q, last_two):
+        """(codes, scales, key or None) of the operand behind MX node q, K-innermost: [*lead, rows, Kp ...]."""
+        if q.tensor_name in graph_q.initializer:
+            key = q.tensor_name + q.suffix
+            if key not in meta["tensors"]:
+                raise KeyError(f"{key} is not in ocp_mx_weights.json")
+            return (*_packed_from_file(meta["tensors"][key], blob, dev), key, int(meta["tensors"][key]["k"]))
+        x = activation(q.tensor_name)
+        axis = int(q.block_axis)
+        if x.dim() < 2 or axis % x.dim() != x.dim() + last_two:
+            raise ValueError(f"blocks along axis {axis} of a tensor of {x.dim()} dimension(s)")
+        return (*ops.mx_encode(x, last_two, elem), None, int(x.shape[last_two]))
+
+    for node in graph_q.graph.node:
+        if node.op_type not in ("MatMul", "Gemm") or len(node.input) < 2:
+            continue
+        qa, qb = by_out.get(node.input[0]), by_out.get(node.input[1])
+        if qa is None and qb is None:
+            continue
+        try:
+            if qa is None or qb is None:
+                raise ValueError("only one operand is block-scaled")
+            trans_b = 0
+            if node.op_type == "Gemm":
+                if int(node.attrs.get("transA", 0) or 0):
+                    raise ValueError("transA = 1")
+                trans_b = int(node.attrs.get("transB", 0) or 0)
+            if qa.tensor_name in graph_q.initializer:
+                raise ValueError("the first operand is a constant")
+            a_codes, a_scales, _, k = operand(qa, -1)
+            b_codes, b_scales, key, k_b = operand(qb, -1 if trans_b else -2)
+            if k_b != k:
+                raise ValueError(f"the operands reduce over {k} and {k_b} elements")
+            lead, lead_b = tuple(a_codes.shape[:-2]), tuple(b_codes.shape[:-2])
+            if lead_b not in ((), lead):
+                if int(np.prod(lead_b, dtype=np.int64)) != 1:
+                    raise ValueError(f"leading dimensions {list(lead)} and {list(lead_b)} need a broadcast")
+                b_codes, b_scales = b_codes.reshape(b_codes.shape[-2:]), b_scales.reshape(b_scales.shape[-2:])
+            got = ops.mx_gemm(a_codes, a_scales, b_codes, b_scales, elem)
+            m, n, kp = int(a_codes.shape[-2]), int(b_codes.shape[-2]), MX_BLOCK * int(a_scales.shape[-1])
+            # S from the bytes themselves: |A^| . |B^|^T in fp64
+            a_hat = ops.mx_decode(a_codes, a_scales, elem, tuple(a_scales.shape[:-1]) + (kp,), -1).double().abs()
+            b_hat = ops.mx_decode(b_codes, b_scales, elem, tuple(b_scales.shape[:-1]) + (kp,), -1).double().abs()
+            s = torch.matmul(a_hat, b_hat.transpose(-1, -2))
+            got = got.double()
+            if node.op_type == "Gemm":
+                alpha, beta = float(node.attrs.get("alpha", 1.0)), float(node.attrs.get("beta", 1.0))
+                got, s = got * alpha, s * abs(alpha)
+                if len(node.input) > 2 and node.input[2] != "":
+                    c = sess.consts[node.input[2]] if node.input[2] in sess.consts else activation(node.input[2])
+                    c = torch.as_tensor(c, device=dev).double() * beta
+                    got, s = got + c, s + c.abs()
+            want = activation(node.output[0]).double()
+            if want.numel() != got.numel():
+                raise ValueError(f"the node's output has {want.numel()} elements, the product {got.numel()}")
+            want = want.reshape(got.shape)
+            bound = 2.0 * BOUND_FACTOR[elem] * kp * 2.0 ** -23 * s + 2.0 ** -149
+            err = (got - want).abs()
+            ratio = float((err / bound).max())
+            cos = float((got * want).sum() / (got.norm() * want.norm()).clamp_min(1e-300))
+            nodes[node.name] = {"op": node.op_type, "m": m, "n": n, "k": k, "constant": key,
+                                "max_abs_err": float(err.max()), "max_err_over_bound": ratio, "cosine": cos,
+                                "within_bound": bool(ratio <= 1.0 and bool(torch.isfinite(got).all()))}
+            logger.info("--mx_verify: {} {} [{} x {} x {}]{}: max |err| {:.3e}, {:.3e} of the bound, cosine {:.9f}".format(
+                node.op_type, node.name, m, n, kp, "" if key is None else " (" + key + " from the file)", float(err.max()), ratio, cos))
+        except (ValueError, KeyError) as e:
+            skipped[node.name] = str(e)
+            logger.warning("--mx_verify: {} {} skipped: {}".format(node.op_type, node.name, e))
+    report = {"format": elem, "images": images, "nodes": nodes, "skipped": skipped}
+    with open(os.path.join(args.output_dir, REPORT), "w") as f:
+        json.dump(report, f, indent=4)
+    bad = [k for k, v in nodes.items() if not v["within_bound"]]
+    if bad:
+        logger.warning("--mx_verify: {} node(s) outside the bound: {}".format(len(bad), ", ".join(bad)))
+    else:
+        logger.info("--mx_verify: {} node(s) within the bound, {} skipped".format(len(nodes), len(skipped)))
+    return report

@@ -1185,6 +1185,59 @@ def mx_decode(codes, scales, elem, shape, axis, out=None):
     return y
 
 
+def mx_gemm(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, out=None):
+    """`--mx_verify`: the product of two packed MX operands on CDNA4's block-scaled matrix instruction (dpl_mx_gemm;
+    tests/mx_gemm_model.py is the definition).  Both operands are what mx_encode writes, K-innermost: a_codes [*batch, m, Kp or
+    Kp / 2] with a_scales [*batch, m, Kp / 32]; b_codes [*batch, n, ...] / b_scales [*batch, n, Kp / 32] with the same leading
+    dimensions, or [n, ...] / [n, Kp / 32], which every batch shares.  -> fp32 [*batch, m, n], C[.., i, j] = sum over the Kp codes
+    of a[.., i, :] * b[.., j, :] (pad codes included).  elem_b: B's element format when it is not A's.  A row that holds a 0xFF
+    scale byte or an E4M3 NaN code makes its row (column) of C NaN.  out: an optional contiguous fp32 device tensor of that shape."""
+    elem_b = elem_a if elem_b is None else elem_b
+    for e in (elem_a, elem_b):
+        if e not in MX_ELEM:
+            raise _hip.DipoorletHipError(f"mx_gemm: elem must be 'mxfp8' or 'mxfp4', got {e!r}")
+    for t, name in ((a_codes, "a_codes"), (a_scales, "a_scales"), (b_codes, "b_codes"), (b_scales, "b_scales")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == a_codes.device):
+            raise _hip.DipoorletHipError(f"mx_gemm: {name} must be a contiguous uint8 ROCm device tensor on one device; dipoorlet_amd has no CPU path")
+
+    def split(codes, scales, elem, who):
+        per = 2 if elem == "mxfp4" else 1                      # codes to a byte
+        ok = codes.dim() >= 2 and scales.dim() == codes.dim() and tuple(scales.shape[:-1]) == tuple(codes.shape[:-1]) \
+            and int(codes.shape[-1]) * per == MX_BLOCK * int(scales.shape[-1])
+        if not ok:
+            raise _hip.DipoorletHipError(f"mx_gemm: {who} must be codes [..., rows, Kp{' / 2' if per == 2 else ''}] and scales [..., rows, Kp / "
+                                         f"{MX_BLOCK}] as mx_encode writes {elem} (K-innermost), got {list(codes.shape)} and {list(scales.shape)}")
+        return tuple(int(d) for d in codes.shape[:-2]), int(codes.shape[-2]), int(scales.shape[-1])
+    lead, m, nblk = split(a_codes, a_scales, elem_a, "A")
+    lead_b, n, nblk_b = split(b_codes, b_scales, elem_b, "B")
+    if nblk_b != nblk or lead_b not in ((), lead):
+        raise _hip.DipoorletHipError(f"mx_gemm: A is {list(lead)} x [{m}, {nblk} blocks] and B {list(lead_b)} x [{n}, {nblk_b} blocks]: the two must "
+                                     "have the same number of K-blocks, and B the leading dimensions of A or none")
+    batch = 1
+    for d in lead:
+        batch *= d
+    shape = lead + (m, n)
+    if out is None:
+        c = torch.empty(shape, dtype=torch.float32, device=a_codes.device)
+    else:
+        _require_cuda(out, "out")
+        if tuple(out.shape) != shape or out.device != a_codes.device:
+            raise _hip.DipoorletHipError(f"mx_gemm: out must have shape {list(shape)} and the codes' device")
+        c = out
+    _hip.check(_hip.lib().dpl_mx_gemm(MX_ELEM[elem_a], MX_ELEM[elem_b], _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales), batch, m, n,
+                                      MX_BLOCK * nblk, int(lead_b == lead and lead != ()), _ptr(c), _stream()), "dpl_mx_gemm")
+    return c
+
+
+def mx_matmul(x, w_codes, w_scales, elem, elem_w=None):
+    """x . W on the block-scaled matrix instruction: x (fp32 [..., m, K]) is encoded along its last axis as `elem` (mx_encode), W is
+    already packed — mx_encode(w, -2, elem_w) of a [K, N] weight, i.e. [N, Kp] codes — and the two go through mx_gemm -> [..., m, N]."""
+    if not isinstance(x, torch.Tensor) or x.dim() < 2:
+        raise _hip.DipoorletHipError("mx_matmul: x must be a tensor of at least two dimensions, [..., m, K]")
+    a_codes, a_scales = mx_encode(x, -1, elem)
+    return mx_gemm(a_codes, a_scales, w_codes, w_scales, elem, elem if elem_w is None else elem_w)
+
+
 def hadamard32(x, out=None):
     """The block-Hadamard rotation of `--mx_rotate` (dpl_hadamard32; tests/mx_rotate_model.py fwht32 is the definition): every 32
     consecutive elements along the last axis are multiplied by the symmetric +-1 Sylvester matrix H32 (no normalisation: the

@@ -19,7 +19,9 @@ Per tensor:
     dipoorlet::fake_quant_mx(Tensor x, int axis, str elem) -> Tensor           the OCP Microscaling pair, 'mxfp8' / 'mxfp4', blocks of 32 along axis (ops.fake_quant_mx)
     dipoorlet::mx_encode(Tensor x, int axis, str elem) -> (Tensor, Tensor)     the same values as bytes: (element codes, E8M0 scales), uint8, K-innermost (ops.mx_encode: --mx_pack)
     dipoorlet::mx_decode(Tensor codes, Tensor scales, str elem, int[] shape, int axis) -> Tensor   those bytes back to fp32 of `shape` (ops.mx_decode)
-    dipoorlet::hadamard32(Tensor x) -> Tensor                                  x . blockdiag(H32) along the last axis, a multiple of 32 (ops.hadamard32: --mx_rotate)
+    dipoorlet::mx_gemm(Tensor a_codes, Tensor a_scales, Tensor b_codes, Tensor b_scales, str elem_a, str elem_b) -> Tensor
+                                                               two packed operands through the block-scaled matrix instruction, fp32 [*batch, m, n] (ops.mx_gemm: --mx_verify)
+    dipoorlet::hadamard32(Tensor x) -> Tensor                           x . blockdiag(H32) along the last axis, a multiple of 32 (ops.hadamard32: --mx_rotate)
     dipoorlet::gptq_block(Tensor(a!) w, int c0, int nb, Tensor u, Tensor scale, Tensor zero_point, int qlo, int qhi, str fmt) -> Tensor
                                                                one block of GPTQ's column recursion in place on w; -> Err [rows, nb] (ops.gptq_block)
 Over every tensor of a batch of images in ONE launch — what the reference's loops over `ort_outputs` stand for
@@ -351,6 +353,16 @@ def mx_decode(codes: torch.Tensor, scales: torch.Tensor, elem: str, shape: List[
 @mx_decode.register_fake
 def _(codes, scales, elem, shape, axis):
     return codes.new_empty(list(shape), dtype=torch.float32)
+
+
+@torch.library.custom_op("dipoorlet::mx_gemm", mutates_args=(), device_types="cuda")
+def mx_gemm(a_codes: torch.Tensor, a_scales: torch.Tensor, b_codes: torch.Tensor, b_scales: torch.Tensor, elem_a: str, elem_b: str) -> torch.Tensor:
+    return ops.mx_gemm(a_codes.contiguous(), a_scales.contiguous(), b_codes.contiguous(), b_scales.contiguous(), elem_a, elem_b)
+
+
+@mx_gemm.register_fake
+def _(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b):
+    return a_codes.new_empty(list(a_codes.shape[:-1]) + [b_codes.shape[-2]], dtype=torch.float32)
 
 
 @torch.library.custom_op("dipoorlet::hadamard32", mutates_args=(), device_types="cuda")

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 30 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 31 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
                               25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
@@ -33,7 +33,8 @@ extern "C" {
                               27: dpl_fake_quant_mx (the OCP Microscaling Q/DQ pair, MXFP8 / MXFP4: --mx);
                               28: dpl_gptq_block (sequential quantise-and-compensate of a block of weight columns: --gptq);
                               29: dpl_hadamard32 (32-point Hadamard rotation of every MX block of an activation: --mx_rotate);
-                              30: dpl_mx_encode / dpl_mx_decode (an MX tensor as packed element codes and E8M0 scale bytes: --mx_pack) */
+                              30: dpl_mx_encode / dpl_mx_decode (an MX tensor as packed element codes and E8M0 scale bytes: --mx_pack);
+                              31: dpl_mx_gemm (two packed MX operands through CDNA4's block-scaled matrix instruction: --mx_verify) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -449,6 +450,26 @@ int dpl_mx_encode(int32_t elem, const float* d_x, uint64_t outer, uint64_t k, ui
                   dpl_stream_t s);
 int dpl_mx_decode(int32_t elem, const uint8_t* d_codes, const uint8_t* d_scales, uint64_t outer, uint64_t k, uint64_t inner, float* d_y,
                   dpl_stream_t s);
+
+/* ---- the product of two packed MX operands on CDNA4's block-scaled matrix instruction, v_mfma_scale_f32_16x16x128_f8f6f4
+ *      (beyond the reference; --mx_verify; the definition is tests/mx_gemm_model.py).  Both operands are K-INNERMOST, exactly what
+ *      dpl_mx_encode writes — an "NT" product.  With kp = 32 * ceil(k / 32) and bits = 8 (E4M3) or 4 (E2M1) per operand:
+ *        d_a_codes  uint8 [batch, m, kp * bits / 8]        d_a_scales  uint8 [batch, m, kp / 32]
+ *        d_b_codes  uint8 [batch or 1, n, kp * bits / 8]   d_b_scales  uint8 [batch or 1, n, kp / 32]   (b_batched != 0: batch)
+ *        d_c        fp32 [batch, m, n]:  C[b, i, j] = sum over kk < kp of a[b, i, kk] * b[b or 0, j, kk]
+ *      a, b: the values dpl_mx_decode gives those bytes.  elem_a and elem_b are chosen independently (DPL_MX_E4M3 / DPL_MX_E2M1).
+ *      The codes past k of a short last block TAKE PART in the sum: the encoder writes 0 there, and non-zero pad codes are summed.
+ *      A [K, N] MatMul weight blocked along axis -2, or a Gemm weight with transB = 1 blocked along axis 1, is [N, kp] as packed.
+ *      The sum is the instruction's own (measured on the MI355X): E2M1 x E2M1 products are added exactly up to the
+ *      fp32 accumulation, |C - exact| <= kp * 2^-23 * S with S = sum |a| |b|; with an E4M3 operand the products of every run of 8
+ *      consecutive k are first truncated to 2^-14 of the run's largest one, which can lose up to 7 * 2^-14 * S.
+ *      NaN rule: C[b, i, j] is NaN if row i of A or row j of B holds a 0xFF scale byte or an E4M3 NaN code (0x7F, 0xFF) anywhere in
+ *      its kp codes — the kernel sees to it whatever the instruction does with such bytes.  An all-zero block as the encoder writes
+ *      it (scale byte 0, codes 0) contributes exactly 0 against finite data.
+ *      d_a_codes and d_b_codes must be 16-byte aligned (refused otherwise).  1 <= m, n, k < 2^31; batch * m * n * k == 0 is a no-op;
+ *      a refused call (-2) launches nothing. */
+int dpl_mx_gemm(int32_t elem_a, int32_t elem_b, const uint8_t* d_a_codes, const uint8_t* d_a_scales, const uint8_t* d_b_codes,
+                const uint8_t* d_b_scales, uint64_t batch, uint64_t m, uint64_t n, uint64_t k, int32_t b_batched, float* d_c, dpl_stream_t s);
 
 /* ---- the block-Hadamard rotation of --mx_rotate (beyond the reference): y = x . blockdiag(H32) along the contiguous last axis of
  *      the [rows, k] tensor, H32[i][j] = (-1)^popcount(i & j) (Sylvester, natural order, symmetric, H32 . H32 = 32 I; NOT
