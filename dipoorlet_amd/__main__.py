@@ -1,5 +1,5 @@
 """`python -m dipoorlet_amd -M model.onnx -I calib_dir -N 1024 -A hist -D trt` — the reference's CLI
-(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, `--mx_rotate`, a block-Hadamard rotation of those operands, `--mx_pack`, the constant ones as packed element codes and E8M0 scales, `--mx_verify`, those bytes multiplied on the block-scaled matrix instruction and compared with the fake-quantised graph, and `--gptq`, Hessian-compensated weight rounding, are this project's additions).
+(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, `--mx_rotate`, a block-Hadamard rotation of those operands, `--mx_pack`, the constant ones as packed element codes and E8M0 scales, `--mx_verify`, those bytes multiplied on the block-scaled matrix instruction and compared with the fake-quantised graph, `--mx_scale_search`, error-minimising block scales for the constant ones, and `--gptq`, Hessian-compensated weight rounding, are this project's additions).
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
@@ -69,6 +69,13 @@ def build_parser():
                         "(ops.mx_gemm) — the activation operand encoded on the device, the constant one from the file's bytes — over the "
                         "first --calib_batch images, and compare with that node's output in the fake-quantised graph: writes "
                         "mx_verify_report.json, changes no other file")
+    p.add_argument("--mx_scale_search", default=False, action="store_true",
+                   help="(not in the reference; with --mx only) give every block of every CONSTANT MatMul / Gemm operand whichever of the "
+                        "floor-rule shared exponent and the next one up gives the smaller squared Q/DQ error (the floor rule clips "
+                        "everything above 6 of 8 (mxfp4) resp. 448 of 512 (mxfp8) in the top binade; ties keep the floor).  Activations "
+                        "keep the floor rule, which a runtime can recompute.  The bytes travel explicitly: as the second input of the "
+                        "weight's MXQuantizeDequantize node in quant_model.onnx, into ocp_mx_weights.bin under --mx_pack, and through "
+                        "--mx_verify; writes mx_scale_report.json and \"weight_scales\": \"search\" in ocp_mx_blocks.json")
     p.add_argument("--gptq_block", type=int, default=128,
                    help="--gptq (not in the reference; every platform, -D ocp_fp8 included): round every Conv (group 1) / Gemm weight column "
                         "by column onto the platform's weight grid, pushing each column's rounding error onto the columns not yet rounded "
@@ -122,6 +129,9 @@ def check_args(args):
     if getattr(args, "mx_pack", False) and not getattr(args, "mx", None):
         raise ValueError("--mx_pack needs --mx mxfp8 or --mx mxfp4: it writes the element codes and block scales of the operands that "
                          "--mx scales, and a static grid has neither")
+    if getattr(args, "mx_scale_search", False) and not getattr(args, "mx", None):
+        raise ValueError("--mx_scale_search needs --mx mxfp8 or --mx mxfp4: it chooses the block scales of the constant operands that "
+                         "--mx scales, and a static grid has none")
     if getattr(args, "mx_verify", False) and not getattr(args, "mx_pack", False):
         raise ValueError("--mx_verify needs --mx_pack: it reads ocp_mx_weights.bin back and multiplies those bytes on the block-scaled "
                          "matrix instruction, and without --mx_pack there is no such file")

@@ -1,15 +1,18 @@
-// What the MX kernels share (mx_kernels.hip: the Q/DQ pair; mx_pack_kernels.hip: the element codes of --mx_pack): the loads and
+// What the MX kernels share (mx_kernels.hip: the Q/DQ pair; mx_pack_kernels.hip: the element codes of --mx_pack;
+// mx_search_kernels.hip: the scale search of --mx_scale_search, whose given-scale rule the first two read too): the loads and
 // stores of a lane's VEC values as bit patterns, a block's maximum inside its lane group, its shared exponent, one element's Q/DQ,
 // and the two decompositions of a launch into blocks — groups of lanes for contiguous blocks, slots for strided ones.
 #pragma once
 #include "common.hpp"
 #include "mx_format.hpp"
+#include "mx_search.hpp"
 
 namespace {
 
 typedef __attribute__((address_space(1))) float* gptr_f32w;
 typedef __attribute__((address_space(1))) f4* gptr_f4w;
 typedef __attribute__((address_space(1))) uint8_t* gptr_u8w;
+typedef const __attribute__((address_space(1))) uint8_t* gptr_u8;
 
 constexpr uint32_t kQuietNaN = 0x7FC00000u;
 constexpr uint32_t kInfBits = 0x7F800000u;
@@ -58,6 +61,14 @@ template <int ELEM>
 __device__ __forceinline__ int mx_block_se(uint32_t a, bool& nan) {
     nan = a >= kInfBits;
     return (nan || a == 0u) ? -127 : dpl_mx::shared_exponent<ELEM>(a);
+}
+
+// se and the NaN flag of a block under a GIVEN scale byte (--mx_scale_search: tests/mx_scale_model.py): a block that holds a NaN or
+// an infinity is a 0xFF block whatever the byte; so is one whose byte is 0xFF or names an exponent above the format's limit.
+template <int ELEM>
+__device__ __forceinline__ int mx_block_se_given(uint32_t a, uint32_t byte, bool& nan) {
+    nan = a >= kInfBits || dpl_mx::given_byte_is_nan<ELEM>(byte);
+    return nan ? -127 : (int)byte - 127;
 }
 
 // The largest |v| pattern of a block held by a group of 32 / VEC adjacent lanes, VEC values each: in every lane of the group.

@@ -15,6 +15,8 @@
 //                     The transpose is paid on the code side, 1/4 (1/8) of the bytes; with four columns to a lane a wave is a tile
 //                     of four K-blocks, so that four lanes fill one run of a column (MxPackColsAt).
 //   k_mx_decode_rows, k_mx_decode_cols  the mirrors: codes and scales in, fp32 [outer, K, inner] out, nothing written past K.
+//   GIVEN (--mx_scale_search: dpl_mx_encode_scaled; tests/mx_scale_model.py) the encode kernels read a block's byte from
+//   [outer, nblk, inner] instead of deriving it; the block maximum is still taken, for the non-finite rule (mx_block_se_given).
 #include "mx_block.hpp"
 
 namespace {
@@ -24,7 +26,6 @@ typedef __attribute__((address_space(1))) u4* gptr_u4w;
 typedef const __attribute__((address_space(1))) u4* gptr_u4;
 typedef const __attribute__((address_space(1))) uint32_t* gptr_u32;
 typedef const __attribute__((address_space(1))) uint16_t* gptr_u16;
-typedef const __attribute__((address_space(1))) uint8_t* gptr_u8;
 
 template <int ELEM>
 struct Pack {
@@ -105,13 +106,23 @@ struct MxPackColsAt {
     }
 };
 
+// The bytes a GIVEN encode kernel reads (--mx_scale_search: dpl_mx_encode_scaled), uint8 [outer, nblk, inner] — the order of
+// dpl_fake_quant_mx's scales, not the K-innermost one the kernel writes.  The derived form carries nothing.
+template <bool GIVEN>
+struct MxGivenBytes {
+    const uint8_t* p;
+};
+template <>
+struct MxGivenBytes<false> {};
+
 // ---------------------------------------------------------------------------------------------- encode, inner == 1
-template <int ELEM, int VEC>
+template <int ELEM, int VEC, bool GIVEN = false>
 __global__ __launch_bounds__(kBlock) void k_mx_encode_rows(const float* x, uint8_t* codes, uint8_t* scales, uint64_t n_groups, uint32_t K,
-                                                           uint32_t nblk) {
+                                                           uint32_t nblk, MxGivenBytes<GIVEN> given) {
     const MxRowsAt<VEC> w(nblk);
     MxVec<VEC> v[kMxRowsIter];
     bool live[kMxRowsIter];
+    uint32_t byte[kMxRowsIter];
 #pragma unroll
     for (int i = 0; i < kMxRowsIter; ++i) {
         uint64_t row;
@@ -121,12 +132,15 @@ __global__ __launch_bounds__(kBlock) void k_mx_encode_rows(const float* x, uint8
 #pragma unroll
         for (int j = 0; j < VEC; ++j) v[i].b[j] = 0u;
         if (live[i]) v[i] = mx_load<VEC>(x + row * K + col);
+        byte[i] = 0u;
+        if constexpr (GIVEN)
+            if (w.group(i) < n_groups) byte[i] = ((gptr_u8)given.p)[w.group(i)];      // (inner == 1: the two orders are one)
     }
 #pragma unroll
     for (int i = 0; i < kMxRowsIter; ++i) {
         const uint32_t a = mx_group_max<VEC>(v[i]);
         bool nan;
-        const int se = mx_block_se<ELEM>(a, nan);
+        const int se = GIVEN ? mx_block_se_given<ELEM>(a, byte[i], nan) : mx_block_se<ELEM>(a, nan);
         uint32_t pay = 0u;
 #pragma unroll
         for (int j = 0; j < VEC; ++j) pay |= mx_code<ELEM>(v[i].b[j], se, nan, live[i]) << (Pack<ELEM>::bits * j);
@@ -138,9 +152,9 @@ __global__ __launch_bounds__(kBlock) void k_mx_encode_rows(const float* x, uint8
 }
 
 // ---------------------------------------------------------------------------------------------- encode, inner > 1
-template <int ELEM, int VEC>
+template <int ELEM, int VEC, bool GIVEN = false>
 __global__ __launch_bounds__(kMxColsBlock, 2) void k_mx_encode_cols(const float* x, uint8_t* codes, uint8_t* scales, uint64_t n_slots, uint32_t K,
-                                                                 uint32_t nblk, uint32_t inner, uint32_t cs) {
+                                                                 uint32_t nblk, uint32_t inner, uint32_t cs, MxGivenBytes<GIVEN> given) {
     const MxPackColsAt<VEC> w(n_slots, nblk, cs);
     if (!w.live) return;
     const uint32_t rows = min(32u, K - w.kb * 32u);
@@ -163,7 +177,11 @@ __global__ __launch_bounds__(kMxColsBlock, 2) void k_mx_encode_cols(const float*
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
         bool nan;
-        const int se = mx_block_se<ELEM>(a[j], nan);
+        int se;
+        if constexpr (GIVEN)
+            se = mx_block_se_given<ELEM>(a[j], ((gptr_u8)given.p)[(w.o * nblk + w.kb) * inner + w.col + (uint32_t)j], nan);
+        else
+            se = mx_block_se<ELEM>(a[j], nan);
         uint32_t wd[NW];
 #pragma unroll
         for (uint32_t d = 0; d < NW; ++d) wd[d] = 0u;
@@ -288,25 +306,28 @@ inline MxPackPlan mx_pack_plan(const void* fp, uint64_t outer, uint64_t k, uint6
     return p;
 }
 
-template <int ELEM>
-int mx_encode_launch(const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, uint8_t* d_codes, uint8_t* d_scales, dpl_stream_t s) {
+template <int ELEM, bool GIVEN = false>
+int mx_encode_launch(const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, uint8_t* d_codes, uint8_t* d_scales, MxGivenBytes<GIVEN> given,
+                     dpl_stream_t s) {
     const MxPackPlan p = mx_pack_plan(d_x, outer, k, inner);
-    if (p.blocks > 0x7FFFFFFFull) return fail_msg("dpl_mx_encode: tensor too large");
+    if (p.blocks > 0x7FFFFFFFull) return fail_msg(GIVEN ? "dpl_mx_encode_scaled: tensor too large" : "dpl_mx_encode: tensor too large");
     const dim3 grid((unsigned)p.blocks);
     if (inner == 1) {
         if (p.vec)
-            hipLaunchKernelGGL((k_mx_encode_rows<ELEM, 4>), grid, dim3(kBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk);
+            hipLaunchKernelGGL((k_mx_encode_rows<ELEM, 4, GIVEN>), grid, dim3(kBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
+                               given);
         else
-            hipLaunchKernelGGL((k_mx_encode_rows<ELEM, 1>), grid, dim3(kBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk);
+            hipLaunchKernelGGL((k_mx_encode_rows<ELEM, 1, GIVEN>), grid, dim3(kBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
+                               given);
         DPL_LAUNCH_CHECK("k_mx_encode_rows");
         return 0;
     }
     if (p.vec)
-        hipLaunchKernelGGL((k_mx_encode_cols<ELEM, 4>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
-                           (uint32_t)inner, p.cs);
+        hipLaunchKernelGGL((k_mx_encode_cols<ELEM, 4, GIVEN>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
+                           (uint32_t)inner, p.cs, given);
     else
-        hipLaunchKernelGGL((k_mx_encode_cols<ELEM, 1>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
-                           (uint32_t)inner, p.cs);
+        hipLaunchKernelGGL((k_mx_encode_cols<ELEM, 1, GIVEN>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
+                           (uint32_t)inner, p.cs, given);
     DPL_LAUNCH_CHECK("k_mx_encode_cols");
     return 0;
 }
@@ -368,8 +389,18 @@ extern "C" int dpl_mx_encode(int32_t elem, const float* d_x, uint64_t outer, uin
                              dpl_stream_t s) {
     const int rc = mx_pack_check("dpl_mx_encode", elem, d_x, d_codes, d_scales, outer, k, inner);
     if (rc != 0) return rc < 0 ? rc : 0;
-    return elem == DPL_MX_E4M3 ? mx_encode_launch<DPL_MX_E4M3>(d_x, outer, k, inner, d_codes, d_scales, s)
-                               : mx_encode_launch<DPL_MX_E2M1>(d_x, outer, k, inner, d_codes, d_scales, s);
+    return elem == DPL_MX_E4M3 ? mx_encode_launch<DPL_MX_E4M3>(d_x, outer, k, inner, d_codes, d_scales, MxGivenBytes<false>{}, s)
+                               : mx_encode_launch<DPL_MX_E2M1>(d_x, outer, k, inner, d_codes, d_scales, MxGivenBytes<false>{}, s);
+}
+
+extern "C" int dpl_mx_encode_scaled(int32_t elem, const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, const uint8_t* d_scales_in,
+                                    uint8_t* d_codes, uint8_t* d_scales_out, dpl_stream_t s) {
+    const int rc = mx_pack_check("dpl_mx_encode_scaled", elem, d_x, d_codes, d_scales_out, outer, k, inner);
+    if (rc != 0) return rc < 0 ? rc : 0;
+    if (d_scales_in == nullptr) return fail_msg("dpl_mx_encode_scaled: d_scales_in must not be null");
+    const MxGivenBytes<true> given{d_scales_in};
+    return elem == DPL_MX_E4M3 ? mx_encode_launch<DPL_MX_E4M3, true>(d_x, outer, k, inner, d_codes, d_scales_out, given, s)
+                               : mx_encode_launch<DPL_MX_E2M1, true>(d_x, outer, k, inner, d_codes, d_scales_out, given, s);
 }
 
 extern "C" int dpl_mx_decode(int32_t elem, const uint8_t* d_codes, const uint8_t* d_scales, uint64_t outer, uint64_t k, uint64_t inner,

@@ -114,13 +114,21 @@ def gen_ocp_mx_blocks(graph, act_clip_val, weight_clip_val, args):
     node has no static scale to list).  A tensor's first node goes by the tensor's name, a second one along another axis by the
     name with that node's suffix (`_ax<k>`).  With --mx_rotate also "rotation": {"block_size": 32, "activations": [...], "weights":
     [...]} — the activations (keys of "tensors": the outputs of the graph's BlockHadamard nodes) in front of whose MX quantiser a
-    runtime applies H32 per block, and the weights that were folded with H32 / 32 along their block axis."""
+    runtime applies H32 per block, and the weights that were folded with H32 / 32 along their block axis.  With --mx_scale_search also
+    "weight_scales": "search" and, per constant tensor, "scales": the uint8 initializer of quant_model.onnx that holds its blocks'
+    E8M0 bytes (the second input of its MXQuantizeDequantize node) — and mx_scale_report.json (gen_mx_scale_report)."""
     from .quantize import MX_BLOCK, quant_graph
     clip = {k: [np.copy(v[0]), np.copy(v[1])] for k, v in {**act_clip_val, **weight_clip_val}.items()}
     graph_q, _ = quant_graph(graph, clip, args)
     tensors = {q.tensor_name + q.suffix: {"axis": int(q.block_axis), "constant": q.tensor_name in graph.initializer}
                for q in graph_q._qdq.values() if q.is_mx}
     res = {"format": args.mx, "block_size": MX_BLOCK, "tensors": tensors}
+    if getattr(args, "mx_scale_search", False):
+        res["weight_scales"] = "search"
+        searched = [q for q in graph_q._qdq.values() if q.is_mx and q.mx_scales is not None]
+        for q in searched:
+            tensors[q.tensor_name + q.suffix]["scales"] = q.scale_name
+        gen_mx_scale_report(graph, searched, args)
     if getattr(args, "mx_rotate", False):
         acts = [n.output[0] for n in graph.graph.node if n.op_type == "BlockHadamard"]
         weights = [r.input[1] for a in acts for r in graph.get_tensor_consumer(a) if not isinstance(r, str) and r.op_type in ("MatMul", "Gemm")]
@@ -128,6 +136,29 @@ def gen_ocp_mx_blocks(graph, act_clip_val, weight_clip_val, args):
     _dump(res, args, "ocp_mx_blocks.json")
     if getattr(args, "mx_pack", False):
         gen_ocp_mx_weights(graph, [q for q in graph_q._qdq.values() if q.is_mx and q.tensor_name in graph.initializer], args)
+
+
+def gen_mx_scale_report(graph, qnodes, args):
+    """--mx_scale_search: {"format", "tensors": {key: {"blocks", "moved_up", "err_floor", "err_chosen"}}} -> mx_scale_report.json,
+    keyed as ocp_mx_blocks.json — per constant operand its number of blocks, how many of them took se0 + 1, and the squared Q/DQ
+    error of the whole tensor under the floor rule and under the chosen bytes: the fp64 sums of ops.mx_scale_search's `err`."""
+    import torch
+
+    from . import ops
+    dev = torch.device("cuda", torch.cuda.current_device())
+    tensors = {}
+    for q in qnodes:
+        w = torch.from_numpy(np.ascontiguousarray(graph.get_initializer(q.tensor_name), dtype=np.float32)).to(dev)
+        axis = int(q.block_axis) % w.dim()
+        floor = torch.empty(q.mx_scales.shape, dtype=torch.uint8, device=dev)
+        ops.fake_quant_mx(w, axis, args.mx, scales=floor)
+        err = torch.empty(tuple(q.mx_scales.shape) + (2,), dtype=torch.float64, device=dev)
+        chosen = ops.mx_scale_search(w, axis, args.mx, err=err)
+        if not np.array_equal(chosen.cpu().numpy(), q.mx_scales):
+            raise RuntimeError(f"--mx_scale_search: the scales of {q.tensor_name} in the graph are not those of its initializer")
+        tensors[q.tensor_name + q.suffix] = {"blocks": int(chosen.numel()), "moved_up": int((chosen != floor).sum()),
+                                             "err_floor": float(err[..., 0].sum()), "err_chosen": float(err[..., 1].sum())}
+    _dump({"format": args.mx, "tensors": tensors}, args, "mx_scale_report.json")
 
 
 MX_WEIGHTS_ALIGN = 64     # every section of ocp_mx_weights.bin starts on a multiple of this, zero fill in between
@@ -141,7 +172,8 @@ def gen_ocp_mx_weights(graph, qnodes, args):
       ocp_mx_weights.json   {"format", "block_size": 32, "layout": "k_innermost", "tensors": {key: {"initializer", "shape", "axis",
                             "k", "k_padded", "codes": {"offset", "nbytes", "shape"}, "scales": {"offset", "nbytes", "shape"}}}}
     Both arrays are K-innermost: the block axis is moved to the end and padded with code 0 to k_padded = 32 * ceil(k / 32); mxfp4
-    holds two codes to a byte, the even index along k in the low nibble."""
+    holds two codes to a byte, the even index along k in the low nibble.  A tensor whose node carries searched scales
+    (--mx_scale_search) is encoded under those bytes (ops.mx_encode_scaled; tests/mx_scale_model.py)."""
     import torch
 
     from . import ops
@@ -161,7 +193,10 @@ def gen_ocp_mx_weights(graph, qnodes, args):
         for q in qnodes:
             w = np.ascontiguousarray(graph.get_initializer(q.tensor_name), dtype=np.float32)
             axis = int(q.block_axis) % w.ndim
-            codes, scales = ops.mx_encode(torch.from_numpy(w).to(dev), axis, args.mx)
+            if q.mx_scales is not None:
+                codes, scales = ops.mx_encode_scaled(torch.from_numpy(w).to(dev), axis, args.mx, torch.from_numpy(q.mx_scales).to(dev))
+            else:
+                codes, scales = ops.mx_encode(torch.from_numpy(w).to(dev), axis, args.mx)
             k = int(w.shape[axis])
             tensors[q.tensor_name + q.suffix] = {"initializer": q.tensor_name, "shape": [int(d) for d in w.shape], "axis": int(q.block_axis),
                                                  "k": k, "k_padded": MX_BLOCK * -(-k // MX_BLOCK), "codes": section(codes),

@@ -1160,6 +1160,75 @@ def mx_encode(x, axis, elem):
     return codes, scales
 
 
+def _mx_block_shape(shape, axis):
+    """`shape` with the block axis (counted from the front) replaced by its number of blocks: the shape of one byte per block."""
+    return tuple(int(d) for d in shape[:axis]) + (-(-int(shape[axis]) // MX_BLOCK),) + tuple(int(d) for d in shape[axis + 1:])
+
+
+def _mx_given_scales(who, x, axis, scales):
+    """The check of the `scales` fake_quant_mx_scaled and mx_encode_scaled read: one byte per block, in x's own order."""
+    want = _mx_block_shape(x.shape, axis)
+    if not (isinstance(scales, torch.Tensor) and scales.is_cuda and scales.device == x.device and scales.dtype == torch.uint8
+            and scales.is_contiguous() and scales.numel() == int(np.prod(want, dtype=np.int64))):
+        raise _hip.DipoorletHipError(f"{who}: scales must be a contiguous uint8 device tensor of shape {list(want)} (x's, with the block "
+                                     f"axis replaced by ceil(K / {MX_BLOCK})) on x's device")
+
+
+def mx_scale_search(x, axis, elem, err=None):
+    """`--mx_scale_search` (dpl_mx_scale_search; tests/mx_scale_model.py is the definition): per block of 32 along `axis`, whichever
+    of the floor-rule shared exponent se0 (fake_quant_mx's) and se0 + 1 gives the smaller squared Q/DQ error — se0 + 1 only where it
+    is strictly smaller, and never above 127 - emax.  -> a uint8 device tensor shaped like x with the block axis replaced by
+    ceil(K / 32): the E8M0 bytes (0xFF: the block holds a NaN or an infinity), in the order of fake_quant_mx's scales=.
+    err: an optional contiguous fp64 device tensor of that shape + (2,) that receives, per block, the error at the floor and the
+    error at the chosen byte (+inf for a 0xFF block) — fp64 sums of exact squares in a fixed order."""
+    _require_cuda(x, "x")
+    axis, outer, k, inner = _mx_split("mx_scale_search", tuple(x.shape), axis, elem)
+    shape = _mx_block_shape(x.shape, axis)
+    if err is not None:
+        if not (isinstance(err, torch.Tensor) and err.is_cuda and err.device == x.device and err.dtype == torch.float64
+                and err.is_contiguous() and err.numel() == 2 * int(np.prod(shape, dtype=np.int64))):
+            raise _hip.DipoorletHipError(f"mx_scale_search: err must be a contiguous float64 device tensor of shape {list(shape) + [2]} on x's device")
+    scales = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    _hip.check(_hip.lib().dpl_mx_scale_search(MX_ELEM[elem], _ptr(x), outer, k, inner, _ptr(scales), None if err is None else _ptr(err),
+                                              _stream()), "dpl_mx_scale_search")
+    return scales
+
+
+def fake_quant_mx_scaled(x, axis, elem, scales, out=None):
+    """fake_quant_mx under GIVEN E8M0 bytes (dpl_fake_quant_mx_scaled; tests/mx_scale_model.py is the definition): scales is what
+    mx_scale_search returns (any bytes are defined: 0xFF, a byte above 254 - emax, or a NaN or an infinity in the block make every
+    element of the block NaN).  With the bytes fake_quant_mx writes it equals fake_quant_mx bit for bit.  out: as fake_quant_mx."""
+    _require_cuda(x, "x")
+    axis, outer, k, inner = _mx_split("fake_quant_mx_scaled", tuple(x.shape), axis, elem)
+    _mx_given_scales("fake_quant_mx_scaled", x, axis, scales)
+    if out is None:
+        y = torch.empty_like(x)
+    else:
+        _require_cuda(out, "out")
+        if out.shape != x.shape or out.device != x.device:
+            raise _hip.DipoorletHipError("fake_quant_mx_scaled: out must have x's shape and device")
+        y = out
+    _hip.check(_hip.lib().dpl_fake_quant_mx_scaled(MX_ELEM[elem], _ptr(x), _ptr(y), outer, k, inner, _ptr(scales), _stream()),
+               "dpl_fake_quant_mx_scaled")
+    return y
+
+
+def mx_encode_scaled(x, axis, elem, scales):
+    """mx_encode under GIVEN E8M0 bytes (dpl_mx_encode_scaled; tests/mx_scale_model.py is the definition) -> (codes, packed scales)
+    as mx_encode returns them, K-innermost.  scales: one byte per block in x's own order, what mx_scale_search returns; the packed
+    scales are those bytes transposed, 0xFF where the block is a 0xFF block.  mx_decode of the result equals
+    fake_quant_mx_scaled(x, axis, elem, scales) bit for bit."""
+    _require_cuda(x, "x")
+    axis, outer, k, inner = _mx_split("mx_encode_scaled", tuple(x.shape), axis, elem)
+    _mx_given_scales("mx_encode_scaled", x, axis, scales)
+    cs, ss = mx_packed_shapes(x.shape, axis, elem)
+    codes = torch.empty(cs, dtype=torch.uint8, device=x.device)
+    packed = torch.empty(ss, dtype=torch.uint8, device=x.device)
+    _hip.check(_hip.lib().dpl_mx_encode_scaled(MX_ELEM[elem], _ptr(x), outer, k, inner, _ptr(scales), _ptr(codes), _ptr(packed), _stream()),
+               "dpl_mx_encode_scaled")
+    return codes, packed
+
+
 def mx_decode(codes, scales, elem, shape, axis, out=None):
     """The inverse of mx_encode (dpl_mx_decode): codes / scales as mx_packed_shapes(shape, axis, elem) lays them out -> the fp32
     tensor of `shape`; mx_decode(*mx_encode(x, axis, elem), elem, x.shape, axis) equals fake_quant_mx(x, axis, elem) bit for bit.

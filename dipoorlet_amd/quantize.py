@@ -188,7 +188,11 @@ class _FP8(NumberFormat):
 class _MX(NumberFormat):
     """OCP Microscaling (`--mx`, platform_settings.mx_setting_table): blocks of MX_BLOCK along QDQNode.block_axis share a
     power-of-two scale taken from the data — no static scale, no zero point, no initializers; the clip range is ignored.  ONNX has
-    no dynamic block-scaled Q/DQ pair to expand into: the node is saved as ONE node of this project's own domain."""
+    no dynamic block-scaled Q/DQ pair to expand into: the node is saved as ONE node of this project's own domain.
+    `--mx_scale_search`: the node of a CONSTANT operand may carry its blocks' E8M0 bytes (QDQNode.mx_scales, ops.mx_scale_search of
+    the weight as it stands) — then it rounds under those (ops.fake_quant_mx_scaled), and is saved with them as a uint8 initializer,
+    the node's optional second input (a block moved up to se0 + 1 is in general no fixed point of the floor rule, so the choice
+    cannot be folded into the weights)."""
     static = takes_pre = False
     block_scaled = True
     opset = {MX_DOMAIN: 1}
@@ -205,14 +209,23 @@ class _MX(NumberFormat):
     def apply(self, q, x, out, pre, x2):
         if pre is not None:
             raise ValueError(f"{q.q_name}: a block-scaled ({self.name}) fake-quant node takes no fused producer ({pre!r})")
+        if q.mx_scales is not None:
+            return ops.fake_quant_mx_scaled(x, q.block_axis, self.elem, q.mx_scales_on_device(x.device), out=out)
         return ops.fake_quant_mx(x, q.block_axis, self.elem, out=out)
 
     def initializers(self, q):
-        return {}
+        return {} if q.mx_scales is None else {q.scale_name: q.mx_scales}
 
     def onnx_nodes(self, q):
-        return [Node("MXQuantizeDequantize", [q.tensor_name], [q.output], name=q.q_name, domain=MX_DOMAIN,
+        inputs = [q.tensor_name] if q.mx_scales is None else [q.tensor_name, q.scale_name]      # (the second input is optional)
+        return [Node("MXQuantizeDequantize", inputs, [q.output], name=q.q_name, domain=MX_DOMAIN,
                      attrs={"axis": int(q.block_axis), "block_size": MX_BLOCK, "elem_type": self.elem_type})]
+
+    def search_scales(self, q, w):
+        """`--mx_scale_search`: give node q the error-minimising E8M0 bytes of the constant w (numpy fp32) it quantises."""
+        dev = torch.device("cuda", torch.cuda.current_device())
+        x = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(dev)
+        q.mx_scales = ops.mx_scale_search(x, int(q.block_axis), self.elem).cpu().numpy()
 
     def gptq_grid(self, q, q_min, q_max, dev):
         return None, NO_STATIC_GRID
@@ -239,6 +252,7 @@ class QDQNode:
         self.axis = (1 if need_transpose else 0) if per_channel else None  # :214, :220
         self.fmt, self.format = fmt, FORMATS[fmt]
         self.block_axis = block_axis
+        self.mx_scales = None           # (block-scaled nodes of constants, --mx_scale_search) uint8: one E8M0 byte per block
         self.suffix = suffix
         self.zp_dtype = self.format.zp_dtype[self.symmetric]
         self.q_name = tensor_name + "_QuantizeLinear" + suffix
@@ -247,7 +261,7 @@ class QDQNode:
         self.zero_point_name = tensor_name + "_zero_point" + suffix
         self.q_output = tensor_name + QTENSORSUFFIX + suffix
         self.output = tensor_name + DQTENSORSUFFIX + suffix
-        self._dev = None
+        self._dev = self._mx_dev = None
 
     @property
     def is_mx(self):
@@ -266,6 +280,12 @@ class QDQNode:
         if self._dev is None or self._dev[0].device != device:
             self._dev = (torch.from_numpy(self.scale).to(device), torch.from_numpy(self.zero_point_as_stored()).to(device))
         return self._dev
+
+    def mx_scales_on_device(self, device):
+        """mx_scales on `device`: uploaded once."""
+        if self._mx_dev is None or self._mx_dev.device != device:
+            self._mx_dev = torch.from_numpy(self.mx_scales).to(device)
+        return self._mx_dev
 
     def mixes_axis(self, k, nd):
         """Is axis k of the node's nd-axis tensor one along which elements do not go through the node each on its own with the same
@@ -375,7 +395,9 @@ def insert_fake_quant_node(graph, node, act_quantized, data_range_list, args):
     With args.mx ('mxfp8' / 'mxfp4'; -D ocp_fp8) both operands of a MatMul / Gemm — a constant one too, whatever its role — take
     the MX parameter set instead, blocked along the operand's reduction axis (mx_block_axis); a Gemm bias is left to the platform's
     rules.  `act_quantized` holds (name, axis) for such a node: a tensor wanted along two axes, or by a static consumer as well,
-    gets one node each — the first has the usual names, a later MX one the suffix `_ax<k>`, a later static one `_static`."""
+    gets one node each — the first has the usual names, a later MX one the suffix `_ax<k>`, a later static one `_static`.
+    With args.mx_scale_search the MX node of a constant operand carries error-minimising block scales (_MX.search_scales), computed
+    here from the weight as it stands in `graph`; an activation's node keeps the floor rule."""
     from .platform_settings import mx_setting_table, platform_setting_table
     plat = platform_setting_table[args.deploy]
     mx = getattr(args, "mx", None) if node.op_type in MX_NODES else None
@@ -391,6 +413,8 @@ def insert_fake_quant_node(graph, node, act_quantized, data_range_list, args):
                                                suffix="" if first in (None, key) else f"_ax{axis}")
             node.input[idx] = q_nodes.output
             if key not in act_quantized:
+                if getattr(args, "mx_scale_search", False) and name in graph.initializer:
+                    q_nodes.format.search_scales(q_nodes, graph.get_initializer(name))
                 graph.insert_qnodes_purely(q_nodes=q_nodes, node=node)
                 act_quantized.append(key)
             continue

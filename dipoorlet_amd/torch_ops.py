@@ -21,6 +21,8 @@ Per tensor:
     dipoorlet::mx_decode(Tensor codes, Tensor scales, str elem, int[] shape, int axis) -> Tensor   those bytes back to fp32 of `shape` (ops.mx_decode)
     dipoorlet::mx_gemm(Tensor a_codes, Tensor a_scales, Tensor b_codes, Tensor b_scales, str elem_a, str elem_b) -> Tensor
                                                                two packed operands through the block-scaled matrix instruction, fp32 [*batch, m, n] (ops.mx_gemm: --mx_verify)
+    dipoorlet::mx_scale_search(Tensor x, int axis, str elem) -> Tensor         uint8, one E8M0 byte per block: the floor rule's or one more, whichever errs less (ops.mx_scale_search: --mx_scale_search)
+    dipoorlet::fake_quant_mx_scaled(Tensor x, int axis, str elem, Tensor scales) -> Tensor   the MX pair under those given bytes (ops.fake_quant_mx_scaled)
     dipoorlet::hadamard32(Tensor x) -> Tensor                           x . blockdiag(H32) along the last axis, a multiple of 32 (ops.hadamard32: --mx_rotate)
     dipoorlet::gptq_block(Tensor(a!) w, int c0, int nb, Tensor u, Tensor scale, Tensor zero_point, int qlo, int qhi, str fmt) -> Tensor
                                                                one block of GPTQ's column recursion in place on w; -> Err [rows, nb] (ops.gptq_block)
@@ -363,6 +365,26 @@ def mx_gemm(a_codes: torch.Tensor, a_scales: torch.Tensor, b_codes: torch.Tensor
 @mx_gemm.register_fake
 def _(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b):
     return a_codes.new_empty(list(a_codes.shape[:-1]) + [b_codes.shape[-2]], dtype=torch.float32)
+
+
+@torch.library.custom_op("dipoorlet::mx_scale_search", mutates_args=(), device_types="cuda")
+def mx_scale_search(x: torch.Tensor, axis: int, elem: str) -> torch.Tensor:
+    return ops.mx_scale_search(x.contiguous(), axis, elem)
+
+
+@mx_scale_search.register_fake
+def _(x, axis, elem):
+    return x.new_empty(ops._mx_block_shape(x.shape, axis % x.dim()), dtype=torch.uint8)
+
+
+@torch.library.custom_op("dipoorlet::fake_quant_mx_scaled", mutates_args=(), device_types="cuda")
+def fake_quant_mx_scaled(x: torch.Tensor, axis: int, elem: str, scales: torch.Tensor) -> torch.Tensor:
+    return ops.fake_quant_mx_scaled(x.contiguous(), axis, elem, scales.contiguous())
+
+
+@fake_quant_mx_scaled.register_fake
+def _(x, axis, elem, scales):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 
 @torch.library.custom_op("dipoorlet::hadamard32", mutates_args=(), device_types="cuda")

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 31 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 32 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
                               25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
@@ -34,7 +34,9 @@ extern "C" {
                               28: dpl_gptq_block (sequential quantise-and-compensate of a block of weight columns: --gptq);
                               29: dpl_hadamard32 (32-point Hadamard rotation of every MX block of an activation: --mx_rotate);
                               30: dpl_mx_encode / dpl_mx_decode (an MX tensor as packed element codes and E8M0 scale bytes: --mx_pack);
-                              31: dpl_mx_gemm (two packed MX operands through CDNA4's block-scaled matrix instruction: --mx_verify) */
+                              31: dpl_mx_gemm (two packed MX operands through CDNA4's block-scaled matrix instruction: --mx_verify);
+                              32: dpl_mx_scale_search / dpl_fake_quant_mx_scaled / dpl_mx_encode_scaled (error-minimising E8M0 scales
+                                  for constant MX operands, and the Q/DQ and the packed bytes under given scales: --mx_scale_search) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -450,6 +452,37 @@ int dpl_mx_encode(int32_t elem, const float* d_x, uint64_t outer, uint64_t k, ui
                   dpl_stream_t s);
 int dpl_mx_decode(int32_t elem, const uint8_t* d_codes, const uint8_t* d_scales, uint64_t outer, uint64_t k, uint64_t inner, float* d_y,
                   dpl_stream_t s);
+
+/* ---- error-minimising E8M0 scales for a constant MX operand (beyond the reference; --mx_scale_search; the definition is
+ *      tests/mx_scale_model.py, nothing is held to a tolerance).  The tensor is [outer, k, inner], blocks of 32 along k as above.
+ *      dpl_mx_scale_search: per block, with a = max |v| over the elements that exist,
+ *        a NaN or inf   the byte is 0xFF, both errors are +inf
+ *        a == 0         the byte is 0 (se = -127), both errors are 0
+ *        otherwise      the candidates are se0 = max(floor(log2 a) - emax, -127), dpl_fake_quant_mx's, and se0 + 1; se0 + 1 is
+ *                       dropped when it exceeds 127 - emax (the largest element times the scale must be an fp32 value).  Under a
+ *                       candidate se: y = round_elem(v / 2^se) * 2^se, saturating; e[i] = (v[i] - y[i])^2 in fp64 (exact: the
+ *                       difference is an fp32 value, its square an fp64 one); elements past k of a short last block are +0.0;
+ *                       err = the fp64 sum of the 32 terms as a balanced tree in index order, e = e[0::2] + e[1::2] five times.
+ *                       se0 + 1 is chosen iff err_1 < err_0: ties keep the floor.
+ *        d_scales       uint8 [outer, ceil(k / 32), inner], the chosen se + 127 (the order of dpl_fake_quant_mx's d_scales_or_null)
+ *        d_err_or_null  fp64 [outer, ceil(k / 32), inner, 2]: the error at the floor, the error at the chosen byte
+ *      Exact whatever the fp32 denormal mode (every fp64 operand is built from bit patterns).  One read of d_x.
+ *      dpl_fake_quant_mx_scaled / dpl_mx_encode_scaled: dpl_fake_quant_mx / dpl_mx_encode under GIVEN bytes, d_scales resp.
+ *      d_scales_in in the [outer, ceil(k / 32), inner] order above.  A block that holds a NaN or an infinity is a 0xFF block
+ *      whatever byte was given; a given byte of 0xFF, or one above 254 - emax, makes the block a 0xFF block too; every other block
+ *      gets se = byte - 127 and the same rounding under it.  A 0xFF block has every element NaN, the packed scale byte 0xFF and the
+ *      element codes 0x7F (E4M3) or 0 (E2M1).  d_scales_out is K-innermost, [outer, inner, kp / 32], like dpl_mx_encode's d_scales:
+ *      the given bytes transposed, 0xFF where the block is a 0xFF block.
+ *      dpl_mx_decode(dpl_mx_encode_scaled(x, s)) == dpl_fake_quant_mx_scaled(x, s) bit for bit, and with the bytes
+ *      dpl_fake_quant_mx writes, dpl_fake_quant_mx_scaled(x, those) == dpl_fake_quant_mx(x).  d_y may equal d_x.
+ *      Limits, the no-op rule, the null checks and the 16-byte rule for d_codes are those of the entry points they stand beside
+ *      (d_scales, d_scales_in, d_scales_out must not be null); a refused call (-2) launches nothing. */
+int dpl_mx_scale_search(int32_t elem, const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, uint8_t* d_scales,
+                        double* d_err_or_null, dpl_stream_t s);
+int dpl_fake_quant_mx_scaled(int32_t elem, const float* d_x, float* d_y, uint64_t outer, uint64_t k, uint64_t inner,
+                             const uint8_t* d_scales, dpl_stream_t s);
+int dpl_mx_encode_scaled(int32_t elem, const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, const uint8_t* d_scales_in,
+                         uint8_t* d_codes, uint8_t* d_scales_out, dpl_stream_t s);
 
 /* ---- the product of two packed MX operands on CDNA4's block-scaled matrix instruction, v_mfma_scale_f32_16x16x128_f8f6f4
  *      (beyond the reference; --mx_verify; the definition is tests/mx_gemm_model.py).  Both operands are K-INNERMOST, exactly what
