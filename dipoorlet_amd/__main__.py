@@ -1,9 +1,9 @@
 """`python -m dipoorlet_amd -M model.onnx -I calib_dir -N 1024 -A hist -D trt` — the reference's CLI
-(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, `--mx_rotate`, a block-Hadamard rotation of those operands, `--mx_pack`, the constant ones as packed element codes and E8M0 scales, `--mx_verify`, those bytes multiplied on the block-scaled matrix instruction and compared with the fake-quantised graph, `--mx_scale_search`, error-minimising block scales for the constant ones, and `--gptq`, Hessian-compensated weight rounding, are this project's additions).
+(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, `--mx_rotate`, a block-Hadamard rotation of those operands, `--mx_pack`, the constant ones as packed element codes and E8M0 scales, `--mx_verify`, those bytes multiplied on the block-scaled matrix instruction and compared with the fake-quantised graph, `--mx_scale_search`, error-minimising block scales for the constant ones, `--gptq`, Hessian-compensated weight rounding, and `--mx_gptq`, the same on the block-scaled grids, are this project's additions).
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
-model, optional) -> weight transforms (--smooth, --mx_rotate, --bc, --we, --update_bn, --adaround, --brecq [--drop], --sparse, --gptq) -> platform deploy file.
+model, optional) -> weight transforms (--smooth, --mx_rotate, --bc, --we, --update_bn, --adaround, --brecq [--drop], --sparse, --gptq, --mx_gptq) -> platform deploy file.
 Extra flags: --calib_batch, --resident_gb, --merge {allreduce,reference}, --skip_profiling, --timing_json.
 """
 import argparse
@@ -76,6 +76,13 @@ def build_parser():
                         "keep the floor rule, which a runtime can recompute.  The bytes travel explicitly: as the second input of the "
                         "weight's MXQuantizeDequantize node in quant_model.onnx, into ocp_mx_weights.bin under --mx_pack, and through "
                         "--mx_verify; writes mx_scale_report.json and \"weight_scales\": \"search\" in ocp_mx_blocks.json")
+    p.add_argument("--mx_gptq", default=False, action="store_true",
+                   help="(not in the reference; with --mx only) GPTQ on the block-scaled grids: every Gemm and every MatMul with a constant "
+                        "2-D weight is rounded column by column with each column's error pushed onto the columns not yet rounded, a "
+                        "block's shared exponent being fixed by the floor rule when the recursion enters the block; the result is a fixed "
+                        "point of the graph's MXQuantizeDequantize node, so nothing but the weights changes.  Conv weights go through "
+                        "--gptq's path on their static E4M3 grid.  Honours --gptq_block (32, 64, 96 or 128) and --gptq_damp; writes "
+                        "gptq.onnx and gptq_report.json.  Not with --gptq or --mx_scale_search")
     p.add_argument("--gptq_block", type=int, default=128,
                    help="--gptq (not in the reference; every platform, -D ocp_fp8 included): round every Conv (group 1) / Gemm weight column "
                         "by column onto the platform's weight grid, pushing each column's rounding error onto the columns not yet rounded "
@@ -112,6 +119,9 @@ def check_args(args):
     alpha = getattr(args, "smooth_alpha", 0.5)
     if not 0.0 <= alpha <= 1.0:      # (a NaN too)
         raise ValueError(f"--smooth_alpha must lie in [0, 1], got {alpha}")
+    if getattr(args, "mx_gptq", False) and getattr(args, "gptq", False):
+        raise ValueError("--mx_gptq and --gptq cannot be combined: --mx_gptq runs --gptq's driver over the block-scaled weights and "
+                         "the static ones alike")
     if getattr(args, "gptq", False):
         for flag in ("adaround", "brecq", "sparse"):
             if getattr(args, flag, False):
@@ -121,6 +131,20 @@ def check_args(args):
                              "grids is not built)")
         if not 1 <= getattr(args, "gptq_block", 128) <= 128:
             raise ValueError(f"--gptq_block must lie in [1, 128], got {args.gptq_block}")
+        if not getattr(args, "gptq_damp", 0.01) > 0.0:      # (a NaN too)
+            raise ValueError(f"--gptq_damp must be positive, got {args.gptq_damp}")
+    if getattr(args, "mx_gptq", False):
+        if not getattr(args, "mx", None):
+            raise ValueError("--mx_gptq needs --mx mxfp8 or --mx mxfp4: it rounds the weights that --mx block-scales (--gptq serves a "
+                             "static grid)")
+        for flag in ("adaround", "brecq", "sparse"):
+            if getattr(args, flag, False):
+                raise ValueError(f"--mx_gptq and --{flag} cannot be combined: two transforms would each decide how the weights are rounded")
+        if getattr(args, "mx_scale_search", False):
+            raise ValueError("--mx_gptq and --mx_scale_search cannot be combined: the searched scale bytes are computed from the weights "
+                             "before GPTQ replaces them and are not refreshed afterwards")
+        if getattr(args, "gptq_block", 128) not in (32, 64, 96, 128):
+            raise ValueError(f"--gptq_block must be 32, 64, 96 or 128 with --mx_gptq (whole MX blocks per kernel call), got {args.gptq_block}")
         if not getattr(args, "gptq_damp", 0.01) > 0.0:      # (a NaN too)
             raise ValueError(f"--gptq_damp must be positive, got {args.gptq_damp}")
     if getattr(args, "mx_rotate", False) and not getattr(args, "mx", None):

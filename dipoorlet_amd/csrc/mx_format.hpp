@@ -78,6 +78,23 @@ DPL_MX_HD uint32_t round_bits(uint32_t b, int se) {
     return Mr ? ((uint32_t)(ex - 1) << 23) + Mr : 0u;
 }
 
+// `--mx_gptq` (tests/mx_gptq_model.py keep_top_closed is the definition): a block rounded under a shared exponent se that is
+// HIGHER than its own floor exponent stays a fixed point of the floor-rule Q/DQ only if its largest |y| is within the range of the
+// finer grid.  E2M1's largest value ends its binade, so it always is.  E4M3's binade ends with 1.875 * 2^8, which the format does
+// not have: a largest |y| of 1.875 * 2^t would be saturated to 1.75 * 2^t.  So a |y| with the significand 1.111b that would become
+// the block's largest so far (m: the largest |y| pattern given out before in the block) gives way to the nearer of its two
+// neighbours on the grid.  y = 15 u with u the value of its lowest set pattern bit; the neighbours are the patterns y - u and y + u
+// (the carry into the exponent field is the next binade's 1.0; fp32 subnormals are contiguous with the normals).
+//   b: |v| as a bit pattern; y: round_bits<ELEM>(b, se).  Returns the |y| to use.
+template <int ELEM>
+DPL_MX_HD uint32_t keep_top_closed(uint32_t b, uint32_t y, uint32_t m) {
+    if (ELEM != 0) return y;
+    const uint32_t u = y & (0u - y);
+    const uint32_t sig = (y >> 23) ? ((y & 0x7FFFFFu) | 0x800000u) : y;
+    const bool hit = y != 0u && sig == (u << 4) - u && y > m;
+    return hit ? (b > y ? y + u : y - u) : y;
+}
+
 // The element codes of `--mx_pack` (tests/mx_pack_model.py is the definition): E4M3 is the OCP FP8 E4M3FN byte S.EEEE.MMM, E2M1 the
 // four bits S.EE.M; both have the exponent bias 1 - emin and subnormals m * 2^(emin - mbits) under the exponent field 0.
 //

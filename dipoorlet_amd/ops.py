@@ -1400,6 +1400,72 @@ def gptq_quantize(w, u, grid, block=GPTQ_MAX_BLOCK):
     return wq, err
 
 
+def gptq_mx_block(w, c0, nb, u, elem, err=None, scales=None):
+    """One call of GPTQ's column recursion on an MX block-scaled grid, in place (dpl_gptq_mx_block; tests/mx_gptq_model.py
+    gptq_mx_block is the definition, matched bit for bit): gptq_block with the grid of every block of 32 columns fixed when the
+    recursion enters it — the floor rule's shared exponent of the block's CURRENT values — and its columns rounded to `elem`
+    ('mxfp8' / 'mxfp4') under it, saturating.  w: contiguous fp32 [rows, K]; whole blocks only: c0 a multiple of 32, nb (1 .. 128) one
+    too unless c0 + nb == K.  -> (err fp32 [rows, nb], scales uint8 [rows, ceil(K / 32)]: the entry bytes of the call's blocks in
+    their columns; a tensor passed as scales= keeps every other column)."""
+    _require_cuda(w, "w")
+    _require_cuda(u, "u")
+    if elem not in MX_ELEM:
+        raise _hip.DipoorletHipError(f"gptq_mx_block: elem must be 'mxfp8' or 'mxfp4', got {elem!r}")
+    if w.dim() != 2 or u.dim() != 2 or u.device != w.device:
+        raise _hip.DipoorletHipError("gptq_mx_block: w and u must be matrices on one device")
+    rows, k = int(w.shape[0]), int(w.shape[1])
+    if int(c0) < 0 or int(c0) + int(nb) > int(u.shape[0]):       # (the C ABI checks the columns of w and u; it cannot see u's rows)
+        raise _hip.DipoorletHipError(f"gptq_mx_block: rows [{c0}, {int(c0) + int(nb)}) lie outside u ({u.shape[0]} rows)")
+    nblk = -(-k // MX_BLOCK)
+    if err is None:
+        err = torch.empty((rows, max(int(nb), 0)), dtype=torch.float32, device=w.device)
+    else:
+        _require_cuda(err, "err")
+        if err.device != w.device or err.numel() != rows * int(nb):
+            raise _hip.DipoorletHipError("gptq_mx_block: err must hold [rows, nb] elements on w's device")
+    if scales is None:
+        scales = torch.zeros((rows, nblk), dtype=torch.uint8, device=w.device)
+    elif not (isinstance(scales, torch.Tensor) and scales.is_cuda and scales.device == w.device and scales.dtype == torch.uint8
+              and scales.is_contiguous() and tuple(scales.shape) == (rows, nblk)):
+        raise _hip.DipoorletHipError(f"gptq_mx_block: scales must be a contiguous uint8 device tensor of shape [{rows}, {nblk}] on w's device")
+    _hip.check(_hip.lib().dpl_gptq_mx_block(MX_ELEM[elem], _ptr(w), rows, k, k, int(c0), int(nb), _ptr(u), int(u.shape[1]), _ptr(err),
+                                            _ptr(scales), nblk, _stream()), "dpl_gptq_mx_block")
+    return err, scales
+
+
+def gptq_mx_nearest(w, elem):
+    """w (fp32 [rows, K]) rounded to nearest on the MX grid of its own blocks along K: what gptq_mx_quantize is measured against,
+    and what the graph's MX node makes of an untouched weight."""
+    return fake_quant_mx(w, 1, elem)
+
+
+def gptq_mx_quantize(w, u, elem, block=GPTQ_MAX_BLOCK):
+    """GPTQ over a whole layer on an MX grid (tests/mx_gptq_model.py gptq_mx_layer32): the calls left to right through
+    gptq_mx_block, and between them W[:, c0 + nb:] -= Err @ U[c0:c0 + nb, c0 + nb:], one fp32 GEMM of the BLAS library.  w: fp32
+    [rows, K], finite (not modified), u: fp32 [K, K]; block: columns per call, a multiple of 32 in [32, 128].  -> (the rounded
+    weight — a fixed point of fake_quant_mx(., 1, elem) —, Err [rows, K], the entry bytes uint8 [rows, ceil(K / 32)])."""
+    _require_cuda(w, "w")
+    _require_cuda(u, "u")
+    if w.dim() != 2 or tuple(u.shape) != (w.shape[1], w.shape[1]):
+        raise _hip.DipoorletHipError("gptq_mx_quantize: w must be [rows, K] and u [K, K]")
+    block = int(block)
+    if block % MX_BLOCK or not MX_BLOCK <= block <= GPTQ_MAX_BLOCK:
+        raise _hip.DipoorletHipError(f"gptq_mx_quantize: block must be a multiple of {MX_BLOCK} in [{MX_BLOCK}, {GPTQ_MAX_BLOCK}], got {block}")
+    if not bool(torch.isfinite(w).all()):
+        raise _hip.DipoorletHipError("gptq_mx_quantize: w holds a NaN or an infinity")
+    wq = w.contiguous().clone()
+    K = int(w.shape[1])
+    err = torch.empty_like(wq)
+    scales = torch.zeros((int(w.shape[0]), -(-K // MX_BLOCK)), dtype=torch.uint8, device=w.device)
+    for c0 in range(0, K, block):
+        nb = min(block, K - c0)
+        e, _ = gptq_mx_block(wq, c0, nb, u, elem, scales=scales)
+        err[:, c0:c0 + nb] = e
+        if c0 + nb < K:
+            wq[:, c0 + nb:].addmm_(e, u[c0:c0 + nb, c0 + nb:], alpha=-1.0)
+    return wq, err, scales
+
+
 class FakeQuantSet:
     """Fused QuantizeLinear -> DequantizeLinear over a WHOLE tensor set in one launch (dpl_fake_quant_items): for a caller that
     holds every tensor of a forward (the profiling flow's fp-vs-quantised comparison, quant_acti over a set) — one launch

@@ -26,6 +26,8 @@ Per tensor:
     dipoorlet::hadamard32(Tensor x) -> Tensor                           x . blockdiag(H32) along the last axis, a multiple of 32 (ops.hadamard32: --mx_rotate)
     dipoorlet::gptq_block(Tensor(a!) w, int c0, int nb, Tensor u, Tensor scale, Tensor zero_point, int qlo, int qhi, str fmt) -> Tensor
                                                                one block of GPTQ's column recursion in place on w; -> Err [rows, nb] (ops.gptq_block)
+    dipoorlet::gptq_mx_block(Tensor(a!) w, int c0, int nb, Tensor u, str elem) -> (Tensor, Tensor)
+                                                               the same on an MX block-scaled grid; -> (Err [rows, nb], E8M0 entry bytes uint8 [rows, ceil(K / 32)]) (ops.gptq_mx_block: --mx_gptq)
 Over every tensor of a batch of images in ONE launch — what the reference's loops over `ort_outputs` stand for
 (forward_net.py:220-235, 265-280, 314-340); xs[t] is tensor t of the batch, [B, ...] contiguous fp32:
     dipoorlet::minmax_batched(Tensor[] xs, Tensor(a!) mins, Tensor(b!) maxs) -> ()   running min / max per tensor, [T] fp32
@@ -407,6 +409,17 @@ def gptq_block(w: torch.Tensor, c0: int, nb: int, u: torch.Tensor, scale: torch.
 @gptq_block.register_fake
 def _(w, c0, nb, u, scale, zero_point, qlo, qhi, fmt):
     return w.new_empty((w.shape[0], nb), dtype=torch.float32)
+
+
+@torch.library.custom_op("dipoorlet::gptq_mx_block", mutates_args=("w",), device_types="cuda")
+def gptq_mx_block(w: torch.Tensor, c0: int, nb: int, u: torch.Tensor, elem: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """elem 'mxfp8' or 'mxfp4'; w, u: contiguous fp32 matrices; whole MX blocks only (ops.gptq_mx_block)."""
+    return ops.gptq_mx_block(w, c0, nb, u, elem)
+
+
+@gptq_mx_block.register_fake
+def _(w, c0, nb, u, elem):
+    return w.new_empty((w.shape[0], nb), dtype=torch.float32), w.new_empty((w.shape[0], -(-w.shape[1] // ops.MX_BLOCK)), dtype=torch.uint8)
 
 
 @torch.library.custom_op("dipoorlet::fake_quant_set", mutates_args=(), device_types="cuda")

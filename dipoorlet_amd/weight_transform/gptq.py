@@ -11,7 +11,14 @@ Conv (group 1, two spatial axes) and Gemm whose weight the graph fake-quantises:
     insert_fake_quant_node makes for that initializer: the graph's own Q/DQ node leaves the result unchanged;
   * the new weight goes into the result, the fake-quantised graph and its session before the node runs, so everything downstream is
     rounded against GPTQ's weights upstream.
-Profiling and deployment go on with the ORIGINAL ranges, as after AdaRound."""
+Profiling and deployment go on with the ORIGINAL ranges, as after AdaRound.
+
+--mx_gptq (with --mx): the same walk over a second kind of layer.  Every Gemm without transA and every MatMul whose second input is
+a constant 2-D initializer, where the graph's own node block-scales the weight (QDQNode.is_mx — asked of the node quant_graph built,
+not of the format's gptq_grid, which has no static grid to give), goes to ops.gptq_mx_quantize as [N, K] with the blocks along K
+(tests/mx_gptq_model.py is the definition): a block's shared exponent is fixed when the recursion enters it, and the finished
+weight is a fixed point of the graph's MXQuantizeDequantize node, so no scale byte has to travel.  Every Conv / Gemm whose weight
+has a static grid (the patch embedding's E4M3 scales) takes the path above.  Report entries carry "grid" then."""
 import json
 import os
 
@@ -31,6 +38,7 @@ from .walk import QuantWalk
 __all__ = ["gptq", "factor", "layer_grid"]
 
 GPTQ_NODE_TYPES = ("Conv", "Gemm")
+MX_GPTQ_NODE_TYPES = GPTQ_NODE_TYPES + ("MatMul",)     # what --mx_gptq visits
 LEFT_NODE_TYPES = ("ConvTranspose",)       # counted in the log, left as they are
 _SLAB_BYTES = 256 << 20                    # bytes of X (fp32 rows) per GEMM; unfold holds a second copy of a slab while it is reshaped
 _SLAB_ROWS = 1 << 16                       # ... and rows of X per fp32 GEMM at the most: longer sums are split and added in fp64
@@ -75,16 +83,43 @@ def _why_left(node, weight):
             return "a grouped convolution"
         if weight.ndim != 4:
             return "not a convolution over two spatial axes"
+    elif node.op_type == "MatMul":
+        if weight.ndim > 2:
+            return "a constant of rank above 2"
+        if weight.ndim < 2:
+            return "a constant of rank below 2"
     elif node.attrs.get("transA", 0):
         return "a Gemm with transA"
     return None
 
 
+def _why_left_matmul(graph, node):
+    """Why --mx_gptq leaves a MatMul whose second input is no initializer."""
+    return "a constant left operand" if node.input[0] in graph.initializer else "a MatMul with two activation operands"
+
+
+def _mx_elem(graph_q, node, ori, weight):
+    """The element format of the MX node quant_graph put on the weight of `node` (graph_q's; `ori`: the same node before) ->
+    (elem, None); (None, None) where the weight's node is a static one; (None, why) where the MX node is not one GPTQ can serve."""
+    producer = graph_q.get_tensor_producer(node.input[1])
+    q = None if isinstance(producer, str) else graph_q._qdq.get(producer.name)
+    if q is None or not q.is_mx:
+        return None, None
+    if q.mx_scales is not None:
+        return None, "its MX node carries searched scales"
+    k_axis = 1 if ori.op_type == "Gemm" and ori.attrs.get("transB", 0) else 0
+    if weight.ndim != 2 or int(q.block_axis) % 2 != k_axis:
+        return None, "its MX blocks do not run along the reduction axis"
+    return q.format.elem, None
+
+
 def input_rows(node, x, weight_shape):
     """The rows X [n, K] of the product the node computes as X @ W^T, W = weight.reshape(C_out, K): a Gemm's input, a Conv's patches
-    in (C_in, kh, kw) order."""
+    in (C_in, kh, kw) order; a MatMul's left operand [..., K] row by row."""
     if node.op_type == "Gemm":
         return x.reshape(x.shape[0], -1)
+    if node.op_type == "MatMul":
+        return x.reshape(-1, x.shape[-1])
     kernel = list(weight_shape[2:])
     strides = node.attrs.get("strides", [1, 1])
     dil = node.attrs.get("dilations", [1, 1])
@@ -96,9 +131,12 @@ def input_rows(node, x, weight_shape):
 
 
 def rows_per_image(node, x, weight_shape):
-    """Rows of input_rows() one image contributes, from the shapes alone: 1 for a Gemm, the output positions of a Conv."""
+    """Rows of input_rows() one image contributes, from the shapes alone: 1 for a Gemm, the output positions of a Conv, the product
+    of a MatMul operand's axes between the first and the last."""
     if node.op_type == "Gemm":
         return 1
+    if node.op_type == "MatMul":
+        return int(np.prod(x.shape[1:-1], dtype=np.int64))
     kernel = list(weight_shape[2:])
     strides = node.attrs.get("strides", [1, 1])
     dil = node.attrs.get("dilations", [1, 1])
@@ -146,23 +184,34 @@ def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
     block = int(getattr(args, "gptq_block", ops.GPTQ_MAX_BLOCK) or ops.GPTQ_MAX_BLOCK)
     damp0 = float(getattr(args, "gptq_damp", 0.01) or 0.01)
     ori_nodes = {n.name: n for n in graph.graph.node}
+    mx_gptq = bool(getattr(args, "mx_gptq", False))
+    flag = "--mx_gptq" if mx_gptq else "--gptq"
+    visited = (MX_GPTQ_NODE_TYPES if mx_gptq else GPTQ_NODE_TYPES) + LEFT_NODE_TYPES
     report, left = [], []
     with torch.no_grad():
         for node in graph_q.graph.node:
             ori = ori_nodes.get(node.name)
-            if ori is None or ori.op_type not in GPTQ_NODE_TYPES + LEFT_NODE_TYPES:
+            if ori is None or ori.op_type not in visited or len(ori.input) < 2:
                 qf.run(node)
                 continue
             wname = ori.input[1]
-            weight = graph_new.get_initializer(wname) if len(ori.input) > 1 and wname in graph_new.initializer else None
+            weight = graph_new.get_initializer(wname) if wname in graph_new.initializer else None
             why = ("in --skip_layers" if node.name in skip else "a ConvTranspose" if ori.op_type in LEFT_NODE_TYPES else
+                   _why_left_matmul(graph_new, ori) if ori.op_type == "MatMul" and weight is None else
                    "its weight is not a constant" if weight is None else
                    "the graph does not fake-quantise its weight" if node.input[1] == wname else _why_left(ori, weight))
-            grid = None
-            if why is None:
-                grid, why = layer_grid(graph_new, ori, walk.clip_val, args, dev)
-            rows_first = ori.op_type == "Conv" or bool(ori.attrs.get("transB", 0))
-            if why is None and grid.scale.numel() > 1 and not (rows_first and grid.scale.numel() == weight.shape[0]):
+            if why is None and mx_gptq and len(graph_new.get_tensor_consumer(wname)) > 1:
+                why = "other nodes read its weight"
+            grid = elem = None
+            if why is None and mx_gptq:
+                elem, why = _mx_elem(graph_q, node, ori, weight)
+            if why is None and elem is None:
+                if ori.op_type == "MatMul":
+                    why = NO_STATIC_GRID
+                else:
+                    grid, why = layer_grid(graph_new, ori, walk.clip_val, args, dev)
+            rows_first = ori.op_type == "Conv" or (ori.op_type == "Gemm" and bool(ori.attrs.get("transB", 0)))
+            if why is None and grid is not None and grid.scale.numel() > 1 and not (rows_first and grid.scale.numel() == weight.shape[0]):
                 why = "its per-channel scales do not run along the output channels"
             if why is not None:
                 left.append((node.name, why))
@@ -176,16 +225,19 @@ def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
                 dist.all_reduce(acc)
             H = acc[:K * K].view(K, K) / acc[K * K]
             U, damp = factor(H.cpu(), damp0)
-            w_near = ops.gptq_nearest(w2d, grid)
+            w_near = ops.gptq_nearest(w2d, grid) if elem is None else ops.gptq_mx_nearest(w2d, elem)
             entry = {"node": node.name, "rows": int(R), "cols": int(K), "damp": damp, "kept": "nearest",
                      "objective_nearest": _objective(w_near, w2d, H), "objective_gptq": None}
+            if mx_gptq:
+                entry["grid"] = grid.fmt if elem is None else elem
             if U is None:       # the only fall-back: the weight stays as it is, the graph's Q/DQ node rounds it to nearest
-                logger.warning("--gptq: the Hessian of %s could not be factorised (damping up to %g): left at round-to-nearest", node.name, damp)
+                logger.warning("%s: the Hessian of %s could not be factorised (damping up to %g): left at round-to-nearest", flag, node.name, damp)
             else:
-                wq, _ = ops.gptq_quantize(w2d, U.to(torch.float32).contiguous().to(dev), grid, block)
+                u32 = U.to(torch.float32).contiguous().to(dev)
+                wq = ops.gptq_quantize(w2d, u32, grid, block)[0] if elem is None else ops.gptq_mx_quantize(w2d, u32, elem, block)[0]
                 entry.update(objective_gptq=_objective(wq, w2d, H), kept="gptq")
                 if entry["objective_gptq"] > entry["objective_nearest"]:       # (reported, not acted on)
-                    logger.warning("--gptq: %s: the compensated rounding did not lower the objective (%g against %g)", node.name,
+                    logger.warning("%s: %s: the compensated rounding did not lower the objective (%g against %g)", flag, node.name,
                                    entry["objective_gptq"], entry["objective_nearest"])
                 w_new = wq if rows_first else wq.t().contiguous()
                 walk.set_const(wname, w_new.reshape(w_host.shape))

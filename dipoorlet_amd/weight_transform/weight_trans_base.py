@@ -87,8 +87,10 @@ def weight_calibration(onnx_graph, act_clip_val, weight_clip_val, args):
     if getattr(args, "brecq", False):      # :59-64
         args.acti_quant = bool(getattr(args, "drop", False))
         graph_after_wt = brecq(onnx_graph, graph_after_wt, act_clip_val, weight_clip_val, args)
-    if getattr(args, "gptq", False):       # (not in the reference) where AdaRound runs, instead of it; the ORIGINAL ranges stay
+    if getattr(args, "gptq", False) or getattr(args, "mx_gptq", False):
+        # (not in the reference) where AdaRound runs, instead of it; the ORIGINAL ranges stay.  --mx_gptq: the same driver over the
+        # block-scaled MatMul / Gemm weights as well
         if dist.get_rank() == 0:
-            logger.info("Weight transform: GPTQ...")
+            logger.info("Weight transform: GPTQ{}...".format(" on the MX grids" if getattr(args, "mx_gptq", False) else ""))
         graph_after_wt, _ = gptq(onnx_graph, graph_after_wt, act_clip_val, weight_clip_val, args)
     return graph_after_wt, onnx_graph, act_clip_val, weight_clip_val

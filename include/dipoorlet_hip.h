@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 32 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 33 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
                               25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
@@ -36,7 +36,8 @@ extern "C" {
                               30: dpl_mx_encode / dpl_mx_decode (an MX tensor as packed element codes and E8M0 scale bytes: --mx_pack);
                               31: dpl_mx_gemm (two packed MX operands through CDNA4's block-scaled matrix instruction: --mx_verify);
                               32: dpl_mx_scale_search / dpl_fake_quant_mx_scaled / dpl_mx_encode_scaled (error-minimising E8M0 scales
-                                  for constant MX operands, and the Q/DQ and the packed bytes under given scales: --mx_scale_search) */
+                                  for constant MX operands, and the Q/DQ and the packed bytes under given scales: --mx_scale_search);
+                              33: dpl_gptq_mx_block (dpl_gptq_block's recursion on the MX block-scaled grids: --mx_gptq) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -527,6 +528,23 @@ int dpl_hadamard32(const float* d_x, float* d_y, uint64_t rows, uint64_t k, dpl_
 #define DPL_GPTQ_MAX_BLOCK 128
 int dpl_gptq_block(float* d_w, int64_t rows, int64_t ldw, int64_t c0, int64_t nb, const float* d_u, int64_t ldu, const float* d_scale,
                    const int32_t* d_zero_point, int64_t n_channels, int32_t qlo, int32_t qhi, int32_t fmt, float* d_err, dpl_stream_t s);
+
+/* ---- the same recursion on an MX block-scaled grid (--mx_gptq; elem: DPL_MX_E4M3 / DPL_MX_E2M1): d_w is [rows, ldw] with k <= ldw
+ *      columns in use, MX blocks of 32 columns from column 0 (the last one holds the k % 32 that exist).  The grid of a block is fixed
+ *      when the recursion ENTERS it: at every column c that is a multiple of 32, per row, a = max |w[r, c .. min(c + 32, k) - 1]| over
+ *      the current values (the compensation of every earlier column included), se = the floor rule's shared exponent of
+ *      dpl_fake_quant_mx (-127 for an all-zero block), d_scales[r * ld_scales + c / 32] = se + 127, and every column of the block is
+ *      rounded as Q(v) = round_elem(v / 2^se) * 2^se, saturating at the largest element times 2^se — on bit patterns, whatever
+ *      the code object's denormal mode.  DPL_MX_E4M3 only: a rounded magnitude of 1.875 * 2^t * 2^se that exceeds every magnitude the
+ *      block has been given so far becomes the nearer of 1.75 * 2^t * 2^se (|v| not above it) and 2 * 2^t * 2^se — the format has no
+ *      1.875 * 2^8, so such a value must not end up as the largest of a block that has shrunk below its entry binade.
+ *      The rest is dpl_gptq_block's, operation for operation: bit-exact against
+ *      tests/mx_gptq_model.py gptq_mx_block, d_err and the bytes included.  The finished block is a fixed point of
+ *      dpl_fake_quant_mx.  A block whose entry maximum is a NaN or an infinity gets the byte 0xFF and NaN elements.
+ *      Whole blocks only: c0 % 32 == 0, and nb % 32 == 0 unless c0 + nb == k; 1 <= nb <= DPL_GPTQ_MAX_BLOCK; c0 + nb <= k and <= ldu;
+ *      ld_scales >= ceil(k / 32); rows below 2^31, rows <= 0 is a no-op.  A refused call (-2) launches nothing. */
+int dpl_gptq_mx_block(int32_t elem, float* d_w, int64_t rows, int64_t ldw, int64_t k, int64_t c0, int64_t nb, const float* d_u, int64_t ldu,
+                      float* d_err, uint8_t* d_scales, int64_t ld_scales, dpl_stream_t s);
 
 /* ---- cosine-similarity partial sums (utils.py:273-278): d_acc[slot*3 + {0,1,2}] += sum(a*b), sum(a*a),
  *      sum(b*b) in fp64. */
