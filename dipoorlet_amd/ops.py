@@ -1055,6 +1055,10 @@ def _fq_args(x, scale, axis, pre, x2, zero_point=None):
     if nch > 1:
         if axis is None:
             raise _hip.DipoorletHipError("per-channel fake_quant needs an axis")
+        # (a negative axis counts from the end, as ONNX QuantizeLinear's does: x.shape[axis + 1:] with axis = -1 would be x.shape[0:])
+        if not isinstance(axis, int) or not -x.dim() <= axis < x.dim():
+            raise _hip.DipoorletHipError(f"fake_quant: axis {axis!r} out of range for a tensor of {x.dim()} dimension(s)")
+        axis %= x.dim()
         if x.shape[axis] != nch:
             raise _hip.DipoorletHipError(f"axis {axis} has {x.shape[axis]} channels, scale has {nch}")
         for d in x.shape[axis + 1:]:
@@ -1062,17 +1066,29 @@ def _fq_args(x, scale, axis, pre, x2, zero_point=None):
     return code, scale, zero_point, nch, inner
 
 
+def _fq_out(who, x, out):
+    """Where the Q/DQ kernels write: a new tensor, or the caller's `out` (x itself is allowed) — which the kernel fills with
+    x.numel() fp32 values in x's order, so anything but a contiguous fp32 tensor of x's shape on x's device is refused."""
+    if out is None:
+        return torch.empty_like(x)
+    if not (isinstance(out, torch.Tensor) and out.device == x.device and out.dtype == torch.float32 and out.shape == x.shape
+            and out.is_contiguous()):
+        raise _hip.DipoorletHipError(f"{who}: out must be a contiguous float32 tensor of x's shape {list(x.shape)} on x's device")
+    return out
+
+
 def fake_quant(x, scale, zero_point, qlo, qhi, axis=None, out=None, pre=None, x2=None):
     """Fused QuantizeLinear -> DequantizeLinear (quantize.py:197-239) on the device.
 
     scale: fp32 device tensor [1] or [C]; zero_point: int32 device tensor of the same length;
-    axis: channel axis when len(scale) > 1.  y = (clamp(rint(x/scale)+zp, qlo, qhi) - zp) * scale.
+    axis: channel axis when len(scale) > 1 (negative: from the end).  y = (clamp(rint(x/scale)+zp, qlo, qhi) - zp) * scale.
+    out: where to write — a contiguous fp32 tensor of x's shape on x's device (x itself: in place); None: a new tensor.
     pre: the producer's activation applied on the way in (dpl_fake_quant_pre) — 'relu': fq(max(x, 0)); 'add_relu':
     fq(max(x + x2, 0)), x2 of x's shape (the residual Add of a bottleneck and its ReLU) — for a forward that does not expose the
     producer's output (the merge-ReLU rule, quantize.py:50-55, puts the Q/DQ pair directly behind that ReLU).
     """
     code, scale, zero_point, nch, inner = _fq_args(x, scale, axis, pre, x2, zero_point)
-    y = torch.empty_like(x) if out is None else out
+    y = _fq_out("fake_quant", x, out)
     _hip.check(_hip.lib().dpl_fake_quant_pre(code, _ptr(x), _ptr(x2) if code == 2 else None, _ptr(y), x.numel(), _ptr(scale),
                                              _ptr(zero_point), nch, inner, int(qlo), int(qhi), _stream()), "dpl_fake_quant_pre")
     return y
@@ -1083,7 +1099,7 @@ def fake_quant_fp8(x, scale, axis=None, out=None, pre=None, x2=None):
     scale)) * scale), the nearest e4m3fn value, ties to even, saturating at +-448, NaN kept (tests/fp8_model.py is the definition).
     scale: fp32 device tensor [1] or [C]; axis, out, pre, x2: as fake_quant.  No zero point, no integer bounds."""
     code, scale, _, nch, inner = _fq_args(x, scale, axis, pre, x2)
-    y = torch.empty_like(x) if out is None else out
+    y = _fq_out("fake_quant_fp8", x, out)
     _hip.check(_hip.lib().dpl_fake_quant_fp8(code, _ptr(x), _ptr(x2) if code == 2 else None, _ptr(y), x.numel(), _ptr(scale),
                                              nch, inner, _stream()), "dpl_fake_quant_fp8")
     return y
@@ -1550,6 +1566,10 @@ def channel_diff_sum(a, b, acc=None):
         inner *= int(d)
     if acc is None:
         acc = torch.zeros(n_ch, dtype=torch.float64, device=a.device)
+    # (the kernel adds C fp64 values at acc: anything smaller, of another type or strided would be written past or between)
+    elif not (isinstance(acc, torch.Tensor) and acc.device == a.device and acc.dtype == torch.float64 and acc.is_contiguous()
+              and acc.numel() == n_ch):
+        raise _hip.DipoorletHipError(f"channel_diff_sum: acc must be a contiguous fp64 tensor of {n_ch} elements on a's device")
     _hip.check(_hip.lib().dpl_channel_diff_sum(_ptr(a), _ptr(b), int(a.shape[0]), n_ch, inner, _ptr(acc), _stream()),
                "dpl_channel_diff_sum")
     return acc

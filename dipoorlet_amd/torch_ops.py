@@ -36,7 +36,8 @@ Over every tensor of a batch of images in ONE launch — what the reference's lo
     dipoorlet::octav_batched(Tensor[] xs, bool dynamic_sym) -> Tensor                 [B, T, 3] fp32 (s, min, max) per (image, tensor)
     dipoorlet::fake_quant_set(Tensor[] xs, Tensor[] scales, Tensor[] zero_points, int[] inner, int[] qlo, int[] qhi) -> Tensor[]
 
-No allocation inside except the outputs, no host synchronisation: everything a launch needs besides its inputs — the work
+No allocation inside except the outputs (hist_kl / hist_qmse: and the two workspace outputs of the C ABI, `best` and `div` / `err`,
+three allocations in all), no host synchronisation: everything a launch needs besides its inputs — the work
 decomposition of the tensor set, the pointer-table slots, accumulators, OCTAV workspace — belongs to a plan cached on
 (per-image sizes, batch, device) and is built by the FIRST call with that key; later calls only launch.  The OCTAV ops run the
 exact-tail form on the caller's stream (ops.octav_batch(inline=True)): the rare pairs that neither the walk nor the rescue finish
@@ -292,7 +293,7 @@ def fake_quant(x: torch.Tensor, scale: torch.Tensor, zero_point: torch.Tensor, a
 
 @fake_quant.register_fake
 def _(x, scale, zero_point, axis, qlo, qhi):
-    return torch.empty_like(x)
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 
 @torch.library.custom_op("dipoorlet::fake_quant_relu", mutates_args=(), device_types="cuda")
@@ -303,7 +304,7 @@ def fake_quant_relu(x: torch.Tensor, scale: torch.Tensor, zero_point: torch.Tens
 
 @fake_quant_relu.register_fake
 def _(x, scale, zero_point, axis, qlo, qhi):
-    return torch.empty_like(x)
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 
 @torch.library.custom_op("dipoorlet::fake_quant_add_relu", mutates_args=(), device_types="cuda")
@@ -315,7 +316,7 @@ def fake_quant_add_relu(x: torch.Tensor, x2: torch.Tensor, scale: torch.Tensor, 
 
 @fake_quant_add_relu.register_fake
 def _(x, x2, scale, zero_point, axis, qlo, qhi):
-    return torch.empty_like(x)
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 
 @torch.library.custom_op("dipoorlet::fake_quant_fp8", mutates_args=(), device_types="cuda")
@@ -325,7 +326,7 @@ def fake_quant_fp8(x: torch.Tensor, scale: torch.Tensor, axis: int) -> torch.Ten
 
 @fake_quant_fp8.register_fake
 def _(x, scale, axis):
-    return torch.empty_like(x)
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 
 @torch.library.custom_op("dipoorlet::fake_quant_mx", mutates_args=(), device_types="cuda")
@@ -441,4 +442,4 @@ def fake_quant_set(xs: List[torch.Tensor], scales: List[torch.Tensor], zero_poin
 
 @fake_quant_set.register_fake
 def _(xs, scales, zero_points, inner, qlo, qhi):
-    return [torch.empty_like(x) for x in xs]
+    return [torch.empty_like(x, memory_format=torch.contiguous_format) for x in xs]

@@ -383,6 +383,228 @@ def test_fake_quant_with_producer_relu_and_add_relu_vs_oracle(dev, shape, axis):
         ops.fake_quant(xt, sc_t, zp_t, qlo, qhi, axis=axis, pre="add_relu")
 
 
+# ---- the argument boundary of ops.fake_quant / fake_quant_fp8 / channel_diff_sum: negative axes, out=, acc=
+# [7, 300]: 300 channels on the last axis (inner = 1), the element path's step of 256 wraps; [2, 3, 1025]: 6150 elements, two
+# workgroup chunks of 3072, the second starting inside a row at channel 3072 % 1025; [4, 6, 3]: inner = 3; [5, 8, 7, 7]: axis -4 is
+# axis 0, inner = 392, whole vectors within a row
+NEGATIVE_AXES = [((7, 300), -1), ((2, 3, 1025), -1), ((4, 6, 3), -2), ((5, 8, 7, 7), -4)]
+
+
+def _fq_edge_inputs(shape, axis, seed):
+    """(x, x2, scale) with the values the neighbouring tests plant: exact ties of the integer grid and of E4M3 under power-of-two
+    scales ((k + 0.5) * scale; odd integers in [16, 32) * scale), +-1e6, -0.0, +-inf (x2 = 1 there: no inf - inf), sums that cancel."""
+    rng = np.random.default_rng(seed)
+    n_ch = shape[axis]
+    scale = rng.uniform(0.01, 0.1, n_ch).astype(np.float32)
+    scale[::3] = np.float32(2.0) ** rng.integers(-6, -2, scale[::3].size)
+    x = (rng.standard_normal(shape) * 4).astype(np.float32)
+    x2 = (rng.standard_normal(shape) * 4).astype(np.float32)
+    f, f2 = x.reshape(-1), x2.reshape(-1)
+    sc_full = np.broadcast_to(scale.reshape([-1 if i == axis % len(shape) else 1 for i in range(len(shape))]), shape).reshape(-1)
+    m = max(8, f.size // 8)
+    idx = rng.choice(f.size, m, replace=False)
+    f[idx[:m // 2]] = (rng.integers(0, 300, m // 2).astype(np.float32) + np.float32(0.5)) * sc_full[idx[:m // 2]]
+    f[idx[m // 2:]] = (2 * rng.integers(8, 16, m - m // 2) + 1).astype(np.float32) * sc_full[idx[m // 2:]]
+    sp = rng.choice(f.size, 40, replace=False)
+    f[sp[0:8]] = np.float32(1e6)
+    f[sp[8:16]] = np.float32(-1e6)
+    f[sp[16:24]] = np.float32(-0.0)
+    f[sp[24:28]] = np.float32(np.inf)
+    f[sp[28:32]] = np.float32(-np.inf)
+    f2[sp[24:32]] = np.float32(1.0)
+    f2[sp[32:36]] = -f[sp[32:36]]
+    f2[sp[36:40]] = np.float32(1e-9)
+    return x, x2, scale
+
+
+def _fq_pre_inputs(x, x2):
+    """What the producer's ReLU hands the pair: negative values become +0 and a -0 stays -0, as torch.relu and fq_pre have it
+    (np.maximum(-0.0, 0) may return either zero, and E4M3 keeps a zero's sign: tests/test_fp8_gpu.py)."""
+    def relu(v):
+        return np.where(v < 0, np.float32(0), v).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        return {None: x, "relu": relu(x), "add_relu": relu((x + x2).astype(np.float32))}
+
+
+def _off_by_4_bytes(t):
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    v = buf[1:].view(t.shape)
+    v.copy_(t)
+    assert t.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 4
+    return v
+
+
+def _bits_differ(got, want):
+    got, want = np.ascontiguousarray(got.cpu().numpy()), np.ascontiguousarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype == np.float32
+    return int((got.view(np.uint32) != want.view(np.uint32)).sum())
+
+
+@pytest.mark.parametrize("fmt", ["int", "e4m3"])
+@pytest.mark.parametrize("shape,axis", NEGATIVE_AXES)
+def test_fake_quant_negative_axis_vs_oracle(dev, shape, axis, fmt):
+    """A channel axis counted from the end (ONNX QuantizeLinear allows it) is the axis it names: ops.fake_quant / fake_quant_fp8
+    with axis = -k and with axis = dim - k give the same bits, the oracle's (np_oracle.fake_quant_qdq, tests/fp8_model.py) — on the
+    integer grid with non-zero zero points (uint8 and their int8 storage forms) and on E4M3, with the producer's ReLU / Add + ReLU,
+    on a 16-byte-aligned buffer and on a view 4 bytes off.  The first two shapes also through the torch ops."""
+    import dipoorlet_amd.torch_ops  # noqa: F401
+    import fp8_model
+    from dipoorlet_amd import ops
+    front = axis % len(shape)
+    x, x2, scale = _fq_edge_inputs(shape, axis, 1000 * len(shape) + shape[-1])
+    src = _fq_pre_inputs(x, x2)
+    xt, x2t, sc_t = torch.from_numpy(x).to(dev), torch.from_numpy(x2).to(dev), torch.from_numpy(scale).to(dev)
+    placed = (("aligned", xt, x2t), ("4 bytes off", _off_by_4_bytes(xt), _off_by_4_bytes(x2t)))
+    through_torch_ops = shape in ((7, 300), (2, 3, 1025))
+    rng = np.random.default_rng(7)
+    for signed in ((False, True) if fmt == "int" else (None,)):
+        if fmt == "int":
+            zp_u = np.array([3, 128, 191, 255], np.int32)[rng.integers(0, 4, scale.size)]
+            zp = np.where(zp_u > 127, zp_u - 256, zp_u).astype(np.int32) if signed else zp_u
+            zp_t = torch.from_numpy(zp).to(dev)
+            qlo, qhi = (-128, 127) if signed else (0, 255)
+            want = {pre: O.fake_quant_qdq(v, scale, zp, axis=axis, signed=signed) for pre, v in src.items()}
+            assert all(np.array_equal(w, O.fake_quant_qdq(src[pre], scale, zp, axis=front, signed=signed)) for pre, w in want.items())
+
+            def run(a, b, ax, pre):
+                return ops.fake_quant(a, sc_t, zp_t, qlo, qhi, axis=ax, pre=pre, x2=b if pre == "add_relu" else None)
+            torch_op = {None: lambda a, b, ax: torch.ops.dipoorlet.fake_quant(a, sc_t, zp_t, ax, qlo, qhi),
+                        "relu": lambda a, b, ax: torch.ops.dipoorlet.fake_quant_relu(a, sc_t, zp_t, ax, qlo, qhi),
+                        "add_relu": lambda a, b, ax: torch.ops.dipoorlet.fake_quant_add_relu(a, b, sc_t, zp_t, ax, qlo, qhi)}
+        else:
+            want = {pre: fp8_model.fake_quant_fp8(v, scale, axis=axis) for pre, v in src.items()}
+
+            def run(a, b, ax, pre):
+                return ops.fake_quant_fp8(a, sc_t, axis=ax, pre=pre, x2=b if pre == "add_relu" else None)
+            torch_op = {None: lambda a, b, ax: torch.ops.dipoorlet.fake_quant_fp8(a, sc_t, ax)}
+        for tag, a, b in placed:
+            for pre in (None, "relu", "add_relu"):
+                y_neg, y_front = run(a, b, axis, pre), run(a, b, front, pre)
+                where = (tag, pre, signed, shape, axis)
+                assert torch.equal(y_neg.view(torch.int32), y_front.view(torch.int32)), where
+                assert _bits_differ(y_neg, want[pre]) == 0, (where, _bits_differ(y_neg, want[pre]))
+                assert _bits_differ(y_front, want[pre]) == 0, (where, _bits_differ(y_front, want[pre]))
+                if through_torch_ops and pre in torch_op:
+                    for ax in (axis, front):
+                        assert _bits_differ(torch_op[pre](a, b, ax), want[pre]) == 0, (where, ax, "torch op")
+
+
+@pytest.mark.parametrize("fmt", ["int", "fp8"])
+def test_fake_quant_set_offset_member_and_wide_last_axis_channels(dev, fmt):
+    """FakeQuantSet (dpl_fake_quant_items / dpl_fake_quant_fp8_items) with one member that is a view 4 bytes off a 16-byte boundary
+    (element by element) and one per-channel member with inner = 1 and 300 channels — more than the 256 the element path advances
+    per step, 6 x 300 elements: the step wraps, rows start at every phase — beside an aligned per-channel one with whole vectors:
+    the oracle's bits, out of place and in place."""
+    import fp8_model
+    from dipoorlet_amd import ops
+    B = 2
+    shapes = [(B, 5, 7, 7), (B, 3, 300, 1), (B, 8, 4, 4)]      # member t seen as [B * shape[1], C = shape[2], inner = shape[3]]
+    rng = np.random.default_rng(77)
+    plan = ops.TensorSetPlan([int(np.prod(s[1:])) for s in shapes], B, dev)
+    xs, params, want = [], [], []
+    for t, s in enumerate(shapes):
+        view = (s[0] * s[1], s[2], s[3])
+        x, _, scale = _fq_edge_inputs(view, 1, 300 + t)
+        xt = torch.from_numpy(x).to(dev)
+        xs.append(_off_by_4_bytes(xt) if t == 0 else xt)
+        if fmt == "fp8":
+            params.append((torch.from_numpy(scale), s[3]))
+            want.append(fp8_model.fake_quant_fp8(x, scale, axis=1))
+        else:
+            signed = t == 2
+            zp_u = np.array([3, 128, 191, 255], np.int32)[rng.integers(0, 4, scale.size)]
+            zp = np.where(zp_u > 127, zp_u - 256, zp_u).astype(np.int32) if signed else zp_u
+            params.append((torch.from_numpy(scale), torch.from_numpy(zp), s[3], *((-128, 127) if signed else (0, 255))))
+            want.append(O.fake_quant_qdq(x, scale, zp, axis=1, signed=signed))
+    assert xs[0].data_ptr() % 16 == 4 and shapes[1][2] > 256 and shapes[1][3] == 1
+    fset = ops.FakeQuantSet(plan, params, fmt=fmt)
+    ys = fset(xs)
+    for t in range(len(shapes)):
+        assert _bits_differ(ys[t], want[t]) == 0, (fmt, t, "out of place", _bits_differ(ys[t], want[t]))
+    again = [_off_by_4_bytes(x.clone()) if t == 0 else x.clone() for t, x in enumerate(xs)]
+    assert fset(again, out=again) is again
+    for t in range(len(shapes)):
+        assert _bits_differ(again[t], want[t]) == 0, (fmt, t, "in place", _bits_differ(again[t], want[t]))
+
+
+GUARD_VALUE = -777.0
+
+
+def _guarded(dev, numel, dtype, device=None):
+    """A block of 3 * numel elements of GUARD_VALUE: whatever a refused target is cut from it, an unchecked launch that writes `numel`
+    elements (of this or a narrower type) from the target's first element on stays inside the block.  A host block is pinned:
+    page-locked host memory is mapped into the device's address space, so even there such a launch writes memory the test owns."""
+    if device == "cpu":
+        return torch.full((3 * numel,), GUARD_VALUE, dtype=dtype).pin_memory()
+    return torch.full((3 * numel,), GUARD_VALUE, dtype=dtype, device=dev)
+
+
+@pytest.mark.parametrize("entry", ["fake_quant", "fake_quant_fp8"])
+def test_fake_quant_refuses_an_out_it_cannot_fill_and_an_axis_out_of_range(dev, entry):
+    """out= of ops.fake_quant / fake_quant_fp8 must be a contiguous fp32 tensor of x's shape on x's device (x itself is allowed):
+    one element short, fp16, transposed or on the host it is refused with a DipoorletHipError and nothing is written — every
+    refused target is a view into a block of guard values three times the size of what the kernel writes, so that an unchecked
+    launch gives a wrong answer inside memory this test owns.  An axis of dim or -dim - 1 is refused too."""
+    from dipoorlet_amd import _hip, ops
+    rng = np.random.default_rng(3)
+    x = torch.from_numpy(rng.standard_normal((6, 8)).astype(np.float32)).to(dev)
+    n = x.numel()
+    sc1 = torch.tensor([0.05], device=dev)
+    scc = torch.from_numpy(rng.uniform(0.01, 0.1, 8).astype(np.float32)).to(dev)
+    zp1, zpc = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(8, dtype=torch.int32, device=dev)
+
+    def call(scale, zp, **kw):
+        if entry == "fake_quant":
+            return ops.fake_quant(x, scale, zp, -128, 127, **kw)
+        return ops.fake_quant_fp8(x, scale, **kw)
+    blocks = {"one element short": _guarded(dev, n, torch.float32), "fp16": _guarded(dev, 2 * n, torch.float16),
+              "transposed": _guarded(dev, n, torch.float32), "on the host": _guarded(dev, n, torch.float32, device="cpu")}
+    targets = {"one element short": blocks["one element short"][n:2 * n - 1],
+               "fp16": blocks["fp16"][2 * n:3 * n].view(6, 8),
+               "transposed": blocks["transposed"][n:2 * n].view(8, 6).t(),
+               "on the host": blocks["on the host"][n:2 * n].view(6, 8)}
+    for why, out in targets.items():
+        with pytest.raises(_hip.DipoorletHipError):
+            call(sc1, zp1, out=out)
+        torch.cuda.synchronize()
+        assert bool((blocks[why] == GUARD_VALUE).all()), (entry, why, "the refused out was written")
+    for axis in (2, -3):
+        good = _guarded(dev, n, torch.float32)
+        with pytest.raises(_hip.DipoorletHipError):
+            call(scc, zpc, axis=axis, out=good[n:2 * n].view(6, 8))
+        torch.cuda.synchronize()
+        assert bool((good == GUARD_VALUE).all()), (entry, axis)
+    # what stays allowed: a contiguous fp32 view of x's shape, and x itself
+    ok = _guarded(dev, n, torch.float32)
+    want = call(scc, zpc, axis=1).clone()
+    assert call(scc, zpc, axis=-1, out=ok[n:2 * n].view(6, 8)).data_ptr() == ok[n:].data_ptr()
+    assert torch.equal(ok[n:2 * n].view(6, 8), want) and bool((ok[:n] == GUARD_VALUE).all()) and bool((ok[2 * n:] == GUARD_VALUE).all())
+    assert call(scc, zpc, axis=1, out=x) is x and torch.equal(x, want)
+
+
+def test_channel_diff_sum_refuses_an_acc_it_cannot_fill(dev):
+    """acc= of ops.channel_diff_sum must be a contiguous fp64 tensor of C elements on a's device: the kernel adds C fp64 values at
+    it.  fp32 or C - 1 elements: refused, and the guard block the target is cut from stays as it was."""
+    from dipoorlet_amd import _hip, ops
+    rng = np.random.default_rng(4)
+    a = torch.from_numpy(rng.standard_normal((3, 6, 5)).astype(np.float32)).to(dev)
+    b = torch.zeros_like(a)
+    C_ = 6
+    blocks = {"fp32": _guarded(dev, 2 * C_, torch.float32), "C - 1 elements": _guarded(dev, C_, torch.float64)}
+    targets = {"fp32": blocks["fp32"][2 * C_:3 * C_], "C - 1 elements": blocks["C - 1 elements"][C_:2 * C_ - 1]}
+    for why, acc in targets.items():
+        with pytest.raises(_hip.DipoorletHipError):
+            ops.channel_diff_sum(a, b, acc)
+        torch.cuda.synchronize()
+        assert bool((blocks[why] == GUARD_VALUE).all()), (why, "the refused acc was written")
+    ok = _guarded(dev, C_, torch.float64)
+    acc = ok[C_:2 * C_]
+    acc.zero_()
+    assert ops.channel_diff_sum(a, b, acc) is acc
+    np.testing.assert_allclose(acc.cpu().numpy(), a.double().sum((0, 2)).cpu().numpy(), rtol=1e-12, atol=1e-12)
+    assert bool((ok[:C_] == GUARD_VALUE).all()) and bool((ok[2 * C_:] == GUARD_VALUE).all())
+
+
 def test_cos_accumulate(dev):
     from dipoorlet_amd import ops
     a = make_tensor("normal", 123457, 1)

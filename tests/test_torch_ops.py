@@ -8,10 +8,10 @@ import pytest
 import torch
 
 import dipoorlet_amd.torch_ops  # noqa: F401
+import torch_op_cases
 from oracle import np_oracle as O
 
-NAMES = ("minmax", "minmax_batched", "abs_hist_", "abs_hist_batched_", "hist_percentile", "octav", "octav_batched", "rowwise_minmax",
-         "fake_quant", "fake_quant_relu", "fake_quant_add_relu", "fake_quant_set")
+NAMES = tuple(torch_op_cases.CASES)      # all 25: tests/test_torch_ops_fake.py holds the table to the ops the library registered
 
 
 def test_registered_and_no_cpu_path():
@@ -154,7 +154,8 @@ def test_batched_ops_against_oracle():
 def test_second_call_allocates_only_outputs_and_does_not_synchronise():
     """"no hidden syncs, no allocation inside except outputs".  Every op once (plans, accumulators, OCTAV workspace
     are built), then again on NEW input tensors of the same geometry under torch.cuda.set_sync_debug_mode('error') with the
-    caching allocator's allocation count read before and after: the difference is the op's outputs, nothing else."""
+    caching allocator's allocation count read before and after: the difference is the op's outputs, nothing else — the number
+    of tensors it returns; for hist_kl / hist_qmse also the two workspace outputs of the C ABI (best; div or err): 3."""
     T = len(SET)
     _, first = _route_batch(11)
     host2, second = _route_batch(12)
@@ -178,7 +179,29 @@ def test_second_call_allocates_only_outputs_and_does_not_synchronise():
         "fake_quant_relu": (lambda xs: torch.ops.dipoorlet.fake_quant_relu(xs[0], sc, zp, 0, -128, 127), 1),
         "fake_quant_add_relu": (lambda xs: torch.ops.dipoorlet.fake_quant_add_relu(xs[0], xs[0], sc, zp, 0, -128, 127), 1),
         "fake_quant_set": (lambda xs: torch.ops.dipoorlet.fake_quant_set(xs, scales, zps, inner, qlo, qhi), T),
+        "rowwise_minmax": (lambda xs: torch.ops.dipoorlet.rowwise_minmax(xs[3]), 2),
+        "colwise_absmax": (lambda xs: torch.ops.dipoorlet.colwise_absmax(xs[3]), 1),
+        "hist_kl": (lambda xs: torch.ops.dipoorlet.hist_kl(h1, -1.0, 5.0, 128), 3),
+        "hist_qmse": (lambda xs: torch.ops.dipoorlet.hist_qmse(h1, -1.0, 5.0, "Linear", 8, 128), 3),
+        "fake_quant_fp8": (lambda xs: torch.ops.dipoorlet.fake_quant_fp8(xs[0], sc, 0), 1),
+        "fake_quant_mx": (lambda xs: torch.ops.dipoorlet.fake_quant_mx(xs[3], -1, "mxfp8"), 1),
+        "mx_encode": (lambda xs: torch.ops.dipoorlet.mx_encode(xs[3], -1, "mxfp4"), 2),
+        "mx_decode": (lambda xs: torch.ops.dipoorlet.mx_decode(*derived(xs)["packed"], "mxfp8", list(xs[3].shape), -1), 1),
+        "mx_gemm": (lambda xs: torch.ops.dipoorlet.mx_gemm(*derived(xs)["packed"], *derived(xs)["packed"], "mxfp8", "mxfp8"), 1),
+        "mx_scale_search": (lambda xs: torch.ops.dipoorlet.mx_scale_search(xs[3], -1, "mxfp8"), 1),
+        "fake_quant_mx_scaled": (lambda xs: torch.ops.dipoorlet.fake_quant_mx_scaled(xs[3], -1, "mxfp8", derived(xs)["bytes"]), 1),
+        "hadamard32": (lambda xs: torch.ops.dipoorlet.hadamard32(xs[3]), 1),
+        "gptq_block": (lambda xs: torch.ops.dipoorlet.gptq_block(derived(xs)["w"], 0, 32, u, sc, zp, -128, 127, "int"), 1),
+        "gptq_mx_block": (lambda xs: torch.ops.dipoorlet.gptq_mx_block(derived(xs)["w"], 32, 64, u, "mxfp8"), 2),
     }
+    assert sorted(calls) == sorted(NAMES)
+    # inputs that are themselves results ([B, 2048]: the uniform tensor, K = 2048), made per batch before anything is counted
+    u = torch.triu(torch.full((128, 128), 0.01, device="cuda")) + torch.eye(128, device="cuda")
+    made = {id(xs): {"packed": torch.ops.dipoorlet.mx_encode(xs[3], -1, "mxfp8"), "bytes": torch.ops.dipoorlet.mx_scale_search(xs[3], -1, "mxfp8"),
+                     "w": xs[3].clone()} for xs in (first, second, third)}
+
+    def derived(xs):
+        return made[id(xs)]
     for name, (fn, _) in calls.items():          # first calls: everything cached is built here
         fn(first)
     torch.cuda.synchronize()
