@@ -65,8 +65,8 @@ def build_parser():
                         "ocp_mx_blocks.json).  Encoded on the device from the weights as they stand after every weight transform")
     p.add_argument("--mx_verify", default=False, action="store_true",
                    help="(not in the reference; with --mx_pack only) after the deploy files are written, read ocp_mx_weights.bin back and "
-                        "run every MatMul / Gemm whose two operands are block-scaled on CDNA4's block-scaled matrix instruction "
-                        "(ops.mx_gemm) — the activation operand encoded on the device, the constant one from the file's bytes — over the "
+                        "run every MatMul / Gemm (ops.mx_gemm) and, under --mx_conv, every Conv (ops.mx_conv) whose two operands are "
+                        "block-scaled on CDNA4's block-scaled matrix instruction — the activation operand encoded on the device, the constant one from the file's bytes — over the "
                         "first --calib_batch images, and compare with that node's output in the fake-quantised graph: writes "
                         "mx_verify_report.json, changes no other file")
     p.add_argument("--mx_scale_search", default=False, action="store_true",
@@ -83,6 +83,14 @@ def build_parser():
                         "point of the graph's MXQuantizeDequantize node, so nothing but the weights changes.  Conv weights go through "
                         "--gptq's path on their static E4M3 grid.  Honours --gptq_block (32, 64, 96 or 128) and --gptq_damp; writes "
                         "gptq.onnx and gptq_report.json.  Not with --gptq or --mx_scale_search")
+    p.add_argument("--mx_conv", default=False, action="store_true",
+                   help="(not in the reference; with --mx only) block-scale both operands of every Conv over two spatial axes with group 1 "
+                        "and a constant weight too: the [N, C, H, W] activation and the [Cout, C, kh, kw] weight along axis 1, so a block "
+                        "is 32 consecutive channels at one pixel resp. at one (cout, ky, kx), a short last one holding the channels that exist.  "
+                        "Every other Conv (grouped or depthwise, 1-D or 3-D, a weight that is no constant) keeps its static E4M3 nodes and "
+                        "is logged with its reason.  --mx_scale_search, --mx_pack and --mx_verify cover these operands as they cover a "
+                        "MatMul's (--mx_verify multiplies them on the block-scaled matrix instruction: ops.mx_conv); --mx_rotate leaves "
+                        "Convs alone.  Adds \"conv\": {\"nodes\", \"left\"} to ocp_mx_blocks.json.  Not with --mx_gptq")
     p.add_argument("--gptq_block", type=int, default=128,
                    help="--gptq (not in the reference; every platform, -D ocp_fp8 included): round every Conv (group 1) / Gemm weight column "
                         "by column onto the platform's weight grid, pushing each column's rounding error onto the columns not yet rounded "
@@ -156,6 +164,13 @@ def check_args(args):
     if getattr(args, "mx_scale_search", False) and not getattr(args, "mx", None):
         raise ValueError("--mx_scale_search needs --mx mxfp8 or --mx mxfp4: it chooses the block scales of the constant operands that "
                          "--mx scales, and a static grid has none")
+    if getattr(args, "mx_conv", False):
+        if not getattr(args, "mx", None):
+            raise ValueError("--mx_conv needs --mx mxfp8 or --mx mxfp4: it block-scales the Conv operands the way --mx block-scales a "
+                             "MatMul's, and a static grid has no blocks")
+        if getattr(args, "mx_gptq", False):
+            raise ValueError("--mx_conv and --mx_gptq cannot be combined: the MX GPTQ kernel wants a weight's blocks contiguous along K of "
+                             "[N, K], and a Conv weight's channel blocks are strided there (not built)")
     if getattr(args, "mx_verify", False) and not getattr(args, "mx_pack", False):
         raise ValueError("--mx_verify needs --mx_pack: it reads ocp_mx_weights.bin back and multiplies those bytes on the block-scaled "
                          "matrix instruction, and without --mx_pack there is no such file")

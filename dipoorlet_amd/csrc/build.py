@@ -11,11 +11,12 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = [os.path.join(HERE, f) for f in ("calib_kernels.hip", "fake_quant_kernels.hip", "side_kernels.hip", "runtime_abi.hip", "octav_kernels.hip",
                                        "octav_tail_host.hip", "round_kernels.hip", "gemm_small.hip", "mx_kernels.hip", "mx_pack_kernels.hip", "gptq_kernels.hip",
-                                       "hadamard_kernels.hip", "mx_gemm_kernels.hip", "mx_search_kernels.hip")]
+                                       "hadamard_kernels.hip", "mx_gemm_kernels.hip", "mx_search_kernels.hip", "mx_conv_kernels.hip")]
 HDR = [os.path.join(HERE, "..", "..", "include", "dipoorlet_hip.h"), os.path.join(HERE, "common.hpp"),
        os.path.join(HERE, "octav_common.hpp"), os.path.join(HERE, "octav_wave.hpp"), os.path.join(HERE, "octav_tail.hpp"),
        os.path.join(HERE, "octav_rescue.hpp"), os.path.join(HERE, "mx_format.hpp"), os.path.join(HERE, "mx_block.hpp"), os.path.join(HERE, "mx_search.hpp"),
-       os.path.join(HERE, "host_plan.hpp"), os.path.join(HERE, "host_error.hpp"), os.path.join(HERE, "octav_geometry.hpp"), os.path.join(HERE, "fq_elem.hpp")]
+       os.path.join(HERE, "host_plan.hpp"), os.path.join(HERE, "host_error.hpp"), os.path.join(HERE, "octav_geometry.hpp"), os.path.join(HERE, "fq_elem.hpp"),
+       os.path.join(HERE, "mx_mfma.hpp")]
 OUT = os.path.join(HERE, "libdipoorlet_hip.so")
 
 

@@ -20,71 +20,9 @@
 // The NaN rule is the kernel's own, whatever the instruction does with such bytes: a lane notes a 0xFF scale byte or an E4M3 NaN
 // code (0x7F, 0xFF) in what it loads, the four lanes of a row combine their notes after the K loop, and every C of that row of A
 // (column of C for B) is stored as NaN.  No atomics, 64-bit indices.
-#include "common.hpp"
+#include "mx_mfma.hpp"      // the fragment of an operand tile: GemmFrag, gemm_load
 
 namespace {
-
-using i8v = __attribute__((ext_vector_type(8))) int;
-using u4g = __attribute__((ext_vector_type(4))) uint32_t;
-typedef const __attribute__((address_space(1))) u4g* gptr_u4g;
-typedef const __attribute__((address_space(1))) uint8_t* gptr_u8g;
-typedef __attribute__((address_space(1))) float* gptr_f32g;
-
-constexpr uint32_t kMxGemmTile = 64;      // rows and columns of C per workgroup
-
-template <int ELEM>
-struct GemmOperand {
-    static constexpr uint32_t block_bytes = ELEM == DPL_MX_E4M3 ? 32u : 16u;      // of one K-block's codes in the file
-    static constexpr int fmt = ELEM == DPL_MX_E4M3 ? 0 : 4;                        // the instruction's format code (cbsz / blgp)
-};
-
-// Does a dword hold an E4M3 NaN byte (0x7F or 0xFF)?  (t's bytes are at most 0x7F: adding 1 carries into bit 7 only from 0x7F.)
-__device__ __forceinline__ uint32_t e4m3_nan_in(uint32_t w) {
-    return (((w & 0x7F7F7F7Fu) + 0x01010101u) & 0x80808080u);
-}
-
-// One lane's fragment of one operand tile.
-struct GemmFrag {
-    i8v v;
-    int scale;
-};
-
-// row: the operand's row this lane reads (already offset by the batch), live: it exists; kb0: the first K-block of the 128-wide
-// step; q = lane >> 4.  By the map above: the scale byte of block kb0 + q; E2M1 — the 16 bytes of that block; E4M3 — half q & 1
-// of block kb0 + (q >> 1) into the low four dwords and the same half of block kb0 + 2 + (q >> 1) into the high four.  A block past
-// Kp / 32 leaves zeros (scale byte 127).
-template <int ELEM>
-__device__ __forceinline__ GemmFrag gemm_load(const uint8_t* codes, const uint8_t* scales, uint64_t row, uint32_t nblk, uint32_t kb0, uint32_t q,
-                                              bool live, uint32_t& bad) {
-    GemmFrag f;
-    f.v = i8v{0, 0, 0, 0, 0, 0, 0, 0};
-    f.scale = 127;
-    const uint64_t blk0 = row * nblk;
-    if constexpr (ELEM == DPL_MX_E4M3) {
-        const uint32_t b_lo = kb0 + (q >> 1), b_hi = b_lo + 2u, half = (q & 1u) * 16u;
-        if (live && b_lo < nblk) {
-            const u4g lo = *(gptr_u4g)(codes + (blk0 + b_lo) * GemmOperand<ELEM>::block_bytes + half);
-            f.v[0] = (int)lo.x, f.v[1] = (int)lo.y, f.v[2] = (int)lo.z, f.v[3] = (int)lo.w;
-            bad |= e4m3_nan_in(lo.x) | e4m3_nan_in(lo.y) | e4m3_nan_in(lo.z) | e4m3_nan_in(lo.w);
-        }
-        if (live && b_hi < nblk) {
-            const u4g hi = *(gptr_u4g)(codes + (blk0 + b_hi) * GemmOperand<ELEM>::block_bytes + half);
-            f.v[4] = (int)hi.x, f.v[5] = (int)hi.y, f.v[6] = (int)hi.z, f.v[7] = (int)hi.w;
-            bad |= e4m3_nan_in(hi.x) | e4m3_nan_in(hi.y) | e4m3_nan_in(hi.z) | e4m3_nan_in(hi.w);
-        }
-    } else {
-        if (live && kb0 + q < nblk) {
-            const u4g lo = *(gptr_u4g)(codes + (blk0 + kb0 + q) * GemmOperand<ELEM>::block_bytes);
-            f.v[0] = (int)lo.x, f.v[1] = (int)lo.y, f.v[2] = (int)lo.z, f.v[3] = (int)lo.w;
-        }
-    }
-    if (live && kb0 + q < nblk) {
-        const uint32_t sc = ((gptr_u8g)scales)[blk0 + kb0 + q];
-        bad |= sc == 0xFFu ? 1u : 0u;
-        f.scale = (int)sc;
-    }
-    return f;
-}
 
 template <int EA, int EB>
 __global__ __launch_bounds__(kBlock) void k_mx_gemm(const uint8_t* a_codes, const uint8_t* a_scales, const uint8_t* b_codes, const uint8_t* b_scales,

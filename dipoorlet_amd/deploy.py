@@ -116,7 +116,9 @@ def gen_ocp_mx_blocks(graph, act_clip_val, weight_clip_val, args):
     [...]} — the activations (keys of "tensors": the outputs of the graph's BlockHadamard nodes) in front of whose MX quantiser a
     runtime applies H32 per block, and the weights that were folded with H32 / 32 along their block axis.  With --mx_scale_search also
     "weight_scales": "search" and, per constant tensor, "scales": the uint8 initializer of quant_model.onnx that holds its blocks'
-    E8M0 bytes (the second input of its MXQuantizeDequantize node) — and mx_scale_report.json (gen_mx_scale_report)."""
+    E8M0 bytes (the second input of its MXQuantizeDequantize node) — and mx_scale_report.json (gen_mx_scale_report).  With --mx_conv
+    also "conv": {"nodes": [...], "left": {node name: reason}} — the Convs whose two operands are block-scaled along axis 1, and those
+    that keep their static nodes, each logged here once with its reason."""
     from .quantize import MX_BLOCK, quant_graph
     clip = {k: [np.copy(v[0]), np.copy(v[1])] for k, v in {**act_clip_val, **weight_clip_val}.items()}
     graph_q, _ = quant_graph(graph, clip, args)
@@ -133,6 +135,12 @@ def gen_ocp_mx_blocks(graph, act_clip_val, weight_clip_val, args):
         acts = [n.output[0] for n in graph.graph.node if n.op_type == "BlockHadamard"]
         weights = [r.input[1] for a in acts for r in graph.get_tensor_consumer(a) if not isinstance(r, str) and r.op_type in ("MatMul", "Gemm")]
         res["rotation"] = {"block_size": MX_BLOCK, "activations": acts, "weights": weights}
+    if getattr(args, "mx_conv", False):
+        from .quantize import mx_conv_nodes
+        taken, left = mx_conv_nodes(graph, args)
+        res["conv"] = {"nodes": taken, "left": left}
+        for name, why in left.items():
+            logger.info("--mx_conv: Conv {} keeps its static nodes: {}".format(name, why))
     _dump(res, args, "ocp_mx_blocks.json")
     if getattr(args, "mx_pack", False):
         gen_ocp_mx_weights(graph, [q for q in graph_q._qdq.values() if q.is_mx and q.tensor_name in graph.initializer], args)

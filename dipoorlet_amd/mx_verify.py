@@ -15,6 +15,11 @@ plus, for a Gemm with a bias, the same factor on |beta . C|.  The factor is 1 fo
 (measured: no error).  For mxfp8 it is twice the worst ratio measured on random data (tests/test_mx_gemm_gpu.py test 4): the
 instruction truncates the E4M3 products of every run of 8 consecutive k to 2^-14 of the run's largest before it adds them, which
 loses up to 7 * 2^-14 * S whatever Kp is.  -> mx_verify_report.json; no other file changes.
+
+`--mx_conv`: a Conv whose two inputs are MX outputs goes through ops.mx_conv the same way — the activation encoded along axis 1 on
+the device (NHWC codes), the weight's [cout, kh, kw, Cp ...] sections of ocp_mx_weights.bin as they stand, the explicit pads from
+executor.conv_padding, the bias added in torch — and is compared with the node's output permuted to NHWC under the same bound with
+Kp = kh * kw * 32 * ceil(C / 32); S = |A^| * |B^| in fp64 as unfold + matmul of the decoded bytes.
 """
 import json
 import os
@@ -73,8 +78,58 @@ def mx_verify(graph, act_clip_val, weight_clip_val, args):
             raise ValueError(f"blocks along axis {axis} of a tensor of {x.dim()} dimension(s)")
         return (*ops.mx_encode(x, last_two, elem), None, int(x.shape[last_two]))
 
+    def conv(node, qa, qb):
+        """A Conv (`--mx_conv`) whose two inputs are MX outputs, blocked along axis 1 -> its report entry."""
+        from .executor import conv_padding
+        if qa.tensor_name in graph_q.initializer or qb.tensor_name not in graph_q.initializer:
+            raise ValueError("not an activation convolved with a constant weight")
+        if int(node.attrs.get("group", 1) or 1) != 1:
+            raise ValueError("a grouped convolution")
+        x = activation(qa.tensor_name)
+        if x.dim() != 4 or int(qa.block_axis) % 4 != 1 or int(qb.block_axis) % 4 != 1:
+            raise ValueError(f"blocks along axes {int(qa.block_axis)} and {int(qb.block_axis)} of a {x.dim()}-D convolution's operands")
+        a_codes, a_scales = ops.mx_encode(x, 1, elem)                                        # [n, h, w, Cp ...]: NHWC
+        b_codes, b_scales, key, c_b = operand(qb, None)                                      # [cout, kh, kw, Cp ...] as the file holds it
+        n, c, h, w = (int(d) for d in x.shape)
+        if b_codes.dim() != 4 or c_b != c:
+            raise ValueError(f"the weight's packed codes are {list(b_codes.shape)} over {c_b} channels, the input has {c}")
+        cout, kh, kw = (int(d) for d in b_codes.shape[:3])
+        strides = tuple(int(v) for v in node.attrs.get("strides", [1, 1]))
+        dil = tuple(int(v) for v in node.attrs.get("dilations", [1, 1]))
+        _, fpad = conv_padding(node, x, (kh, kw), strides, dil)                              # F.pad's order: left, right, top, bottom
+        want = activation(node.output[0]).double()
+        if want.dim() != 4 or int(want.shape[0]) != n or int(want.shape[1]) != cout:
+            raise ValueError(f"the node's output is {list(want.shape)}")
+        oh, ow = int(want.shape[2]), int(want.shape[3])
+        got = ops.mx_conv(a_codes, a_scales, b_codes, b_scales, elem, strides=strides, pads=(int(fpad[2]), int(fpad[0])), dilations=dil,
+                          out_hw=(oh, ow)).double()
+        cb = int(a_scales.shape[-1])
+        kp = kh * kw * MX_BLOCK * cb
+        # S from the bytes themselves: |A^| * |B^| in fp64 — the patches of |A^| (unfold) times |B^| as a matrix
+        a_hat = ops.mx_decode(a_codes, a_scales, elem, (n, MX_BLOCK * cb, h, w), 1).double().abs()
+        b_hat = ops.mx_decode(b_codes, b_scales, elem, (cout, MX_BLOCK * cb, kh, kw), 1).double().abs()
+        cols = torch.nn.functional.unfold(torch.nn.functional.pad(a_hat, [int(v) for v in fpad]), (kh, kw), dilation=dil, stride=strides)
+        if int(cols.shape[-1]) != oh * ow:
+            raise ValueError(f"{int(cols.shape[-1])} patches for an output of {oh} x {ow}")
+        s = torch.matmul(b_hat.reshape(cout, -1), cols).reshape(n, cout, oh, ow).permute(0, 2, 3, 1)
+        if len(node.input) > 2 and node.input[2] != "":
+            bias = sess.consts[node.input[2]] if node.input[2] in sess.consts else activation(node.input[2])
+            bias = torch.as_tensor(bias, device=dev).double().reshape(-1)
+            got, s = got + bias, s + bias.abs()
+        want = want.permute(0, 2, 3, 1)
+        bound = 2.0 * BOUND_FACTOR[elem] * kp * 2.0 ** -23 * s + 2.0 ** -149
+        err = (got - want).abs()
+        ratio = float((err / bound).max())
+        cos = float((got * want).sum() / (got.norm() * want.norm()).clamp_min(1e-300))
+        logger.info("--mx_verify: Conv {} [{} x {} x {} x {}] * [{} x {} x {}] ({} from the file): max |err| {:.3e}, {:.3e} of the bound, cosine "
+                    "{:.9f}".format(node.name, n, c, h, w, cout, kh, kw, key, float(err.max()), ratio, cos))
+        return {"op": "Conv", "n": n, "c": c, "h": h, "w": w, "cout": cout, "kernel": [kh, kw], "strides": list(strides),
+                "pads": [int(fpad[2]), int(fpad[0]), int(fpad[3]), int(fpad[1])], "dilations": list(dil), "k": kh * kw * c, "constant": key,
+                "max_abs_err": float(err.max()), "max_err_over_bound": ratio, "cosine": cos,
+                "within_bound": bool(ratio <= 1.0 and bool(torch.isfinite(got).all()))}
+
     for node in graph_q.graph.node:
-        if node.op_type not in ("MatMul", "Gemm") or len(node.input) < 2:
+        if node.op_type not in ("MatMul", "Gemm", "Conv") or len(node.input) < 2:
             continue
         qa, qb = by_out.get(node.input[0]), by_out.get(node.input[1])
         if qa is None and qb is None:
@@ -82,6 +137,9 @@ def mx_verify(graph, act_clip_val, weight_clip_val, args):
         try:
             if qa is None or qb is None:
                 raise ValueError("only one operand is block-scaled")
+            if node.op_type == "Conv":
+                nodes[node.name] = conv(node, qa, qb)
+                continue
             trans_b = 0
             if node.op_type == "Gemm":
                 if int(node.attrs.get("transA", 0) or 0):

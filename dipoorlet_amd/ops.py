@@ -1314,6 +1314,56 @@ def mx_gemm(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, out=None)
     return c
 
 
+def mx_conv(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, *, strides, pads, dilations, out_hw, out=None):
+    """`--mx_conv`: a convolution (group 1) of two packed MX operands on the block-scaled matrix instruction, as an implicit GEMM
+    (dpl_mx_conv; tests/mx_conv_model.py is the definition).  Both operands are what mx_encode writes along axis 1: a_codes [n, h, w,
+    Cp or Cp / 2] with a_scales [n, h, w, Cp / 32] of an [n, c, h, w] activation, b_codes [cout, kh, kw, ...] / b_scales [cout, kh, kw,
+    Cp / 32] of a [cout, c, kh, kw] weight.  strides (sh, sw), pads (top, left), dilations (dh, dw), out_hw (oh, ow): the caller's —
+    nothing is derived here; a tap outside the image contributes nothing.  -> fp32 [n, oh, ow, cout] (NHWC).  elem_b: B's element
+    format when it is not A's.  An output is NaN if a block inside one of its in-image taps, or any block of its weight row, holds a
+    0xFF scale byte or an E4M3 NaN code.  out: an optional contiguous fp32 device tensor of that shape."""
+    elem_b = elem_a if elem_b is None else elem_b
+    for e in (elem_a, elem_b):
+        if e not in MX_ELEM:
+            raise _hip.DipoorletHipError(f"mx_conv: elem must be 'mxfp8' or 'mxfp4', got {e!r}")
+    for t, name in ((a_codes, "a_codes"), (a_scales, "a_scales"), (b_codes, "b_codes"), (b_scales, "b_scales")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == a_codes.device):
+            raise _hip.DipoorletHipError(f"mx_conv: {name} must be a contiguous uint8 ROCm device tensor on one device; dipoorlet_amd has no CPU path")
+
+    def split(codes, scales, elem, who, dims):
+        per = 2 if elem == "mxfp4" else 1                      # codes to a byte
+        ok = codes.dim() == 4 and scales.dim() == 4 and tuple(scales.shape[:-1]) == tuple(codes.shape[:-1]) \
+            and int(codes.shape[-1]) * per == MX_BLOCK * int(scales.shape[-1])
+        if not ok:
+            raise _hip.DipoorletHipError(f"mx_conv: {who} must be codes [{dims}, Cp{' / 2' if per == 2 else ''}] and scales [{dims}, Cp / "
+                                         f"{MX_BLOCK}] as mx_encode writes {elem} along axis 1 (K-innermost), got {list(codes.shape)} and "
+                                         f"{list(scales.shape)}")
+        return tuple(int(d) for d in codes.shape[:-1]), int(scales.shape[-1])
+    (n, h, w), cb = split(a_codes, a_scales, elem_a, "A", "n, h, w")
+    (cout, kh, kw), cb_b = split(b_codes, b_scales, elem_b, "B", "cout, kh, kw")
+    if cb_b != cb:
+        raise _hip.DipoorletHipError(f"mx_conv: A has {cb} channel block(s) a pixel and B {cb_b}: the two must have the same number of K-blocks a tap")
+    geom = []
+    for v, name in ((strides, "strides"), (pads, "pads"), (dilations, "dilations"), (out_hw, "out_hw")):
+        if not (isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(d, (int, np.integer)) and not isinstance(d, bool) for d in v)):
+            raise _hip.DipoorletHipError(f"mx_conv: {name} must be two integers, got {v!r}")
+        geom.append((int(v[0]), int(v[1])))
+    (sh, sw), (pt, pl), (dh, dw), (oh, ow) = geom
+    if oh < 0 or ow < 0:
+        raise _hip.DipoorletHipError(f"mx_conv: out_hw must not be negative, got {out_hw!r}")
+    shape = (n, oh, ow, cout)
+    if out is None:
+        c = torch.empty(shape, dtype=torch.float32, device=a_codes.device)
+    else:
+        _require_cuda(out, "out")
+        if tuple(out.shape) != shape or out.device != a_codes.device:
+            raise _hip.DipoorletHipError(f"mx_conv: out must have shape {list(shape)} and the codes' device")
+        c = out
+    _hip.check(_hip.lib().dpl_mx_conv(MX_ELEM[elem_a], MX_ELEM[elem_b], _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales), n, h, w,
+                                      MX_BLOCK * cb, cout, kh, kw, sh, sw, pt, pl, dh, dw, oh, ow, _ptr(c), _stream()), "dpl_mx_conv")
+    return c
+
+
 def mx_matmul(x, w_codes, w_scales, elem, elem_w=None):
     """x . W on the block-scaled matrix instruction: x (fp32 [..., m, K]) is encoded along its last axis as `elem` (mx_encode), W is
     already packed — mx_encode(w, -2, elem_w) of a [K, N] weight, i.e. [N, Kp] codes — and the two go through mx_gemm -> [..., m, N]."""

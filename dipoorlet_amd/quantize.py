@@ -373,11 +373,47 @@ class _NodeRules:
 def mx_block_axis(node, idx, shape):
     """The axis of operand `idx` (0 or 1) of a MatMul / Gemm that the product reduces over — the one MX blocks run along: MatMul
     A -1, B -2 (-1 for a 1-D B), counted from the end as MatMul's own rule is (the same answer whether or not the graph knows an
-    activation's shape yet); Gemm A 0 if transA else 1, B 1 if transB else 0."""
+    activation's shape yet); Gemm A 0 if transA else 1, B 1 if transB else 0; Conv (`--mx_conv`) 1 for both."""
+    if node.op_type == "Conv":      # (--mx_conv) channels of the [N, C, H, W] activation, input channels of the [Cout, C, kh, kw] weight
+        return 1
     if node.op_type == "Gemm":
         t = int(node.attrs.get("transA" if idx == 0 else "transB", 0) or 0)
         return (0 if t else 1) if idx == 0 else (1 if t else 0)
     return -1 if idx == 0 or (shape is not None and len(shape) == 1) else -2
+
+
+def mx_conv_left(graph, node):
+    """`--mx_conv`: why Conv `node` of `graph` (not yet fake-quantised) keeps its static nodes — or None: both its operands take the
+    MX parameter set, blocked along axis 1.  Taken: a convolution over two spatial axes (4-D input, 4-D weight), group 1, whose
+    weight is a constant."""
+    if len(node.input) < 2 or node.input[1] not in graph.initializer:
+        return "the weight is not a constant"
+    nd = np.asarray(graph.get_initializer(node.input[1])).ndim - 2
+    x_shape = graph.tensor_name_shape_map.get(node.input[0])
+    if nd != 2 or (x_shape is not None and len(x_shape) != 4):
+        return f"a {nd}-D convolution" if nd != 2 else f"an input of {len(x_shape)} dimension(s)"
+    group = int(node.attrs.get("group", 1) or 1)
+    if group != 1:
+        return f"group = {group}"
+    return None
+
+
+def mx_conv_nodes(graph, args):
+    """`--mx_conv` over the Convs of `graph` (not yet fake-quantised) that quant_graph considers -> (the names of those it
+    block-scales, {name: reason} of those it leaves on their static grid)."""
+    from .platform_settings import platform_setting_table
+    skipped = set(getattr(args, "skip_layers", None) or ())
+    taken, left = [], {}
+    if "Conv" not in platform_setting_table[args.deploy]["quant_nodes"]:
+        return taken, left
+    for node in graph.graph.node:
+        if node.op_type == "Conv" and node.name not in skipped:
+            why = mx_conv_left(graph, node)
+            if why is None:
+                taken.append(node.name)
+            else:
+                left[node.name] = why
+    return taken, left
 
 
 def _taken(act_quantized, name):
@@ -394,13 +430,16 @@ def insert_fake_quant_node(graph, node, act_quantized, data_range_list, args):
     fake-quantised tensor, and insert the FakeQuant node unless the tensor already has one (`act_quantized`).
     With args.mx ('mxfp8' / 'mxfp4'; -D ocp_fp8) both operands of a MatMul / Gemm — a constant one too, whatever its role — take
     the MX parameter set instead, blocked along the operand's reduction axis (mx_block_axis); a Gemm bias is left to the platform's
-    rules.  `act_quantized` holds (name, axis) for such a node: a tensor wanted along two axes, or by a static consumer as well,
+    rules.  With args.mx_conv so do both operands of every Conv that mx_conv_left lets through, along axis 1; its bias too is left
+    to the platform's rules.  `act_quantized` holds (name, axis) for such a node: a tensor wanted along two axes, or by a static consumer as well,
     gets one node each — the first has the usual names, a later MX one the suffix `_ax<k>`, a later static one `_static`.
     With args.mx_scale_search the MX node of a constant operand carries error-minimising block scales (_MX.search_scales), computed
     here from the weight as it stands in `graph`; an activation's node keeps the floor rule."""
     from .platform_settings import mx_setting_table, platform_setting_table
     plat = platform_setting_table[args.deploy]
-    mx = getattr(args, "mx", None) if node.op_type in MX_NODES else None
+    mx = getattr(args, "mx", None)
+    if node.op_type not in MX_NODES and not (node.op_type == "Conv" and getattr(args, "mx_conv", False) and mx_conv_left(graph, node) is None):
+        mx = None
     rules = _NodeRules(graph, node, plat, args.deploy)
     for idx, name in enumerate(list(node.input)):
         role = rules.role(name)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 33 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 34 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
                               25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
@@ -37,7 +37,8 @@ extern "C" {
                               31: dpl_mx_gemm (two packed MX operands through CDNA4's block-scaled matrix instruction: --mx_verify);
                               32: dpl_mx_scale_search / dpl_fake_quant_mx_scaled / dpl_mx_encode_scaled (error-minimising E8M0 scales
                                   for constant MX operands, and the Q/DQ and the packed bytes under given scales: --mx_scale_search);
-                              33: dpl_gptq_mx_block (dpl_gptq_block's recursion on the MX block-scaled grids: --mx_gptq) */
+                              33: dpl_gptq_mx_block (dpl_gptq_block's recursion on the MX block-scaled grids: --mx_gptq);
+                              34: dpl_mx_conv (a convolution of two packed MX operands on the block-scaled matrix instruction: --mx_conv) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -504,6 +505,29 @@ int dpl_mx_encode_scaled(int32_t elem, const float* d_x, uint64_t outer, uint64_
  *      a refused call (-2) launches nothing. */
 int dpl_mx_gemm(int32_t elem_a, int32_t elem_b, const uint8_t* d_a_codes, const uint8_t* d_a_scales, const uint8_t* d_b_codes,
                 const uint8_t* d_b_scales, uint64_t batch, uint64_t m, uint64_t n, uint64_t k, int32_t b_batched, float* d_c, dpl_stream_t s);
+
+/* ---- a convolution of two packed MX operands on the same instruction, as an implicit GEMM (beyond the reference; --mx_conv; the
+ *      definition is tests/mx_conv_model.py).  Both operands are what dpl_mx_encode writes along axis 1 (channels).  With
+ *      cb = ceil(c / 32) and bb = 32 (E4M3) or 16 (E2M1) bytes per block of the operand's element format:
+ *        d_a_codes  uint8 [n, h, w, cb * bb]          d_a_scales  uint8 [n, h, w, cb]          of an [n, c, h, w] activation (NHWC)
+ *        d_b_codes  uint8 [cout, kh, kw, cb * bb]     d_b_scales  uint8 [cout, kh, kw, cb]     of a [cout, c, kh, kw] weight
+ *        d_c        fp32 [n, oh, ow, cout] (NHWC):
+ *          C[b, oy, ox, co] = sum over ky < kh, kx < kw, ch < 32 * cb of
+ *                             a[b, oy * stride_h - pad_top + ky * dil_h, ox * stride_w - pad_left + kx * dil_w, ch] * b[co, ky, kx, ch]
+ *      a, b: the values dpl_mx_decode gives those bytes; the pad codes of a short last channel block take part.  A tap outside the
+ *      image contributes nothing and is never read, whatever oh and ow are: the caller computes them (and the pads at the bottom
+ *      and on the right follow from them).  group = 1 only.  The sum is the instruction's own, over the kh * kw * cb K-blocks in the
+ *      weight's memory order, four to a step: dpl_mx_gemm's error bound holds with kp = kh * kw * 32 * cb.
+ *      NaN rule: C[b, oy, ox, co] is NaN if a block of A inside an in-image tap of that output, or any block of row co of B, holds a
+ *      0xFF scale byte or an E4M3 NaN code (0x7F, 0xFF); a bad pixel that no tap of an output reaches leaves that output finite.
+ *      The un-staged form: operands come straight from global memory, an activation block is read again for every tap.
+ *      Refused (-2, nothing launched): an unknown element code; kh, kw, a stride or a dilation below 1; a negative pad; any argument
+ *      negative or >= 2^31; null pointers; d_a_codes or d_b_codes not 16-byte aligned; kh * kw * cb or oh * ow >= 2^31, a tensor
+ *      beyond 2^63 bytes or a grid beyond 2^31 workgroups.  n * h * w * c * cout * oh * ow == 0 is a no-op that returns 0. */
+int dpl_mx_conv(int32_t elem_a, int32_t elem_b, const uint8_t* d_a_codes, const uint8_t* d_a_scales, const uint8_t* d_b_codes,
+                const uint8_t* d_b_scales, int64_t n, int64_t h, int64_t w, int64_t c, int64_t cout, int64_t kh, int64_t kw, int64_t stride_h,
+                int64_t stride_w, int64_t pad_top, int64_t pad_left, int64_t dil_h, int64_t dil_w, int64_t oh, int64_t ow, float* d_c,
+                dpl_stream_t s);
 
 /* ---- the block-Hadamard rotation of --mx_rotate (beyond the reference): y = x . blockdiag(H32) along the contiguous last axis of
  *      the [rows, k] tensor, H32[i][j] = (-1)^popcount(i & j) (Sylvester, natural order, symmetric, H32 . H32 = 32 I; NOT
