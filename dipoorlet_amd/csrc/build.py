@@ -14,7 +14,7 @@ SRC = [os.path.join(HERE, f) for f in ("calib_kernels.hip", "fake_quant_kernels.
                                        "hadamard_kernels.hip", "mx_gemm_kernels.hip", "mx_search_kernels.hip", "mx_conv_kernels.hip")]
 HDR = [os.path.join(HERE, "..", "..", "include", "dipoorlet_hip.h"), os.path.join(HERE, "common.hpp"),
        os.path.join(HERE, "octav_common.hpp"), os.path.join(HERE, "octav_wave.hpp"), os.path.join(HERE, "octav_tail.hpp"),
-       os.path.join(HERE, "octav_rescue.hpp"), os.path.join(HERE, "mx_format.hpp"), os.path.join(HERE, "mx_block.hpp"), os.path.join(HERE, "mx_search.hpp"),
+       os.path.join(HERE, "octav_rescue.hpp"), os.path.join(HERE, "mx_format.hpp"), os.path.join(HERE, "mx_block.hpp"), os.path.join(HERE, "mx_plan.hpp"), os.path.join(HERE, "mx_search.hpp"),
        os.path.join(HERE, "host_plan.hpp"), os.path.join(HERE, "host_error.hpp"), os.path.join(HERE, "octav_geometry.hpp"), os.path.join(HERE, "fq_elem.hpp"),
        os.path.join(HERE, "mx_mfma.hpp")]
 OUT = os.path.join(HERE, "libdipoorlet_hip.so")

@@ -1,7 +1,7 @@
 // K7b: `--mx_pack` — an MX tensor as packed element codes and E8M0 scale bytes, and back (tests/mx_pack_model.py is the definition;
 // mx_format.hpp round_code / decode_bits the arithmetic; mx_block.hpp what is shared with the Q/DQ pair of mx_kernels.hip: the
-// loads, the block maximum, the shared exponent, the decomposition of a launch).  The tensor is fp32 [outer, K, inner], blocks of 32
-// along K.  Codes and scales are K-INNERMOST, the order a block-scaled GEMM reads both operands in: with nblk = ceil(K / 32),
+// block walk — MxRowsLoad, MxColsLoad over MxPackColsAt —, the block maximum, the shared exponent and its byte; mx_plan.hpp the
+// argument check, the launch plan and the dispatch).  The tensor is fp32 [outer, K, inner], blocks of 32 along K.  Codes and scales are K-INNERMOST, the order a block-scaled GEMM reads both operands in: with nblk = ceil(K / 32),
 // codes is [outer, inner, nblk * 32] bytes (E4M3) or [outer, inner, nblk * 16] (E2M1: two to a byte, the even index along K in the
 // low nibble), scales [outer, inner, nblk].  For inner > 1 that is a transpose of the element order, and NOT the order of
 // dpl_fake_quant_mx's scales ([outer, nblk, inner]).  The elements past K of a short last block get code 0.  A block is 32 or 16
@@ -78,76 +78,39 @@ __device__ __forceinline__ void mx_store_group_codes(uint8_t* dst, uint32_t pay,
     if (go && lane % keep == 0u) __builtin_nontemporal_store(out, (gptr_u4w)(dst + off));
 }
 
-// Where a lane of a cols kernel works.  One column to a lane (VEC = 1): the slots of k_fake_quant_mx_cols (MxColsAt) — a wave is
-// one K-block of 64 columns.  Four columns to a lane (VEC = 4): a wave is a TILE of four consecutive K-blocks of sixteen column
-// groups, lane = 16 * (K-block in the tile) + column group: an fp32 access of the wave is four runs of 256 contiguous bytes (whole
-// lines, as many as the slot form touches), and the four lanes that hold the four K-blocks of one column access one run of 128
-// (64) contiguous code bytes instead of four runs Kp bytes apart.  Tiles: [outer, ceil(nblk / 4), ceil(cs / 16)].
-template <int VEC>
-struct MxPackColsAt {
-    uint64_t o;
-    uint32_t kb, col;
-    bool live;
-    __device__ __forceinline__ MxPackColsAt(uint64_t n_slots, uint32_t nblk, uint32_t cs) {
-        if constexpr (VEC == 1) {
-            live = (uint64_t)blockIdx.x * kMxColsBlock + threadIdx.x < n_slots;
-            const MxColsAt w(nblk, cs, 1);
-            o = w.o, kb = w.kb, col = w.col;
-        } else {
-            const uint32_t nct = (cs + 15u) / 16u, nkt = (nblk + 3u) / 4u;
-            const uint32_t r = blockIdx.x / nct, ct = blockIdx.x - r * nct;       // (the grid is below 2^31)
-            const uint32_t ob = r / nkt, kt = r - ob * nkt;
-            const uint32_t cg = ct * 16u + (threadIdx.x & 15u);
-            o = ob;
-            kb = kt * 4u + (threadIdx.x >> 4);
-            col = cg * VEC;
-            live = kb < nblk && cg < cs;
-        }
-    }
-};
-
 // The bytes a GIVEN encode kernel reads (--mx_scale_search: dpl_mx_encode_scaled), uint8 [outer, nblk, inner] — the order of
 // dpl_fake_quant_mx's scales, not the K-innermost one the kernel writes.  The derived form carries nothing.
 template <bool GIVEN>
 struct MxGivenBytes {
     const uint8_t* p;
+    __host__ __device__ const uint8_t* ptr() const { return p; }
 };
 template <>
-struct MxGivenBytes<false> {};
+struct MxGivenBytes<false> {
+    __host__ __device__ const uint8_t* ptr() const { return nullptr; }
+};
 
 // ---------------------------------------------------------------------------------------------- encode, inner == 1
 template <int ELEM, int VEC, bool GIVEN = false>
 __global__ __launch_bounds__(kBlock) void k_mx_encode_rows(const float* x, uint8_t* codes, uint8_t* scales, uint64_t n_groups, uint32_t K,
                                                            uint32_t nblk, MxGivenBytes<GIVEN> given) {
-    const MxRowsAt<VEC> w(nblk);
-    MxVec<VEC> v[kMxRowsIter];
-    bool live[kMxRowsIter];
-    uint32_t byte[kMxRowsIter];
+    MxRowsLoad<VEC> in(n_groups, K, nblk);
+    in.load(x);
+    uint32_t byte[kMxRowsIter];                        // (inner == 1: the two orders are one; read by every lane whose group exists)
+#pragma unroll
+    for (int i = 0; i < kMxRowsIter; ++i) byte[i] = in.template given_byte<GIVEN>(given.ptr(), i, in.exists(i));
 #pragma unroll
     for (int i = 0; i < kMxRowsIter; ++i) {
-        uint64_t row;
-        uint32_t col;
-        w.at(i, nblk, row, col);
-        live[i] = w.group(i) < n_groups && col < K;    // (K % VEC == 0: a vector that starts inside a row ends inside it)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) v[i].b[j] = 0u;
-        if (live[i]) v[i] = mx_load<VEC>(x + row * K + col);
-        byte[i] = 0u;
-        if constexpr (GIVEN)
-            if (w.group(i) < n_groups) byte[i] = ((gptr_u8)given.p)[w.group(i)];      // (inner == 1: the two orders are one)
-    }
-#pragma unroll
-    for (int i = 0; i < kMxRowsIter; ++i) {
-        const uint32_t a = mx_group_max<VEC>(v[i]);
+        const uint32_t a = mx_group_max<VEC>(in.v[i]);
         bool nan;
         const int se = GIVEN ? mx_block_se_given<ELEM>(a, byte[i], nan) : mx_block_se<ELEM>(a, nan);
         uint32_t pay = 0u;
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) pay |= mx_code<ELEM>(v[i].b[j], se, nan, live[i]) << (Pack<ELEM>::bits * j);
-        const uint64_t g = w.group(i);
-        const bool go = g < n_groups;                  // (the pad lanes of a short last block are part of it: code 0)
-        mx_store_group_codes<ELEM, VEC>(codes + g * Pack<ELEM>::block_bytes, pay, w.lane, go);
-        if (go && w.lane == 0u) ((gptr_u8w)scales)[g] = nan ? 0xFFu : (uint8_t)(se + 127);
+        for (int j = 0; j < VEC; ++j) pay |= mx_code<ELEM>(in.v[i].b[j], se, nan, in.live[i]) << (Pack<ELEM>::bits * j);
+        const uint64_t g = in.group(i);
+        const bool go = in.exists(i);                  // (the pad lanes of a short last block are part of it: code 0)
+        mx_store_group_codes<ELEM, VEC>(codes + g * Pack<ELEM>::block_bytes, pay, in.w.lane, go);
+        if (go && in.w.lane == 0u) ((gptr_u8w)scales)[g] = mx_scale_byte(se, nan);
     }
 }
 
@@ -157,47 +120,34 @@ __global__ __launch_bounds__(kMxColsBlock, 2) void k_mx_encode_cols(const float*
                                                                  uint32_t nblk, uint32_t inner, uint32_t cs, MxGivenBytes<GIVEN> given) {
     const MxPackColsAt<VEC> w(n_slots, nblk, cs);
     if (!w.live) return;
-    const uint32_t rows = min(32u, K - w.kb * 32u);
-    const uint64_t base = (w.o * K + (uint64_t)w.kb * 32u) * inner + w.col;
-    MxVec<VEC> v[32];
-#pragma unroll
-    for (int r = 0; r < 32; ++r) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) v[r].b[j] = 0u;
-        if ((uint32_t)r < rows) v[r] = mx_load<VEC>(x + base + (uint64_t)r * inner);
-    }
+    MxColsLoad<VEC> in(w, K, inner);
+    in.load(x);
     uint32_t a[VEC];
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) a[j] = 0u;
-#pragma unroll
-    for (int r = 0; r < 32; ++r)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) a[j] = max(a[j], v[r].b[j] & 0x7FFFFFFFu);
+    for (int j = 0; j < VEC; ++j) a[j] = MX_COL_MAX(in, j);
     constexpr uint32_t BITS = Pack<ELEM>::bits, NW = Pack<ELEM>::block_bytes / 4u;      // dwords of one column's block: 8 or 4
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
         bool nan;
         int se;
         if constexpr (GIVEN)
-            se = mx_block_se_given<ELEM>(a[j], ((gptr_u8)given.p)[(w.o * nblk + w.kb) * inner + w.col + (uint32_t)j], nan);
+            se = mx_block_se_given<ELEM>(a[j], ((gptr_u8)given.p)[w.block(nblk, inner, j)], nan);
         else
             se = mx_block_se<ELEM>(a[j], nan);
         uint32_t wd[NW];
 #pragma unroll
         for (uint32_t d = 0; d < NW; ++d) wd[d] = 0u;
 #pragma unroll
-        for (int r = 0; r < 32; ++r)
-            wd[(uint32_t)r * BITS / 32u] |= mx_code<ELEM>(v[r].b[j], se, nan, (uint32_t)r < rows) << ((uint32_t)r * BITS % 32u);
-        const uint64_t blk = ((w.o * inner + w.col + (uint32_t)j) * nblk + w.kb);      // of [outer, inner, nblk]
+        for (int r = 0; r < 32; ++r) wd[(uint32_t)r * BITS / 32u] |= mx_code<ELEM>(in.v[r].b[j], se, nan, in.has(r)) << ((uint32_t)r * BITS % 32u);
+        const uint64_t blk = w.packed_block(nblk, inner, j);
         uint8_t* dst = codes + blk * Pack<ELEM>::block_bytes;
 #pragma unroll
         for (uint32_t d = 0; d < NW; d += 4) __builtin_nontemporal_store(u4{wd[d], wd[d + 1], wd[d + 2], wd[d + 3]}, (gptr_u4w)(dst + 4u * d));
-        ((gptr_u8w)scales)[blk] = nan ? 0xFFu : (uint8_t)(se + 127);
+        ((gptr_u8w)scales)[blk] = mx_scale_byte(se, nan);
     }
 }
 
 // ---------------------------------------------------------------------------------------------- decode
-// Element `i` (0 .. 31) of a block whose codes are the dwords wd[]; scale byte sc.
 template <int ELEM>
 __device__ __forceinline__ uint32_t mx_decode_code(uint32_t code, uint32_t sc) {
     return sc == 0xFFu ? kQuietNaN : dpl_mx::decode_bits<ELEM>(code, (int)sc - 127);
@@ -209,37 +159,30 @@ template <int ELEM, int VEC>
 __global__ __launch_bounds__(kBlock) void k_mx_decode_rows(const uint8_t* codes, const uint8_t* scales, float* y, uint64_t n_groups, uint32_t K,
                                                            uint32_t nblk) {
     constexpr uint32_t BITS = Pack<ELEM>::bits;
-    const MxRowsAt<VEC> w(nblk);
+    const MxRowsLoad<VEC> out(n_groups, K, nblk);      // (where the lane writes: nothing is loaded from the fp32 side)
     uint32_t pay[kMxRowsIter], sc[kMxRowsIter];
-    uint64_t at[kMxRowsIter];
-    bool live[kMxRowsIter];
 #pragma unroll
     for (int i = 0; i < kMxRowsIter; ++i) {
-        uint64_t row;
-        uint32_t col;
-        w.at(i, nblk, row, col);
-        const uint64_t g = w.group(i);
-        live[i] = g < n_groups && col < K;
-        at[i] = row * K + col;
+        const uint64_t g = out.group(i);
         pay[i] = sc[i] = 0u;
-        if (live[i]) {
-            const uint8_t* src = codes + g * Pack<ELEM>::block_bytes + w.lane * VEC * BITS / 8u;
+        if (out.live[i]) {
+            const uint8_t* src = codes + g * Pack<ELEM>::block_bytes + out.w.lane * VEC * BITS / 8u;
             if constexpr (VEC * BITS == 32)
                 pay[i] = *(gptr_u32)src;
             else if constexpr (VEC * BITS == 16)
                 pay[i] = *(gptr_u16)src;
             else
-                pay[i] = (uint32_t)(*(gptr_u8)src) >> (w.lane * BITS % 8u);
+                pay[i] = (uint32_t)(*(gptr_u8)src) >> (out.w.lane * BITS % 8u);
             sc[i] = ((gptr_u8)scales)[g];
         }
     }
 #pragma unroll
     for (int i = 0; i < kMxRowsIter; ++i) {
-        if (live[i]) {
+        if (out.live[i]) {
             MxVec<VEC> r;
 #pragma unroll
             for (int j = 0; j < VEC; ++j) r.b[j] = mx_decode_code<ELEM>((pay[i] >> (BITS * j)) & ((1u << BITS) - 1u), sc[i]);
-            mx_store<VEC>(y + at[i], r);
+            mx_store<VEC>(y + out.at[i], r);
         }
     }
 }
@@ -252,12 +195,11 @@ __global__ __launch_bounds__(kMxColsBlock, 2) void k_mx_decode_cols(const uint8_
     constexpr uint32_t BITS = Pack<ELEM>::bits, NW = Pack<ELEM>::block_bytes / 4u;
     const MxPackColsAt<VEC> w(n_slots, nblk, cs);
     if (!w.live) return;
-    const uint32_t rows = min(32u, K - w.kb * 32u);
-    const uint64_t base = (w.o * K + (uint64_t)w.kb * 32u) * inner + w.col;
+    const MxColsLoad<VEC> out(w, K, inner);            // (as above)
     uint32_t wd[VEC][NW], sc[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-        const uint64_t blk = ((w.o * inner + w.col + (uint32_t)j) * nblk + w.kb);
+        const uint64_t blk = w.packed_block(nblk, inner, j);
         const uint8_t* src = codes + blk * Pack<ELEM>::block_bytes;
 #pragma unroll
         for (uint32_t d = 0; d < NW; d += 4) {
@@ -268,145 +210,77 @@ __global__ __launch_bounds__(kMxColsBlock, 2) void k_mx_decode_cols(const uint8_
     }
 #pragma unroll
     for (int r = 0; r < 32; ++r) {
-        if ((uint32_t)r < rows) {
+        if (out.has(r)) {
             MxVec<VEC> o;
 #pragma unroll
             for (int j = 0; j < VEC; ++j)
                 o.b[j] = mx_decode_code<ELEM>((wd[j][(uint32_t)r * BITS / 32u] >> ((uint32_t)r * BITS % 32u)) & ((1u << BITS) - 1u), sc[j]);
-            mx_store<VEC>(y + base + (uint64_t)r * inner, o);
+            mx_store<VEC>(y + out.at(r), o);
         }
     }
 }
 
 // ---------------------------------------------------------------------------------------------- launches
-struct MxPackPlan {
-    uint32_t K, nblk, cs;
-    bool vec;
-    uint64_t n, blocks;       // groups (inner == 1) or slots, and workgroups
-};
-
-// fp: the fp32 side's base (d_x of encode, d_y of decode) — its alignment decides between 16-byte vectors and single elements
-inline MxPackPlan mx_pack_plan(const void* fp, uint64_t outer, uint64_t k, uint64_t inner) {
-    MxPackPlan p;
-    p.K = (uint32_t)k;
-    p.nblk = (p.K + 31u) / 32u;
-    const bool aligned = ((uintptr_t)fp & 15u) == 0u;
-    if (inner == 1) {
-        p.vec = aligned && (p.K & 3u) == 0u;
-        p.cs = 1;
-        p.n = outer * p.nblk;
-        const uint64_t per_wg = (uint64_t)kMxRowsIter * kBlock * (p.vec ? 4 : 1) / 32;
-        p.blocks = (p.n + per_wg - 1) / per_wg;
-    } else {
-        p.vec = aligned && (inner & 3u) == 0u;
-        p.cs = (uint32_t)(p.vec ? inner / 4 : inner);
-        p.n = outer * p.nblk * p.cs;
-        p.blocks = p.vec ? outer * ((p.nblk + 3u) / 4u) * ((p.cs + 15u) / 16u) : (p.n + kMxColsBlock - 1) / kMxColsBlock;      // tiles : slots
-    }
-    return p;
-}
-
-template <int ELEM, bool GIVEN = false>
-int mx_encode_launch(const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, uint8_t* d_codes, uint8_t* d_scales, MxGivenBytes<GIVEN> given,
-                     dpl_stream_t s) {
-    const MxPackPlan p = mx_pack_plan(d_x, outer, k, inner);
-    if (p.blocks > 0x7FFFFFFFull) return fail_msg(GIVEN ? "dpl_mx_encode_scaled: tensor too large" : "dpl_mx_encode: tensor too large");
-    const dim3 grid((unsigned)p.blocks);
-    if (inner == 1) {
-        if (p.vec)
-            hipLaunchKernelGGL((k_mx_encode_rows<ELEM, 4, GIVEN>), grid, dim3(kBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
-                               given);
-        else
-            hipLaunchKernelGGL((k_mx_encode_rows<ELEM, 1, GIVEN>), grid, dim3(kBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
-                               given);
-        DPL_LAUNCH_CHECK("k_mx_encode_rows");
+// (fp: the fp32 side's base, d_x of encode and d_y of decode; the VEC = 4 cols kernels take the tile grid)
+template <bool GIVEN>
+int mx_encode_launch(const char* who, int32_t elem, const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, uint8_t* d_codes, uint8_t* d_scales,
+                     MxGivenBytes<GIVEN> given, dpl_stream_t s) {
+    MxPlan p;
+    if (const int rc = mx_plan(p, who, (uintptr_t)d_x, outer, k, inner, true)) return rc;
+    return mx_dispatch(elem, inner == 1, p.vec, [&](auto E, auto ROWS, auto VEC) {
+        if constexpr (ROWS) {
+            hipLaunchKernelGGL((k_mx_encode_rows<E, VEC, GIVEN>), dim3((unsigned)p.blocks), dim3(kBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n,
+                               p.K, p.nblk, given);
+            DPL_LAUNCH_CHECK("k_mx_encode_rows");
+        } else {
+            hipLaunchKernelGGL((k_mx_encode_cols<E, VEC, GIVEN>), dim3((unsigned)p.blocks), dim3(kMxColsBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales,
+                               p.n, p.K, p.nblk, (uint32_t)inner, p.cs, given);
+            DPL_LAUNCH_CHECK("k_mx_encode_cols");
+        }
         return 0;
-    }
-    if (p.vec)
-        hipLaunchKernelGGL((k_mx_encode_cols<ELEM, 4, GIVEN>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
-                           (uint32_t)inner, p.cs, given);
-    else
-        hipLaunchKernelGGL((k_mx_encode_cols<ELEM, 1, GIVEN>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_x, d_codes, d_scales, p.n, p.K, p.nblk,
-                           (uint32_t)inner, p.cs, given);
-    DPL_LAUNCH_CHECK("k_mx_encode_cols");
-    return 0;
+    });
 }
 
-template <int ELEM>
-int mx_decode_launch(const uint8_t* d_codes, const uint8_t* d_scales, uint64_t outer, uint64_t k, uint64_t inner, float* d_y, dpl_stream_t s) {
-    const MxPackPlan p = mx_pack_plan(d_y, outer, k, inner);
-    if (p.blocks > 0x7FFFFFFFull) return fail_msg("dpl_mx_decode: tensor too large");
-    const dim3 grid((unsigned)p.blocks);
-    if (inner == 1) {
-        if (p.vec)
-            hipLaunchKernelGGL((k_mx_decode_rows<ELEM, 4>), grid, dim3(kBlock), 0, (hipStream_t)s, d_codes, d_scales, d_y, p.n, p.K, p.nblk);
-        else
-            hipLaunchKernelGGL((k_mx_decode_rows<ELEM, 1>), grid, dim3(kBlock), 0, (hipStream_t)s, d_codes, d_scales, d_y, p.n, p.K, p.nblk);
-        DPL_LAUNCH_CHECK("k_mx_decode_rows");
+int mx_decode_launch(const char* who, int32_t elem, const uint8_t* d_codes, const uint8_t* d_scales, uint64_t outer, uint64_t k, uint64_t inner,
+                     float* d_y, dpl_stream_t s) {
+    MxPlan p;
+    if (const int rc = mx_plan(p, who, (uintptr_t)d_y, outer, k, inner, true)) return rc;
+    return mx_dispatch(elem, inner == 1, p.vec, [&](auto E, auto ROWS, auto VEC) {
+        if constexpr (ROWS) {
+            hipLaunchKernelGGL((k_mx_decode_rows<E, VEC>), dim3((unsigned)p.blocks), dim3(kBlock), 0, (hipStream_t)s, d_codes, d_scales, d_y, p.n, p.K,
+                               p.nblk);
+            DPL_LAUNCH_CHECK("k_mx_decode_rows");
+        } else {
+            hipLaunchKernelGGL((k_mx_decode_cols<E, VEC>), dim3((unsigned)p.blocks), dim3(kMxColsBlock), 0, (hipStream_t)s, d_codes, d_scales, d_y, p.n,
+                               p.K, p.nblk, (uint32_t)inner, p.cs);
+            DPL_LAUNCH_CHECK("k_mx_decode_cols");
+        }
         return 0;
-    }
-    if (p.vec)
-        hipLaunchKernelGGL((k_mx_decode_cols<ELEM, 4>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_codes, d_scales, d_y, p.n, p.K, p.nblk,
-                           (uint32_t)inner, p.cs);
-    else
-        hipLaunchKernelGGL((k_mx_decode_cols<ELEM, 1>), grid, dim3(kMxColsBlock), 0, (hipStream_t)s, d_codes, d_scales, d_y, p.n, p.K, p.nblk,
-                           (uint32_t)inner, p.cs);
-    DPL_LAUNCH_CHECK("k_mx_decode_cols");
-    return 0;
+    });
 }
 
-// The argument rules both entry points share (those of dpl_fake_quant_mx, plus the codes' alignment).  1: nothing to do.
-int mx_pack_check(const char* who, int32_t elem, const void* fp, const void* codes, const void* scales, uint64_t outer, uint64_t k, uint64_t inner) {
-    char msg[160];
-    if (elem != DPL_MX_E4M3 && elem != DPL_MX_E2M1) {
-        snprintf(msg, sizeof(msg), "%s: elem must be DPL_MX_E4M3 or DPL_MX_E2M1", who);
-        return fail_msg(msg);
-    }
-    if (outer == 0 || k == 0 || inner == 0) return 1;
-    if (fp == nullptr || codes == nullptr || scales == nullptr) {
-        snprintf(msg, sizeof(msg), "%s: the tensor, d_codes and d_scales must not be null", who);
-        return fail_msg(msg);
-    }
-    if (k > 0x7FFFFFFFull || inner > 0x7FFFFFFFull) {
-        snprintf(msg, sizeof(msg), "%s: k and inner must be in [1, 2^31)", who);
-        return fail_msg(msg);
-    }
-    // (the padded tensor, 32 * nblk <= k + 31 along K, must be indexable too)
-    if (outer > (0x7FFFFFFFFFFFFFFFull / (32ull * ((k + 31u) / 32u))) / inner) {
-        snprintf(msg, sizeof(msg), "%s: tensor too large", who);
-        return fail_msg(msg);
-    }
-    if (((uintptr_t)codes & 15u) != 0u) {
-        snprintf(msg, sizeof(msg), "%s: d_codes must be 16-byte aligned (a block's codes are stored and loaded as 16-byte vectors)", who);
-        return fail_msg(msg);
-    }
-    return 0;
-}
+constexpr const char* kPackPtrs = "the tensor, d_codes and d_scales";
 
 }  // namespace
 
 extern "C" int dpl_mx_encode(int32_t elem, const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, uint8_t* d_codes, uint8_t* d_scales,
                              dpl_stream_t s) {
-    const int rc = mx_pack_check("dpl_mx_encode", elem, d_x, d_codes, d_scales, outer, k, inner);
-    if (rc != 0) return rc < 0 ? rc : 0;
-    return elem == DPL_MX_E4M3 ? mx_encode_launch<DPL_MX_E4M3>(d_x, outer, k, inner, d_codes, d_scales, MxGivenBytes<false>{}, s)
-                               : mx_encode_launch<DPL_MX_E2M1>(d_x, outer, k, inner, d_codes, d_scales, MxGivenBytes<false>{}, s);
+    int rc;
+    if (mx_check(rc, "dpl_mx_encode", elem, kPackPtrs, {d_x, d_codes, d_scales}, outer, k, inner, true, d_codes)) return rc;
+    return mx_encode_launch("dpl_mx_encode", elem, d_x, outer, k, inner, d_codes, d_scales, MxGivenBytes<false>{}, s);
 }
 
 extern "C" int dpl_mx_encode_scaled(int32_t elem, const float* d_x, uint64_t outer, uint64_t k, uint64_t inner, const uint8_t* d_scales_in,
                                     uint8_t* d_codes, uint8_t* d_scales_out, dpl_stream_t s) {
-    const int rc = mx_pack_check("dpl_mx_encode_scaled", elem, d_x, d_codes, d_scales_out, outer, k, inner);
-    if (rc != 0) return rc < 0 ? rc : 0;
+    int rc;
+    if (mx_check(rc, "dpl_mx_encode_scaled", elem, kPackPtrs, {d_x, d_codes, d_scales_out}, outer, k, inner, true, d_codes)) return rc;
     if (d_scales_in == nullptr) return fail_msg("dpl_mx_encode_scaled: d_scales_in must not be null");
-    const MxGivenBytes<true> given{d_scales_in};
-    return elem == DPL_MX_E4M3 ? mx_encode_launch<DPL_MX_E4M3, true>(d_x, outer, k, inner, d_codes, d_scales_out, given, s)
-                               : mx_encode_launch<DPL_MX_E2M1, true>(d_x, outer, k, inner, d_codes, d_scales_out, given, s);
+    return mx_encode_launch("dpl_mx_encode_scaled", elem, d_x, outer, k, inner, d_codes, d_scales_out, MxGivenBytes<true>{d_scales_in}, s);
 }
 
 extern "C" int dpl_mx_decode(int32_t elem, const uint8_t* d_codes, const uint8_t* d_scales, uint64_t outer, uint64_t k, uint64_t inner,
                              float* d_y, dpl_stream_t s) {
-    const int rc = mx_pack_check("dpl_mx_decode", elem, d_y, d_codes, d_scales, outer, k, inner);
-    if (rc != 0) return rc < 0 ? rc : 0;
-    return elem == DPL_MX_E4M3 ? mx_decode_launch<DPL_MX_E4M3>(d_codes, d_scales, outer, k, inner, d_y, s)
-                               : mx_decode_launch<DPL_MX_E2M1>(d_codes, d_scales, outer, k, inner, d_y, s);
+    int rc;
+    if (mx_check(rc, "dpl_mx_decode", elem, kPackPtrs, {d_y, d_codes, d_scales}, outer, k, inner, true, d_codes)) return rc;
+    return mx_decode_launch("dpl_mx_decode", elem, d_codes, d_scales, outer, k, inner, d_y, s);
 }

@@ -1117,13 +1117,7 @@ def fake_quant_mx(x, axis, elem, out=None, scales=None):
     that holds a NaN or an infinity, whose elements all come out NaN)."""
     _require_cuda(x, "x")
     axis, outer, k, inner = _mx_split("fake_quant_mx", tuple(x.shape), axis, elem)
-    if out is None:
-        y = torch.empty_like(x)
-    else:
-        _require_cuda(out, "out")
-        if out.shape != x.shape or out.device != x.device:
-            raise _hip.DipoorletHipError("fake_quant_mx: out must have x's shape and device")
-        y = out
+    y = _mx_out("fake_quant_mx", out, x.shape, x.device, "x's shape and device")
     if scales is not None:
         want = outer * (-(-k // MX_BLOCK)) * inner
         if not (isinstance(scales, torch.Tensor) and scales.is_cuda and scales.device == x.device and scales.dtype == torch.uint8
@@ -1133,6 +1127,17 @@ def fake_quant_mx(x, axis, elem, out=None, scales=None):
     _hip.check(_hip.lib().dpl_fake_quant_mx(MX_ELEM[elem], _ptr(x), _ptr(y), outer, k, inner, None if scales is None else _ptr(scales),
                                             _stream()), "dpl_fake_quant_mx")
     return y
+
+
+def _mx_out(who, out, shape, device, what):
+    """Where an MX op writes its fp32 result: the caller's `out`, which must have `shape` on `device` (`what`: the message's words
+    for the two), or a new tensor."""
+    if out is None:
+        return torch.empty(tuple(shape), dtype=torch.float32, device=device)
+    _require_cuda(out, "out")
+    if tuple(out.shape) != tuple(shape) or out.device != device:
+        raise _hip.DipoorletHipError(f"{who}: out must have {what}")
+    return out
 
 
 def _mx_split(who, shape, axis, elem):
@@ -1217,13 +1222,7 @@ def fake_quant_mx_scaled(x, axis, elem, scales, out=None):
     _require_cuda(x, "x")
     axis, outer, k, inner = _mx_split("fake_quant_mx_scaled", tuple(x.shape), axis, elem)
     _mx_given_scales("fake_quant_mx_scaled", x, axis, scales)
-    if out is None:
-        y = torch.empty_like(x)
-    else:
-        _require_cuda(out, "out")
-        if out.shape != x.shape or out.device != x.device:
-            raise _hip.DipoorletHipError("fake_quant_mx_scaled: out must have x's shape and device")
-        y = out
+    y = _mx_out("fake_quant_mx_scaled", out, x.shape, x.device, "x's shape and device")
     _hip.check(_hip.lib().dpl_fake_quant_mx_scaled(MX_ELEM[elem], _ptr(x), _ptr(y), outer, k, inner, _ptr(scales), _stream()),
                "dpl_fake_quant_mx_scaled")
     return y
@@ -1259,15 +1258,32 @@ def mx_decode(codes, scales, elem, shape, axis, out=None):
     if codes.numel() != int(np.prod(cs, dtype=np.int64)) or scales.numel() != int(np.prod(ss, dtype=np.int64)) or scales.device != codes.device:
         raise _hip.DipoorletHipError(f"mx_decode: a tensor of shape {list(shape)} along axis {axis} has codes {list(cs)} and scales {list(ss)} "
                                      f"(K-innermost), got {list(codes.shape)} and {list(scales.shape)}")
-    if out is None:
-        y = torch.empty(shape, dtype=torch.float32, device=codes.device)
-    else:
-        _require_cuda(out, "out")
-        if tuple(out.shape) != shape or out.device != codes.device:
-            raise _hip.DipoorletHipError("mx_decode: out must have the given shape and the codes' device")
-        y = out
+    y = _mx_out("mx_decode", out, shape, codes.device, "the given shape and the codes' device")
     _hip.check(_hip.lib().dpl_mx_decode(MX_ELEM[elem], _ptr(codes), _ptr(scales), outer, k, inner, _ptr(y), _stream()), "dpl_mx_decode")
     return y
+
+
+def _mx_packed_pair(who, a, b, elem_a, elem_b, dims_ok, kp, how):
+    """The checks mx_gemm and mx_conv share on their two packed MX operands (codes, scales, the message's words for the leading
+    dimensions), each what mx_encode writes, K-innermost -> (elem_b, A's (leading dimensions, K-blocks), B's).  dims_ok: the rule on the
+    number of dimensions; kp, how: the message's name of the padded block axis and of the axis that was encoded."""
+    elem_b = elem_a if elem_b is None else elem_b
+    for e in (elem_a, elem_b):
+        if e not in MX_ELEM:
+            raise _hip.DipoorletHipError(f"{who}: elem must be 'mxfp8' or 'mxfp4', got {e!r}")
+    for t, name in ((a[0], "a_codes"), (a[1], "a_scales"), (b[0], "b_codes"), (b[1], "b_scales")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == a[0].device):
+            raise _hip.DipoorletHipError(f"{who}: {name} must be a contiguous uint8 ROCm device tensor on one device; dipoorlet_amd has no CPU path")
+
+    def split(codes, scales, dims, elem, label):
+        per = 2 if elem == "mxfp4" else 1                      # codes to a byte
+        if not (dims_ok(codes.dim()) and scales.dim() == codes.dim() and tuple(scales.shape[:-1]) == tuple(codes.shape[:-1])
+                and int(codes.shape[-1]) * per == MX_BLOCK * int(scales.shape[-1])):
+            raise _hip.DipoorletHipError(f"{who}: {label} must be codes [{dims}, {kp}{' / 2' if per == 2 else ''}] and scales [{dims}, {kp} / "
+                                         f"{MX_BLOCK}] as mx_encode writes {elem}{how} (K-innermost), got {list(codes.shape)} and "
+                                         f"{list(scales.shape)}")
+        return tuple(int(d) for d in codes.shape[:-1]), int(scales.shape[-1])
+    return elem_b, split(*a, elem_a, "A"), split(*b, elem_b, "B")
 
 
 def mx_gemm(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, out=None):
@@ -1277,24 +1293,9 @@ def mx_gemm(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, out=None)
     dimensions, or [n, ...] / [n, Kp / 32], which every batch shares.  -> fp32 [*batch, m, n], C[.., i, j] = sum over the Kp codes
     of a[.., i, :] * b[.., j, :] (pad codes included).  elem_b: B's element format when it is not A's.  A row that holds a 0xFF
     scale byte or an E4M3 NaN code makes its row (column) of C NaN.  out: an optional contiguous fp32 device tensor of that shape."""
-    elem_b = elem_a if elem_b is None else elem_b
-    for e in (elem_a, elem_b):
-        if e not in MX_ELEM:
-            raise _hip.DipoorletHipError(f"mx_gemm: elem must be 'mxfp8' or 'mxfp4', got {e!r}")
-    for t, name in ((a_codes, "a_codes"), (a_scales, "a_scales"), (b_codes, "b_codes"), (b_scales, "b_scales")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == a_codes.device):
-            raise _hip.DipoorletHipError(f"mx_gemm: {name} must be a contiguous uint8 ROCm device tensor on one device; dipoorlet_amd has no CPU path")
-
-    def split(codes, scales, elem, who):
-        per = 2 if elem == "mxfp4" else 1                      # codes to a byte
-        ok = codes.dim() >= 2 and scales.dim() == codes.dim() and tuple(scales.shape[:-1]) == tuple(codes.shape[:-1]) \
-            and int(codes.shape[-1]) * per == MX_BLOCK * int(scales.shape[-1])
-        if not ok:
-            raise _hip.DipoorletHipError(f"mx_gemm: {who} must be codes [..., rows, Kp{' / 2' if per == 2 else ''}] and scales [..., rows, Kp / "
-                                         f"{MX_BLOCK}] as mx_encode writes {elem} (K-innermost), got {list(codes.shape)} and {list(scales.shape)}")
-        return tuple(int(d) for d in codes.shape[:-2]), int(codes.shape[-2]), int(scales.shape[-1])
-    lead, m, nblk = split(a_codes, a_scales, elem_a, "A")
-    lead_b, n, nblk_b = split(b_codes, b_scales, elem_b, "B")
+    elem_b, ((*lead, m), nblk), ((*lead_b, n), nblk_b) = _mx_packed_pair(
+        "mx_gemm", (a_codes, a_scales, "..., rows"), (b_codes, b_scales, "..., rows"), elem_a, elem_b, lambda nd: nd >= 2, "Kp", "")
+    lead, lead_b = tuple(lead), tuple(lead_b)
     if nblk_b != nblk or lead_b not in ((), lead):
         raise _hip.DipoorletHipError(f"mx_gemm: A is {list(lead)} x [{m}, {nblk} blocks] and B {list(lead_b)} x [{n}, {nblk_b} blocks]: the two must "
                                      "have the same number of K-blocks, and B the leading dimensions of A or none")
@@ -1302,13 +1303,7 @@ def mx_gemm(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, out=None)
     for d in lead:
         batch *= d
     shape = lead + (m, n)
-    if out is None:
-        c = torch.empty(shape, dtype=torch.float32, device=a_codes.device)
-    else:
-        _require_cuda(out, "out")
-        if tuple(out.shape) != shape or out.device != a_codes.device:
-            raise _hip.DipoorletHipError(f"mx_gemm: out must have shape {list(shape)} and the codes' device")
-        c = out
+    c = _mx_out("mx_gemm", out, shape, a_codes.device, f"shape {list(shape)} and the codes' device")
     _hip.check(_hip.lib().dpl_mx_gemm(MX_ELEM[elem_a], MX_ELEM[elem_b], _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales), batch, m, n,
                                       MX_BLOCK * nblk, int(lead_b == lead and lead != ()), _ptr(c), _stream()), "dpl_mx_gemm")
     return c
@@ -1322,25 +1317,8 @@ def mx_conv(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, *, stride
     nothing is derived here; a tap outside the image contributes nothing.  -> fp32 [n, oh, ow, cout] (NHWC).  elem_b: B's element
     format when it is not A's.  An output is NaN if a block inside one of its in-image taps, or any block of its weight row, holds a
     0xFF scale byte or an E4M3 NaN code.  out: an optional contiguous fp32 device tensor of that shape."""
-    elem_b = elem_a if elem_b is None else elem_b
-    for e in (elem_a, elem_b):
-        if e not in MX_ELEM:
-            raise _hip.DipoorletHipError(f"mx_conv: elem must be 'mxfp8' or 'mxfp4', got {e!r}")
-    for t, name in ((a_codes, "a_codes"), (a_scales, "a_scales"), (b_codes, "b_codes"), (b_scales, "b_scales")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == a_codes.device):
-            raise _hip.DipoorletHipError(f"mx_conv: {name} must be a contiguous uint8 ROCm device tensor on one device; dipoorlet_amd has no CPU path")
-
-    def split(codes, scales, elem, who, dims):
-        per = 2 if elem == "mxfp4" else 1                      # codes to a byte
-        ok = codes.dim() == 4 and scales.dim() == 4 and tuple(scales.shape[:-1]) == tuple(codes.shape[:-1]) \
-            and int(codes.shape[-1]) * per == MX_BLOCK * int(scales.shape[-1])
-        if not ok:
-            raise _hip.DipoorletHipError(f"mx_conv: {who} must be codes [{dims}, Cp{' / 2' if per == 2 else ''}] and scales [{dims}, Cp / "
-                                         f"{MX_BLOCK}] as mx_encode writes {elem} along axis 1 (K-innermost), got {list(codes.shape)} and "
-                                         f"{list(scales.shape)}")
-        return tuple(int(d) for d in codes.shape[:-1]), int(scales.shape[-1])
-    (n, h, w), cb = split(a_codes, a_scales, elem_a, "A", "n, h, w")
-    (cout, kh, kw), cb_b = split(b_codes, b_scales, elem_b, "B", "cout, kh, kw")
+    elem_b, ((n, h, w), cb), ((cout, kh, kw), cb_b) = _mx_packed_pair(
+        "mx_conv", (a_codes, a_scales, "n, h, w"), (b_codes, b_scales, "cout, kh, kw"), elem_a, elem_b, lambda nd: nd == 4, "Cp", " along axis 1")
     if cb_b != cb:
         raise _hip.DipoorletHipError(f"mx_conv: A has {cb} channel block(s) a pixel and B {cb_b}: the two must have the same number of K-blocks a tap")
     geom = []
@@ -1352,13 +1330,7 @@ def mx_conv(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, *, stride
     if oh < 0 or ow < 0:
         raise _hip.DipoorletHipError(f"mx_conv: out_hw must not be negative, got {out_hw!r}")
     shape = (n, oh, ow, cout)
-    if out is None:
-        c = torch.empty(shape, dtype=torch.float32, device=a_codes.device)
-    else:
-        _require_cuda(out, "out")
-        if tuple(out.shape) != shape or out.device != a_codes.device:
-            raise _hip.DipoorletHipError(f"mx_conv: out must have shape {list(shape)} and the codes' device")
-        c = out
+    c = _mx_out("mx_conv", out, shape, a_codes.device, f"shape {list(shape)} and the codes' device")
     _hip.check(_hip.lib().dpl_mx_conv(MX_ELEM[elem_a], MX_ELEM[elem_b], _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales), n, h, w,
                                       MX_BLOCK * cb, cout, kh, kw, sh, sw, pt, pl, dh, dw, oh, ow, _ptr(c), _stream()), "dpl_mx_conv")
     return c

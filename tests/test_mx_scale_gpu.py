@@ -180,7 +180,8 @@ def test_rows_path(dev, k):
                                         ((2, 40, 17), -2),    # odd inner: one column to a lane
                                         ((1, 64, 64), -2),    # 32 slots of four columns / 128 blocks
                                         ((2, 33, 3), -2),     # a last block of one row
-                                        ((40, 6), 0)])        # outer == 1 along axis 0
+                                        ((40, 6), 0),         # outer == 1 along axis 0
+                                        ((2, 160, 68), 1)])   # the encoder's tiles of 4 K-blocks x 16 column groups: 5 and 17
 def test_cols_path(dev, shape, axis):
     outer, k, inner = (1,) + shape if len(shape) == 2 else shape
     x = _tensor(outer, k, inner, 100000 * outer + 1000 * k + inner).reshape(shape)
