@@ -1,11 +1,14 @@
-// What the two kernels on v_mfma_scale_f32_16x16x128_f8f6f4 share (mx_gemm_kernels.hip: k_mx_gemm; mx_conv_kernels.hip: k_mx_conv):
-// a lane's fragment of a K-INNERMOST packed MX operand, as dpl_mx_encode writes it.  The lane map (confirmed with
-// exact data): lane l supplies row (column) l & 15 and, as its scale, the E8M0 byte of K-block l >> 4 of the 128-wide step.  Codes:
-// E2M1 — the 32 K values of that same block, 16 bytes, byte j holding k = 2j in its low and k = 2j + 1 in its high nibble, the other
-// four dwords 0.  E4M3 — NOT that block: dwords 0 .. 3 are k = 16 (l >> 4) .. + 15 of the step and dwords 4 .. 7 k = 64 + 16 (l >> 4)
-// .. + 15, byte j of a run being k = j.  C/D: lane l holds column l & 15, rows 4 * (l >> 4) + reg.
+// The two kernels on v_mfma_scale_f32_16x16x128_f8f6f4 (mx_gemm_kernels.hip: k_mx_gemm; mx_conv_kernels.hip: k_mx_conv), defined once:
+// a lane's fragment of a packed MX operand as dpl_mx_encode writes it (mx_frag_load) and the 64 x 64 tile of C a workgroup computes
+// (mx_mfma_tile).  The kernels differ in how K-block kb of a row of A resolves to a block of the operand, and state only that; the
+// host side — argument checks, tile grid, dispatch — is mx_plan.hpp.  The lane map (confirmed with exact data): lane
+// l supplies row (column) l & 15 and, as its scale, the E8M0 byte of K-block l >> 4 of the 128-wide step.  Codes: E2M1 — the 32 K
+// values of that same block, 16 bytes, byte j holding k = 2j in its low and k = 2j + 1 in its high nibble, the other four dwords 0.
+// E4M3 — NOT that block: dwords 0 .. 3 are k = 16 (l >> 4) .. + 15 of the step and dwords 4 .. 7 k = 64 + 16 (l >> 4) .. + 15, byte
+// j of a run being k = j.  C/D: lane l holds column l & 15, rows 4 * (l >> 4) + reg.
 #pragma once
 #include "common.hpp"
+#include "mx_plan.hpp"
 
 namespace {
 
@@ -14,8 +17,6 @@ using u4g = __attribute__((ext_vector_type(4))) uint32_t;
 typedef const __attribute__((address_space(1))) u4g* gptr_u4g;
 typedef const __attribute__((address_space(1))) uint8_t* gptr_u8g;
 typedef __attribute__((address_space(1))) float* gptr_f32g;
-
-constexpr uint32_t kMxGemmTile = 64;      // rows and columns of C per workgroup
 
 template <int ELEM>
 struct GemmOperand {
@@ -34,41 +35,117 @@ struct GemmFrag {
     int scale;
 };
 
-// row: the operand's row this lane reads (already offset by the batch), live: it exists; kb0: the first K-block of the 128-wide
-// step; q = lane >> 4.  By the map above: the scale byte of block kb0 + q; E2M1 — the 16 bytes of that block; E4M3 — half q & 1
-// of block kb0 + (q >> 1) into the low four dwords and the same half of block kb0 + 2 + (q >> 1) into the high four.  A block past
-// Kp / 32 leaves zeros (scale byte 127).
-template <int ELEM>
-__device__ __forceinline__ GemmFrag gemm_load(const uint8_t* codes, const uint8_t* scales, uint64_t row, uint32_t nblk, uint32_t kb0, uint32_t q,
-                                              bool live, uint32_t& bad) {
+// A row resolves its K-blocks: at(kb, blk) -> is K-block kb of the row there?  blk: its index among the operand's blocks.
+// This one is the plain K-innermost row (B in both kernels, A of the GEMM): blk0 = row * nblk, the row already offset by the batch.
+struct MxRowBlocks {
+    uint64_t blk0;
+    uint32_t nblk;
+    bool live;                                // the row exists
+    __device__ __forceinline__ bool operator()(uint32_t kb, uint64_t& blk) const {
+        blk = blk0 + kb;
+        return live && kb < nblk;
+    }
+};
+
+// kb0: the first K-block of the 128-wide step; q = lane >> 4.  By the map above: the scale byte of block kb0 + q; E2M1 — the 16
+// bytes of that block; E4M3 — half q & 1 of block kb0 + (q >> 1) into the low four dwords and the same half of block
+// kb0 + 2 + (q >> 1) into the high four.  A block that is not there leaves zeros (scale byte 127), and nothing is loaded for it.
+// bad: the lane's NaN notes, a 0xFF scale byte or an E4M3 NaN code in what it loaded.
+template <int ELEM, class At>
+__device__ __forceinline__ GemmFrag mx_frag_load(const uint8_t* codes, const uint8_t* scales, const At& at, uint32_t kb0, uint32_t q, uint32_t& bad) {
     GemmFrag f;
     f.v = i8v{0, 0, 0, 0, 0, 0, 0, 0};
     f.scale = 127;
-    const uint64_t blk0 = row * nblk;
+    uint64_t blk;
     if constexpr (ELEM == DPL_MX_E4M3) {
-        const uint32_t b_lo = kb0 + (q >> 1), b_hi = b_lo + 2u, half = (q & 1u) * 16u;
-        if (live && b_lo < nblk) {
-            const u4g lo = *(gptr_u4g)(codes + (blk0 + b_lo) * GemmOperand<ELEM>::block_bytes + half);
-            f.v[0] = (int)lo.x, f.v[1] = (int)lo.y, f.v[2] = (int)lo.z, f.v[3] = (int)lo.w;
-            bad |= e4m3_nan_in(lo.x) | e4m3_nan_in(lo.y) | e4m3_nan_in(lo.z) | e4m3_nan_in(lo.w);
-        }
-        if (live && b_hi < nblk) {
-            const u4g hi = *(gptr_u4g)(codes + (blk0 + b_hi) * GemmOperand<ELEM>::block_bytes + half);
-            f.v[4] = (int)hi.x, f.v[5] = (int)hi.y, f.v[6] = (int)hi.z, f.v[7] = (int)hi.w;
-            bad |= e4m3_nan_in(hi.x) | e4m3_nan_in(hi.y) | e4m3_nan_in(hi.z) | e4m3_nan_in(hi.w);
-        }
-    } else {
-        if (live && kb0 + q < nblk) {
-            const u4g lo = *(gptr_u4g)(codes + (blk0 + kb0 + q) * GemmOperand<ELEM>::block_bytes);
-            f.v[0] = (int)lo.x, f.v[1] = (int)lo.y, f.v[2] = (int)lo.z, f.v[3] = (int)lo.w;
-        }
+#pragma unroll
+        for (int hi = 0; hi < 2; ++hi)
+            if (at(kb0 + 2u * hi + (q >> 1), blk)) {
+                const u4g w = *(gptr_u4g)(codes + blk * GemmOperand<ELEM>::block_bytes + (q & 1u) * 16u);
+                f.v[4 * hi] = (int)w.x, f.v[4 * hi + 1] = (int)w.y, f.v[4 * hi + 2] = (int)w.z, f.v[4 * hi + 3] = (int)w.w;
+                bad |= e4m3_nan_in(w.x) | e4m3_nan_in(w.y) | e4m3_nan_in(w.z) | e4m3_nan_in(w.w);
+            }
+    } else if (at(kb0 + q, blk)) {
+        const u4g w = *(gptr_u4g)(codes + blk * GemmOperand<ELEM>::block_bytes);
+        f.v[0] = (int)w.x, f.v[1] = (int)w.y, f.v[2] = (int)w.z, f.v[3] = (int)w.w;
     }
-    if (live && kb0 + q < nblk) {
-        const uint32_t sc = ((gptr_u8g)scales)[blk0 + kb0 + q];
+    if (at(kb0 + q, blk)) {
+        const uint32_t sc = ((gptr_u8g)scales)[blk];
         bad |= sc == 0xFFu ? 1u : 0u;
         f.scale = (int)sc;
     }
     return f;
+}
+
+// A workgroup's 64 x 64 tile of C fp32 [batch, m, n] = A [batch, m, nblk blocks] x B [batch or 1, n, nblk blocks]: 256 threads, each
+// wave 32 x 32 as 2 x 2 instruction tiles, four accumulators, operands straight from global memory (L2), no LDS.  row_a(bi, r) ->
+// the resolver of row r (which may be >= m: it is then not live) of A in batch bi.  Rows >= m, columns >= n and the K-blocks past
+// nblk of the last step are masked.  The NaN rule is the kernels' own, whatever the instruction does with such bytes: the four
+// lanes of a row combine their notes after the K loop, and every C of that row of A (column of C for B) is stored as NaN.
+template <int EA, int EB, class RowA>
+__device__ __forceinline__ void mx_mfma_tile(const uint8_t* a_codes, const uint8_t* a_scales, const uint8_t* b_codes, const uint8_t* b_scales, float* c,
+                                             uint32_t m, uint32_t n, uint32_t nblk, uint32_t tiles_m, uint32_t tiles_n, bool b_batched, RowA row_a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    using f4v = __attribute__((ext_vector_type(4))) float;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t per_batch = tiles_m * tiles_n;                       // (the grid is below 2^31)
+    const uint32_t bi = blockIdx.x / per_batch, t = blockIdx.x - bi * per_batch;
+    const uint32_t tm = t / tiles_n, tn = t - tm * tiles_n;
+    const uint64_t row0 = (uint64_t)tm * kMxGemmTile + (wave >> 1) * 32u, col0 = (uint64_t)tn * kMxGemmTile + (wave & 1u) * 32u;
+    const uint32_t r16 = lane & 15u, q = lane >> 4;
+
+    const uint64_t r_lo = row0 + r16, c_lo = col0 + r16, b0 = b_batched ? (uint64_t)bi * n : 0ull;
+    const decltype(row_a(bi, r_lo)) a_at[2] = {row_a(bi, r_lo), row_a(bi, r_lo + 16u)};
+    const MxRowBlocks b_at[2] = {{(b0 + c_lo) * nblk, nblk, c_lo < n}, {(b0 + c_lo + 16u) * nblk, nblk, c_lo + 16u < n}};
+    f4v acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = f4v{0.f, 0.f, 0.f, 0.f};
+    uint32_t a_bad[2] = {0u, 0u}, b_bad[2] = {0u, 0u};
+
+    for (uint32_t kb0 = 0; kb0 < nblk; kb0 += 4u) {
+        GemmFrag fa[2], fb[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            fa[i] = mx_frag_load<EA>(a_codes, a_scales, a_at[i], kb0, q, a_bad[i]);
+            fb[i] = mx_frag_load<EB>(b_codes, b_scales, b_at[i], kb0, q, b_bad[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[i].v, fb[j].v, acc[i][j], GemmOperand<EA>::fmt, GemmOperand<EB>::fmt, 0,
+                                                                             fa[i].scale, 0, fb[j].scale);
+    }
+
+    // the notes of the four lanes of a row (column); every lane of the wave is here
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        a_bad[i] |= (uint32_t)__shfl_xor((int)a_bad[i], 16, kWave);
+        a_bad[i] |= (uint32_t)__shfl_xor((int)a_bad[i], 32, kWave);
+        b_bad[i] |= (uint32_t)__shfl_xor((int)b_bad[i], 16, kWave);
+        b_bad[i] |= (uint32_t)__shfl_xor((int)b_bad[i], 32, kWave);
+    }
+    // C/D: lane l holds column l & 15 and rows 4 * (l >> 4) + reg of its 16 x 16 tile; row r's note sits in lanes r, r + 16, ...
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const uint32_t rr = 4u * q + (uint32_t)reg;
+            const uint32_t row_bad = (uint32_t)__shfl((int)a_bad[i], (int)rr, kWave);
+            const uint64_t r = row0 + 16u * i + rr;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const uint64_t cc = col0 + 16u * j + r16;
+                if (r < m && cc < n) {
+                    const float v = (row_bad | b_bad[j]) ? __uint_as_float(0x7FC00000u) : acc[i][j][reg];
+                    ((gptr_f32g)c)[((uint64_t)bi * m + r) * n + cc] = v;
+                }
+            }
+        }
+    }
+#endif
 }
 
 }  // namespace

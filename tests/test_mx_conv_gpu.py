@@ -151,17 +151,17 @@ def test_exact_class_at_every_masking_shape(dev, elem_a, elem_b):
 
 
 # ------------------------------------------------------------------------------------------------ 3. 1 x 1 is the GEMM
-@pytest.mark.parametrize("elem", ELEMS)
-def test_one_by_one_is_mx_gemm(dev, elem):
+@pytest.mark.parametrize("elem_a,elem_b", PAIRS)
+def test_one_by_one_is_mx_gemm(dev, elem_a, elem_b):
     from dipoorlet_amd import ops
     rng = np.random.default_rng(31)
     x = torch.from_numpy(rng.standard_normal((2, 70, 9, 8)).astype(np.float32)).to(dev)
     wt = torch.from_numpy(rng.standard_normal((72, 70, 1, 1)).astype(np.float32)).to(dev)
-    ac, a_s = ops.mx_encode(x, 1, elem)
-    bc, b_s = ops.mx_encode(wt, 1, elem)
+    ac, a_s = ops.mx_encode(x, 1, elem_a)
+    bc, b_s = ops.mx_encode(wt, 1, elem_b)
     assert tuple(a_s.shape) == (2, 9, 8, 3) and tuple(b_s.shape) == (72, 1, 1, 3)
-    got = ops.mx_conv(ac, a_s, bc, b_s, elem, strides=(1, 1), pads=(0, 0), dilations=(1, 1), out_hw=(9, 8))
-    want = ops.mx_gemm(ac.reshape(2, 72, -1), a_s.reshape(2, 72, -1), bc.reshape(72, -1), b_s.reshape(72, -1), elem)
+    got = ops.mx_conv(ac, a_s, bc, b_s, elem_a, elem_b, strides=(1, 1), pads=(0, 0), dilations=(1, 1), out_hw=(9, 8))
+    want = ops.mx_gemm(ac.reshape(2, 72, -1), a_s.reshape(2, 72, -1), bc.reshape(72, -1), b_s.reshape(72, -1), elem_a, elem_b)
     assert tuple(got.shape) == (2, 9, 8, 72) and torch.isfinite(got).all() and (got != 0).any()
     assert torch.equal(got.reshape(2, 72, 72).view(torch.int32), want.view(torch.int32))
 
