@@ -1,9 +1,9 @@
 """`python -m dipoorlet_amd -M model.onnx -I calib_dir -N 1024 -A hist -D trt` — the reference's CLI
-(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, `--mx_rotate`, a block-Hadamard rotation of those operands, `--mx_pack`, the constant ones as packed element codes and E8M0 scales, `--mx_verify`, those bytes multiplied on the block-scaled matrix instruction and compared with the fake-quantised graph, `--mx_scale_search`, error-minimising block scales for the constant ones, `--gptq`, Hessian-compensated weight rounding, and `--mx_gptq`, the same on the block-scaled grids, are this project's additions).
+(dipoorlet/__main__.py:23-161) over the MI355X calibration core (`-A kl`, the entropy search, `-A qmse`, the quantisation-MSE search on the platform's grid, `-D ocp_fp8`, static OCP FP8 E4M3 scales, `--mx`, OCP Microscaling on MatMul / Gemm operands, `--mx_rotate`, a block-Hadamard rotation of those operands, `--mx_pack`, the constant ones as packed element codes and E8M0 scales, `--mx_verify`, those bytes multiplied on the block-scaled matrix instruction and compared with the fake-quantised graph, `--mx_scale_search`, error-minimising block scales for the constant ones, `--gptq`, Hessian-compensated weight rounding, `--mx_gptq`, the same on the block-scaled grids, and `--mx_mixed`, MXFP4 or MXFP8 per node under a weight-bit budget, are this project's additions).
 
 Same flags; same phases where they are in scope: load model -> tensor calibration (sharded over ranks)
 -> per-rank clip JSON -> rank-0 reduce -> load -> profiling (cosine similarity of the fake-quantised
-model, optional) -> weight transforms (--smooth, --mx_rotate, --bc, --we, --update_bn, --adaround, --brecq [--drop], --sparse, --gptq, --mx_gptq) -> platform deploy file.
+model, optional) -> weight transforms (--smooth, --mx_rotate, --mx_mixed, --bc, --we, --update_bn, --adaround, --brecq [--drop], --sparse, --gptq, --mx_gptq) -> platform deploy file.
 Extra flags: --calib_batch, --resident_gb, --merge {allreduce,reference}, --skip_profiling, --timing_json.
 """
 import argparse
@@ -91,6 +91,16 @@ def build_parser():
                         "is logged with its reason.  --mx_scale_search, --mx_pack and --mx_verify cover these operands as they cover a "
                         "MatMul's (--mx_verify multiplies them on the block-scaled matrix instruction: ops.mx_conv); --mx_rotate leaves "
                         "Convs alone.  Adds \"conv\": {\"nodes\", \"left\"} to ocp_mx_blocks.json.  Not with --mx_gptq")
+    p.add_argument("--mx_mixed", type=float, default=None, metavar="BITS",
+                   help="(not in the reference; with --mx mxfp4 only) MXFP4 or MXFP8 per node under a weight-bit budget: BITS in [4, 8] is "
+                        "the average element bits allowed over the weights of the candidate nodes — every Gemm (no transA, alpha = beta = "
+                        "1, a bias absent or [n]) and every MatMul whose right operand is a constant 2-D weight that nothing else reads.  "
+                        "Over the first --calib_batch images each candidate's product is formed in both formats on the block-scaled "
+                        "matrix instruction and held against its fp32 output (ops.mx_gemm_err); the nodes that gain most per weight bit "
+                        "are promoted, both operands, to mxfp8 while the budget lasts.  Runs after --smooth / --mx_rotate and before "
+                        "--bc; everything else stays at mxfp4 and is logged with its reason.  Writes mx_mixed_report.json; "
+                        "ocp_mx_blocks.json, ocp_mx_weights.json, mx_scale_report.json and mx_verify_report.json then say \"format\": "
+                        "\"mixed\" and name each entry's own format")
     p.add_argument("--gptq_block", type=int, default=128,
                    help="--gptq (not in the reference; every platform, -D ocp_fp8 included): round every Conv (group 1) / Gemm weight column "
                         "by column onto the platform's weight grid, pushing each column's rounding error onto the columns not yet rounded "
@@ -171,6 +181,16 @@ def check_args(args):
         if getattr(args, "mx_gptq", False):
             raise ValueError("--mx_conv and --mx_gptq cannot be combined: the MX GPTQ kernel wants a weight's blocks contiguous along K of "
                              "[N, K], and a Conv weight's channel blocks are strided there (not built)")
+    if getattr(args, "mx_mixed", None) is not None:
+        if not getattr(args, "mx", None):
+            raise ValueError("--mx_mixed needs --mx mxfp4: it promotes nodes of a block-scaled graph from the base format mxfp4 to "
+                             "mxfp8, and a static grid has neither")
+        if args.mx != "mxfp4":
+            raise ValueError(f"--mx_mixed is not supported with --mx {args.mx}: the base format is mxfp4 and the budget buys mxfp8 "
+                             "where it helps most; with mxfp8 everywhere there is nothing to promote to")
+        if not 4.0 <= args.mx_mixed <= 8.0:      # (a NaN too)
+            raise ValueError(f"--mx_mixed must lie in [4, 8], the average element bits of mxfp4 everywhere and of mxfp8 everywhere, "
+                             f"got {args.mx_mixed}")
     if getattr(args, "mx_verify", False) and not getattr(args, "mx_pack", False):
         raise ValueError("--mx_verify needs --mx_pack: it reads ocp_mx_weights.bin back and multiplies those bytes on the block-scaled "
                          "matrix instruction, and without --mx_pack there is no such file")

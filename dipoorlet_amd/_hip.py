@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPL_LIB: another build of the same sources (the host-sanitizer build of scripts/asan_host_check.sh); never a different code path
 LIB_PATH = os.environ.get("DPL_LIB") or os.path.join(_HERE, "csrc", "libdipoorlet_hip.so")
 
-ABI_VERSION = 34
+ABI_VERSION = 35
 MAX_BINS = 16384
 GRID_UNIFORM, GRID_E4M3 = 0, 1          # DPL_GRID_*: the grids of dpl_hist_qmse
 HIST_SPEC_MAX_TENSORS = 2048
@@ -143,6 +143,7 @@ SIGNATURES = {
     "dpl_fake_quant_mx_scaled": (C.c_int, [_I32, _P, _P, _U64, _U64, _U64, _P, _P]),
     "dpl_mx_encode_scaled": (C.c_int, [_I32, _P, _U64, _U64, _U64, _P, _P, _P, _P]),
     "dpl_mx_gemm": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _U64, _U64, _U64, _U64, _I32, _P, _P]),
+    "dpl_mx_gemm_err": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _U64, _U64, _U64, _U64, _I32, _P, _P, _P, _P]),
     "dpl_mx_conv": (C.c_int, [_I32, _I32, _P, _P, _P, _P] + [_I64] * 15 + [_P, _P]),
     "dpl_gptq_block": (C.c_int, [_P, _I64, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
     "dpl_gptq_mx_block": (C.c_int, [_I32, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _P]),

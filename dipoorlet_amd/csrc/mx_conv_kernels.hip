@@ -48,10 +48,10 @@ template <int EA, int EB>
 __global__ __launch_bounds__(kBlock) void k_mx_conv(const uint8_t* a_codes, const uint8_t* a_scales, const uint8_t* b_codes, const uint8_t* b_scales,
                                                     float* c, ConvGeom g) {
     const uint32_t m = g.oh * g.ow;                                     // (below 2^31)
-    mx_mfma_tile<EA, EB>(a_codes, a_scales, b_codes, b_scales, c, m, g.cout, g.nblk, g.tiles_m, g.tiles_n, false, [&](uint32_t bi, uint64_t r) {
+    mx_mfma_tile<EA, EB>(a_codes, a_scales, b_codes, b_scales, m, g.cout, g.nblk, g.tiles_m, g.tiles_n, false, [&](uint32_t bi, uint64_t r) {
         const uint32_t rr = r < m ? (uint32_t)r : 0u, oy = rr / g.ow, ox = rr - oy * g.ow;
         return ConvRowBlocks{g, bi, (int64_t)oy * g.sh - (int64_t)g.pt, (int64_t)ox * g.sw - (int64_t)g.pl, r < m};
-    });
+    }, MxStoreC{c, m, g.cout});
 }
 
 }  // namespace

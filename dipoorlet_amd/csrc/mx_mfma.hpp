@@ -1,6 +1,7 @@
-// The two kernels on v_mfma_scale_f32_16x16x128_f8f6f4 (mx_gemm_kernels.hip: k_mx_gemm; mx_conv_kernels.hip: k_mx_conv), defined once:
-// a lane's fragment of a packed MX operand as dpl_mx_encode writes it (mx_frag_load) and the 64 x 64 tile of C a workgroup computes
-// (mx_mfma_tile).  The kernels differ in how K-block kb of a row of A resolves to a block of the operand, and state only that; the
+// The kernels on v_mfma_scale_f32_16x16x128_f8f6f4 (mx_gemm_kernels.hip: k_mx_gemm, k_mx_gemm_err; mx_conv_kernels.hip: k_mx_conv),
+// defined once: a lane's fragment of a packed MX operand as dpl_mx_encode writes it (mx_frag_load) and the 64 x 64 tile of C a
+// workgroup computes (mx_mfma_tile).  The kernels differ in how K-block kb of a row of A resolves to a block of the operand and in
+// what becomes of a finished element of C (the epilogue: MxStoreC writes it, k_mx_gemm_err adds its error up), and state only that; the
 // host side — argument checks, tile grid, dispatch — is mx_plan.hpp.  The lane map (confirmed with exact data): lane
 // l supplies row (column) l & 15 and, as its scale, the E8M0 byte of K-block l >> 4 of the 128-wide step.  Codes: E2M1 — the 32 K
 // values of that same block, 16 bytes, byte j holding k = 2j in its low and k = 2j + 1 in its high nibble, the other four dwords 0.
@@ -77,14 +78,26 @@ __device__ __forceinline__ GemmFrag mx_frag_load(const uint8_t* codes, const uin
     return f;
 }
 
+// The epilogue that stores C fp32 [batch, m, n].
+struct MxStoreC {
+    float* c;
+    uint32_t m, n;
+    __device__ __forceinline__ void operator()(uint32_t bi, uint64_t r, uint64_t cc, bool live, float v) const {
+        if (live) ((gptr_f32g)c)[((uint64_t)bi * m + r) * n + cc] = v;
+    }
+};
+
 // A workgroup's 64 x 64 tile of C fp32 [batch, m, n] = A [batch, m, nblk blocks] x B [batch or 1, n, nblk blocks]: 256 threads, each
 // wave 32 x 32 as 2 x 2 instruction tiles, four accumulators, operands straight from global memory (L2), no LDS.  row_a(bi, r) ->
 // the resolver of row r (which may be >= m: it is then not live) of A in batch bi.  Rows >= m, columns >= n and the K-blocks past
 // nblk of the last step are masked.  The NaN rule is the kernels' own, whatever the instruction does with such bytes: the four
-// lanes of a row combine their notes after the K loop, and every C of that row of A (column of C for B) is stored as NaN.
-template <int EA, int EB, class RowA>
-__device__ __forceinline__ void mx_mfma_tile(const uint8_t* a_codes, const uint8_t* a_scales, const uint8_t* b_codes, const uint8_t* b_scales, float* c,
-                                             uint32_t m, uint32_t n, uint32_t nblk, uint32_t tiles_m, uint32_t tiles_n, bool b_batched, RowA row_a) {
+// lanes of a row combine their notes after the K loop, and every C of that row of A (column of C for B) is NaN.
+// epi(bi, r, cc, live, v): the epilogue, called by every lane for each of its 16 elements in the order (i, reg, j) — row r =
+// 16 i + 4 (lane >> 4) + reg and column cc = 16 j + (lane & 15) of the wave's quadrant —, live: r < m and cc < n, v: the element.
+template <int EA, int EB, class RowA, class Epi>
+__device__ __forceinline__ void mx_mfma_tile(const uint8_t* a_codes, const uint8_t* a_scales, const uint8_t* b_codes, const uint8_t* b_scales,
+                                             uint32_t m, uint32_t n, uint32_t nblk, uint32_t tiles_m, uint32_t tiles_n, bool b_batched, RowA row_a,
+                                             Epi&& epi) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using f4v = __attribute__((ext_vector_type(4))) float;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -138,10 +151,7 @@ __device__ __forceinline__ void mx_mfma_tile(const uint8_t* a_codes, const uint8
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const uint64_t cc = col0 + 16u * j + r16;
-                if (r < m && cc < n) {
-                    const float v = (row_bad | b_bad[j]) ? __uint_as_float(0x7FC00000u) : acc[i][j][reg];
-                    ((gptr_f32g)c)[((uint64_t)bi * m + r) * n + cc] = v;
-                }
+                epi(bi, r, cc, r < m && cc < n, (row_bad | b_bad[j]) ? __uint_as_float(0x7FC00000u) : acc[i][j][reg]);
             }
         }
     }

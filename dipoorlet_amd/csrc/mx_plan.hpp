@@ -3,7 +3,7 @@
 // along K (mx_plan), and the way from (elem, inner == 1, vec) to a kernel instantiation (mx_dispatch).  And of the two kernels on the
 // block-scaled MFMA (mx_gemm_kernels.hip, mx_conv_kernels.hip): what they hold a pair of packed operands to (mx_pair_elems,
 // mx_pair_null, mx_pair_aligned), their grid of 64 x 64 tiles (mx_tiles), each entry point's rules in their order (mx_gemm_check,
-// mx_conv_check) and the way from (elem_a, elem_b) to an instantiation (mx_pair_dispatch).  A wrong value here is an out-of-range
+// mx_gemm_err_check, mx_conv_check) and the way from (elem_a, elem_b) to an instantiation (mx_pair_dispatch).  A wrong value here is an out-of-range
 // address in a kernel, so a plain C++ compiler can build this: tests/mx_plan_host.cpp is a stand-alone program that runs it under
 // the address and undefined-behaviour sanitizers (tests/test_mx_plan_host.py).
 #pragma once
@@ -90,9 +90,11 @@ inline int mx_pair_elems(const char* who, const MxPair& o) {
     const auto known = [](int32_t e) { return e == DPL_MX_E4M3 || e == DPL_MX_E2M1; };
     return known(o.elem_a) && known(o.elem_b) ? 0 : mx_fail(who, "elem_a and elem_b must be DPL_MX_E4M3 or DPL_MX_E2M1");
 }
+inline bool mx_pair_operands(const MxPair& o) {
+    return o.a_codes != nullptr && o.a_scales != nullptr && o.b_codes != nullptr && o.b_scales != nullptr;
+}
 inline int mx_pair_null(const char* who, const MxPair& o) {
-    const bool all = o.a_codes != nullptr && o.a_scales != nullptr && o.b_codes != nullptr && o.b_scales != nullptr && o.c != nullptr;
-    return all ? 0 : mx_fail(who, "the codes, the scales and d_c must not be null");
+    return mx_pair_operands(o) && o.c != nullptr ? 0 : mx_fail(who, "the codes, the scales and d_c must not be null");
 }
 inline int mx_pair_aligned(const char* who, const MxPair& o) {
     if ((((uintptr_t)o.a_codes | (uintptr_t)o.b_codes) & 15u) == 0u) return 0;
@@ -116,15 +118,31 @@ inline int mx_tiles(MxTiles& t, const char* who, uint64_t batch, uint64_t m, uin
     return 0;
 }
 
+// The sizes of a [batch, m, k] x [.., n, k] product, none of them 0 -> 0 or the refusal: m, n and k in range, and the padded
+// operands, 32 * ceil(k / 32) <= k + 31 codes a row, and the [batch, m, n] array (C, or the reference) indexable.
+inline int mx_gemm_sizes(const char* who, uint64_t batch, uint64_t m, uint64_t n, uint64_t k) {
+    if (m > 0x7FFFFFFFull || n > 0x7FFFFFFFull || k > 0x7FFFFFFFull) return mx_fail(who, "m, n and k must be in [1, 2^31)");
+    const uint64_t kp = 32ull * ((k + 31u) / 32u), big = m > n ? m : n;
+    if (batch > (0x7FFFFFFFFFFFFFFFull / kp) / big || batch > (0x7FFFFFFFFFFFFFFFull / m) / n) return mx_fail(who, "tensor too large");
+    return 0;
+}
+
 // dpl_mx_gemm's argument rules in their order.  -> true: the call is over and rc its result (0: nothing to do).
 inline bool mx_gemm_check(int& rc, MxTiles& t, const MxPair& o, uint64_t batch, uint64_t m, uint64_t n, uint64_t k) {
     const char* who = "dpl_mx_gemm";
     if ((rc = mx_pair_elems(who, o)) != 0 || batch == 0 || m == 0 || n == 0 || k == 0 || (rc = mx_pair_null(who, o)) != 0) return true;
-    if (m > 0x7FFFFFFFull || n > 0x7FFFFFFFull || k > 0x7FFFFFFFull) return (rc = mx_fail(who, "m, n and k must be in [1, 2^31)")), true;
-    // (the padded operands, 32 * ceil(k / 32) <= k + 31 codes a row, and C must be indexable)
-    const uint64_t kp = 32ull * ((k + 31u) / 32u), big = m > n ? m : n;
-    if (batch > (0x7FFFFFFFFFFFFFFFull / kp) / big || batch > (0x7FFFFFFFFFFFFFFFull / m) / n) return (rc = mx_fail(who, "tensor too large")), true;
-    return (rc = mx_pair_aligned(who, o)) != 0 || (rc = mx_tiles(t, who, batch, m, n)) != 0;
+    return (rc = mx_gemm_sizes(who, batch, m, n, k)) != 0 || (rc = mx_pair_aligned(who, o)) != 0 || (rc = mx_tiles(t, who, batch, m, n)) != 0;
+}
+
+// dpl_mx_gemm_err's: dpl_mx_gemm's with the reference and the partial sums where that has C (o.c is not looked at).  The partial
+// sums, two doubles a workgroup, are indexable wherever the grid is.
+inline bool mx_gemm_err_check(int& rc, MxTiles& t, const MxPair& o, const float* ref, const double* part, uint64_t batch, uint64_t m, uint64_t n,
+                              uint64_t k) {
+    const char* who = "dpl_mx_gemm_err";
+    if ((rc = mx_pair_elems(who, o)) != 0 || batch == 0 || m == 0 || n == 0 || k == 0) return true;
+    if (!mx_pair_operands(o) || ref == nullptr || part == nullptr)
+        return (rc = mx_fail(who, "the codes, the scales, d_ref and d_part must not be null")), true;
+    return (rc = mx_gemm_sizes(who, batch, m, n, k)) != 0 || (rc = mx_pair_aligned(who, o)) != 0 || (rc = mx_tiles(t, who, batch, m, n)) != 0;
 }
 
 // acc *= f unless that passes limit

@@ -118,13 +118,16 @@ def gen_ocp_mx_blocks(graph, act_clip_val, weight_clip_val, args):
     "weight_scales": "search" and, per constant tensor, "scales": the uint8 initializer of quant_model.onnx that holds its blocks'
     E8M0 bytes (the second input of its MXQuantizeDequantize node) — and mx_scale_report.json (gen_mx_scale_report).  With --mx_conv
     also "conv": {"nodes": [...], "left": {node name: reason}} — the Convs whose two operands are block-scaled along axis 1, and those
-    that keep their static nodes, each logged here once with its reason."""
+    that keep their static nodes, each logged here once with its reason.  With --mx_mixed "format" is "mixed" and every tensor's entry
+    names its own "format" (its node's), here and in ocp_mx_weights.json and mx_scale_report.json."""
     from .quantize import MX_BLOCK, quant_graph
     clip = {k: [np.copy(v[0]), np.copy(v[1])] for k, v in {**act_clip_val, **weight_clip_val}.items()}
     graph_q, _ = quant_graph(graph, clip, args)
-    tensors = {q.tensor_name + q.suffix: {"axis": int(q.block_axis), "constant": q.tensor_name in graph.initializer}
+    mixed = getattr(args, "mx_mixed", None) is not None
+    tensors = {q.tensor_name + q.suffix: {"axis": int(q.block_axis), "constant": q.tensor_name in graph.initializer,
+                                          **({"format": q.format.elem} if mixed else {})}
                for q in graph_q._qdq.values() if q.is_mx}
-    res = {"format": args.mx, "block_size": MX_BLOCK, "tensors": tensors}
+    res = {"format": "mixed" if mixed else args.mx, "block_size": MX_BLOCK, "tensors": tensors}
     if getattr(args, "mx_scale_search", False):
         res["weight_scales"] = "search"
         searched = [q for q in graph_q._qdq.values() if q.is_mx and q.mx_scales is not None]
@@ -154,19 +157,23 @@ def gen_mx_scale_report(graph, qnodes, args):
 
     from . import ops
     dev = torch.device("cuda", torch.cuda.current_device())
+    mixed = getattr(args, "mx_mixed", None) is not None
     tensors = {}
     for q in qnodes:
         w = torch.from_numpy(np.ascontiguousarray(graph.get_initializer(q.tensor_name), dtype=np.float32)).to(dev)
         axis = int(q.block_axis) % w.dim()
         floor = torch.empty(q.mx_scales.shape, dtype=torch.uint8, device=dev)
-        ops.fake_quant_mx(w, axis, args.mx, scales=floor)
+        elem = q.format.elem                # (the node's own format: --mx_mixed)
+        ops.fake_quant_mx(w, axis, elem, scales=floor)
         err = torch.empty(tuple(q.mx_scales.shape) + (2,), dtype=torch.float64, device=dev)
-        chosen = ops.mx_scale_search(w, axis, args.mx, err=err)
+        chosen = ops.mx_scale_search(w, axis, elem, err=err)
         if not np.array_equal(chosen.cpu().numpy(), q.mx_scales):
             raise RuntimeError(f"--mx_scale_search: the scales of {q.tensor_name} in the graph are not those of its initializer")
         tensors[q.tensor_name + q.suffix] = {"blocks": int(chosen.numel()), "moved_up": int((chosen != floor).sum()),
                                              "err_floor": float(err[..., 0].sum()), "err_chosen": float(err[..., 1].sum())}
-    _dump({"format": args.mx, "tensors": tensors}, args, "mx_scale_report.json")
+        if mixed:
+            tensors[q.tensor_name + q.suffix]["format"] = elem
+    _dump({"format": "mixed" if mixed else args.mx, "tensors": tensors}, args, "mx_scale_report.json")
 
 
 MX_WEIGHTS_ALIGN = 64     # every section of ocp_mx_weights.bin starts on a multiple of this, zero fill in between
@@ -180,13 +187,15 @@ def gen_ocp_mx_weights(graph, qnodes, args):
       ocp_mx_weights.json   {"format", "block_size": 32, "layout": "k_innermost", "tensors": {key: {"initializer", "shape", "axis",
                             "k", "k_padded", "codes": {"offset", "nbytes", "shape"}, "scales": {"offset", "nbytes", "shape"}}}}
     Both arrays are K-innermost: the block axis is moved to the end and padded with code 0 to k_padded = 32 * ceil(k / 32); mxfp4
-    holds two codes to a byte, the even index along k in the low nibble.  A tensor whose node carries searched scales
+    holds two codes to a byte, the even index along k in the low nibble.  The element format is the tensor's node's (--mx_mixed: the
+    file then says "format": "mixed" and every entry its own "format").  A tensor whose node carries searched scales
     (--mx_scale_search) is encoded under those bytes (ops.mx_encode_scaled; tests/mx_scale_model.py)."""
     import torch
 
     from . import ops
     from .quantize import MX_BLOCK
     dev = torch.device("cuda", torch.cuda.current_device())
+    mixed = getattr(args, "mx_mixed", None) is not None
     tensors, offset = {}, 0
     with open(os.path.join(args.output_dir, "ocp_mx_weights.bin"), "wb") as f:
         def section(t):
@@ -201,15 +210,18 @@ def gen_ocp_mx_weights(graph, qnodes, args):
         for q in qnodes:
             w = np.ascontiguousarray(graph.get_initializer(q.tensor_name), dtype=np.float32)
             axis = int(q.block_axis) % w.ndim
+            elem = q.format.elem            # (the node's own format: --mx_mixed)
             if q.mx_scales is not None:
-                codes, scales = ops.mx_encode_scaled(torch.from_numpy(w).to(dev), axis, args.mx, torch.from_numpy(q.mx_scales).to(dev))
+                codes, scales = ops.mx_encode_scaled(torch.from_numpy(w).to(dev), axis, elem, torch.from_numpy(q.mx_scales).to(dev))
             else:
-                codes, scales = ops.mx_encode(torch.from_numpy(w).to(dev), axis, args.mx)
+                codes, scales = ops.mx_encode(torch.from_numpy(w).to(dev), axis, elem)
             k = int(w.shape[axis])
             tensors[q.tensor_name + q.suffix] = {"initializer": q.tensor_name, "shape": [int(d) for d in w.shape], "axis": int(q.block_axis),
                                                  "k": k, "k_padded": MX_BLOCK * -(-k // MX_BLOCK), "codes": section(codes),
                                                  "scales": section(scales)}
-    _dump({"format": args.mx, "block_size": MX_BLOCK, "layout": "k_innermost", "tensors": tensors}, args, "ocp_mx_weights.json")
+            if mixed:
+                tensors[q.tensor_name + q.suffix]["format"] = elem
+    _dump({"format": "mixed" if mixed else args.mx, "block_size": MX_BLOCK, "layout": "k_innermost", "tensors": tensors}, args, "ocp_mx_weights.json")
 
 
 def to_deploy(graph, act_clip_val, weight_clip_val, args, **kwargs):

@@ -14,7 +14,9 @@ product of dequantised values.  The bound is that of ops.mx_gemm against its def
 plus, for a Gemm with a bias, the same factor on |beta . C|.  The factor is 1 for mxfp4, where the instruction adds exact products
 (measured: no error).  For mxfp8 it is twice the worst ratio measured on random data (tests/test_mx_gemm_gpu.py test 4): the
 instruction truncates the E4M3 products of every run of 8 consecutive k to 2^-14 of the run's largest before it adds them, which
-loses up to 7 * 2^-14 * S whatever Kp is.  -> mx_verify_report.json; no other file changes.
+loses up to 7 * 2^-14 * S whatever Kp is.  The element format is the node's own, read from its two MX nodes (they
+agree; under --mx_mixed ocp_mx_weights.json says "mixed", every tensor's entry names its format, and so does every node's entry of
+the report), and the factor that format's.  -> mx_verify_report.json; no other file changes.
 
 `--mx_conv`: a Conv whose two inputs are MX outputs goes through ops.mx_conv the same way — the activation encoded along axis 1 on
 the device (NHWC codes), the weight's [cout, kh, kw, Cp ...] sections of ocp_mx_weights.bin as they stand, the explicit pads from
@@ -54,7 +56,7 @@ def mx_verify(graph, act_clip_val, weight_clip_val, args):
     with open(os.path.join(args.output_dir, "ocp_mx_weights.json")) as f:
         meta = json.load(f)
     blob = np.fromfile(os.path.join(args.output_dir, "ocp_mx_weights.bin"), dtype=np.uint8)
-    elem = meta["format"]
+    mixed = meta["format"] == "mixed"       # (--mx_mixed) every tensor's entry then names its own format
     images = max(1, min(int(args.data_num), int(getattr(args, "calib_batch", None) or 16)))
     cache = ActivationCache(graph_q, args, 0, images)
     sess = cache._session()
@@ -65,12 +67,14 @@ def mx_verify(graph, act_clip_val, weight_clip_val, args):
     def activation(name):
         return torch.cat(list(cache.chunks(name))).contiguous()
 
-    def operand(q, last_two):
+    def operand(q, last_two, elem):
         """(codes, scales, key or None) of the operand behind MX node q, K-innermost: [*lead, rows, Kp ...]."""
         if q.tensor_name in graph_q.initializer:
             key = q.tensor_name + q.suffix
             if key not in meta["tensors"]:
                 raise KeyError(f"{key} is not in ocp_mx_weights.json")
+            if meta["tensors"][key].get("format", meta["format"]) != elem:
+                raise ValueError(f"{key} is {meta['tensors'][key].get('format', meta['format'])} in ocp_mx_weights.json and {elem} in the graph")
             return (*_packed_from_file(meta["tensors"][key], blob, dev), key, int(meta["tensors"][key]["k"]))
         x = activation(q.tensor_name)
         axis = int(q.block_axis)
@@ -78,7 +82,7 @@ def mx_verify(graph, act_clip_val, weight_clip_val, args):
             raise ValueError(f"blocks along axis {axis} of a tensor of {x.dim()} dimension(s)")
         return (*ops.mx_encode(x, last_two, elem), None, int(x.shape[last_two]))
 
-    def conv(node, qa, qb):
+    def conv(node, qa, qb, elem):
         """A Conv (`--mx_conv`) whose two inputs are MX outputs, blocked along axis 1 -> its report entry."""
         from .executor import conv_padding
         if qa.tensor_name in graph_q.initializer or qb.tensor_name not in graph_q.initializer:
@@ -89,7 +93,7 @@ def mx_verify(graph, act_clip_val, weight_clip_val, args):
         if x.dim() != 4 or int(qa.block_axis) % 4 != 1 or int(qb.block_axis) % 4 != 1:
             raise ValueError(f"blocks along axes {int(qa.block_axis)} and {int(qb.block_axis)} of a {x.dim()}-D convolution's operands")
         a_codes, a_scales = ops.mx_encode(x, 1, elem)                                        # [n, h, w, Cp ...]: NHWC
-        b_codes, b_scales, key, c_b = operand(qb, None)                                      # [cout, kh, kw, Cp ...] as the file holds it
+        b_codes, b_scales, key, c_b = operand(qb, None, elem)                                    # [cout, kh, kw, Cp ...] as the file holds it
         n, c, h, w = (int(d) for d in x.shape)
         if b_codes.dim() != 4 or c_b != c:
             raise ValueError(f"the weight's packed codes are {list(b_codes.shape)} over {c_b} channels, the input has {c}")
@@ -137,8 +141,13 @@ def mx_verify(graph, act_clip_val, weight_clip_val, args):
         try:
             if qa is None or qb is None:
                 raise ValueError("only one operand is block-scaled")
+            if qa.format.elem != qb.format.elem:
+                raise ValueError(f"its operands are {qa.format.elem} and {qb.format.elem}")
+            elem = qa.format.elem               # the node's own format, from its MX nodes
             if node.op_type == "Conv":
-                nodes[node.name] = conv(node, qa, qb)
+                nodes[node.name] = conv(node, qa, qb, elem)
+                if mixed:
+                    nodes[node.name]["format"] = elem
                 continue
             trans_b = 0
             if node.op_type == "Gemm":
@@ -147,8 +156,8 @@ def mx_verify(graph, act_clip_val, weight_clip_val, args):
                 trans_b = int(node.attrs.get("transB", 0) or 0)
             if qa.tensor_name in graph_q.initializer:
                 raise ValueError("the first operand is a constant")
-            a_codes, a_scales, _, k = operand(qa, -1)
-            b_codes, b_scales, key, k_b = operand(qb, -1 if trans_b else -2)
+            a_codes, a_scales, _, k = operand(qa, -1, elem)
+            b_codes, b_scales, key, k_b = operand(qb, -1 if trans_b else -2, elem)
             if k_b != k:
                 raise ValueError(f"the operands reduce over {k} and {k_b} elements")
             lead, lead_b = tuple(a_codes.shape[:-2]), tuple(b_codes.shape[:-2])
@@ -181,12 +190,14 @@ def mx_verify(graph, act_clip_val, weight_clip_val, args):
             nodes[node.name] = {"op": node.op_type, "m": m, "n": n, "k": k, "constant": key,
                                 "max_abs_err": float(err.max()), "max_err_over_bound": ratio, "cosine": cos,
                                 "within_bound": bool(ratio <= 1.0 and bool(torch.isfinite(got).all()))}
+            if mixed:
+                nodes[node.name]["format"] = elem
             logger.info("--mx_verify: {} {} [{} x {} x {}]{}: max |err| {:.3e}, {:.3e} of the bound, cosine {:.9f}".format(
                 node.op_type, node.name, m, n, kp, "" if key is None else " (" + key + " from the file)", float(err.max()), ratio, cos))
         except (ValueError, KeyError) as e:
             skipped[node.name] = str(e)
             logger.warning("--mx_verify: {} {} skipped: {}".format(node.op_type, node.name, e))
-    report = {"format": elem, "images": images, "nodes": nodes, "skipped": skipped}
+    report = {"format": meta["format"], "images": images, "nodes": nodes, "skipped": skipped}
     with open(os.path.join(args.output_dir, REPORT), "w") as f:
         json.dump(report, f, indent=4)
     bad = [k for k, v in nodes.items() if not v["within_bound"]]

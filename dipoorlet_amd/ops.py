@@ -1286,6 +1286,23 @@ def _mx_packed_pair(who, a, b, elem_a, elem_b, dims_ok, kp, how):
     return elem_b, split(*a, elem_a, "A"), split(*b, elem_b, "B")
 
 
+MX_GEMM_TILE = 64                       # rows and columns of C per workgroup of k_mx_gemm / k_mx_gemm_err (mx_plan.hpp kMxGemmTile)
+
+
+def _mx_gemm_pair(who, a_codes, a_scales, b_codes, b_scales, elem_a, elem_b):
+    """The operand checks of mx_gemm and mx_gemm_err -> (elem_b, A's leading dimensions, m, n, K-blocks, batch, b_batched)."""
+    elem_b, ((*lead, m), nblk), ((*lead_b, n), nblk_b) = _mx_packed_pair(
+        who, (a_codes, a_scales, "..., rows"), (b_codes, b_scales, "..., rows"), elem_a, elem_b, lambda nd: nd >= 2, "Kp", "")
+    lead, lead_b = tuple(lead), tuple(lead_b)
+    if nblk_b != nblk or lead_b not in ((), lead):
+        raise _hip.DipoorletHipError(f"{who}: A is {list(lead)} x [{m}, {nblk} blocks] and B {list(lead_b)} x [{n}, {nblk_b} blocks]: the two must "
+                                     "have the same number of K-blocks, and B the leading dimensions of A or none")
+    batch = 1
+    for d in lead:
+        batch *= d
+    return elem_b, lead, m, n, nblk, batch, int(lead_b == lead and lead != ())
+
+
 def mx_gemm(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, out=None):
     """`--mx_verify`: the product of two packed MX operands on CDNA4's block-scaled matrix instruction (dpl_mx_gemm;
     tests/mx_gemm_model.py is the definition).  Both operands are what mx_encode writes, K-innermost: a_codes [*batch, m, Kp or
@@ -1293,20 +1310,38 @@ def mx_gemm(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, out=None)
     dimensions, or [n, ...] / [n, Kp / 32], which every batch shares.  -> fp32 [*batch, m, n], C[.., i, j] = sum over the Kp codes
     of a[.., i, :] * b[.., j, :] (pad codes included).  elem_b: B's element format when it is not A's.  A row that holds a 0xFF
     scale byte or an E4M3 NaN code makes its row (column) of C NaN.  out: an optional contiguous fp32 device tensor of that shape."""
-    elem_b, ((*lead, m), nblk), ((*lead_b, n), nblk_b) = _mx_packed_pair(
-        "mx_gemm", (a_codes, a_scales, "..., rows"), (b_codes, b_scales, "..., rows"), elem_a, elem_b, lambda nd: nd >= 2, "Kp", "")
-    lead, lead_b = tuple(lead), tuple(lead_b)
-    if nblk_b != nblk or lead_b not in ((), lead):
-        raise _hip.DipoorletHipError(f"mx_gemm: A is {list(lead)} x [{m}, {nblk} blocks] and B {list(lead_b)} x [{n}, {nblk_b} blocks]: the two must "
-                                     "have the same number of K-blocks, and B the leading dimensions of A or none")
-    batch = 1
-    for d in lead:
-        batch *= d
+    elem_b, lead, m, n, nblk, batch, b_batched = _mx_gemm_pair("mx_gemm", a_codes, a_scales, b_codes, b_scales, elem_a, elem_b)
     shape = lead + (m, n)
     c = _mx_out("mx_gemm", out, shape, a_codes.device, f"shape {list(shape)} and the codes' device")
     _hip.check(_hip.lib().dpl_mx_gemm(MX_ELEM[elem_a], MX_ELEM[elem_b], _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales), batch, m, n,
-                                      MX_BLOCK * nblk, int(lead_b == lead and lead != ()), _ptr(c), _stream()), "dpl_mx_gemm")
+                                      MX_BLOCK * nblk, b_batched, _ptr(c), _stream()), "dpl_mx_gemm")
     return c
+
+
+def mx_gemm_err(a_codes, a_scales, b_codes, b_scales, ref, elem_a, elem_b=None, bias=None, out=None):
+    """`--mx_mixed`: mx_gemm's product held against a reference without being written (dpl_mx_gemm_err; tests/mx_mixed_model.py
+    gemm_err_partials is the definition).  The operands are mx_gemm's; ref: fp32 [*batch, m, n]; bias: None or fp32 [n].  -> fp64
+    [*batch, tiles_m, tiles_n, 2], per 64 x 64 tile of C the sums of d * d and of ref * ref over the tile's elements, d = (C + bias)
+    - ref in fp32, each square exact in fp64 and the additions in the kernel's fixed order.  A NaN of C (mx_gemm's rule) makes its
+    tile's first sum NaN.  out: an optional contiguous fp64 device tensor of that shape."""
+    elem_b, lead, m, n, nblk, batch, b_batched = _mx_gemm_pair("mx_gemm_err", a_codes, a_scales, b_codes, b_scales, elem_a, elem_b)
+    _require_cuda(ref, "ref")
+    if tuple(ref.shape) != lead + (m, n) or ref.device != a_codes.device:
+        raise _hip.DipoorletHipError(f"mx_gemm_err: ref must have shape {list(lead + (m, n))} and the codes' device")
+    if bias is not None:
+        _require_cuda(bias, "bias")
+        if tuple(bias.shape) != (n,) or bias.device != a_codes.device:
+            raise _hip.DipoorletHipError(f"mx_gemm_err: bias must have shape [{n}] and the codes' device")
+    shape = lead + (-(-m // MX_GEMM_TILE), -(-n // MX_GEMM_TILE), 2)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=a_codes.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
+              and tuple(out.shape) == shape and out.device == a_codes.device):
+        raise _hip.DipoorletHipError(f"mx_gemm_err: out must be a contiguous float64 tensor of shape {list(shape)} on the codes' device")
+    _hip.check(_hip.lib().dpl_mx_gemm_err(MX_ELEM[elem_a], MX_ELEM[elem_b], _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales), batch, m,
+                                          n, MX_BLOCK * nblk, b_batched, _ptr(ref), None if bias is None else _ptr(bias), _ptr(out), _stream()),
+               "dpl_mx_gemm_err")
+    return out
 
 
 def mx_conv(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, *, strides, pads, dilations, out_hw, out=None):

@@ -433,6 +433,9 @@ def insert_fake_quant_node(graph, node, act_quantized, data_range_list, args):
     rules.  With args.mx_conv so do both operands of every Conv that mx_conv_left lets through, along axis 1; its bias too is left
     to the platform's rules.  `act_quantized` holds (name, axis) for such a node: a tensor wanted along two axes, or by a static consumer as well,
     gets one node each — the first has the usual names, a later MX one the suffix `_ax<k>`, a later static one `_static`.
+    With args.mx_formats ({node name: 'mxfp8' / 'mxfp4'}, --mx_mixed: mx_mixed.py) a node named there takes that format for both
+    its operands instead of args.mx; a tensor that nodes of two formats read along one axis gets a node each, entry (name, axis,
+    format) and suffix `_ax<k>_<format>` for the one that is not args.mx's.
     With args.mx_scale_search the MX node of a constant operand carries error-minimising block scales (_MX.search_scales), computed
     here from the weight as it stands in `graph`; an activation's node keeps the floor rule."""
     from .platform_settings import mx_setting_table, platform_setting_table
@@ -446,10 +449,11 @@ def insert_fake_quant_node(graph, node, act_quantized, data_range_list, args):
         if mx and idx < 2 and name != "":
             shape = graph.tensor_name_shape_map.get(name)
             axis = mx_block_axis(node, idx, shape)
-            key = (name, axis)
+            fmt = (getattr(args, "mx_formats", None) or {}).get(node.name, mx)     # (--mx_mixed: this node's own format)
+            key = (name, axis) if fmt == mx else (name, axis, fmt)
             first = _taken(act_quantized, name)
-            q_nodes, _, _ = get_qnode_by_param(mx_setting_table[mx], name, shape, None, block_axis=axis,
-                                               suffix="" if first in (None, key) else f"_ax{axis}")
+            q_nodes, _, _ = get_qnode_by_param(mx_setting_table[fmt], name, shape, None, block_axis=axis,
+                                               suffix="" if first in (None, key) else f"_ax{axis}" if fmt == mx else f"_ax{axis}_{fmt}")
             node.input[idx] = q_nodes.output
             if key not in act_quantized:
                 if getattr(args, "mx_scale_search", False) and name in graph.initializer:

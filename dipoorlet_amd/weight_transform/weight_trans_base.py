@@ -72,6 +72,14 @@ def weight_calibration(onnx_graph, act_clip_val, weight_clip_val, args):
     bc_sharded = dist.get_world_size() > 1 and getattr(args, "merge", "allreduce") != "reference"
     stage("smooth", "Weight transform: smoothing MatMul inputs...", True, lambda g: smooth_quant(g, args), "smooth_model", "all")
     stage("mx_rotate", "Weight transform: rotating MX blocks...", True, lambda g: mx_rotate(g, args), "rotate_model", "all")
+    if getattr(args, "mx_mixed", None) is not None:
+        # --mx_mixed (not in the reference): on the model as --smooth / --mx_rotate leave it and before anything that runs the
+        # fake-quantised graph, whose MX nodes take the chosen formats from here on (args.mx_formats).  Every rank runs it.
+        from ..mx_mixed import mx_mixed
+        if rank == 0:
+            logger.info("Choosing MXFP4 or MXFP8 per node...")
+        mx_mixed(graph_after_wt, args)
+        dist.barrier()
     stage("bc", "Weight transform: bias correction...", bc_sharded,
           lambda g: bias_correction(g, act_clip_val, weight_clip_val, args), "update_bias_model", "weight")
     stage("we", "Weight transform: cross-layer equalisation...", False, lambda g: weight_equalization(g, args), "weight_equal_model", "all")

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 34 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 35 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
                               25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
@@ -38,7 +38,8 @@ extern "C" {
                               32: dpl_mx_scale_search / dpl_fake_quant_mx_scaled / dpl_mx_encode_scaled (error-minimising E8M0 scales
                                   for constant MX operands, and the Q/DQ and the packed bytes under given scales: --mx_scale_search);
                               33: dpl_gptq_mx_block (dpl_gptq_block's recursion on the MX block-scaled grids: --mx_gptq);
-                              34: dpl_mx_conv (a convolution of two packed MX operands on the block-scaled matrix instruction: --mx_conv) */
+                              34: dpl_mx_conv (a convolution of two packed MX operands on the block-scaled matrix instruction: --mx_conv);
+                              35: dpl_mx_gemm_err (dpl_mx_gemm's product against a reference, as per-tile fp64 error sums: --mx_mixed) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -505,6 +506,27 @@ int dpl_mx_encode_scaled(int32_t elem, const float* d_x, uint64_t outer, uint64_
  *      a refused call (-2) launches nothing. */
 int dpl_mx_gemm(int32_t elem_a, int32_t elem_b, const uint8_t* d_a_codes, const uint8_t* d_a_scales, const uint8_t* d_b_codes,
                 const uint8_t* d_b_scales, uint64_t batch, uint64_t m, uint64_t n, uint64_t k, int32_t b_batched, float* d_c, dpl_stream_t s);
+
+/* ---- dpl_mx_gemm's product held against a reference without being written (beyond the reference; --mx_mixed measures a node in
+ *      both element formats with it; the definition is tests/mx_mixed_model.py gemm_err_partials).  The operands, their layout, the
+ *      grid (a workgroup per 64 x 64 tile of C) and the accumulators are dpl_mx_gemm's, bit for bit, its NaN rule included.
+ *        d_ref           fp32 [batch, m, n]       d_bias_or_null  fp32 [n] or null
+ *        d_part          fp64 [batch * tiles_m * tiles_n, 2], tiles_m = ceil(m / 64), tiles_n = ceil(n / 64), the row of tile
+ *                        (tm, tn) of batch b being (b * tiles_m + tm) * tiles_n + tn
+ *      Per element v of C inside the arrays: d = v - ref in fp32, with a bias (v + bias[col]) - ref as two fp32 operations;
+ *      part[tile][0] = sum of (double)d * (double)d, part[tile][1] = sum of (double)ref * (double)ref, both squares exact.  Rows >= m
+ *      and columns >= n contribute +0.0 and are not read from d_ref.  The order of the additions is part of the definition: with
+ *      wave w owning rows 32 (w >> 1) .. and columns 32 (w & 1) .. of the tile, lane l adds its 16 terms one after the other over
+ *      (i, reg, j) nested in that order, the term's row being 16 i + 4 (l >> 4) + reg and its column 16 j + (l & 15) of that
+ *      quadrant; the 64 lane sums fold pairwise by xor-shuffles 1, 2, 4, 8, 16, 32 (as an array: e = e[0::2] + e[1::2], six
+ *      times); the four wave sums are added as (w0 + w1) + (w2 + w3).  Every workgroup writes its own row of d_part with plain
+ *      stores: no atomics, nothing to clear beforehand, the same bits on every run.
+ *      Rules in their order: elem_a / elem_b; batch * m * n * k == 0 is a no-op that returns 0; null pointers (d_ref and d_part
+ *      included, the bias may be null); 1 <= m, n, k < 2^31; "tensor too large"; d_a_codes and d_b_codes 16-byte aligned; the grid.
+ *      A refused call (-2) launches nothing. */
+int dpl_mx_gemm_err(int32_t elem_a, int32_t elem_b, const uint8_t* d_a_codes, const uint8_t* d_a_scales, const uint8_t* d_b_codes,
+                    const uint8_t* d_b_scales, uint64_t batch, uint64_t m, uint64_t n, uint64_t k, int32_t b_batched, const float* d_ref,
+                    const float* d_bias_or_null, double* d_part, dpl_stream_t s);
 
 /* ---- a convolution of two packed MX operands on the same instruction, as an implicit GEMM (beyond the reference; --mx_conv; the
  *      definition is tests/mx_conv_model.py).  Both operands are what dpl_mx_encode writes along axis 1 (channels).  With
