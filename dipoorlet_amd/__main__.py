@@ -22,6 +22,7 @@ from .utils import MARKS, load_clip_val, logger, mark, reduce_clip_val, save_cli
 
 
 def build_parser():
+    from .platform_settings import MX_CHOICES
     p = argparse.ArgumentParser(prog="dipoorlet_amd")
     p.add_argument("-M", "--model", help="onnx model")
     p.add_argument("-I", "--input_dir", help="calibration data", required=True)
@@ -47,10 +48,11 @@ def build_parser():
     p.add_argument("--smooth_alpha", type=float, default=0.5,
                    help="--smooth (not in the reference): fold per-channel scales s = max|x|^alpha / max|w|^(1 - alpha) of every LayerNorm "
                         "affine that feeds only MatMul / Gemm weights into those weights; alpha in [0, 1]")
-    p.add_argument("--mx", choices=["mxfp8", "mxfp4"], default=None,
+    p.add_argument("--mx", choices=list(MX_CHOICES), default=None,
                    help="(not in the reference; with -D ocp_fp8 only) OCP Microscaling on both operands of every MatMul / Gemm, constant "
                         "ones included: blocks of 32 along the reduction axis share a power-of-two scale taken from the data, the elements "
-                        "are FP8 E4M3 (mxfp8) or FP4 E2M1 (mxfp4); every other node keeps the platform's static E4M3 scales")
+                        "are FP8 E4M3 (mxfp8), FP6 E2M3 or E3M2 (mxfp6_e2m3, mxfp6_e3m2: no --mx_gptq, no --mx_mixed) or FP4 E2M1 (mxfp4); every "
+                        "other node keeps the platform's static E4M3 scales")
     p.add_argument("--mx_rotate", default=False, action="store_true",
                    help="(not in the reference; with --mx only) rotate every MX block of both operands of every MatMul / Gemm that has a "
                         "constant 2-D weight and a reduction length K that is a multiple of 32, by the 32-point Hadamard matrix H32: "
@@ -132,8 +134,8 @@ def check_args(args):
     sign: the integer grid of `-D trt` / `stpu` and the E4M3 codes of `-D ocp_fp8`.  A floating-point grid (`-D ocp_fp8`) is reached through the
     FakeQuant nodes only: the clip sweeps that know nothing of the grid and the transforms that run the fake-quantised forward
     work unchanged; what assumes or learns an integer grid does not."""
-    from .platform_settings import platform_setting_table
-    from .quantize import FORMATS
+    from .platform_settings import mx_fp6_setting_table, platform_setting_table
+    from .quantize import number_format
     alpha = getattr(args, "smooth_alpha", 0.5)
     if not 0.0 <= alpha <= 1.0:      # (a NaN too)
         raise ValueError(f"--smooth_alpha must lie in [0, 1], got {alpha}")
@@ -155,6 +157,9 @@ def check_args(args):
         if not getattr(args, "mx", None):
             raise ValueError("--mx_gptq needs --mx mxfp8 or --mx mxfp4: it rounds the weights that --mx block-scales (--gptq serves a "
                              "static grid)")
+        if args.mx in mx_fp6_setting_table:
+            raise ValueError(f"--mx_gptq is not supported with --mx {args.mx}: the recursion's model and kernel are held to the two grids "
+                             "of mxfp8 and mxfp4 (E4M3, E2M1); an FP6 grid is not built")
         for flag in ("adaround", "brecq", "sparse"):
             if getattr(args, flag, False):
                 raise ValueError(f"--mx_gptq and --{flag} cannot be combined: two transforms would each decide how the weights are rounded")
@@ -185,6 +190,9 @@ def check_args(args):
         if not getattr(args, "mx", None):
             raise ValueError("--mx_mixed needs --mx mxfp4: it promotes nodes of a block-scaled graph from the base format mxfp4 to "
                              "mxfp8, and a static grid has neither")
+        if args.mx in mx_fp6_setting_table:
+            raise ValueError(f"--mx_mixed is not supported with --mx {args.mx}: its budget arithmetic is two-level, 4 bits (mxfp4) or 8 "
+                             "(mxfp8) per weight element, and its error kernel is built for those two formats")
         if args.mx != "mxfp4":
             raise ValueError(f"--mx_mixed is not supported with --mx {args.mx}: the base format is mxfp4 and the budget buys mxfp8 "
                              "where it helps most; with mxfp8 everywhere there is nothing to promote to")
@@ -206,7 +214,7 @@ def check_args(args):
         if why:
             raise ValueError(f"-A qmse is not supported with -D {args.deploy}: {why}, and the search models a symmetric grid with a "
                              "free scale.  Supported: -D trt, -D stpu, -D ocp_fp8")
-    if FORMATS[qi["type"]].integer:
+    if number_format(qi["type"]).integer:
         return
     bad = [flag for flag, on in (("-A mse", args.act_quant == "mse"),        # OCTAV's fixed point assumes a uniform grid
                                  ("-A kl", args.act_quant == "kl"),          # its levels are integer levels

@@ -15,12 +15,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPL_LIB: another build of the same sources (the host-sanitizer build of scripts/asan_host_check.sh); never a different code path
 LIB_PATH = os.environ.get("DPL_LIB") or os.path.join(_HERE, "csrc", "libdipoorlet_hip.so")
 
-ABI_VERSION = 35
+ABI_VERSION = 36
 MAX_BINS = 16384
 GRID_UNIFORM, GRID_E4M3 = 0, 1          # DPL_GRID_*: the grids of dpl_hist_qmse
 HIST_SPEC_MAX_TENSORS = 2048
 GPTQ_MAX_BLOCK = 128                   # DPL_GPTQ_MAX_BLOCK
-MX_E4M3, MX_E2M1 = 0, 1                # DPL_MX_*: the element formats of dpl_fake_quant_mx, dpl_mx_encode / _decode
+MX_E4M3, MX_E2M1, MX_E2M3, MX_E3M2 = 0, 1, 6, 7                # DPL_MX_*: the element formats of dpl_fake_quant_mx, dpl_mx_encode / _decode
 
 
 class Span(C.Structure):

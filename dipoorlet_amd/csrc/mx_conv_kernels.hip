@@ -1,7 +1,7 @@
 // K7d: `--mx_conv` — a convolution of two packed MX operands on CDNA4's block-scaled matrix instruction, as an implicit GEMM
 // (tests/mx_conv_model.py is the definition; DESIGN.md §3r the tap addressing and the measurements; §3o the lane map).  Both operands
 // are what dpl_mx_encode writes along axis 1: the activation [n, c, h, w] as NHWC codes [n, h, w, Cb * bb] with scales [n, h, w, Cb],
-// the weight [cout, c, kh, kw] as [cout, kh, kw, Cb * bb] with scales [cout, kh, kw, Cb]; Cb = ceil(c / 32), bb = 32 (E4M3) or 16
+// the weight [cout, c, kh, kw] as [cout, kh, kw, Cb * bb] with scales [cout, kh, kw, Cb]; Cb = ceil(c / 32), bb = 32 (E4M3), 24 (E2M3 / E3M2) or 16
 // (E2M1) bytes a block.  C fp32 [n, oh, ow, cout]:
 //   C[b, oy, ox, co] = sum over ky, kx and ch < 32 Cb of a[b, oy sh - pt + ky dh, ox sw - pl + kx dw, ch] * b[co, ky, kx, ch]
 // a tap outside the image contributing nothing.  That is k_mx_gemm's product with m = oh * ow rows per image and K = the kh * kw * Cb
@@ -68,7 +68,7 @@ extern "C" int dpl_mx_conv(int32_t elem_a, int32_t elem_b, const uint8_t* d_a_co
     g.h = (uint32_t)h, g.w = (uint32_t)w, g.cb = (uint32_t)p.cb, g.cout = (uint32_t)cout, g.kw = (uint32_t)kw, g.oh = (uint32_t)oh, g.ow = (uint32_t)ow;
     g.sh = (uint32_t)stride_h, g.sw = (uint32_t)stride_w, g.pt = (uint32_t)pad_top, g.pl = (uint32_t)pad_left, g.dh = (uint32_t)dil_h, g.dw = (uint32_t)dil_w;
     g.nblk = (uint32_t)p.nblk, g.tiles_m = p.t.tiles_m, g.tiles_n = p.t.tiles_n;
-    return mx_pair_dispatch(o, [&](auto EA, auto EB) {
+    return mx_pair_dispatch_all(o, [&](auto EA, auto EB) {
         hipLaunchKernelGGL((k_mx_conv<EA, EB>), dim3((unsigned)p.t.blocks), dim3(kBlock), 0, (hipStream_t)s, o.a_codes, o.a_scales, o.b_codes, o.b_scales,
                            o.c, g);
         DPL_LAUNCH_CHECK("k_mx_conv");

@@ -20,18 +20,35 @@ namespace dpl_mx {
 constexpr int kBlock32 = 32;   // elements per block
 
 // The element formats: emax (the exponent of the largest value), mantissa bits, the exponent of the smallest normal value, the
-// exponent bits of the code, and the mantissa field of the largest value as fp32 (E4M3: 448 = 1.75 * 2^8; E2M1: 6 = 1.5 * 2^2).
+// exponent bits of the code, and the mantissa field of the largest value as fp32 (E4M3: 448 = 1.75 * 2^8; E2M1: 6 = 1.5 * 2^2;
+// E2M3: 7.5 = 1.875 * 2^2; E3M2: 28 = 1.75 * 2^4).  And what the packed form and the block-scaled MFMA key on: the bits a code takes
+// in the file (a block of 32 is 4 * bits bytes: 32, 16 or 24), the code of every element of a 0xFF block, and the instruction's
+// format code (cbsz / blgp).  The two FP6 formats (tests/mx_fp6_model.py) have no NaN or inf codes, like E2M1.
 template <int ELEM>
 struct Fmt;
 template <>
 struct Fmt<0> {   // DPL_MX_E4M3
     static constexpr int emax = 8, mbits = 3, emin = -6, ebits = 4;
-    static constexpr uint32_t top_mant = 0x600000u;
+    static constexpr uint32_t top_mant = 0x600000u, bits = 8u, nan_code = 0x7Fu;
+    static constexpr int mfma = 0;
 };
 template <>
 struct Fmt<1> {   // DPL_MX_E2M1
     static constexpr int emax = 2, mbits = 1, emin = 0, ebits = 2;
-    static constexpr uint32_t top_mant = 0x400000u;
+    static constexpr uint32_t top_mant = 0x400000u, bits = 4u, nan_code = 0u;
+    static constexpr int mfma = 4;
+};
+template <>
+struct Fmt<6> {   // DPL_MX_E2M3
+    static constexpr int emax = 2, mbits = 3, emin = 0, ebits = 2;
+    static constexpr uint32_t top_mant = 0x700000u, bits = 6u, nan_code = 0u;
+    static constexpr int mfma = 2;
+};
+template <>
+struct Fmt<7> {   // DPL_MX_E3M2
+    static constexpr int emax = 4, mbits = 2, emin = -2, ebits = 3;
+    static constexpr uint32_t top_mant = 0x600000u, bits = 6u, nan_code = 0u;
+    static constexpr int mfma = 3;
 };
 
 DPL_MX_HD int clz32(uint32_t v) {   // 32 for 0

@@ -5,8 +5,9 @@
 // a[b, i, kk] * b[b or 0, j, kk], fp32 [batch, m, n].  The pad codes take part in the sum (the encoder writes 0).
 //
 // v_mfma_scale_f32_16x16x128_f8f6f4 multiplies a 16 x 128 by a 128 x 16 tile; which lane supplies what is mx_mfma.hpp's comment.
-// A lane's fragment is one (E2M1) or two (E4M3, 64 bytes apart) 16-byte loads straight from the file's order, and the four lanes
-// of a row read one run of 64 bytes or two.
+// A lane's fragment is one (E2M1) or two (E4M3, 64 bytes apart) 16-byte loads, or three 8-byte ones (E2M3 / E3M2: a 24-byte block),
+// straight from the file's order, and the four lanes of a row read one run of 64 or 96 bytes, or two of 64.  k_mx_gemm is instantiated
+// for all sixteen pairs of the four formats (mx_pair_dispatch_all), k_mx_gemm_err for the four of E4M3 / E2M1 (--mx_mixed's).
 //
 //   k_mx_gemm<EA, EB>  mx_mfma_tile with plain K-innermost rows on both sides: 256 threads, a 64 x 64 tile of C per workgroup; each
 //                      wave owns 32 x 32 of it as 2 x 2 instruction tiles, four accumulators.  Operands come straight from global
@@ -90,7 +91,7 @@ extern "C" int dpl_mx_gemm(int32_t elem_a, int32_t elem_b, const uint8_t* d_a_co
     int rc;
     MxTiles t;
     if (mx_gemm_check(rc, t, o, batch, m, n, k)) return rc;
-    return mx_pair_dispatch(o, [&](auto EA, auto EB) {
+    return mx_pair_dispatch_all(o, [&](auto EA, auto EB) {
         hipLaunchKernelGGL((k_mx_gemm<EA, EB>), dim3((unsigned)t.blocks), dim3(kBlock), 0, (hipStream_t)s, o.a_codes, o.a_scales, o.b_codes, o.b_scales,
                            o.c, (uint32_t)m, (uint32_t)n, (uint32_t)((k + 31u) / 32u), t.tiles_m, t.tiles_n, (uint32_t)(b_batched != 0));
         DPL_LAUNCH_CHECK("k_mx_gemm");

@@ -1,5 +1,5 @@
 // K7: the OCP Microscaling (MX) Q/DQ pair — blocks of 32 elements along one axis share a power-of-two scale (E8M0), the elements
-// are FP8 E4M3 (MXFP8) or FP4 E2M1 (MXFP4).  y = round_elem(v / 2^se) * 2^se with se from the block's largest |v|
+// are FP8 E4M3 (MXFP8), FP6 E2M3 or E3M2 (the two MXFP6: tests/mx_fp6_model.py) or FP4 E2M1 (MXFP4).  y = round_elem(v / 2^se) * 2^se with se from the block's largest |v|
 // (tests/mx_model.py is the definition; mx_format.hpp the arithmetic, on bit patterns).  The tensor is [outer, K, inner], blocks
 // along K.  One read and one write per element (8 B), non-temporal; no atomics, no LDS, no scratch; 64-bit element indices.
 // The block walk is mx_block.hpp's (MxRowsLoad, MxColsLoad), the argument check, launch plan and dispatch mx_plan.hpp's: a kernel
@@ -80,7 +80,7 @@ int fake_quant_mx_launch(const char* who, int32_t elem, const float* d_x, float*
                          dpl_stream_t s) {
     MxPlan p;
     if (const int rc = mx_plan(p, who, (uintptr_t)d_x | (uintptr_t)d_y, outer, k, inner, false)) return rc;
-    return mx_dispatch(elem, inner == 1, p.vec, [&](auto E, auto ROWS, auto VEC) {
+    return mx_dispatch_all(elem, inner == 1, p.vec, [&](auto E, auto ROWS, auto VEC) {
         if constexpr (ROWS) {
             hipLaunchKernelGGL((k_fake_quant_mx_rows<E, VEC, GIVEN>), dim3((unsigned)p.blocks), dim3(kBlock), 0, (hipStream_t)s, d_x, d_y, p.n, p.K,
                                p.nblk, d_scales);

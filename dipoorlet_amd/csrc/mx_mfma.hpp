@@ -7,8 +7,13 @@
 // values of that same block, 16 bytes, byte j holding k = 2j in its low and k = 2j + 1 in its high nibble, the other four dwords 0.
 // E4M3 — NOT that block: dwords 0 .. 3 are k = 16 (l >> 4) .. + 15 of the step and dwords 4 .. 7 k = 64 + 16 (l >> 4) .. + 15, byte
 // j of a run being k = j.  C/D: lane l holds column l & 15, rows 4 * (l >> 4) + reg.
+// E2M3 / E3M2 (format codes 2 / 3; DESIGN.md §3v, confirmed with one-product outputs that use every bit of the codes) — as E2M1, the
+// 32 K values of block l >> 4 under that block's scale byte: dwords 0 .. 5 are the block's 24 bytes as the file holds them, ONE
+// little-endian string of 192 bits with k = i in bits [6 i, 6 i + 6), the other two dwords 0.  No repack: the file's order is the
+// instruction's.  A 24-byte block lies at a multiple of 8 bytes, so it is loaded as three 8-byte vectors.
 #pragma once
 #include "common.hpp"
+#include "mx_format.hpp"
 #include "mx_plan.hpp"
 
 namespace {
@@ -16,13 +21,15 @@ namespace {
 using i8v = __attribute__((ext_vector_type(8))) int;
 using u4g = __attribute__((ext_vector_type(4))) uint32_t;
 typedef const __attribute__((address_space(1))) u4g* gptr_u4g;
+using u2g = __attribute__((ext_vector_type(2))) uint32_t;
+typedef const __attribute__((address_space(1))) u2g* gptr_u2g;
 typedef const __attribute__((address_space(1))) uint8_t* gptr_u8g;
 typedef __attribute__((address_space(1))) float* gptr_f32g;
 
 template <int ELEM>
 struct GemmOperand {
-    static constexpr uint32_t block_bytes = ELEM == DPL_MX_E4M3 ? 32u : 16u;      // of one K-block's codes in the file
-    static constexpr int fmt = ELEM == DPL_MX_E4M3 ? 0 : 4;                        // the instruction's format code (cbsz / blgp)
+    static constexpr uint32_t block_bytes = 4u * dpl_mx::Fmt<ELEM>::bits;          // of one K-block's codes in the file: 32, 16 or 24
+    static constexpr int fmt = dpl_mx::Fmt<ELEM>::mfma;                            // the instruction's format code (cbsz / blgp)
 };
 
 // Does a dword hold an E4M3 NaN byte (0x7F or 0xFF)?  (t's bytes are at most 0x7F: adding 1 carries into bit 7 only from 0x7F.)
@@ -49,9 +56,9 @@ struct MxRowBlocks {
 };
 
 // kb0: the first K-block of the 128-wide step; q = lane >> 4.  By the map above: the scale byte of block kb0 + q; E2M1 — the 16
-// bytes of that block; E4M3 — half q & 1 of block kb0 + (q >> 1) into the low four dwords and the same half of block
+// bytes of that block; E2M3 / E3M2 — its 24 bytes; E4M3 — half q & 1 of block kb0 + (q >> 1) into the low four dwords and the same half of block
 // kb0 + 2 + (q >> 1) into the high four.  A block that is not there leaves zeros (scale byte 127), and nothing is loaded for it.
-// bad: the lane's NaN notes, a 0xFF scale byte or an E4M3 NaN code in what it loaded.
+// bad: the lane's NaN notes, a 0xFF scale byte or an E4M3 NaN code in what it loaded (an FP6 or E2M1 code is never one).
 template <int ELEM, class At>
 __device__ __forceinline__ GemmFrag mx_frag_load(const uint8_t* codes, const uint8_t* scales, const At& at, uint32_t kb0, uint32_t q, uint32_t& bad) {
     GemmFrag f;
@@ -66,6 +73,14 @@ __device__ __forceinline__ GemmFrag mx_frag_load(const uint8_t* codes, const uin
                 f.v[4 * hi] = (int)w.x, f.v[4 * hi + 1] = (int)w.y, f.v[4 * hi + 2] = (int)w.z, f.v[4 * hi + 3] = (int)w.w;
                 bad |= e4m3_nan_in(w.x) | e4m3_nan_in(w.y) | e4m3_nan_in(w.z) | e4m3_nan_in(w.w);
             }
+    } else if constexpr (GemmOperand<ELEM>::block_bytes == 24u) {
+        // (a 24-byte block lies at a multiple of 8, and the last one of an odd number ends 8 bytes short of a 16-byte boundary:
+        // three 8-byte loads, nothing read past the block)
+        if (at(kb0 + q, blk)) {
+            gptr_u2g src = (gptr_u2g)(codes + blk * 24u);
+            const u2g w0 = src[0], w1 = src[1], w2 = src[2];
+            f.v[0] = (int)w0.x, f.v[1] = (int)w0.y, f.v[2] = (int)w1.x, f.v[3] = (int)w1.y, f.v[4] = (int)w2.x, f.v[5] = (int)w2.y;
+        }
     } else if (at(kb0 + q, blk)) {
         const u4g w = *(gptr_u4g)(codes + blk * GemmOperand<ELEM>::block_bytes);
         f.v[0] = (int)w.x, f.v[1] = (int)w.y, f.v[2] = (int)w.z, f.v[3] = (int)w.w;

@@ -1,9 +1,9 @@
 // HOST side of the MX block kernels (mx_kernels.hip, mx_pack_kernels.hip, mx_search_kernels.hip), defined once — pure arithmetic, no
 // HIP: the argument check of their entry points (mx_check), the launch plan of an fp32 [outer, K, inner] tensor in blocks of 32
-// along K (mx_plan), and the way from (elem, inner == 1, vec) to a kernel instantiation (mx_dispatch).  And of the two kernels on the
+// along K (mx_plan), and the way from (elem, inner == 1, vec) to a kernel instantiation (mx_dispatch, mx_dispatch_all).  And of the two kernels on the
 // block-scaled MFMA (mx_gemm_kernels.hip, mx_conv_kernels.hip): what they hold a pair of packed operands to (mx_pair_elems,
 // mx_pair_null, mx_pair_aligned), their grid of 64 x 64 tiles (mx_tiles), each entry point's rules in their order (mx_gemm_check,
-// mx_gemm_err_check, mx_conv_check) and the way from (elem_a, elem_b) to an instantiation (mx_pair_dispatch).  A wrong value here is an out-of-range
+// mx_gemm_err_check, mx_conv_check) and the way from (elem_a, elem_b) to an instantiation (mx_pair_dispatch, mx_pair_dispatch_all).  A wrong value here is an out-of-range
 // address in a kernel, so a plain C++ compiler can build this: tests/mx_plan_host.cpp is a stand-alone program that runs it under
 // the address and undefined-behaviour sanitizers (tests/test_mx_plan_host.py).
 #pragma once
@@ -26,6 +26,9 @@ inline int mx_fail(const char* who, const char* what, const char* more = "") {
     return -2;
 }
 
+// The element formats there are: the two of mx_dispatch and the two FP6 formats mx_dispatch_all adds (2 .. 5 are no formats).
+inline bool mx_known(int32_t elem) { return elem == DPL_MX_E4M3 || elem == DPL_MX_E2M1 || elem == DPL_MX_E2M3 || elem == DPL_MX_E3M2; }
+
 // The argument rules of every entry point, in their order: elem, a zero size, null pointers, k and inner in [1, 2^31), a tensor
 // whose elements 64-bit indices reach, the codes' alignment.  -> true: the call is over and rc its result (0: nothing to do).
 //   names / ptrs  the pointers that must not be null, and what the message calls them;
@@ -34,7 +37,7 @@ inline int mx_fail(const char* who, const char* what, const char* more = "") {
 inline bool mx_check(int& rc, const char* who, int32_t elem, const char* names, std::initializer_list<const void*> ptrs, uint64_t outer,
                      uint64_t k, uint64_t inner, bool padded, const void* codes) {
     rc = 0;
-    if (elem != DPL_MX_E4M3 && elem != DPL_MX_E2M1) return (rc = mx_fail(who, "elem must be DPL_MX_E4M3 or DPL_MX_E2M1")), true;
+    if (!mx_known(elem)) return (rc = mx_fail(who, "elem must be DPL_MX_E4M3 or DPL_MX_E2M1 (or DPL_MX_E2M3 / DPL_MX_E3M2)")), true;
     if (outer == 0 || k == 0 || inner == 0) return true;
     for (const void* p : ptrs)
         if (p == nullptr) return (rc = mx_fail(who, names, " must not be null")), true;
@@ -66,12 +69,27 @@ inline int mx_plan(MxPlan& p, const char* who, uintptr_t fp, uint64_t outer, uin
     return p.blocks > 0x7FFFFFFFull ? mx_fail(who, "tensor too large") : 0;
 }
 
+// f(e, rows, VEC) for one element type e (a std::integral_constant), rows and VEC as such constants too: what both dispatches below
+// do once they know the format.
+template <class E, class F>
+inline int mx_dispatch_elem(E e, bool rows, bool vec, F f) {
+    const auto by_vec = [&](auto r) { return vec ? f(e, r, std::integral_constant<int, 4>{}) : f(e, r, std::integral_constant<int, 1>{}); };
+    return rows ? by_vec(std::true_type{}) : by_vec(std::false_type{});
+}
+
 // f(element type, rows, VEC) with the three as std::integral_constant values: one instantiation of a kernel family per call.
 template <class F>
 inline int mx_dispatch(int32_t elem, bool rows, bool vec, F f) {
-    const auto by_vec = [&](auto e, auto r) { return vec ? f(e, r, std::integral_constant<int, 4>{}) : f(e, r, std::integral_constant<int, 1>{}); };
-    const auto by_rows = [&](auto e) { return rows ? by_vec(e, std::true_type{}) : by_vec(e, std::false_type{}); };
-    return elem == DPL_MX_E4M3 ? by_rows(std::integral_constant<int, DPL_MX_E4M3>{}) : by_rows(std::integral_constant<int, DPL_MX_E2M1>{});
+    return elem == DPL_MX_E4M3 ? mx_dispatch_elem(std::integral_constant<int, DPL_MX_E4M3>{}, rows, vec, f)
+                               : mx_dispatch_elem(std::integral_constant<int, DPL_MX_E2M1>{}, rows, vec, f);
+}
+
+// The same over all four formats: the two FP6 formats are taken here, E4M3 and E2M1 go on to mx_dispatch.  What the entry points call.
+template <class F>
+inline int mx_dispatch_all(int32_t elem, bool rows, bool vec, F f) {
+    if (elem == DPL_MX_E2M3) return mx_dispatch_elem(std::integral_constant<int, DPL_MX_E2M3>{}, rows, vec, f);
+    if (elem == DPL_MX_E3M2) return mx_dispatch_elem(std::integral_constant<int, DPL_MX_E3M2>{}, rows, vec, f);
+    return mx_dispatch(elem, rows, vec, f);
 }
 
 // ---- The two kernels on the block-scaled MFMA (mx_gemm_kernels.hip, mx_conv_kernels.hip; their device side is mx_mfma.hpp) ----
@@ -87,8 +105,15 @@ struct MxPair {
 
 // The three rules both entry points hold the pair to, each -> 0 or the refusal (they stand apart: what lies between them differs).
 inline int mx_pair_elems(const char* who, const MxPair& o) {
+    return mx_known(o.elem_a) && mx_known(o.elem_b) ? 0
+                                                    : mx_fail(who, "elem_a and elem_b must be DPL_MX_E4M3 or DPL_MX_E2M1 (or DPL_MX_E2M3 / DPL_MX_E3M2)");
+}
+// dpl_mx_gemm_err's: --mx_mixed chooses between E2M1 and E4M3, and its kernel is instantiated for those two (mx_pair_dispatch).
+inline int mx_pair_elems_mixed(const char* who, const MxPair& o) {
     const auto known = [](int32_t e) { return e == DPL_MX_E4M3 || e == DPL_MX_E2M1; };
-    return known(o.elem_a) && known(o.elem_b) ? 0 : mx_fail(who, "elem_a and elem_b must be DPL_MX_E4M3 or DPL_MX_E2M1");
+    return known(o.elem_a) && known(o.elem_b)
+               ? 0
+               : mx_fail(who, "elem_a and elem_b must be DPL_MX_E4M3 or DPL_MX_E2M1 (--mx_mixed chooses between these two: no FP6 format here)");
 }
 inline bool mx_pair_operands(const MxPair& o) {
     return o.a_codes != nullptr && o.a_scales != nullptr && o.b_codes != nullptr && o.b_scales != nullptr;
@@ -139,7 +164,7 @@ inline bool mx_gemm_check(int& rc, MxTiles& t, const MxPair& o, uint64_t batch, 
 inline bool mx_gemm_err_check(int& rc, MxTiles& t, const MxPair& o, const float* ref, const double* part, uint64_t batch, uint64_t m, uint64_t n,
                               uint64_t k) {
     const char* who = "dpl_mx_gemm_err";
-    if ((rc = mx_pair_elems(who, o)) != 0 || batch == 0 || m == 0 || n == 0 || k == 0) return true;
+    if ((rc = mx_pair_elems_mixed(who, o)) != 0 || batch == 0 || m == 0 || n == 0 || k == 0) return true;
     if (!mx_pair_operands(o) || ref == nullptr || part == nullptr)
         return (rc = mx_fail(who, "the codes, the scales, d_ref and d_part must not be null")), true;
     return (rc = mx_gemm_sizes(who, batch, m, n, k)) != 0 || (rc = mx_pair_aligned(who, o)) != 0 || (rc = mx_tiles(t, who, batch, m, n)) != 0;
@@ -191,6 +216,21 @@ inline int mx_pair_dispatch(const MxPair& o, F f) {
         return o.elem_b == DPL_MX_E4M3 ? f(ea, std::integral_constant<int, DPL_MX_E4M3>{}) : f(ea, std::integral_constant<int, DPL_MX_E2M1>{});
     };
     return o.elem_a == DPL_MX_E4M3 ? by_b(std::integral_constant<int, DPL_MX_E4M3>{}) : by_b(std::integral_constant<int, DPL_MX_E2M1>{});
+}
+
+// The same over all sixteen pairs of the four formats: a pair of E4M3 / E2M1 goes on to mx_pair_dispatch, a pair with an FP6 format
+// on either side is taken here.  What dpl_mx_gemm and dpl_mx_conv call (dpl_mx_gemm_err stays with mx_pair_dispatch).
+template <class F>
+inline int mx_pair_dispatch_all(const MxPair& o, F f) {
+    const auto old = [](int32_t e) { return e == DPL_MX_E4M3 || e == DPL_MX_E2M1; };
+    if (old(o.elem_a) && old(o.elem_b)) return mx_pair_dispatch(o, f);
+    const auto by_elem = [](int32_t e, auto g) {
+        return e == DPL_MX_E4M3   ? g(std::integral_constant<int, DPL_MX_E4M3>{})
+               : e == DPL_MX_E2M1 ? g(std::integral_constant<int, DPL_MX_E2M1>{})
+               : e == DPL_MX_E2M3 ? g(std::integral_constant<int, DPL_MX_E2M3>{})
+                                  : g(std::integral_constant<int, DPL_MX_E3M2>{});
+    };
+    return by_elem(o.elem_a, [&](auto ea) { return by_elem(o.elem_b, [&](auto eb) { return f(ea, eb); }); });
 }
 
 }  // namespace

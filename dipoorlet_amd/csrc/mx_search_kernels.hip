@@ -121,7 +121,7 @@ extern "C" int dpl_mx_scale_search(int32_t elem, const float* d_x, uint64_t oute
     if (mx_check(rc, who, elem, "d_x and d_scales", {d_x, d_scales}, outer, k, inner, false, nullptr)) return rc;
     MxPlan p;
     if ((rc = mx_plan(p, who, (uintptr_t)d_x, outer, k, inner, false)) != 0) return rc;
-    return mx_dispatch(elem, inner == 1, p.vec, [&](auto E, auto ROWS, auto VEC) {
+    return mx_dispatch_all(elem, inner == 1, p.vec, [&](auto E, auto ROWS, auto VEC) {
         if constexpr (ROWS) {
             hipLaunchKernelGGL((k_mx_scale_search_rows<E, VEC>), dim3((unsigned)p.blocks), dim3(kBlock), 0, (hipStream_t)s, d_x, p.n, p.K, p.nblk,
                                d_scales, d_err_or_null);

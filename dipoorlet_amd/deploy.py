@@ -109,7 +109,7 @@ def gen_ocp_fp8_scales(graph, clip_val, args, **kwargs):
 
 
 def gen_ocp_mx_blocks(graph, act_clip_val, weight_clip_val, args):
-    """--mx: {"format": "mxfp8" | "mxfp4", "block_size": 32, "tensors": {name: {"axis": k, "constant": bool}}} ->
+    """--mx: {"format": "mxfp8" | "mxfp6_e2m3" | "mxfp6_e3m2" | "mxfp4", "block_size": 32, "tensors": {name: {"axis": k, "constant": bool}}} ->
     ocp_mx_blocks.json — the operands of MatMul / Gemm that the fake-quantised graph block-scales, and along which axis (an MX
     node has no static scale to list).  A tensor's first node goes by the tensor's name, a second one along another axis by the
     name with that node's suffix (`_ax<k>`).  With --mx_rotate also "rotation": {"block_size": 32, "activations": [...], "weights":
@@ -187,7 +187,9 @@ def gen_ocp_mx_weights(graph, qnodes, args):
       ocp_mx_weights.json   {"format", "block_size": 32, "layout": "k_innermost", "tensors": {key: {"initializer", "shape", "axis",
                             "k", "k_padded", "codes": {"offset", "nbytes", "shape"}, "scales": {"offset", "nbytes", "shape"}}}}
     Both arrays are K-innermost: the block axis is moved to the end and padded with code 0 to k_padded = 32 * ceil(k / 32); mxfp4
-    holds two codes to a byte, the even index along k in the low nibble.  The element format is the tensor's node's (--mx_mixed: the
+    holds two codes to a byte, the even index along k in the low nibble; the two mxfp6 formats hold a block's 32 codes as one
+    little-endian string of 192 bits, code i in bits [6 i, 6 i + 6) (tests/mx_fp6_model.py), so a codes section is rows * k_padded
+    bytes for mxfp8, rows * k_padded * 3 / 4 for mxfp6_e2m3 / mxfp6_e3m2 and rows * k_padded / 2 for mxfp4.  The element format is the tensor's node's (--mx_mixed: the
     file then says "format": "mixed" and every entry its own "format").  A tensor whose node carries searched scales
     (--mx_scale_search) is encoded under those bytes (ops.mx_encode_scaled; tests/mx_scale_model.py)."""
     import torch

@@ -20,7 +20,7 @@ Choice       choose(): every candidate starts at mxfp4; gain = e4 - e8, cost = 4
              one walk promotes a node when the promoted costs stay <= (BITS - 4) * (the elements of all candidates) — a node that
              does not fit is skipped and the walk goes on.  Both operands of a promoted node become mxfp8.
 -> {node name: format} of the candidates, which quantize.insert_fake_quant_node consults (args.mx_formats) in place of
-mx_setting_table[args.mx]; rank 0 writes mx_mixed_report.json.
+platform_settings.mx_setting(args.mx); rank 0 writes mx_mixed_report.json.
 """
 import json
 import math

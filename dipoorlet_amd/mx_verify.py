@@ -11,8 +11,8 @@ nodes, multiplies the operands as BYTES on CDNA4's block-scaled matrix instructi
 then alpha / beta / bias as the node defines them, in torch, and compares with the node's own output in the same forward: an fp32
 product of dequantised values.  The bound is that of ops.mx_gemm against its definition, BOUND_FACTOR[format] * Kp * 2^-23 * S
 (S = |A^| . |B^|, computed in the run from the decoded bytes), taken twice because the node's side carries an fp32 summation too —
-plus, for a Gemm with a bias, the same factor on |beta . C|.  The factor is 1 for mxfp4, where the instruction adds exact products
-(measured: no error).  For mxfp8 it is twice the worst ratio measured on random data (tests/test_mx_gemm_gpu.py test 4): the
+plus, for a Gemm with a bias, the same factor on |beta . C|.  The factor is 1 for mxfp4 and mxfp6_e2m3, where the instruction adds exact products
+(measured: no error), and twice the worst measured ratio, 10.38, for mxfp6_e3m2.  For mxfp8 it is twice the worst ratio measured on random data (tests/test_mx_gemm_gpu.py test 4): the
 instruction truncates the E4M3 products of every run of 8 consecutive k to 2^-14 of the run's largest before it adds them, which
 loses up to 7 * 2^-14 * S whatever Kp is.  The element format is the node's own, read from its two MX nodes (they
 agree; under --mx_mixed ocp_mx_weights.json says "mixed", every tensor's entry names its format, and so does every node's entry of
@@ -32,7 +32,11 @@ import torch
 from .utils import logger
 
 REPORT = "mx_verify_report.json"
-BOUND_FACTOR = {"mxfp4": 1.0, "mxfp8": 2 * 19.51}      # on Kp * 2^-23 * S; mxfp8: twice the worst measured ratio, 19.51
+BOUND_FACTOR = {"mxfp4": 1.0, "mxfp8": 2 * 19.51,      # on Kp * 2^-23 * S; mxfp8: twice the worst measured ratio, 19.51
+                # the two MXFP6 formats on the same data and shapes (tests/test_mx_fp6_gemm_gpu.py test 5): E2M3 x E2M3
+                # measured 0 and 0 — its products, about 12 bits wide, are added exactly — so factor 1 as for mxfp4; E3M2 x E3M2
+                # measured 5.007 on [34, 96] x [96, 24] and 10.38 on [2, 17, 64] x [64, 48]: twice the worst
+                "mxfp6_e2m3": 1.0, "mxfp6_e3m2": 2 * 10.38}
 
 
 def _packed_from_file(entry, blob, dev):

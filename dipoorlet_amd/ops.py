@@ -1105,14 +1105,18 @@ def fake_quant_fp8(x, scale, axis=None, out=None, pre=None, x2=None):
     return y
 
 
-MX_ELEM = {"mxfp8": _hip.MX_E4M3, "mxfp4": _hip.MX_E2M1}     # include/dipoorlet_hip.h DPL_MX_*
+MX_ELEM = {"mxfp8": _hip.MX_E4M3, "mxfp4": _hip.MX_E2M1,     # include/dipoorlet_hip.h DPL_MX_*
+           "mxfp6_e2m3": _hip.MX_E2M3, "mxfp6_e3m2": _hip.MX_E3M2}
+MX_CODE_BITS = {"mxfp8": 8, "mxfp4": 4, "mxfp6_e2m3": 6, "mxfp6_e3m2": 6}     # of an element code in the packed form (mx_encode)
+MX_ELEM_MIXED = ("mxfp8", "mxfp4")      # what mx_gemm_err (--mx_mixed) and gptq_mx_block (--mx_gptq) are held to: no FP6 format
 MX_BLOCK = 32
+_MX_ELEM_WORDS = "elem must be 'mxfp8' or 'mxfp4' (or 'mxfp6_e2m3' / 'mxfp6_e3m2')"
 
 
 def fake_quant_mx(x, axis, elem, out=None, scales=None):
     """The OCP Microscaling Q/DQ pair (dpl_fake_quant_mx; tests/mx_model.py is the definition): every 32 consecutive elements
     along `axis` (negative: from the end) share a power-of-two scale taken from their largest |v|, and are rounded to FP8 E4M3
-    (elem 'mxfp8') or FP4 E2M1 ('mxfp4') under it.  No parameters: the scales are the data's own.  out: as fake_quant (may be x);
+    (elem 'mxfp8'), FP6 E2M3 / E3M2 ('mxfp6_e2m3' / 'mxfp6_e3m2'; tests/mx_fp6_model.py is their definition) or FP4 E2M1 ('mxfp4') under it.  No parameters: the scales are the data's own.  out: as fake_quant (may be x);
     scales: an optional uint8 device tensor of [outer, ceil(K / 32), inner] elements that receives the E8M0 codes (0xFF: a block
     that holds a NaN or an infinity, whose elements all come out NaN)."""
     _require_cuda(x, "x")
@@ -1143,7 +1147,7 @@ def _mx_out(who, out, shape, device, what):
 def _mx_split(who, shape, axis, elem):
     """The argument checks fake_quant_mx, mx_encode and mx_decode share -> (axis from the front, outer, k, inner)."""
     if elem not in MX_ELEM:
-        raise _hip.DipoorletHipError(f"{who}: elem must be 'mxfp8' or 'mxfp4', got {elem!r}")
+        raise _hip.DipoorletHipError(f"{who}: {_MX_ELEM_WORDS}, got {elem!r}")
     nd = len(shape)
     if not isinstance(axis, int) or not -nd <= axis < nd:
         raise _hip.DipoorletHipError(f"{who}: axis {axis!r} out of range for a tensor of {nd} dimension(s)")
@@ -1158,18 +1162,19 @@ def _mx_split(who, shape, axis, elem):
 
 def mx_packed_shapes(shape, axis, elem):
     """(codes shape, scales shape) of an MX tensor of `shape` blocked along `axis` as mx_encode writes it: K-innermost, [*outer
-    dims, *inner dims, Kp (mxfp8) or Kp / 2 (mxfp4)] and [..., Kp / 32] with Kp = 32 * ceil(K / 32)."""
+    dims, *inner dims, Kp (mxfp8), Kp * 3 / 4 (the two mxfp6) or Kp / 2 (mxfp4)] and [..., Kp / 32] with Kp = 32 * ceil(K / 32)."""
     axis, _, k, _ = _mx_split("mx_packed_shapes", tuple(shape), axis, elem)
     kp = MX_BLOCK * -(-k // MX_BLOCK)
     lead = tuple(int(d) for d in shape[:axis]) + tuple(int(d) for d in shape[axis + 1:])
-    return lead + (kp // 2 if elem == "mxfp4" else kp,), lead + (kp // MX_BLOCK,)
+    return lead + (kp * MX_CODE_BITS[elem] // 8,), lead + (kp // MX_BLOCK,)
 
 
 def mx_encode(x, axis, elem):
     """`--mx_pack`: what fake_quant_mx(x, axis, elem) computes, as bytes (dpl_mx_encode; tests/mx_pack_model.py is the definition)
     -> (codes, scales), uint8 device tensors.  scales: the E8M0 byte per block (0xFF: the block holds a NaN or an infinity);
-    codes: OCP FP8 E4M3FN bytes ('mxfp8'; 0x7F in a 0xFF block) or E2M1 nibbles, two to a byte, the even index along `axis` in the
-    low nibble ('mxfp4'; 0 in a 0xFF block).  Both are K-INNERMOST — mx_packed_shapes(x.shape, axis, elem): the block axis moves
+    codes: OCP FP8 E4M3FN bytes ('mxfp8'; 0x7F in a 0xFF block), E2M1 nibbles, two to a byte, the even index along `axis` in the
+    low nibble ('mxfp4'; 0 in a 0xFF block), or 6-bit codes, a block's 32 as one little-endian string of 192 bits with code i in
+    bits [6 i, 6 i + 6) (the two 'mxfp6'; 0 in a 0xFF block).  Both are K-INNERMOST — mx_packed_shapes(x.shape, axis, elem): the block axis moves
     to the end, padded with code 0 to a multiple of 32 —, which for an axis that is not the last is a transpose of x's element
     order, and not the order of fake_quant_mx's scales=."""
     _require_cuda(x, "x")
@@ -1270,16 +1275,17 @@ def _mx_packed_pair(who, a, b, elem_a, elem_b, dims_ok, kp, how):
     elem_b = elem_a if elem_b is None else elem_b
     for e in (elem_a, elem_b):
         if e not in MX_ELEM:
-            raise _hip.DipoorletHipError(f"{who}: elem must be 'mxfp8' or 'mxfp4', got {e!r}")
+            raise _hip.DipoorletHipError(f"{who}: {_MX_ELEM_WORDS}, got {e!r}")
     for t, name in ((a[0], "a_codes"), (a[1], "a_scales"), (b[0], "b_codes"), (b[1], "b_scales")):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == a[0].device):
             raise _hip.DipoorletHipError(f"{who}: {name} must be a contiguous uint8 ROCm device tensor on one device; dipoorlet_amd has no CPU path")
 
     def split(codes, scales, dims, elem, label):
-        per = 2 if elem == "mxfp4" else 1                      # codes to a byte
+        bits = MX_CODE_BITS[elem]
+        part = {8: "", 6: " * 3 / 4", 4: " / 2"}[bits]          # of Kp: the bytes of a row of codes
         if not (dims_ok(codes.dim()) and scales.dim() == codes.dim() and tuple(scales.shape[:-1]) == tuple(codes.shape[:-1])
-                and int(codes.shape[-1]) * per == MX_BLOCK * int(scales.shape[-1])):
-            raise _hip.DipoorletHipError(f"{who}: {label} must be codes [{dims}, {kp}{' / 2' if per == 2 else ''}] and scales [{dims}, {kp} / "
+                and int(codes.shape[-1]) * 8 == bits * MX_BLOCK * int(scales.shape[-1])):
+            raise _hip.DipoorletHipError(f"{who}: {label} must be codes [{dims}, {kp}{part}] and scales [{dims}, {kp} / "
                                          f"{MX_BLOCK}] as mx_encode writes {elem}{how} (K-innermost), got {list(codes.shape)} and "
                                          f"{list(scales.shape)}")
         return tuple(int(d) for d in codes.shape[:-1]), int(scales.shape[-1])
@@ -1324,6 +1330,9 @@ def mx_gemm_err(a_codes, a_scales, b_codes, b_scales, ref, elem_a, elem_b=None, 
     [*batch, tiles_m, tiles_n, 2], per 64 x 64 tile of C the sums of d * d and of ref * ref over the tile's elements, d = (C + bias)
     - ref in fp32, each square exact in fp64 and the additions in the kernel's fixed order.  A NaN of C (mx_gemm's rule) makes its
     tile's first sum NaN.  out: an optional contiguous fp64 device tensor of that shape."""
+    for e in (elem_a, elem_a if elem_b is None else elem_b):
+        if e not in MX_ELEM_MIXED:
+            raise _hip.DipoorletHipError(f"mx_gemm_err: elem must be 'mxfp8' or 'mxfp4' (--mx_mixed chooses between these two), got {e!r}")
     elem_b, lead, m, n, nblk, batch, b_batched = _mx_gemm_pair("mx_gemm_err", a_codes, a_scales, b_codes, b_scales, elem_a, elem_b)
     _require_cuda(ref, "ref")
     if tuple(ref.shape) != lead + (m, n) or ref.device != a_codes.device:
@@ -1482,8 +1491,8 @@ def gptq_mx_block(w, c0, nb, u, elem, err=None, scales=None):
     their columns; a tensor passed as scales= keeps every other column)."""
     _require_cuda(w, "w")
     _require_cuda(u, "u")
-    if elem not in MX_ELEM:
-        raise _hip.DipoorletHipError(f"gptq_mx_block: elem must be 'mxfp8' or 'mxfp4', got {elem!r}")
+    if elem not in MX_ELEM_MIXED:
+        raise _hip.DipoorletHipError(f"gptq_mx_block: elem must be 'mxfp8' or 'mxfp4' (the recursion is held to these two grids), got {elem!r}")
     if w.dim() != 2 or u.dim() != 2 or u.device != w.device:
         raise _hip.DipoorletHipError("gptq_mx_block: w and u must be matrices on one device")
     rows, k = int(w.shape[0]), int(w.shape[1])

@@ -59,3 +59,15 @@ mx_setting_table = {
     "mxfp8": {"bit_width": 8, "type": "MXFP8E4M3", "block_size": 32},
     "mxfp4": {"bit_width": 4, "type": "MXFP4E2M1", "block_size": 32},
 }
+# The two OCP MXFP6 formats of `--mx` (tests/mx_fp6_model.py), beside the table above: everything --mx offers but --mx_gptq and
+# --mx_mixed, which are held to the two formats of mx_setting_table.
+mx_fp6_setting_table = {
+    "mxfp6_e2m3": {"bit_width": 6, "type": "MXFP6E2M3", "block_size": 32},
+    "mxfp6_e3m2": {"bit_width": 6, "type": "MXFP6E3M2", "block_size": 32},
+}
+MX_CHOICES = tuple(mx_setting_table) + tuple(mx_fp6_setting_table)      # what --mx takes
+
+
+def mx_setting(name):
+    """The parameter set of `--mx name`: the one way from a format's name to its set, whichever table holds it."""
+    return mx_setting_table[name] if name in mx_setting_table else mx_fp6_setting_table[name]

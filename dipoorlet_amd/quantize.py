@@ -186,7 +186,7 @@ class _FP8(NumberFormat):
 
 
 class _MX(NumberFormat):
-    """OCP Microscaling (`--mx`, platform_settings.mx_setting_table): blocks of MX_BLOCK along QDQNode.block_axis share a
+    """OCP Microscaling (`--mx`, platform_settings.mx_setting_table and mx_fp6_setting_table): blocks of MX_BLOCK along QDQNode.block_axis share a
     power-of-two scale taken from the data — no static scale, no zero point, no initializers; the clip range is ignored.  ONNX has
     no dynamic block-scaled Q/DQ pair to expand into: the node is saved as ONE node of this project's own domain.
     `--mx_scale_search`: the node of a CONSTANT operand may carry its blocks' E8M0 bytes (QDQNode.mx_scales, ops.mx_scale_search of
@@ -234,11 +234,19 @@ class _MX(NumberFormat):
 FORMATS = {f.name: f for f in (_Linear("Linear"), _FP8(FP8_E4M3), _MX("MXFP8E4M3", "mxfp8", "float8e4m3fn", 448),
                                _MX("MXFP4E2M1", "mxfp4", "float4e2m1", 6))}
 MX_TYPES = {k: f for k, f in FORMATS.items() if f.block_scaled}
+# The two OCP MXFP6 formats (platform_settings.mx_fp6_setting_table; tests/mx_fp6_model.py): the records of _MX's kind that
+# --mx_gptq and --mx_mixed do not serve, kept beside the two they do.
+MX_FP6_TYPES = {f.name: f for f in (_MX("MXFP6E2M3", "mxfp6_e2m3", "float6e2m3", 7.5), _MX("MXFP6E3M2", "mxfp6_e3m2", "float6e3m2", 28))}
+
+
+def number_format(type_name):
+    """The record of a quantisation "type", or None: the one lookup every reader goes through, whichever table holds the record."""
+    return FORMATS.get(type_name) or MX_FP6_TYPES.get(type_name)
 
 
 class QDQNode:
     """The fused fake-quant stand-in for the reference's 2-node `graph_quant` (quantize.py:197-239).  `fmt`: the number format
-    of the grid, a key of FORMATS (`format`: its record).  `suffix`: appended to every name of the node — a tensor that already
+    of the grid, a key of FORMATS or MX_FP6_TYPES (`format`: its record, number_format).  `suffix`: appended to every name of the node — a tensor that already
     has a fake-quant node of another kind keeps that one's names for it."""
 
     def __init__(self, tensor_name, tensor_shape, scale, zero_point, need_transpose, per_channel, symmetric, fmt="Linear",
@@ -250,7 +258,7 @@ class QDQNode:
         self.per_channel = bool(per_channel)
         self.symmetric = bool(symmetric)
         self.axis = (1 if need_transpose else 0) if per_channel else None  # :214, :220
-        self.fmt, self.format = fmt, FORMATS[fmt]
+        self.fmt, self.format = fmt, number_format(fmt)
         self.block_axis = block_axis
         self.mx_scales = None           # (block-scaled nodes of constants, --mx_scale_search) uint8: one E8M0 byte per block
         self.suffix = suffix
@@ -305,8 +313,8 @@ def get_qnode_by_param(param, in_tensor_name, tensor_shape, range, need_transpos
     rely on it: a per-tensor platform collapses `range` to its overall min / max IN PLACE (type "Float8E4M3FN" too: scale =
     max(|lo|, |hi|) / 448, zero point 0, q_min / q_max = -448 / 448); `dynamic_sym` platforms switch a non-negative activation
     (|lo| < 1e-6) to the asymmetric grid — one more bit; `log_scale` snaps scales to powers of two.  An MX type
-    (mx_setting_table) ignores `range`: its node is block-scaled along `block_axis`, q_min / q_max = the element format's."""
-    fmt = FORMATS.get(param["type"])
+    (mx_setting_table, mx_fp6_setting_table) ignores `range`: its node is block-scaled along `block_axis`, q_min / q_max = the element format's."""
+    fmt = number_format(param["type"])
     if fmt is None:
         return None, None, None
     return fmt.qnode(param, in_tensor_name, tensor_shape, range, need_transpose, block_axis, suffix)
@@ -428,7 +436,7 @@ def _taken(act_quantized, name):
 def insert_fake_quant_node(graph, node, act_quantized, data_range_list, args):
     """quantize.py:40-95 for one node: derive the grid of every input that has a role, re-wire the input to the
     fake-quantised tensor, and insert the FakeQuant node unless the tensor already has one (`act_quantized`).
-    With args.mx ('mxfp8' / 'mxfp4'; -D ocp_fp8) both operands of a MatMul / Gemm — a constant one too, whatever its role — take
+    With args.mx ('mxfp8' / 'mxfp6_e2m3' / 'mxfp6_e3m2' / 'mxfp4': platform_settings.mx_setting; -D ocp_fp8) both operands of a MatMul / Gemm — a constant one too, whatever its role — take
     the MX parameter set instead, blocked along the operand's reduction axis (mx_block_axis); a Gemm bias is left to the platform's
     rules.  With args.mx_conv so do both operands of every Conv that mx_conv_left lets through, along axis 1; its bias too is left
     to the platform's rules.  `act_quantized` holds (name, axis) for such a node: a tensor wanted along two axes, or by a static consumer as well,
@@ -438,7 +446,7 @@ def insert_fake_quant_node(graph, node, act_quantized, data_range_list, args):
     format) and suffix `_ax<k>_<format>` for the one that is not args.mx's.
     With args.mx_scale_search the MX node of a constant operand carries error-minimising block scales (_MX.search_scales), computed
     here from the weight as it stands in `graph`; an activation's node keeps the floor rule."""
-    from .platform_settings import mx_setting_table, platform_setting_table
+    from .platform_settings import mx_setting, platform_setting_table
     plat = platform_setting_table[args.deploy]
     mx = getattr(args, "mx", None)
     if node.op_type not in MX_NODES and not (node.op_type == "Conv" and getattr(args, "mx_conv", False) and mx_conv_left(graph, node) is None):
@@ -452,7 +460,7 @@ def insert_fake_quant_node(graph, node, act_quantized, data_range_list, args):
             fmt = (getattr(args, "mx_formats", None) or {}).get(node.name, mx)     # (--mx_mixed: this node's own format)
             key = (name, axis) if fmt == mx else (name, axis, fmt)
             first = _taken(act_quantized, name)
-            q_nodes, _, _ = get_qnode_by_param(mx_setting_table[fmt], name, shape, None, block_axis=axis,
+            q_nodes, _, _ = get_qnode_by_param(mx_setting(fmt), name, shape, None, block_axis=axis,
                                                suffix="" if first in (None, key) else f"_ax{axis}" if fmt == mx else f"_ax{axis}_{fmt}")
             node.input[idx] = q_nodes.output
             if key not in act_quantized:

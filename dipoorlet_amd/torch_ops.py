@@ -16,7 +16,7 @@ Per tensor:
     dipoorlet::fake_quant_relu(Tensor x, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor          fq(relu(x))
     dipoorlet::fake_quant_add_relu(Tensor x, Tensor x2, Tensor scale, Tensor zero_point, int axis, int qlo, int qhi) -> Tensor
     dipoorlet::fake_quant_fp8(Tensor x, Tensor scale, int axis) -> Tensor      the pair on the OCP FP8 E4M3 grid (ops.fake_quant_fp8)
-    dipoorlet::fake_quant_mx(Tensor x, int axis, str elem) -> Tensor           the OCP Microscaling pair, 'mxfp8' / 'mxfp4', blocks of 32 along axis (ops.fake_quant_mx)
+    dipoorlet::fake_quant_mx(Tensor x, int axis, str elem) -> Tensor           the OCP Microscaling pair, 'mxfp8' / 'mxfp6_e2m3' / 'mxfp6_e3m2' / 'mxfp4', blocks of 32 along axis (ops.fake_quant_mx)
     dipoorlet::mx_encode(Tensor x, int axis, str elem) -> (Tensor, Tensor)     the same values as bytes: (element codes, E8M0 scales), uint8, K-innermost (ops.mx_encode: --mx_pack)
     dipoorlet::mx_decode(Tensor codes, Tensor scales, str elem, int[] shape, int axis) -> Tensor   those bytes back to fp32 of `shape` (ops.mx_decode)
     dipoorlet::mx_gemm(Tensor a_codes, Tensor a_scales, Tensor b_codes, Tensor b_scales, str elem_a, str elem_b) -> Tensor
@@ -414,7 +414,7 @@ def _(w, c0, nb, u, scale, zero_point, qlo, qhi, fmt):
 
 @torch.library.custom_op("dipoorlet::gptq_mx_block", mutates_args=("w",), device_types="cuda")
 def gptq_mx_block(w: torch.Tensor, c0: int, nb: int, u: torch.Tensor, elem: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    """elem 'mxfp8' or 'mxfp4'; w, u: contiguous fp32 matrices; whole MX blocks only (ops.gptq_mx_block)."""
+    """elem 'mxfp8' or 'mxfp4' (the two mxfp6 formats are refused: the recursion is held to two grids); w, u: contiguous fp32 matrices; whole MX blocks only (ops.gptq_mx_block)."""
     return ops.gptq_mx_block(w, c0, nb, u, elem)
 
 

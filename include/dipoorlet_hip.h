@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 35 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 36 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
                               25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
@@ -39,7 +39,8 @@ extern "C" {
                                   for constant MX operands, and the Q/DQ and the packed bytes under given scales: --mx_scale_search);
                               33: dpl_gptq_mx_block (dpl_gptq_block's recursion on the MX block-scaled grids: --mx_gptq);
                               34: dpl_mx_conv (a convolution of two packed MX operands on the block-scaled matrix instruction: --mx_conv);
-                              35: dpl_mx_gemm_err (dpl_mx_gemm's product against a reference, as per-tile fp64 error sums: --mx_mixed) */
+                              35: dpl_mx_gemm_err (dpl_mx_gemm's product against a reference, as per-tile fp64 error sums: --mx_mixed);
+                              36: DPL_MX_E2M3 / DPL_MX_E3M2 (the two OCP MXFP6 element formats, through the MX entry points there are) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -429,6 +430,16 @@ int dpl_fake_quant_fp8_items(const dpl_work_item* d_items, int64_t n_items, cons
  *      1 <= k, inner < 2^31; outer * k * inner == 0 is a no-op. */
 #define DPL_MX_E4M3 0
 #define DPL_MX_E2M1 1
+/* The two OCP MXFP6 formats (--mx mxfp6_e2m3 / mxfp6_e3m2; tests/mx_fp6_model.py is the definition).  Neither has NaN or inf codes.
+ *      DPL_MX_E2M3  S.EE.MMM, bias 1: m / 8 under the exponent field 0, else (1 + m / 8) * 2^(field - 1); largest value 7.5, emax 2.
+ *      DPL_MX_E3M2  S.EEE.MM, bias 3: m / 16 under the field 0, else (1 + m / 4) * 2^(field - 3); largest value 28, emax 4.
+ * dpl_fake_quant_mx, dpl_fake_quant_mx_scaled, dpl_mx_scale_search, dpl_mx_encode, dpl_mx_encode_scaled, dpl_mx_decode, dpl_mx_gemm and
+ * dpl_mx_conv take them; dpl_mx_gemm_err and dpl_gptq_mx_block are held to the first two.  Packed, a block's 32 codes are ONE little-endian
+ * string of 192 bits, 24 bytes: code i occupies bits [6 i, 6 i + 6), i.e. byte (6 i) / 8 from bit (6 i) % 8 upward, carrying into the
+ * next byte; codes [outer, inner, nblk * 24].  The codes' base must be 16-byte aligned as for the others (a block then lies at a
+ * multiple of 8 bytes).  In a 0xFF block every code is 0.  The codes 2 .. 5 are not formats. */
+#define DPL_MX_E2M3 6
+#define DPL_MX_E3M2 7
 int dpl_fake_quant_mx(int32_t elem, const float* d_x, float* d_y, uint64_t outer, uint64_t k, uint64_t inner,
                       uint8_t* d_scales_or_null, dpl_stream_t s);
 

@@ -1,4 +1,4 @@
-"""The MX Q/DQ kernel (dpl_fake_quant_mx, both element formats, both paths) beside the static FP8 one (dpl_fake_quant_fp8) on the
+"""The MX Q/DQ kernel (dpl_fake_quant_mx, all four element formats, both paths) beside the static FP8 one (dpl_fake_quant_fp8) on the
 same tensors, HIP events around each window.
 
 All three read 4 B and write 4 B per element, so the yardstick of the MX kernel is the FP8 kernel on the same tensors in this
@@ -23,7 +23,7 @@ import torch  # noqa: E402
 from dipoorlet_amd import ops  # noqa: E402
 
 PEAK_GBS = 8000.0
-KERNELS = ("fp8", "mxfp8", "mxfp4")
+KERNELS = ("fp8", "mxfp8", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp4")
 LAUNCHES = 16                  # per timed window
 POOL_BYTES = 512 * 1024 * 1024  # of inputs (and as much of outputs) per case: twice the Infinity Cache
 
@@ -66,7 +66,7 @@ def main():
             x, y = nxt()
             ops.fake_quant_fp8(x, s1, out=y)
         fns = {"fp8": fp8}
-        for elem in ("mxfp8", "mxfp4"):
+        for elem in KERNELS[1:]:
             def mx(nxt=nxt, axis=axis, elem=elem):
                 x, y = nxt()
                 ops.fake_quant_mx(x, axis, elem, out=y)
@@ -83,7 +83,7 @@ def main():
             f()
     ms = {(name, k): [] for name, _, fns in cases for k in fns}
     for r in range(a.rounds):
-        order = KERNELS[r % 3:] + KERNELS[:r % 3]      # rotate who goes first
+        order = KERNELS[r % len(KERNELS):] + KERNELS[:r % len(KERNELS)]      # rotate who goes first
         for name, _, fns in cases:
             for k in order:
                 ms[(name, k)].append(timed(lambda: window(fns[k])) / LAUNCHES)
@@ -99,7 +99,7 @@ def main():
         result.append(row)
         print(f"{name}: " + " | ".join(f"{k} {row[k]['median_gbs']:.0f} GB/s [{row[k]['min_gbs']:.0f} .. {row[k]['max_gbs']:.0f}] = "
                                        f"{row[k]['median_of_peak']:.3f} of 8 TB/s" for k in KERNELS)
-              + f" | mxfp8 / fp8 {row['mxfp8_over_fp8_median']:.3f}, mxfp4 / fp8 {row['mxfp4_over_fp8_median']:.3f}", flush=True)
+              + " | " + ", ".join(f"{k} / fp8 {row[k + '_over_fp8_median']:.3f}" for k in KERNELS[1:]), flush=True)
     if a.json:
         with open(a.json, "w") as f:
             json.dump({"rounds": a.rounds, "launches_per_window": LAUNCHES, "cases": result}, f, indent=1)

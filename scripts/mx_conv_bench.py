@@ -1,5 +1,5 @@
 """The block-scaled convolution of --mx_conv (dpl_mx_conv) beside what a checker would run without it — ops.mx_decode of both
-operands plus torch's fp32 convolution — on ResNet-50 layer shapes at 64 images, both element formats, HIP events around each
+operands plus torch's fp32 convolution — on ResNet-50 layer shapes at 64 images, all four element formats, HIP events around each
 window.
 
 scripts/mx_gemm_bench.py's method: every array a launch touches comes from a pool of more than 512 MB — twice the 256 MiB Infinity
@@ -67,9 +67,9 @@ def main():
         cp = 32 * -(-c // 32)
         cs = Ring([torch.empty(n, oh, ow, cout, device=dev) for _ in range(-(-POOL_BYTES // (4 * n * oh * ow * cout)))])
         a_hat, b_hat = torch.empty(n, c, h, w, device=dev), torch.empty(cout, c, k, k, device=dev)      # its decoded operands
-        for elem in ("mxfp8", "mxfp4"):
+        for elem in ("mxfp8", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp4"):
             e = ops.MX_ELEM[elem]
-            per = 2 if elem == "mxfp4" else 1
+            bits = ops.MX_CODE_BITS[elem]
             x, wt = torch.randn(n, c, h, w, device=dev), torch.randn(cout, c, k, k, device=dev)
 
             def pool(t, nbytes):      # valid code arrays, each its own data
@@ -77,7 +77,7 @@ def main():
                 for i in range(-(-POOL_BYTES // nbytes)):
                     out.append(ops.mx_encode(t.roll(i, 0) if i else t, 1, elem))
                 return Ring(out)
-            fa, fb = pool(x, n * h * w * cp // per), pool(wt, cout * k * k * cp // per)
+            fa, fb = pool(x, n * h * w * cp * bits // 8), pool(wt, cout * k * k * cp * bits // 8)
             del x, wt
             geo = (n, h, w, c, cout, k, k, stride, stride, pad, pad, 1, 1, oh, ow)
 

@@ -1,5 +1,5 @@
 """The block-scaled product of --mx_verify (dpl_mx_gemm) beside what a checker would run without it — ops.mx_decode of both
-operands plus torch.matmul in fp32 — on the two large products of a ViT-B MLP at 64 images, both element formats, HIP events
+operands plus torch.matmul in fp32 — on the two large products of a ViT-B MLP at 64 images, all four element formats, HIP events
 around each window.
 
 scripts/mx_bench.py's method: every array a launch touches comes from a pool of more than 512 MB — twice the 256 MiB Infinity
@@ -61,14 +61,14 @@ def main():
     for name, m, n, k in CASES:
         cs = Ring([torch.empty(m, n, device=dev) for _ in range(-(-POOL_BYTES // (4 * m * n)))])
         a_hat, b_hat = torch.empty(m, k, device=dev), torch.empty(n, k, device=dev)      # the yardstick's decoded operands
-        for elem in ("mxfp8", "mxfp4"):
+        for elem in ("mxfp8", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp4"):
             e = ops.MX_ELEM[elem]
-            per = 2 if elem == "mxfp4" else 1
+            bits = ops.MX_CODE_BITS[elem]
             x, w = torch.randn(m, k, device=dev), torch.randn(n, k, device=dev)
 
             def pool(t, rows):      # valid code arrays, each its own data
                 out = []
-                for i in range(-(-POOL_BYTES // (rows * k // per))):
+                for i in range(-(-POOL_BYTES // (rows * k * bits // 8))):
                     out.append(ops.mx_encode(t.roll(i, 0) if i else t, -1, elem))
                 return Ring(out)
             fa, fb = pool(x, m), pool(w, n)

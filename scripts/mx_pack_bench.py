@@ -1,11 +1,11 @@
 """The element-code kernels of --mx_pack (dpl_mx_encode, dpl_mx_decode) beside the MX Q/DQ kernel (dpl_fake_quant_mx) on the same
-tensors, both element formats, HIP events around each window.
+tensors, all four element formats, HIP events around each window.
 
 scripts/mx_bench.py's method and tensors: every array a launch touches comes from a pool of more than 512 MB — twice the 256 MiB
 Infinity Cache —, the fp32 tensors and the (four or eight times smaller, so that many more) code arrays alike, and every launch
 takes the next member of each pool, so that no launch finds its data in a cache; a timed window is LAUNCHES launches in a row
 between two events; rounds rotate which kernel goes first.  Encode and decode move fewer bytes than the Q/DQ kernel's 8 B per
-element — 4 + 1 + 1/32 (E4M3) or 4 + 0.5 + 1/32 (E2M1) —, so GB/s on their own bytes says how well they stream, and the yardstick
+element — 4 + 1 + 1/32 (E4M3), 4 + 0.75 + 1/32 (the two FP6) or 4 + 0.5 + 1/32 (E2M1) —, so GB/s on their own bytes says how well they stream, and the yardstick
 is the Q/DQ kernel's time per launch on the same tensor in the same run: all three are printed.
 
     python scripts/mx_pack_bench.py [--rounds 12] [--json out.json]
@@ -72,7 +72,7 @@ def main():
         xs = [torch.randn(shape, device=dev) for _ in range(pool)]
         ys = [torch.empty_like(xs[0]) for _ in range(pool)]
         fx, fy = Ring(xs), Ring(ys)
-        for elem in ("mxfp8", "mxfp4"):
+        for elem in ("mxfp8", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp4"):
             e = ops.MX_ELEM[elem]
             cs, ss = ops.mx_packed_shapes(shape, axis, elem)
             nc, ns = 1, 1
