@@ -110,6 +110,10 @@ def build_parser():
                         "per kernel call, 1 .. 128")
     p.add_argument("--gptq_damp", type=float, default=0.01,
                    help="--gptq: damp * mean(diag H) is added to the Hessian's diagonal before it is factorised; > 0")
+    p.add_argument("--gptq_factor", choices=["host", "device"], default="host",
+                   help="--gptq / --mx_gptq: where a layer's Hessian is factorised, in fp64 either way: 'host' (LAPACK on the CPU, one "
+                        "download and one upload per layer) or 'device' (the library's own blocked Cholesky and triangular inverse on "
+                        "the fp64 matrix instruction; gptq_report.json then says \"factor\": \"device\")")
     p.add_argument("--pattern", choices=["unstruction", "nv24"], default="unstruction")
     p.add_argument("--model_type", choices=["unet"], default=None)
     p.add_argument("--quant_format", default="QDQ", type=str, choices=["QOP", "QDQ"])
@@ -142,6 +146,8 @@ def check_args(args):
     if getattr(args, "mx_gptq", False) and getattr(args, "gptq", False):
         raise ValueError("--mx_gptq and --gptq cannot be combined: --mx_gptq runs --gptq's driver over the block-scaled weights and "
                          "the static ones alike")
+    if getattr(args, "gptq_factor", "host") != "host" and not (getattr(args, "gptq", False) or getattr(args, "mx_gptq", False)):
+        raise ValueError(f"--gptq_factor {args.gptq_factor} needs --gptq or --mx_gptq: it says where their Hessians are factorised")
     if getattr(args, "gptq", False):
         for flag in ("adaround", "brecq", "sparse"):
             if getattr(args, flag, False):

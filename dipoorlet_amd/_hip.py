@@ -15,11 +15,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPL_LIB: another build of the same sources (the host-sanitizer build of scripts/asan_host_check.sh); never a different code path
 LIB_PATH = os.environ.get("DPL_LIB") or os.path.join(_HERE, "csrc", "libdipoorlet_hip.so")
 
-ABI_VERSION = 36
+ABI_VERSION = 37
 MAX_BINS = 16384
 GRID_UNIFORM, GRID_E4M3 = 0, 1          # DPL_GRID_*: the grids of dpl_hist_qmse
 HIST_SPEC_MAX_TENSORS = 2048
 GPTQ_MAX_BLOCK = 128                   # DPL_GPTQ_MAX_BLOCK
+GPTQ_FACTOR_MAX_K = 16384              # DPL_GPTQ_FACTOR_MAX_K
 MX_E4M3, MX_E2M1, MX_E2M3, MX_E3M2 = 0, 1, 6, 7                # DPL_MX_*: the element formats of dpl_fake_quant_mx, dpl_mx_encode / _decode
 
 
@@ -147,6 +148,9 @@ SIGNATURES = {
     "dpl_mx_conv": (C.c_int, [_I32, _I32, _P, _P, _P, _P] + [_I64] * 15 + [_P, _P]),
     "dpl_gptq_block": (C.c_int, [_P, _I64, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
     "dpl_gptq_mx_block": (C.c_int, [_I32, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _P]),
+    "dpl_gptq_factor_workspace": (_U64, [_I64]),
+    "dpl_gptq_factor": (C.c_int, [_P, _I64, _DBL, _P, _P, _P, _U64, _P]),
+    "dpl_gptq_factor_phase": (C.c_int, [_P, _I64, _DBL, _P, _P, _P, _U64, _I32, _P]),
     "dpl_cos_accumulate": (C.c_int, [_P, _P, _I64, _P, _I64, _P]),
     "dpl_channel_diff_sum": (C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
     "dpl_cos_items_accumulate": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P]),

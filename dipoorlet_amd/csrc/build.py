@@ -7,16 +7,23 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = [os.path.join(HERE, f) for f in ("calib_kernels.hip", "fake_quant_kernels.hip", "side_kernels.hip", "runtime_abi.hip", "octav_kernels.hip",
                                        "octav_tail_host.hip", "round_kernels.hip", "gemm_small.hip", "mx_kernels.hip", "mx_pack_kernels.hip", "gptq_kernels.hip",
                                        "hadamard_kernels.hip", "mx_gemm_kernels.hip", "mx_search_kernels.hip", "mx_conv_kernels.hip")]
+# Built on their own, with the packed fp32 instructions (v_pk_*_f32) switched off for the device code, and linked in as objects: the fp64
+# factorisation has no use for them.  (A command-line feature, not a function attribute: the runtime header's inline functions,
+# __syncthreads among them, must have the same features as their callers or they are not inlined.  The host pass notes that it does
+# not know the feature and ignores it.)
+SRC_NO_PACKED_FP32 = [os.path.join(HERE, "gptq_factor_kernels.hip")]
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HDR = [os.path.join(HERE, "..", "..", "include", "dipoorlet_hip.h"), os.path.join(HERE, "common.hpp"),
        os.path.join(HERE, "octav_common.hpp"), os.path.join(HERE, "octav_wave.hpp"), os.path.join(HERE, "octav_tail.hpp"),
        os.path.join(HERE, "octav_rescue.hpp"), os.path.join(HERE, "mx_format.hpp"), os.path.join(HERE, "mx_block.hpp"), os.path.join(HERE, "mx_plan.hpp"), os.path.join(HERE, "mx_search.hpp"),
        os.path.join(HERE, "host_plan.hpp"), os.path.join(HERE, "host_error.hpp"), os.path.join(HERE, "octav_geometry.hpp"), os.path.join(HERE, "fq_elem.hpp"),
-       os.path.join(HERE, "mx_mfma.hpp")]
+       os.path.join(HERE, "mx_mfma.hpp"), os.path.join(HERE, "gptq_factor_plan.hpp")]
 OUT = os.path.join(HERE, "libdipoorlet_hip.so")
 
 
@@ -31,21 +38,26 @@ def needs_build():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    return any(os.path.getmtime(f) > t for f in SRC + HDR + [os.path.abspath(__file__)])
+    return any(os.path.getmtime(f) > t for f in SRC + SRC_NO_PACKED_FP32 + HDR + [os.path.abspath(__file__)])
 
 
 def build(force=False, verbose=False):
     if not force and not needs_build():
         return OUT
-    cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC",
-           "-fno-fast-math", "-ffp-contract=off", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-o", OUT] + SRC
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc failed:\n" + r.stdout + r.stderr)
-    if verbose and r.stderr.strip():
-        print(r.stderr)
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off", "-munsafe-fp-atomics", "-Wall",
+             "-Wno-unused-function"]
+    with tempfile.TemporaryDirectory() as tmp:
+        objs = [os.path.join(tmp, os.path.splitext(os.path.basename(f))[0] + ".o") for f in SRC_NO_PACKED_FP32]
+        cmds = [[hipcc_path()] + flags + NO_PACKED_FP32 + ["-c", f, "-o", o] for f, o in zip(SRC_NO_PACKED_FP32, objs)]
+        cmds.append([hipcc_path()] + flags + ["-shared", "-o", OUT] + objs + SRC)      # (objects first: hipcc puts -x hip before each source)
+        for cmd in cmds:
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError("hipcc failed:\n" + r.stdout + r.stderr)
+            if verbose and r.stderr.strip():
+                print(r.stderr)
     return OUT
 
 

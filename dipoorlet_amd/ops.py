@@ -1482,6 +1482,36 @@ def gptq_quantize(w, u, grid, block=GPTQ_MAX_BLOCK):
     return wq, err
 
 
+GPTQ_FACTOR_MAX_K = _hip.GPTQ_FACTOR_MAX_K
+
+
+def gptq_factor(H, damp=0.01, retries=3):
+    """GPTQ's Hessian factorisation on the device (dpl_gptq_factor, csrc/gptq_factor_kernels.hip; tests/gptq_model.py factor is the
+    definition).  H: fp64 device tensor [K, K], contiguous, symmetric (not modified).  -> (U fp64 [K, K] on H's device, upper, with
+    (H')^-1 = U^T U, the damping used), H' = H with dead columns' (H[j, j] == 0) diagonal set to 1 plus damp * mean(diag H') * I — or
+    (None, the last damping) when the factorisation still fails after the damping has been multiplied by 10 `retries` times.  One
+    attempt is one call; after each the status word (a pivot that was not > 0) and U's finiteness are read back."""
+    if not (isinstance(H, torch.Tensor) and H.is_cuda and H.dtype == torch.float64 and H.is_contiguous()):
+        raise _hip.DipoorletHipError("gptq_factor: H must be a contiguous float64 ROCm device tensor; dipoorlet_amd has no CPU path")
+    if H.dim() != 2 or H.shape[0] != H.shape[1] or not 1 <= int(H.shape[0]) <= GPTQ_FACTOR_MAX_K:
+        raise _hip.DipoorletHipError(f"gptq_factor: H must be [K, K] with 1 <= K <= {GPTQ_FACTOR_MAX_K}, got {tuple(H.shape)}")
+    damp = float(damp)
+    if not damp > 0.0:      # (a NaN too)
+        raise _hip.DipoorletHipError(f"gptq_factor: damp must be positive, got {damp}")
+    K = int(H.shape[0])
+    with torch.cuda.device(H.device):
+        nbytes = int(_hip.lib().dpl_gptq_factor_workspace(K))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=H.device)
+        U = torch.empty((K, K), dtype=torch.float64, device=H.device)
+        status = torch.empty(1, dtype=torch.int32, device=H.device)
+        for _ in range(int(retries) + 1):
+            _hip.check(_hip.lib().dpl_gptq_factor(_ptr(H), K, damp, _ptr(U), _ptr(status), _ptr(ws), nbytes, _stream()), "dpl_gptq_factor")
+            if int(status.item()) == 0 and bool(torch.isfinite(U).all()):
+                return U, damp
+            damp *= 10.0
+    return None, damp
+
+
 def gptq_mx_block(w, c0, nb, u, elem, err=None, scales=None):
     """One call of GPTQ's column recursion on an MX block-scaled grid, in place (dpl_gptq_mx_block; tests/mx_gptq_model.py
     gptq_mx_block is the definition, matched bit for bit): gptq_block with the grid of every block of 32 columns fixed when the

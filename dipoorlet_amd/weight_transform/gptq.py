@@ -6,7 +6,8 @@ Conv (group 1, two spatial axes) and Gemm whose weight the graph fake-quantises:
   * H = sum X^T X / rows over the node's fake-quantised input — a Gemm's input rows, a Conv's unfolded patches (pads applied
     explicitly, so asymmetric ONNX pads are right) — fp32 GEMMs per slab summed in fp64, one fp64 SUM all-reduce per node;
   * U = the upper Cholesky factor of (H + damp * mean(diag H) * I)^-1, on the host in fp64 (factor(): every rank computes the same
-    matrix, whatever device solver the torch build ships);
+    matrix, whatever device solver the torch build ships) — or, with --gptq_factor device, in fp64 on the device by the library's
+    own kernels (ops.gptq_factor: a fixed summation order, so every rank still computes the same matrix; H never leaves the device);
   * ops.gptq_quantize rounds the weight column by column (csrc/gptq_kernels.hip) under the grid of the very get_qnode_by_param call
     insert_fake_quant_node makes for that initializer: the graph's own Q/DQ node leaves the result unchanged;
   * the new weight goes into the result, the fake-quantised graph and its session before the node runs, so everything downstream is
@@ -186,6 +187,9 @@ def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
     ori_nodes = {n.name: n for n in graph.graph.node}
     mx_gptq = bool(getattr(args, "mx_gptq", False))
     flag = "--mx_gptq" if mx_gptq else "--gptq"
+    on_device = getattr(args, "gptq_factor", "host") == "device"
+    if rank == 0:
+        logger.info("%s: the Hessians are factorised on the %s", flag, "device (ops.gptq_factor)" if on_device else "host (factor)")
     visited = (MX_GPTQ_NODE_TYPES if mx_gptq else GPTQ_NODE_TYPES) + LEFT_NODE_TYPES
     report, left = [], []
     with torch.no_grad():
@@ -224,7 +228,7 @@ def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
             if walk.world > 1:
                 dist.all_reduce(acc)
             H = acc[:K * K].view(K, K) / acc[K * K]
-            U, damp = factor(H.cpu(), damp0)
+            U, damp = ops.gptq_factor(H.contiguous(), damp0, _DAMP_RETRIES) if on_device else factor(H.cpu(), damp0)
             w_near = ops.gptq_nearest(w2d, grid) if elem is None else ops.gptq_mx_nearest(w2d, elem)
             entry = {"node": node.name, "rows": int(R), "cols": int(K), "damp": damp, "kept": "nearest",
                      "objective_nearest": _objective(w_near, w2d, H), "objective_gptq": None}
@@ -254,5 +258,6 @@ def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
             "".join("\n  {}: {}".format(n, w) for n, w in left)))
         if getattr(args, "output_dir", None):
             with open(os.path.join(args.output_dir, "gptq_report.json"), "w") as f:
-                json.dump({"layers": report, "left": [{"node": n, "why": w} for n, w in left]}, f, indent=1)
+                json.dump({"layers": report, "left": [{"node": n, "why": w} for n, w in left], **({"factor": "device"} if on_device else {})},
+                          f, indent=1)
     return walk.finish("gptq"), report

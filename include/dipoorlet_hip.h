@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DPL_ABI_VERSION 36 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
+#define DPL_ABI_VERSION 37 /* 20: dpl_fake_quant_pre (the producer's ReLU / Add + ReLU inside the Q/DQ kernel); 21: dpl_stream_*; 22: dpl_hist_kl;
                               23: dpl_minmax_hist_accumulate / dpl_hist_spec_* (a batch's histogram taken in the range pass);
                               24: dpl_fake_quant_fp8 / dpl_fake_quant_fp8_items (the Q/DQ pair on the OCP FP8 E4M3 grid);
                               25: dpl_hist_qmse (quantisation-MSE clip search on the integer or the E4M3 grid);
@@ -40,7 +40,9 @@ extern "C" {
                               33: dpl_gptq_mx_block (dpl_gptq_block's recursion on the MX block-scaled grids: --mx_gptq);
                               34: dpl_mx_conv (a convolution of two packed MX operands on the block-scaled matrix instruction: --mx_conv);
                               35: dpl_mx_gemm_err (dpl_mx_gemm's product against a reference, as per-tile fp64 error sums: --mx_mixed);
-                              36: DPL_MX_E2M3 / DPL_MX_E3M2 (the two OCP MXFP6 element formats, through the MX entry points there are) */
+                              36: DPL_MX_E2M3 / DPL_MX_E3M2 (the two OCP MXFP6 element formats, through the MX entry points there are);
+                              37: dpl_gptq_factor / dpl_gptq_factor_workspace / dpl_gptq_factor_phase (GPTQ's fp64 Hessian factorisation on the device, whole
+                                  and in its two phases for timing: --gptq_factor device) */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -602,6 +604,26 @@ int dpl_gptq_block(float* d_w, int64_t rows, int64_t ldw, int64_t c0, int64_t nb
  *      ld_scales >= ceil(k / 32); rows below 2^31, rows <= 0 is a no-op.  A refused call (-2) launches nothing. */
 int dpl_gptq_mx_block(int32_t elem, float* d_w, int64_t rows, int64_t ldw, int64_t k, int64_t c0, int64_t nb, const float* d_u, int64_t ldu,
                       float* d_err, uint8_t* d_scales, int64_t ld_scales, dpl_stream_t s);
+
+/* ---- GPTQ's Hessian factorisation on the device (--gptq_factor device; fp64 throughout; csrc/gptq_factor_kernels.hip, DESIGN.md
+ *      §3w).  d_h: [k, k] fp64 contiguous, symmetric, not modified.  With H' = H, every diagonal element that is 0 set to 1, plus
+ *      damp * mean(diag) * I (the mean taken after the 1s, in a fixed order), d_u: [k, k] fp64 receives U, the upper Cholesky factor of
+ *      H'^-1 (H'^-1 = U^T U, U H' U^T = I; positive diagonal, exact zeros below it): what tests/gptq_model.py factor computes at one
+ *      damping, by one blocked Cholesky factorisation of the index-reversed H' and one triangular inverse on
+ *      v_mfma_f64_16x16x4_f64.  ONE attempt: *d_status becomes 0, or 1 + the column of H whose pivot was the first not > 0 (a NaN
+ *      too; never 0 after a bad pivot); d_u then holds whatever the arithmetic gave (NaNs as a rule) and the caller retries with more damping.  Every sum has one
+ *      fixed order: the same sources on the same hardware give the same bits.  d_workspace: dpl_gptq_factor_workspace(k) bytes of
+ *      device memory ((2 kp^2 + 64 kp) * 8, kp = k rounded up to a multiple of 64; 0 for a k outside [1, DPL_GPTQ_FACTOR_MAX_K]),
+ *      overwritten.  Refused (-2), nothing launched: a null pointer, k outside [1, DPL_GPTQ_FACTOR_MAX_K], damp not > 0 (a NaN
+ *      too), workspace_bytes too small.
+ *      dpl_gptq_factor_phase: the same call in parts, for timing (scripts/gptq_factor_bench.py): phases 1 the Cholesky factorisation
+ *      into the workspace (and the status word), 2 the inverse and d_u from the workspace a phase-1 call of the same k left, 3 both. */
+#define DPL_GPTQ_FACTOR_MAX_K 16384
+uint64_t dpl_gptq_factor_workspace(int64_t k);
+int dpl_gptq_factor(const double* d_h, int64_t k, double damp, double* d_u, int32_t* d_status, void* d_workspace, uint64_t workspace_bytes,
+                    dpl_stream_t s);
+int dpl_gptq_factor_phase(const double* d_h, int64_t k, double damp, double* d_u, int32_t* d_status, void* d_workspace,
+                          uint64_t workspace_bytes, int32_t phases, dpl_stream_t s);
 
 /* ---- cosine-similarity partial sums (utils.py:273-278): d_acc[slot*3 + {0,1,2}] += sum(a*b), sum(a*a),
  *      sum(b*b) in fp64. */
