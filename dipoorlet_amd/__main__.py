@@ -114,6 +114,11 @@ def build_parser():
                    help="--gptq / --mx_gptq: where a layer's Hessian is factorised, in fp64 either way: 'host' (LAPACK on the CPU, one "
                         "download and one upload per layer) or 'device' (the library's own blocked Cholesky and triangular inverse on "
                         "the fp64 matrix instruction; gptq_report.json then says \"factor\": \"device\")")
+    p.add_argument("--gptq_hessian", choices=["blas", "device"], default="blas",
+                   help="--gptq / --mx_gptq: how a layer's Hessian sum X^T X is formed: 'blas' (unfold for a Conv, fp32 GEMMs per slab "
+                        "on the BLAS library, the slabs added in fp64) or 'device' (the library's own fp64 kernel straight from the "
+                        "activation: Conv patches gathered in the kernel, exact products summed in fp64 in one fixed order on the fp64 "
+                        "matrix instruction; gptq_report.json then says \"hessian\": \"device\")")
     p.add_argument("--pattern", choices=["unstruction", "nv24"], default="unstruction")
     p.add_argument("--model_type", choices=["unet"], default=None)
     p.add_argument("--quant_format", default="QDQ", type=str, choices=["QOP", "QDQ"])
@@ -148,6 +153,8 @@ def check_args(args):
                          "the static ones alike")
     if getattr(args, "gptq_factor", "host") != "host" and not (getattr(args, "gptq", False) or getattr(args, "mx_gptq", False)):
         raise ValueError(f"--gptq_factor {args.gptq_factor} needs --gptq or --mx_gptq: it says where their Hessians are factorised")
+    if getattr(args, "gptq_hessian", "blas") != "blas" and not (getattr(args, "gptq", False) or getattr(args, "mx_gptq", False)):
+        raise ValueError(f"--gptq_hessian {args.gptq_hessian} needs --gptq or --mx_gptq: it says how their Hessians are summed")
     if getattr(args, "gptq", False):
         for flag in ("adaround", "brecq", "sparse"):
             if getattr(args, flag, False):

@@ -52,6 +52,12 @@ class RoundStepParams(C.Structure):
                 ("reserved2", C.c_float)]
 
 
+class GptqHessianGeom(C.Structure):
+    """dpl_gptq_hessian_geom: the convolution whose patches are the rows of X (dpl_gptq_hessian's conv form)."""
+    _fields_ = [(f, C.c_int64) for f in ("batch", "channels", "height", "width", "kh", "kw", "stride_h", "stride_w",
+                                         "pad_top", "pad_left", "pad_bottom", "pad_right", "dil_h", "dil_w")]
+
+
 class FakeQuantParams(C.Structure):
     """dpl_fake_quant_params: one tensor's quantisation parameters for dpl_fake_quant_items."""
     _fields_ = [("d_scale", C.c_void_p), ("d_zero_point", C.c_void_p), ("n_channels", C.c_int64), ("inner", C.c_int64),
@@ -151,6 +157,8 @@ SIGNATURES = {
     "dpl_gptq_factor_workspace": (_U64, [_I64]),
     "dpl_gptq_factor": (C.c_int, [_P, _I64, _DBL, _P, _P, _P, _U64, _P]),
     "dpl_gptq_factor_phase": (C.c_int, [_P, _I64, _DBL, _P, _P, _P, _U64, _I32, _P]),
+    "dpl_gptq_hessian_workspace": (_U64, [_I64, _I64]),
+    "dpl_gptq_hessian": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _U64, _P]),
     "dpl_cos_accumulate": (C.c_int, [_P, _P, _I64, _P, _I64, _P]),
     "dpl_channel_diff_sum": (C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
     "dpl_cos_items_accumulate": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P]),

@@ -14,16 +14,17 @@ SRC = [os.path.join(HERE, f) for f in ("calib_kernels.hip", "fake_quant_kernels.
                                        "octav_tail_host.hip", "round_kernels.hip", "gemm_small.hip", "mx_kernels.hip", "mx_pack_kernels.hip", "gptq_kernels.hip",
                                        "hadamard_kernels.hip", "mx_gemm_kernels.hip", "mx_search_kernels.hip", "mx_conv_kernels.hip")]
 # Built on their own, with the packed fp32 instructions (v_pk_*_f32) switched off for the device code, and linked in as objects: the fp64
-# factorisation has no use for them.  (A command-line feature, not a function attribute: the runtime header's inline functions,
+# factorisation and the fp64 Hessian have no use for them.  (A command-line feature, not a function attribute: the runtime header's inline functions,
 # __syncthreads among them, must have the same features as their callers or they are not inlined.  The host pass notes that it does
 # not know the feature and ignores it.)
-SRC_NO_PACKED_FP32 = [os.path.join(HERE, "gptq_factor_kernels.hip")]
+SRC_NO_PACKED_FP32 = [os.path.join(HERE, "gptq_factor_kernels.hip"), os.path.join(HERE, "gptq_hessian_kernels.hip")]
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HDR = [os.path.join(HERE, "..", "..", "include", "dipoorlet_hip.h"), os.path.join(HERE, "common.hpp"),
        os.path.join(HERE, "octav_common.hpp"), os.path.join(HERE, "octav_wave.hpp"), os.path.join(HERE, "octav_tail.hpp"),
        os.path.join(HERE, "octav_rescue.hpp"), os.path.join(HERE, "mx_format.hpp"), os.path.join(HERE, "mx_block.hpp"), os.path.join(HERE, "mx_plan.hpp"), os.path.join(HERE, "mx_search.hpp"),
        os.path.join(HERE, "host_plan.hpp"), os.path.join(HERE, "host_error.hpp"), os.path.join(HERE, "octav_geometry.hpp"), os.path.join(HERE, "fq_elem.hpp"),
-       os.path.join(HERE, "mx_mfma.hpp"), os.path.join(HERE, "gptq_factor_plan.hpp")]
+       os.path.join(HERE, "mx_mfma.hpp"), os.path.join(HERE, "gptq_factor_plan.hpp"), os.path.join(HERE, "gptq_f64_tile.hpp"),
+       os.path.join(HERE, "gptq_hessian_plan.hpp")]
 OUT = os.path.join(HERE, "libdipoorlet_hip.so")
 
 

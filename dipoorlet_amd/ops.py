@@ -1512,6 +1512,67 @@ def gptq_factor(H, damp=0.01, retries=3):
     return None, damp
 
 
+_GPTQ_HESSIAN_WS = {}      # device index -> the partial-tile workspace of gptq_hessian, kept between calls and replaced only by a larger
+                           # one (a layer's chunks all ask for the same size; the plan never asks for more than about 70 MB)
+
+
+def gptq_hessian_splits(rows, K):
+    """The number of row ranges S dpl_gptq_hessian cuts `rows` rows of a K-column X into — from (rows, K) alone, read off the
+    workspace size (S * tiles * 64 * 64 * 8 bytes; none for S == 1)."""
+    nt = -(-int(K) // 64)
+    nbytes = int(_hip.lib().dpl_gptq_hessian_workspace(int(K), int(rows)))
+    return max(1, nbytes // (nt * (nt + 1) // 2 * 64 * 64 * 8))
+
+
+def gptq_hessian(x, H, *, weight_shape=None, strides=None, pads=None, dilations=None):
+    """H += X^T X in fp64 (dpl_gptq_hessian, csrc/gptq_hessian_kernels.hip): GPTQ's layer Hessian from the activation as it lies, X
+    never materialised.  H: fp64 device tensor [K, K], contiguous, symmetric.  weight_shape None, the dense form: x is fp32 [rows, K]
+    contiguous.  Otherwise the conv form: x is fp32 [B, C, H, W] contiguous and X the patches of the group-1 convolution with weight
+    [C_out, C, kh, kw] = weight_shape, `strides` and `dilations` (default 1) per axis and the ONNX `pads` [top, left, bottom, right]
+    (default 0): one row per output position, columns in (C, kh, kw) order — weight_transform.gptq.input_rows's.  Exact fp32 x fp32
+    products summed in fp64 in one fixed order: two calls on the same data give the same bits.  -> the number of rows added."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and isinstance(H, torch.Tensor) and H.is_cuda and H.device == x.device):
+        raise _hip.DipoorletHipError("gptq_hessian: x and H must be ROCm device tensors on one device; dipoorlet_amd has no CPU path")
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise _hip.DipoorletHipError(f"gptq_hessian: x must be contiguous float32, got {x.dtype}")
+    if H.dtype != torch.float64 or not H.is_contiguous() or H.dim() != 2 or H.shape[0] != H.shape[1]:
+        raise _hip.DipoorletHipError(f"gptq_hessian: H must be a contiguous float64 [K, K] tensor, got {H.dtype} {tuple(H.shape)}")
+    K = int(H.shape[0])
+    geom = None
+    if weight_shape is None:
+        if x.dim() != 2 or int(x.shape[1]) != K:
+            raise _hip.DipoorletHipError(f"gptq_hessian: K mismatch: x must be [rows, {K}] for H [{K}, {K}], got {tuple(x.shape)}")
+        rows = int(x.shape[0])
+    else:
+        if x.dim() != 4 or len(weight_shape) != 4:
+            raise _hip.DipoorletHipError("gptq_hessian: the conv form takes x [B, C, H, W] and a weight_shape [C_out, C, kh, kw]")
+        kh, kw = int(weight_shape[2]), int(weight_shape[3])
+        (sh, sw), (dh, dw) = [int(v) for v in strides or (1, 1)], [int(v) for v in dilations or (1, 1)]
+        pt, pl, pb, pr = [int(v) for v in pads or (0, 0, 0, 0)]
+        B, Cin, Hi, Wi = [int(v) for v in x.shape]
+        if int(weight_shape[1]) != Cin or Cin * kh * kw != K:
+            raise _hip.DipoorletHipError(f"gptq_hessian: K mismatch: {Cin} channels under a weight {tuple(weight_shape)} against H [{K}, {K}]")
+        if min(sh, sw, dh, dw) < 1:
+            raise _hip.DipoorletHipError("gptq_hessian: strides and dilations must be positive")
+        oh, ow = [(size - d * (k - 1) - 1) // s + 1 for size, d, k, s in ((Hi + pt + pb, dh, kh, sh), (Wi + pl + pr, dw, kw, sw))]
+        if oh < 1 or ow < 1:
+            raise _hip.DipoorletHipError(f"gptq_hessian: the output extent of the geometry is not positive ({oh} x {ow})")
+        rows = B * oh * ow
+        geom = _hip.GptqHessianGeom(B, Cin, Hi, Wi, kh, kw, sh, sw, pt, pl, pb, pr, dh, dw)
+    if rows == 0:
+        return 0
+    with torch.cuda.device(x.device):
+        nbytes = int(_hip.lib().dpl_gptq_hessian_workspace(K, rows))
+        ws = None
+        if nbytes:
+            ws = _GPTQ_HESSIAN_WS.get(x.device.index)
+            if ws is None or ws.numel() < nbytes:
+                ws = _GPTQ_HESSIAN_WS[x.device.index] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _hip.check(_hip.lib().dpl_gptq_hessian(_ptr(x), None if geom is None else C.byref(geom), K, rows, _ptr(H),
+                                               None if ws is None else _ptr(ws), 0 if ws is None else ws.numel(), _stream()), "dpl_gptq_hessian")
+    return rows
+
+
 def gptq_mx_block(w, c0, nb, u, elem, err=None, scales=None):
     """One call of GPTQ's column recursion on an MX block-scaled grid, in place (dpl_gptq_mx_block; tests/mx_gptq_model.py
     gptq_mx_block is the definition, matched bit for bit): gptq_block with the grid of every block of 32 columns fixed when the

@@ -4,7 +4,9 @@ grid the platform's fake-quant nodes round weights to (an integer grid or OCP FP
 The fake-quantised network is walked once, node-major, exactly as AdaRound's driver walks it (walk.QuantWalk).  For every
 Conv (group 1, two spatial axes) and Gemm whose weight the graph fake-quantises:
   * H = sum X^T X / rows over the node's fake-quantised input — a Gemm's input rows, a Conv's unfolded patches (pads applied
-    explicitly, so asymmetric ONNX pads are right) — fp32 GEMMs per slab summed in fp64, one fp64 SUM all-reduce per node;
+    explicitly, so asymmetric ONNX pads are right) — fp32 GEMMs per slab summed in fp64, or, with --gptq_hessian device, the
+    library's fp64 kernel straight from the activation (ops.gptq_hessian: no unfold, a fixed summation order); one fp64 SUM
+    all-reduce per node;
   * U = the upper Cholesky factor of (H + damp * mean(diag H) * I)^-1, on the host in fp64 (factor(): every rank computes the same
     matrix, whatever device solver the torch build ships) — or, with --gptq_factor device, in fp64 on the device by the library's
     own kernels (ops.gptq_factor: a fixed summation order, so every rank still computes the same matrix; H never leaves the device);
@@ -149,13 +151,30 @@ def rows_per_image(node, x, weight_shape):
     return n
 
 
-def hessian(node, chunks, weight_shape, K, dev):
+def _hessian_device(node, x, weight_shape, H):
+    """--gptq_hessian device: one chunk onto H by ops.gptq_hessian, from the chunk as it lies — no unfold, no slabs, no BLAS call.
+    -> the rows added."""
+    if node.op_type != "Conv":
+        return ops.gptq_hessian(x.contiguous().reshape(-1, H.shape[0]) if node.op_type == "MatMul" else
+                                x.contiguous().reshape(x.shape[0], -1), H)
+    kernel = list(weight_shape[2:])
+    strides = node.attrs.get("strides", [1, 1])
+    dil = node.attrs.get("dilations", [1, 1])
+    _, fpad = conv_padding(node, x, kernel, strides, dil)       # F.pad order: (left, right, top, bottom)
+    return ops.gptq_hessian(x.contiguous(), H, weight_shape=weight_shape, strides=strides, dilations=dil,
+                            pads=(fpad[2], fpad[0], fpad[3], fpad[1]))
+
+
+def hessian(node, chunks, weight_shape, K, dev, on_device=False):
     """sum X^T X over this rank's chunks of the node's input, and the number of rows, in ONE fp64 device vector [K * K + 1] (what is
     all-reduced).  A chunk is taken in slabs of whole images of at most _SLAB_BYTES of fp32 rows (and _SLAB_ROWS rows; one image
-    at the least)."""
+    at the least) — or, on_device (--gptq_hessian device), whole, by the library's own fp64 kernel."""
     acc = torch.zeros(K * K + 1, dtype=torch.float64, device=dev)
     H = acc[:K * K].view(K, K)
     for x in chunks:
+        if on_device:
+            acc[K * K] += _hessian_device(node, x, weight_shape, H)
+            continue
         per_image = max(1, rows_per_image(node, x, weight_shape))
         step = max(1, min(_SLAB_ROWS, _SLAB_BYTES // (4 * K)) // per_image)
         for i in range(0, x.shape[0], step):
@@ -188,8 +207,11 @@ def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
     mx_gptq = bool(getattr(args, "mx_gptq", False))
     flag = "--mx_gptq" if mx_gptq else "--gptq"
     on_device = getattr(args, "gptq_factor", "host") == "device"
+    hessian_on_device = getattr(args, "gptq_hessian", "blas") == "device"
     if rank == 0:
         logger.info("%s: the Hessians are factorised on the %s", flag, "device (ops.gptq_factor)" if on_device else "host (factor)")
+        if hessian_on_device:
+            logger.info("%s: the Hessians are summed by the library's fp64 kernel (ops.gptq_hessian)", flag)
     visited = (MX_GPTQ_NODE_TYPES if mx_gptq else GPTQ_NODE_TYPES) + LEFT_NODE_TYPES
     report, left = [], []
     with torch.no_grad():
@@ -224,7 +246,7 @@ def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
             w_host = np.ascontiguousarray(weight, dtype=np.float32)
             w2d = torch.from_numpy(w_host.reshape(w_host.shape[0], -1) if rows_first else np.ascontiguousarray(w_host.T)).to(dev)
             R, K = w2d.shape
-            acc = hessian(ori, qf.env[node.input[0]], w_host.shape, K, dev)
+            acc = hessian(ori, qf.env[node.input[0]], w_host.shape, K, dev, hessian_on_device)
             if walk.world > 1:
                 dist.all_reduce(acc)
             H = acc[:K * K].view(K, K) / acc[K * K]
@@ -258,6 +280,7 @@ def gptq(graph_ori, graph, act_clip_val, weight_clip_val, args):
             "".join("\n  {}: {}".format(n, w) for n, w in left)))
         if getattr(args, "output_dir", None):
             with open(os.path.join(args.output_dir, "gptq_report.json"), "w") as f:
-                json.dump({"layers": report, "left": [{"node": n, "why": w} for n, w in left], **({"factor": "device"} if on_device else {})},
+                json.dump({"layers": report, "left": [{"node": n, "why": w} for n, w in left], **({"factor": "device"} if on_device else {}),
+                           **({"hessian": "device"} if hessian_on_device else {})},
                           f, indent=1)
     return walk.finish("gptq"), report

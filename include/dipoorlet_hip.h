@@ -42,7 +42,9 @@ extern "C" {
                               35: dpl_mx_gemm_err (dpl_mx_gemm's product against a reference, as per-tile fp64 error sums: --mx_mixed);
                               36: DPL_MX_E2M3 / DPL_MX_E3M2 (the two OCP MXFP6 element formats, through the MX entry points there are);
                               37: dpl_gptq_factor / dpl_gptq_factor_workspace / dpl_gptq_factor_phase (GPTQ's fp64 Hessian factorisation on the device, whole
-                                  and in its two phases for timing: --gptq_factor device) */
+                                  and in its two phases for timing: --gptq_factor device);
+                                  added under 37: dpl_gptq_hessian / dpl_gptq_hessian_workspace (GPTQ's layer Hessian X^T X as an fp64 SYRK
+                                  over a dense or a convolution-patch X: --gptq_hessian device) — a pure addition, no number taken */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -624,6 +626,32 @@ int dpl_gptq_factor(const double* d_h, int64_t k, double damp, double* d_u, int3
                     dpl_stream_t s);
 int dpl_gptq_factor_phase(const double* d_h, int64_t k, double damp, double* d_u, int32_t* d_status, void* d_workspace,
                           uint64_t workspace_bytes, int32_t phases, dpl_stream_t s);
+
+/* ---- GPTQ's layer Hessian on the device (--gptq_hessian device; csrc/gptq_hessian_kernels.hip; added under 37: two new
+ *      symbols, nothing that was there changes).  d_h[i * k + j] += sum over r of X[r][i] * X[r][j] for the fp64 [k, k] matrix d_h
+ *      (symmetric on entry: the tiles on and below the diagonal are computed, each new value is written to its mirror as well), X
+ *      [rows, k] fp32 never materialised: the exact fp32 x fp32 products are summed in fp64 on v_mfma_f64_16x16x4_f64.
+ *      geom == NULL, the dense form: X[r][c] = d_x[r * k + c].
+ *      geom != NULL, the conv form: d_x is [batch, channels, height, width] contiguous; row r = (b, oy, ox) over the output positions,
+ *      column c = (ci, ky, kx) in (channels, kh, kw) order, X[r][c] = d_x[b, ci, oy * stride_h - pad_top + ky * dil_h,
+ *      ox * stride_w - pad_left + kx * dil_w], or 0 outside the image: the patches of a group-1 convolution over two spatial axes.
+ *      The rows are cut into S ranges on multiples of 32, S a function of (rows, k) alone; S > 1: every (tile, range) stores its
+ *      partial tile into d_workspace (dpl_gptq_hessian_workspace(k, rows) = S * tiles * 64 * 64 * 8 bytes, tiles = n (n + 1) / 2,
+ *      n = ceil(k / 64); 0 when S == 1, d_workspace may then be NULL) and a second kernel adds them onto d_h in ascending range.  No
+ *      atomics: an element is one fixed sequence of additions for a given (rows, k, geometry).  rows == 0 is a no-op.  Refused
+ *      (-2), nothing launched: a null d_x / d_h, k outside [1, DPL_GPTQ_FACTOR_MAX_K], rows outside [0, 2^31 - 33], a geometry with a
+ *      size, stride or dilation < 1 or a pad < 0, with k != channels * kh * kw, with an image of 2^31 elements or a padded axis or a
+ *      window's reach of 2^15 or more, with an output extent that is not positive, or with rows != batch * out_h * out_w; a
+ *      workspace that is too small. */
+typedef struct dpl_gptq_hessian_geom {
+    int64_t batch, channels, height, width;
+    int64_t kh, kw, stride_h, stride_w;
+    int64_t pad_top, pad_left, pad_bottom, pad_right;
+    int64_t dil_h, dil_w;
+} dpl_gptq_hessian_geom;
+uint64_t dpl_gptq_hessian_workspace(int64_t k, int64_t rows);
+int dpl_gptq_hessian(const float* d_x, const dpl_gptq_hessian_geom* geom, int64_t k, int64_t rows, double* d_h, void* d_workspace,
+                     uint64_t workspace_bytes, dpl_stream_t s);
 
 /* ---- cosine-similarity partial sums (utils.py:273-278): d_acc[slot*3 + {0,1,2}] += sum(a*b), sum(a*a),
  *      sum(b*b) in fp64. */
