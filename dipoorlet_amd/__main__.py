@@ -48,6 +48,12 @@ def build_parser():
     p.add_argument("--smooth_alpha", type=float, default=0.5,
                    help="--smooth (not in the reference): fold per-channel scales s = max|x|^alpha / max|w|^(1 - alpha) of every LayerNorm "
                         "affine that feeds only MatMul / Gemm weights into those weights; alpha in [0, 1]")
+    p.add_argument("--smooth_search", default=False, action="store_true",
+                   help="(not in the reference; with --smooth and --mx mxfp8 | mxfp4 only) choose every --smooth site's strength by "
+                        "measurement instead of one --smooth_alpha (which is then ignored): the site is left alone or folded with alpha = "
+                        "0.0, 0.1, ..., 1.0, whichever gives the smallest error of the site's products with both operands MX-encoded, "
+                        "formed on the block-scaled matrix instruction over the first --calib_batch images (ops.mx_smooth_err: all twelve "
+                        "candidates in one launch per reader).  Writes smooth_search_report.json")
     p.add_argument("--mx", choices=list(MX_CHOICES), default=None,
                    help="(not in the reference; with -D ocp_fp8 only) OCP Microscaling on both operands of every MatMul / Gemm, constant "
                         "ones included: blocks of 32 along the reduction axis share a power-of-two scale taken from the data, the elements "
@@ -148,6 +154,15 @@ def check_args(args):
     alpha = getattr(args, "smooth_alpha", 0.5)
     if not 0.0 <= alpha <= 1.0:      # (a NaN too)
         raise ValueError(f"--smooth_alpha must lie in [0, 1], got {alpha}")
+    if getattr(args, "smooth_search", False):
+        if not getattr(args, "smooth", False):
+            raise ValueError("--smooth_search needs --smooth: it chooses the strength of --smooth's sites, and without --smooth nothing is folded")
+        if not getattr(args, "mx", None):
+            raise ValueError("--smooth_search needs --mx mxfp8 or --mx mxfp4: it measures what the block-scaled format does to a site's "
+                             "products, and a static grid has no blocks")
+        if args.mx in mx_fp6_setting_table:
+            raise ValueError(f"--smooth_search is not supported with --mx {args.mx}: its error kernel is built for mxfp8 and mxfp4 "
+                             "(ops.mx_smooth_err), as --mx_mixed's is")
     if getattr(args, "mx_gptq", False) and getattr(args, "gptq", False):
         raise ValueError("--mx_gptq and --gptq cannot be combined: --mx_gptq runs --gptq's driver over the block-scaled weights and "
                          "the static ones alike")

@@ -151,6 +151,8 @@ SIGNATURES = {
     "dpl_mx_encode_scaled": (C.c_int, [_I32, _P, _U64, _U64, _U64, _P, _P, _P, _P]),
     "dpl_mx_gemm": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _U64, _U64, _U64, _U64, _I32, _P, _P]),
     "dpl_mx_gemm_err": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _U64, _U64, _U64, _U64, _I32, _P, _P, _P, _P]),
+    "dpl_mx_smooth_err": (C.c_int, [_I32, _P, _P, _P, _U64, _U64, _U64, _U64, _P, _P, _P]),
+    "dpl_mx_smooth_sum": (C.c_int, [_P, _U64, _U64, _P, _P]),
     "dpl_mx_conv": (C.c_int, [_I32, _I32, _P, _P, _P, _P] + [_I64] * 15 + [_P, _P]),
     "dpl_gptq_block": (C.c_int, [_P, _I64, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
     "dpl_gptq_mx_block": (C.c_int, [_I32, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _P]),

@@ -12,7 +12,8 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = [os.path.join(HERE, f) for f in ("calib_kernels.hip", "fake_quant_kernels.hip", "side_kernels.hip", "runtime_abi.hip", "octav_kernels.hip",
                                        "octav_tail_host.hip", "round_kernels.hip", "gemm_small.hip", "mx_kernels.hip", "mx_pack_kernels.hip", "gptq_kernels.hip",
-                                       "hadamard_kernels.hip", "mx_gemm_kernels.hip", "mx_search_kernels.hip", "mx_conv_kernels.hip")]
+                                       "hadamard_kernels.hip", "mx_gemm_kernels.hip", "mx_search_kernels.hip", "mx_conv_kernels.hip",
+                                       "mx_smooth_kernels.hip")]
 # Built on their own, with the packed fp32 instructions (v_pk_*_f32) switched off for the device code, and linked in as objects: the fp64
 # factorisation and the fp64 Hessian have no use for them.  (A command-line feature, not a function attribute: the runtime header's inline functions,
 # __syncthreads among them, must have the same features as their callers or they are not inlined.  The host pass notes that it does

@@ -76,6 +76,14 @@ __device__ __forceinline__ int mx_block_se_given(uint32_t a, uint32_t byte, bool
 // The E8M0 byte of a block (se, nan).
 __device__ __forceinline__ uint8_t mx_scale_byte(int se, bool nan) { return nan ? 0xFFu : (uint8_t)(se + 127); }
 
+// The code of element v of a block (se, nan) in the packed form; `exists`: false past K.  (The encode kernels of mx_pack_kernels.hip
+// and k_mx_smooth_err of mx_smooth_kernels.hip.)
+template <int ELEM>
+__device__ __forceinline__ uint32_t mx_code(uint32_t vbits, int se, bool nan, bool exists) {
+    const uint32_t c = ((vbits >> 31) << (dpl_mx::Fmt<ELEM>::ebits + dpl_mx::Fmt<ELEM>::mbits)) | dpl_mx::round_code<ELEM>(vbits & 0x7FFFFFFFu, se);
+    return exists ? (nan ? dpl_mx::Fmt<ELEM>::nan_code : c) : 0u;
+}
+
 // The largest |v| pattern of a block held by a group of 32 / VEC adjacent lanes, VEC values each: in every lane of the group.
 template <int VEC>
 __device__ __forceinline__ uint32_t mx_group_max(const MxVec<VEC>& v) {

@@ -42,28 +42,13 @@ template <int EA, int EB>
 __global__ __launch_bounds__(kBlock) void k_mx_gemm_err(const uint8_t* a_codes, const uint8_t* a_scales, const uint8_t* b_codes, const uint8_t* b_scales,
                                                         const float* ref, const float* bias, double* part, uint32_t m, uint32_t n, uint32_t nblk,
                                                         uint32_t tiles_m, uint32_t tiles_n, uint32_t b_batched) {
-    double sum_d = 0.0, sum_r = 0.0;
+    MxErrSums sums;
     mx_mfma_tile<EA, EB>(a_codes, a_scales, b_codes, b_scales, m, n, nblk, tiles_m, tiles_n, b_batched != 0u,
                          [=](uint32_t bi, uint64_t r) { return MxRowBlocks{((uint64_t)bi * m + r) * nblk, nblk, r < m}; },
                          [&](uint32_t bi, uint64_t r, uint64_t cc, bool live, float v) {
-                             double dd = 0.0, rr = 0.0;
-                             if (live) {
-                                 const float rf = ref[((uint64_t)bi * m + r) * n + cc];
-                                 const float d = __fsub_rn(bias != nullptr ? __fadd_rn(v, bias[cc]) : v, rf);
-                                 dd = (double)d * (double)d, rr = (double)rf * (double)rf;
-                             }
-                             sum_d += dd, sum_r += rr;
+                             sums.add(ref, bias, ((uint64_t)bi * m + r) * n + cc, cc, live, v);
                          });
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        sum_d += __shfl_xor(sum_d, o, kWave);
-        sum_r += __shfl_xor(sum_r, o, kWave);
-    }
-    __shared__ double waves[kBlock / kWave][2];
-    if ((threadIdx.x & (kWave - 1)) == 0) waves[threadIdx.x / kWave][0] = sum_d, waves[threadIdx.x / kWave][1] = sum_r;
-    __syncthreads();
-    const uint32_t t = threadIdx.x;      // threads 0 and 1: the tile's two sums
-    if (t < 2) part[2ull * blockIdx.x + t] = (waves[0][t] + waves[1][t]) + (waves[2][t] + waves[3][t]);
+    sums.store(part, blockIdx.x);
 }
 
 }  // namespace

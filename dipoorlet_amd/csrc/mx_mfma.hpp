@@ -2,9 +2,11 @@
 // defined once: a lane's fragment of a packed MX operand as dpl_mx_encode writes it (mx_frag_load) and the 64 x 64 tile of C a
 // workgroup computes (mx_mfma_tile).  The kernels differ in how K-block kb of a row of A resolves to a block of the operand and in
 // what becomes of a finished element of C (the epilogue: MxStoreC writes it, k_mx_gemm_err adds its error up), and state only that; the
-// host side — argument checks, tile grid, dispatch — is mx_plan.hpp.  The lane map (confirmed with exact data): lane
-// l supplies row (column) l & 15 and, as its scale, the E8M0 byte of K-block l >> 4 of the 128-wide step.  Codes: E2M1 — the 32 K
-// values of that same block, 16 bytes, byte j holding k = 2j in its low and k = 2j + 1 in its high nibble, the other four dwords 0.
+// host side — argument checks, tile grid, dispatch — is mx_plan.hpp.  k_mx_smooth_err (mx_smooth_kernels.hip) encodes its operands
+// itself and feeds the instruction from LDS; it shares the tile's end (mx_mfma_finish) and k_mx_gemm_err's sums (MxErrSums).
+// The lane map (confirmed with exact data): lane l supplies row (column) l & 15 and, as its scale, the E8M0 byte of
+// K-block l >> 4 of the 128-wide step.  Codes: E2M1 — the 32 K values of that same block, 16 bytes, byte j holding k = 2j in its
+// low and k = 2j + 1 in its high nibble, the other four dwords 0.
 // E4M3 — NOT that block: dwords 0 .. 3 are k = 16 (l >> 4) .. + 15 of the step and dwords 4 .. 7 k = 64 + 16 (l >> 4) .. + 15, byte
 // j of a run being k = j.  C/D: lane l holds column l & 15, rows 4 * (l >> 4) + reg.
 // E2M3 / E3M2 (format codes 2 / 3; DESIGN.md §3v, confirmed with one-product outputs that use every bit of the codes) — as E2M1, the
@@ -19,6 +21,7 @@
 namespace {
 
 using i8v = __attribute__((ext_vector_type(8))) int;
+using f4v = __attribute__((ext_vector_type(4))) float;
 using u4g = __attribute__((ext_vector_type(4))) uint32_t;
 typedef const __attribute__((address_space(1))) u4g* gptr_u4g;
 using u2g = __attribute__((ext_vector_type(2))) uint32_t;
@@ -102,6 +105,67 @@ struct MxStoreC {
     }
 };
 
+// What becomes of a wave's finished quadrant (mx_mfma_tile's end, and k_mx_smooth_err's): acc[i][j] the four accumulators, a_bad[i] /
+// b_bad[j] each lane's NaN notes of its row of A / column of C; row0 / col0: the quadrant's first row and column, q = lane >> 4,
+// r16 = lane & 15.  Every lane of the wave is here.
+template <class Epi>
+__device__ __forceinline__ void mx_mfma_finish(const f4v (&acc)[2][2], uint32_t (&a_bad)[2], uint32_t (&b_bad)[2], uint32_t bi, uint64_t row0,
+                                               uint64_t col0, uint32_t q, uint32_t r16, uint32_t m, uint32_t n, Epi&& epi) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // the notes of the four lanes of a row (column); every lane of the wave is here
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        a_bad[i] |= (uint32_t)__shfl_xor((int)a_bad[i], 16, kWave);
+        a_bad[i] |= (uint32_t)__shfl_xor((int)a_bad[i], 32, kWave);
+        b_bad[i] |= (uint32_t)__shfl_xor((int)b_bad[i], 16, kWave);
+        b_bad[i] |= (uint32_t)__shfl_xor((int)b_bad[i], 32, kWave);
+    }
+    // C/D: lane l holds column l & 15 and rows 4 * (l >> 4) + reg of its 16 x 16 tile; row r's note sits in lanes r, r + 16, ...
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const uint32_t rr = 4u * q + (uint32_t)reg;
+            const uint32_t row_bad = (uint32_t)__shfl((int)a_bad[i], (int)rr, kWave);
+            const uint64_t r = row0 + 16u * i + rr;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const uint64_t cc = col0 + 16u * j + r16;
+                epi(bi, r, cc, r < m && cc < n, (row_bad | b_bad[j]) ? __uint_as_float(0x7FC00000u) : acc[i][j][reg]);
+            }
+        }
+    }
+#endif
+}
+
+// k_mx_gemm_err's epilogue (mx_gemm_kernels.hip's comment is its definition; k_mx_smooth_err's too): add() per element of C in the
+// tile body's order — at: the element's index in ref, cc its column —, then store() by every thread of the workgroup: the tile's two
+// sums go to row `row` of part fp64 [.., 2].
+struct MxErrSums {
+    double sum_d = 0.0, sum_r = 0.0;
+    __device__ __forceinline__ void add(const float* ref, const float* bias, uint64_t at, uint64_t cc, bool live, float v) {
+        double dd = 0.0, rr = 0.0;
+        if (live) {
+            const float rf = ref[at];
+            const float d = __fsub_rn(bias != nullptr ? __fadd_rn(v, bias[cc]) : v, rf);
+            dd = (double)d * (double)d, rr = (double)rf * (double)rf;
+        }
+        sum_d += dd, sum_r += rr;
+    }
+    __device__ __forceinline__ void store(double* part, uint64_t row) {
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            sum_d += __shfl_xor(sum_d, o, kWave);
+            sum_r += __shfl_xor(sum_r, o, kWave);
+        }
+        __shared__ double waves[kBlock / kWave][2];
+        if ((threadIdx.x & (kWave - 1)) == 0) waves[threadIdx.x / kWave][0] = sum_d, waves[threadIdx.x / kWave][1] = sum_r;
+        __syncthreads();
+        const uint32_t t = threadIdx.x;      // threads 0 and 1: the tile's two sums
+        if (t < 2) part[2ull * row + t] = (waves[0][t] + waves[1][t]) + (waves[2][t] + waves[3][t]);
+    }
+};
+
 // A workgroup's 64 x 64 tile of C fp32 [batch, m, n] = A [batch, m, nblk blocks] x B [batch or 1, n, nblk blocks]: 256 threads, each
 // wave 32 x 32 as 2 x 2 instruction tiles, four accumulators, operands straight from global memory (L2), no LDS.  row_a(bi, r) ->
 // the resolver of row r (which may be >= m: it is then not live) of A in batch bi.  Rows >= m, columns >= n and the K-blocks past
@@ -114,7 +178,6 @@ __device__ __forceinline__ void mx_mfma_tile(const uint8_t* a_codes, const uint8
                                              uint32_t m, uint32_t n, uint32_t nblk, uint32_t tiles_m, uint32_t tiles_n, bool b_batched, RowA row_a,
                                              Epi&& epi) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    using f4v = __attribute__((ext_vector_type(4))) float;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t per_batch = tiles_m * tiles_n;                       // (the grid is below 2^31)
     const uint32_t bi = blockIdx.x / per_batch, t = blockIdx.x - bi * per_batch;
@@ -147,29 +210,7 @@ __device__ __forceinline__ void mx_mfma_tile(const uint8_t* a_codes, const uint8
                                                                              fa[i].scale, 0, fb[j].scale);
     }
 
-    // the notes of the four lanes of a row (column); every lane of the wave is here
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        a_bad[i] |= (uint32_t)__shfl_xor((int)a_bad[i], 16, kWave);
-        a_bad[i] |= (uint32_t)__shfl_xor((int)a_bad[i], 32, kWave);
-        b_bad[i] |= (uint32_t)__shfl_xor((int)b_bad[i], 16, kWave);
-        b_bad[i] |= (uint32_t)__shfl_xor((int)b_bad[i], 32, kWave);
-    }
-    // C/D: lane l holds column l & 15 and rows 4 * (l >> 4) + reg of its 16 x 16 tile; row r's note sits in lanes r, r + 16, ...
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const uint32_t rr = 4u * q + (uint32_t)reg;
-            const uint32_t row_bad = (uint32_t)__shfl((int)a_bad[i], (int)rr, kWave);
-            const uint64_t r = row0 + 16u * i + rr;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const uint64_t cc = col0 + 16u * j + r16;
-                epi(bi, r, cc, r < m && cc < n, (row_bad | b_bad[j]) ? __uint_as_float(0x7FC00000u) : acc[i][j][reg]);
-            }
-        }
-    }
+    mx_mfma_finish(acc, a_bad, b_bad, bi, row0, col0, q, r16, m, n, epi);
 #endif
 }
 

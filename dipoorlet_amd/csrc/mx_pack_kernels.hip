@@ -91,13 +91,6 @@ __device__ __forceinline__ uint32_t mx_get_code(const uint32_t* wd, uint32_t r) 
     return c & ((1u << BITS) - 1u);
 }
 
-// The code of element v of a block (se, nan); `exists`: false past K.
-template <int ELEM>
-__device__ __forceinline__ uint32_t mx_code(uint32_t vbits, int se, bool nan, bool exists) {
-    const uint32_t c = ((vbits >> 31) << (dpl_mx::Fmt<ELEM>::ebits + dpl_mx::Fmt<ELEM>::mbits)) | dpl_mx::round_code<ELEM>(vbits & 0x7FFFFFFFu, se);
-    return exists ? (nan ? Pack<ELEM>::nan_code : c) : 0u;
-}
-
 // v of lane J of the caller's quad (lanes 4q .. 4q + 3), in every lane of the quad: one DPP move.  All 64 lanes must be active.
 template <int J>
 __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {

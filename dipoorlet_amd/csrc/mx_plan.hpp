@@ -5,7 +5,8 @@
 // mx_pair_null, mx_pair_aligned), their grid of 64 x 64 tiles (mx_tiles), each entry point's rules in their order (mx_gemm_check,
 // mx_gemm_err_check, mx_conv_check) and the way from (elem_a, elem_b) to an instantiation (mx_pair_dispatch, mx_pair_dispatch_all).  A wrong value here is an out-of-range
 // address in a kernel, so a plain C++ compiler can build this: tests/mx_plan_host.cpp is a stand-alone program that runs it under
-// the address and undefined-behaviour sanitizers (tests/test_mx_plan_host.py).
+// the address and undefined-behaviour sanitizers (tests/test_mx_plan_host.py).  dpl_mx_smooth_err's rules (mx_smooth_check) are here
+// too; tests/test_smooth_search_args.py builds a program of its own for them, under the same sanitizers.
 #pragma once
 #include <stdint.h>
 
@@ -168,6 +169,27 @@ inline bool mx_gemm_err_check(int& rc, MxTiles& t, const MxPair& o, const float*
     if (!mx_pair_operands(o) || ref == nullptr || part == nullptr)
         return (rc = mx_fail(who, "the codes, the scales, d_ref and d_part must not be null")), true;
     return (rc = mx_gemm_sizes(who, batch, m, n, k)) != 0 || (rc = mx_pair_aligned(who, o)) != 0 || (rc = mx_tiles(t, who, batch, m, n)) != 0;
+}
+
+constexpr uint64_t kMxSmoothMaxCand = 64;     // candidate scale vectors a dpl_mx_smooth_err call may bring
+
+// dpl_mx_smooth_err's (mx_smooth_kernels.hip): elem — the two formats of dpl_mx_gemm_err, the same on both sides —, a zero size, null
+// pointers, m, n and k in [1, 2^31) (x, w, ref and the scale vectors are then indexable: at most 2^62 elements each), the number of
+// candidates, and the grid of n_cand * tiles_m * tiles_n workgroups (t: the candidate is the tile grid's batch).  vec: 16-byte loads of
+// x, w and the scale vectors are possible; no refusal where they are not.
+inline bool mx_smooth_check(int& rc, MxTiles& t, bool& vec, int32_t elem, const float* x, const float* w, const float* sv, uint64_t n_cand,
+                            uint64_t m, uint64_t n, uint64_t k, const float* ref, const double* part) {
+    const char* who = "dpl_mx_smooth_err";
+    rc = 0;
+    if (elem != DPL_MX_E4M3 && elem != DPL_MX_E2M1)
+        return (rc = mx_fail(who, "elem must be DPL_MX_E4M3 or DPL_MX_E2M1 (the error kernels are built for these two: no FP6 format here)")), true;
+    if (n_cand == 0 || m == 0 || n == 0 || k == 0) return true;
+    if (x == nullptr || w == nullptr || sv == nullptr || ref == nullptr || part == nullptr)
+        return (rc = mx_fail(who, "d_x, d_w, d_s, d_ref and d_part must not be null")), true;
+    if (m > 0x7FFFFFFFull || n > 0x7FFFFFFFull || k > 0x7FFFFFFFull) return (rc = mx_fail(who, "m, n and k must be in [1, 2^31)")), true;
+    if (n_cand > kMxSmoothMaxCand) return (rc = mx_fail(who, "n_cand must be in [1, 64]")), true;
+    vec = ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)sv) & 15u) == 0u) && (k & 3u) == 0u;
+    return (rc = mx_tiles(t, who, n_cand, m, n, " (the grid)")) != 0;
 }
 
 // acc *= f unless that passes limit

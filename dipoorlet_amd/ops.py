@@ -1353,6 +1353,41 @@ def mx_gemm_err(a_codes, a_scales, b_codes, b_scales, ref, elem_a, elem_b=None, 
     return out
 
 
+MX_SMOOTH_MAX_CAND = 64                 # candidate vectors of one mx_smooth_err call (mx_plan.hpp kMxSmoothMaxCand)
+
+
+def mx_smooth_err(x, w, s, ref, elem, part=None):
+    """`--smooth_search`: the MX error of the product x . w^T under each of s's candidate smoothing vectors, in one launch
+    (dpl_mx_smooth_err; tests/mx_smooth_model.py is the definition).  x fp32 [m, k], w fp32 [n, k], s fp32 [n_cand, k] (1 .. 64
+    candidates), ref fp32 [m, n], all contiguous on one device; elem 'mxfp8' or 'mxfp4'.  For candidate c the kernel encodes x / s[c]
+    and w * s[c] as mx_encode would, multiplies the bytes as mx_gemm would and sums as mx_gemm_err would — bit for bit, with nothing
+    but the sums written.  -> fp64 [n_cand, 2]: sum d * d and sum ref * ref, the 64 x 64 tiles' sums added in ascending tile order on
+    the device.  part: an optional contiguous fp64 device tensor [n_cand, tiles_m, tiles_n, 2] that receives the tiles' own sums.
+    A bad shape or dtype raises ValueError before anything is launched."""
+    if elem not in MX_ELEM_MIXED:
+        raise ValueError(f"mx_smooth_err: elem must be 'mxfp8' or 'mxfp4' (the error kernels are built for these two), got {elem!r}")
+    for t, name in ((x, "x"), (w, "w"), (s, "s"), (ref, "ref")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
+                and t.device == x.device):
+            raise ValueError(f"mx_smooth_err: {name} must be a contiguous 2-D float32 ROCm device tensor on x's device; dipoorlet_amd has no CPU path")
+    (m, k), n, n_cand = (int(d) for d in x.shape), int(w.shape[0]), int(s.shape[0])
+    if min(m, n, k) < 1 or not 1 <= n_cand <= MX_SMOOTH_MAX_CAND or int(w.shape[1]) != k or int(s.shape[1]) != k or tuple(ref.shape) != (m, n):
+        raise ValueError(f"mx_smooth_err: x [m, k], w [n, k], s [1 .. {MX_SMOOTH_MAX_CAND}, k] and ref [m, n], none of them empty; got "
+                         f"{list(x.shape)}, {list(w.shape)}, {list(s.shape)} and {list(ref.shape)}")
+    tiles = (-(-m // MX_GEMM_TILE), -(-n // MX_GEMM_TILE))
+    shape = (n_cand,) + tiles + (2,)
+    if part is None:
+        part = torch.empty(shape, dtype=torch.float64, device=x.device)
+    elif not (isinstance(part, torch.Tensor) and part.is_cuda and part.dtype == torch.float64 and part.is_contiguous()
+              and tuple(part.shape) == shape and part.device == x.device):
+        raise ValueError(f"mx_smooth_err: part must be a contiguous float64 tensor of shape {list(shape)} on x's device")
+    sums = torch.empty((n_cand, 2), dtype=torch.float64, device=x.device)
+    _hip.check(_hip.lib().dpl_mx_smooth_err(MX_ELEM[elem], _ptr(x), _ptr(w), _ptr(s), n_cand, m, n, k, _ptr(ref), _ptr(part), _stream()),
+               "dpl_mx_smooth_err")
+    _hip.check(_hip.lib().dpl_mx_smooth_sum(_ptr(part), n_cand, tiles[0] * tiles[1], _ptr(sums), _stream()), "dpl_mx_smooth_sum")
+    return sums
+
+
 def mx_conv(a_codes, a_scales, b_codes, b_scales, elem_a, elem_b=None, *, strides, pads, dilations, out_hw, out=None):
     """`--mx_conv`: a convolution (group 1) of two packed MX operands on the block-scaled matrix instruction, as an implicit GEMM
     (dpl_mx_conv; tests/mx_conv_model.py is the definition).  Both operands are what mx_encode writes along axis 1: a_codes [n, h, w,

@@ -13,8 +13,22 @@ where both sides are weights; here one side is an activation, so its per-channel
 GPU (k_colwise_absmax: one read of the tensor, a running maximum per channel, no host synchronisation until the single read-back).
 The folding itself is a handful of fp32 array operations on weights of a few MB: host work, as in `--we`.  Saved as
 smooth_model.onnx.
+
+`--smooth_search` (with `--mx mxfp8 | mxfp4`) replaces the one global alpha by a choice per site, made from what the block-scaled
+format does to the site's products.  Candidates, in this order: s = 1 (leave the site alone), then smooth_scales(a, w, alpha) for
+alpha = 0.0, 0.1, ..., 1.0.  X is the site tensor of the first --calib_batch images of the WHOLE calibration set from the
+un-quantised graph (every rank measures the same images, so all ranks decide alike without communication); per reader, W as [N, C]
+and ref = X . W^T from one fp32 torch.matmul, and ONE ops.mx_smooth_err call gives every candidate's sum d^2 and sum ref^2 of the
+product of the MX-encoded X / s and W * s on the block-scaled matrix instruction.  E_c = sum over readers of sum d^2
+/ sum over readers of sum ref^2; the smallest E_c wins, ties keep the earliest candidate, a NaN never wins, and a site whose every
+E_c is NaN is left alone with a warning.  Written down, not fixed: the measurement divides the site tensor, fl32(T / s), where the
+folded graph computes Z . (g / s) + b / s; it ignores --mx_rotate, which runs later; with --mx_mixed it measures in mxfp4, the format
+every node starts in.  Writes smooth_search_report.json beside smooth_model.onnx.
 """
 import collections
+import collections.abc
+import json
+import os
 
 import numpy as np
 import torch
@@ -26,7 +40,11 @@ from ..graph import ONNXGraph
 from ..utils import logger
 from .utils import update_weight
 
-__all__ = ["SmoothSite", "SmoothReader", "find_smooth_sites", "smooth_scales", "apply_smooth", "smooth_statistics", "smooth_quant"]
+__all__ = ["SmoothSite", "SmoothReader", "find_smooth_sites", "smooth_scales", "apply_smooth", "smooth_statistics", "smooth_search",
+           "smooth_quant", "SEARCH_ALPHAS", "SEARCH_REPORT"]
+
+SEARCH_ALPHAS = (None,) + tuple(i / 10 for i in range(11))       # --smooth_search's candidates in their order; None: s = 1
+SEARCH_REPORT = "smooth_search_report.json"
 
 # tensor: the site T; gamma / beta: the initializers g and b of the affine; channels: C; readers: every consumer of T
 SmoothSite = collections.namedtuple("SmoothSite", "tensor gamma beta channels readers")
@@ -134,12 +152,17 @@ def _weight_rows_absmax(graph, site):
 
 
 def apply_smooth(graph, sites, stats, alpha):
-    """-> (a copy of `graph` with every site folded, {site tensor: s fp32 [C]}).  stats: {site tensor: a fp32 [C]}."""
+    """-> (a copy of `graph` with every site folded, {site tensor: s fp32 [C]}).  stats: {site tensor: a fp32 [C]}.  alpha: one
+    strength for every site, or {site tensor: its strength, None: the site is left alone (s = 1, its initializers untouched)}."""
     out = ONNXGraph()
     out.copy_from(graph)
     scales = {}
     for site in sites:
-        s = smooth_scales(stats[site.tensor], _weight_rows_absmax(out, site), alpha)
+        a = alpha[site.tensor] if isinstance(alpha, collections.abc.Mapping) else alpha
+        if a is None:
+            scales[site.tensor] = np.ones(site.channels, np.float32)
+            continue
+        s = smooth_scales(stats[site.tensor], _weight_rows_absmax(out, site), a)
         scales[site.tensor] = s
         for name in (site.gamma, site.beta):
             v = np.asarray(out.get_initializer(name), np.float32)
@@ -177,6 +200,50 @@ def smooth_statistics(graph, sites, args, session=None):
     return {n: host[offs[k]:offs[k + 1]].copy() for k, n in enumerate(names)}
 
 
+def choose_candidate(errs):
+    """The index of the smallest of `errs`, the earliest of equal ones, a NaN never; None where every one is NaN."""
+    best = None
+    for i, e in enumerate(errs):
+        if e == e and (best is None or e < errs[best]):
+            best = i
+    return best
+
+
+@torch.no_grad()
+def smooth_search(graph, sites, stats, args, session=None):
+    """`--smooth_search` (the module's docstring) -> ({site tensor: alpha or None}, the report as it is written)."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    images = max(1, min(int(args.data_num), int(getattr(args, "calib_batch", None) or 16)))
+    sess = session if session is not None else GraphSession(graph, device=dev)
+    bounds, inputs = load_chunks(graph, args, 0, images, dev)
+    names = [s.tensor for s in sites]
+    rows = [[] for _ in sites]
+    for c in range(len(bounds)):
+        for k, t in enumerate(sess.run_named({n: v[c] for n, v in inputs.items()}, names)):
+            rows[k].append(t.reshape(-1, sites[k].channels).to(torch.float32))
+    chosen, report = {}, []
+    for site, parts in zip(sites, rows):
+        x = torch.cat(parts).contiguous()
+        wmax = _weight_rows_absmax(graph, site)
+        cand = np.stack([np.ones(site.channels, np.float32) if a is None else smooth_scales(stats[site.tensor], wmax, a) for a in SEARCH_ALPHAS])
+        s = torch.from_numpy(cand).to(dev)
+        sums = torch.zeros((len(SEARCH_ALPHAS), 2), dtype=torch.float64, device=dev)
+        for r in site.readers:
+            w = torch.from_numpy(np.asarray(graph.get_initializer(r.weight), np.float32)).to(dev)
+            w = (w if r.transposed else w.t()).contiguous()                       # [N, C]
+            sums += ops.mx_smooth_err(x, w, s, torch.matmul(x, w.t()).contiguous(), args.mx)
+        num, den = sums.cpu().numpy().T
+        errs = [float(n / d) if d > 0.0 else float("nan") for n, d in zip(num, den)]
+        best = choose_candidate(errs)
+        if best is None:
+            logger.warning("--smooth_search: {}: every candidate's error is NaN; the site is left alone".format(site.gamma))
+            best = 0
+        chosen[site.tensor] = SEARCH_ALPHAS[best]
+        report.append({"gamma": site.gamma, "tensor": site.tensor, "channels": site.channels, "readers": [r.node for r in site.readers],
+                       "E": [e if e == e else None for e in errs], "chosen": best, "alpha": SEARCH_ALPHAS[best]})      # (a NaN: null in the file)
+    return chosen, {"format": args.mx, "images": images, "candidates": ["identity" if a is None else a for a in SEARCH_ALPHAS], "sites": report}
+
+
 def smooth_quant(graph, args):
     """-> the smoothed graph (rank 0 saves it as smooth_model.onnx); `graph` itself, nothing written, where it has no site.
     Every rank calls it (the statistics are shared over the process group) and ends with the same model."""
@@ -187,9 +254,23 @@ def smooth_quant(graph, args):
             logger.info("--smooth: no LayerNorm affine feeding only MatMul / Gemm weights in this graph: nothing to do")
         return graph
     alpha = float(getattr(args, "smooth_alpha", 0.5))
-    stats = smooth_statistics(graph, sites, args)
+    search = bool(getattr(args, "smooth_search", False))
+    session = GraphSession(graph, device=torch.device("cuda", torch.cuda.current_device())) if search else None
+    stats = smooth_statistics(graph, sites, args, session=session)
+    report = None
+    if search:
+        if rank == 0:
+            logger.info("--smooth_search: --smooth_alpha ({:g}) is ignored; every site's strength is chosen by its measured {} error".format(
+                alpha, args.mx))
+        alpha, report = smooth_search(graph, sites, stats, args, session=session)
     graph_s, scales = apply_smooth(graph, sites, stats, alpha)
     if rank == 0:
+        for e in report["sites"] if report else ():
+            logger.info("--smooth_search: {} -> {} (E {}; left alone {})".format(
+                e["gamma"], "left alone" if e["alpha"] is None else "alpha {:g}".format(e["alpha"]), e["E"][e["chosen"]], e["E"][0]))
+        if report is not None and getattr(args, "output_dir", None):
+            with open(os.path.join(args.output_dir, SEARCH_REPORT), "w") as f:
+                json.dump(report, f, indent=1, allow_nan=False)
         for site in sites:
             a, s = stats[site.tensor], scales[site.tensor]
             with np.errstate(all="ignore"):

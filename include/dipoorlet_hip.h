@@ -44,7 +44,9 @@ extern "C" {
                               37: dpl_gptq_factor / dpl_gptq_factor_workspace / dpl_gptq_factor_phase (GPTQ's fp64 Hessian factorisation on the device, whole
                                   and in its two phases for timing: --gptq_factor device);
                                   added under 37: dpl_gptq_hessian / dpl_gptq_hessian_workspace (GPTQ's layer Hessian X^T X as an fp64 SYRK
-                                  over a dense or a convolution-patch X: --gptq_hessian device) — a pure addition, no number taken */
+                                  over a dense or a convolution-patch X: --gptq_hessian device) — a pure addition, no number taken;
+                                  added under 37: dpl_mx_smooth_err (the MX error of a product under many smoothing vectors, encoded and
+                                  multiplied in one launch: --smooth_search) — a pure addition too */
 #define DPL_MAX_BINS 16384 /* LDS-privatised histogram: bins * 4 B per workgroup */
 #define DPL_HIST_SPEC_MAX_TENSORS 2048 /* dpl_hist_spec_accumulate keeps a prefix sum over the tensors in LDS */
 
@@ -542,6 +544,27 @@ int dpl_mx_gemm(int32_t elem_a, int32_t elem_b, const uint8_t* d_a_codes, const 
 int dpl_mx_gemm_err(int32_t elem_a, int32_t elem_b, const uint8_t* d_a_codes, const uint8_t* d_a_scales, const uint8_t* d_b_codes,
                     const uint8_t* d_b_scales, uint64_t batch, uint64_t m, uint64_t n, uint64_t k, int32_t b_batched, const float* d_ref,
                     const float* d_bias_or_null, double* d_part, dpl_stream_t s);
+
+/* ---- the MX error of one product under many candidate smoothing vectors, in one launch (beyond the reference; --smooth_search;
+ *      csrc/mx_smooth_kernels.hip; the definition is tests/mx_smooth_model.py; added under 37: one new symbol, nothing
+ *      that was there changes).
+ *        d_x  fp32 [m, k]       d_w  fp32 [n, k] (K-innermost)       d_s  fp32 [n_cand, k]       d_ref  fp32 [m, n]
+ *        d_part  fp64 [n_cand * tiles_m * tiles_n, 2], the row of tile (tm, tn) of candidate c being (c * tiles_m + tm) * tiles_n + tn
+ *      For candidate c: A = dpl_mx_encode's bytes (the floor rule, blocks of 32 along k, a short last block) of fl32(x[i, kk] /
+ *      s[c, kk]), B = those of fl32(w[j, kk] * s[c, kk]) — one IEEE fp32 division resp. product per element, no reciprocal, no
+ *      contraction —, C = dpl_mx_gemm's product of those bytes, its NaN rule included, and d_part = dpl_mx_gemm_err's two sums per
+ *      64 x 64 tile, no bias, in its order of additions: bit for bit what dpl_mx_encode of the two scaled tensors followed by
+ *      dpl_mx_gemm_err writes, with nothing but the sums stored.  Plain stores, the same bits on every run.  elem: DPL_MX_E4M3 or
+ *      DPL_MX_E2M1, the same on both sides (no FP6 format, as for dpl_mx_gemm_err).
+ *      Rules in their order: elem; n_cand * m * n * k == 0 is a no-op that returns 0; null pointers; 1 <= m, n, k < 2^31;
+ *      1 <= n_cand <= 64; the grid ("tensor too large").  d_x, d_w and d_s 16-byte aligned with k % 4 == 0 take 16-byte loads, anything
+ *      else single ones: no refusal.  A refused call (-2) launches nothing. */
+int dpl_mx_smooth_err(int32_t elem, const float* d_x, const float* d_w, const float* d_s, uint64_t n_cand, uint64_t m, uint64_t n,
+                      uint64_t k, const float* d_ref, double* d_part, dpl_stream_t s);
+/* d_sums fp64 [n_cand, 2]: candidate c's `tiles` (= tiles_m * tiles_n, below 2^31) rows of d_part added in ascending order, starting
+ * from +0.0 — one fixed order of fp64 additions (added under 37 with dpl_mx_smooth_err).  n_cand == 0 is a no-op; null pointers and
+ * n_cand > 64 are refused (-2). */
+int dpl_mx_smooth_sum(const double* d_part, uint64_t n_cand, uint64_t tiles, double* d_sums, dpl_stream_t s);
 
 /* ---- a convolution of two packed MX operands on the same instruction, as an implicit GEMM (beyond the reference; --mx_conv; the
  *      definition is tests/mx_conv_model.py).  Both operands are what dpl_mx_encode writes along axis 1 (channels).  With
