@@ -314,7 +314,9 @@ __global__ void k_hist_prepare(const float* __restrict__ gmin, const float* __re
 // guess costs what it always cost, so no count can change.
 //
 // A ledger entry (device memory, 16-byte aligned; the documented format: callers read the flags at n_slots * sizeof(dpl_hist_range)):
-//   dpl_hist_range snap[n_slots] | uint32 flags[n_slots] | pad to 16 bytes | uint32 counts[n_slots, bins]
+//   dpl_hist_range snap[n_slots] | uint32 flags[n_slots] | pad to 16 bytes | uint32 counts[n_slots, bins] | pad to 16 bytes | uint32 queue[4]
+// (queue[0]: the tail entries of the range pass's launch handed out so far, k_minmax_hist — with the entry, so that two
+// accumulators on two streams never share one)
 struct SpecEntry {
     dpl_hist_range* snap;
     uint32_t* flags;
@@ -324,17 +326,22 @@ struct SpecEntry {
     static uint64_t counts_offset(int64_t n_slots) {
         return (((uint64_t)n_slots * (sizeof(dpl_hist_range) + sizeof(uint32_t))) + 15ull) & ~15ull;
     }
-    static uint64_t bytes(int64_t n_slots, int bins) { return counts_offset(n_slots) + (uint64_t)n_slots * (uint64_t)bins * sizeof(uint32_t); }
+    static uint64_t queue_offset(int64_t n_slots, int bins) {
+        return (counts_offset(n_slots) + (uint64_t)n_slots * (uint64_t)bins * sizeof(uint32_t) + 15ull) & ~15ull;
+    }
+    static uint32_t* queue(void* d_entry, int64_t n_slots, int bins) { return (uint32_t*)((char*)d_entry + queue_offset(n_slots, bins)); }
+    static uint64_t bytes(int64_t n_slots, int bins) { return queue_offset(n_slots, bins) + 16ull; }
 };
 
-// Snapshot of the provisional ranges + the entry's counts zeroed.  A slot with no data yet, a NaN flag or a range numpy would
+// Snapshot of the provisional ranges + the entry's counts and its queue counter zeroed.  A slot with no data yet, a NaN flag or a range numpy would
 // refuse comes out with status != 0 ("no guess": the fused kernel takes its min / max only and k_hist_spec never accepts it).
 __global__ __launch_bounds__(kBlock) void k_hist_snapshot(const uint32_t* __restrict__ mn, const uint32_t* __restrict__ mx,
                                                            const uint32_t* __restrict__ nan, int64_t n, int bins,
                                                            dpl_hist_range* __restrict__ snap, uint32_t* __restrict__ flags,
-                                                           uint32_t* __restrict__ counts) {
+                                                           uint32_t* __restrict__ counts, uint32_t* __restrict__ queue) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    if (i == 0) queue[0] = 0u;
     if (i < n) {
         float gmin, gmax;
         minmax_decode(mn[i], mx[i], nan[i], gmin, gmax);
@@ -355,60 +362,103 @@ struct MinMaxHistOp {
     }
 };
 
+// What a workgroup of k_minmax_hist holds of the slot it is on, between the items it streams: the lanes' min / max / NaN and
+// non-zero counts, the elements streamed so far (hist_flush takes the zeros as elements - non-zeros) — and, in LDS, the counters.
+struct RangeCarry {
+    uint32_t slot;  // kNoSlot: nothing held
+    uint32_t count, nonzero;
+    MinMaxOp m;
+    static constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+};
+
 template <bool kFast>
 __device__ __forceinline__ void minmax_hist_body(const dpl_work_item& it, const float* const* __restrict__ segs,
-                                                 const dpl_hist_range& r, int bins, uint32_t* __restrict__ counts,
-                                                 uint32_t* lds, uint32_t* s_nz, MinMaxOp& m) {
+                                                 const dpl_hist_range& r, int bins, uint32_t* lds, RangeCarry& c) {
     MinMaxHistOp<kFast> op;
-    op.m = m;
+    op.m = c.m;
     hist_op_init(op.h, r, bins, lds);
+    op.h.nonzero = c.nonzero;
     stream_span(segs[it.seg] + it.offset, it.count, op);
-    m = op.m;
-    hist_flush(op.h.nonzero, it, r, bins, counts, lds, s_nz);
+    c.m = op.m;
+    c.nonzero = op.h.nonzero;
 }
 
-// LDS of k_minmax_hist:  HistLds | float s_mn[waves] | float s_mx[waves] | uint32 s_nan[waves]   (minmax_commit's words)
+// LDS of k_minmax_hist:  HistLds | float s_mn[waves] | float s_mx[waves] | uint32 s_nan[waves] | uint32 s_claim
+// (minmax_commit's words; the tail entry thread 0 claimed for the workgroup)
 struct MinMaxHistLds {
     static __host__ __device__ float* s_mn(uint32_t* base, int bins) { return reinterpret_cast<float*>(HistLds::end(base, bins)); }
     static __host__ __device__ float* s_mx(uint32_t* base, int bins) { return s_mn(base, bins) + kBlock / kWave; }
     static __host__ __device__ uint32_t* s_nan(uint32_t* base, int bins) {
         return reinterpret_cast<uint32_t*>(s_mx(base, bins) + kBlock / kWave);
     }
-    static __host__ __device__ size_t bytes(int bins) { return HistLds::bytes(bins) + 3 * (kBlock / kWave) * sizeof(uint32_t); }
+    static __host__ __device__ uint32_t* s_claim(uint32_t* base, int bins) { return s_nan(base, bins) + kBlock / kWave; }
+    static __host__ __device__ size_t bytes(int bins) { return HistLds::bytes(bins) + (3 * (kBlock / kWave) + 1) * sizeof(uint32_t); }
 };
 
 // k_minmax and k_abs_hist in one read: min / max / NaN into the accumulators as k_minmax does, counts against snap[slot] into the
 // ledger entry as k_abs_hist does (same HistOp, same flush).
+//
+// Schedule: the grid is the BODY, workgroup b streams block b of the table; the blocks from gridDim.x on are the TAIL, small
+// entries handed out by a queue (*queue, zeroed by k_hist_snapshot: thread 0 claims, LDS broadcasts) to whichever workgroup is
+// done first — a launch of fixed shares ends with its slowest workgroup, 12 % of the workgroup-time idle on MI355X
+// (profiles/range_queue).  A workgroup flushes its counters and commits its min / max only when the slot changes and at the end:
+// consecutive items of one slot, claimed entries included, cost one flush.  Any split of the table gives the same sums.
 __global__ __launch_bounds__(kBlock) void k_minmax_hist(const dpl_work_item* __restrict__ items,
-                                                         const uint32_t* __restrict__ bb,
+                                                         const uint32_t* __restrict__ bb, uint32_t n_blocks,
                                                          const float* const* __restrict__ segs,
                                                          uint32_t* __restrict__ min_enc, uint32_t* __restrict__ max_enc,
                                                          uint32_t* __restrict__ nan_flag,
                                                          const dpl_hist_range* __restrict__ snap, int bins,
-                                                         uint32_t* __restrict__ counts) {
+                                                         uint32_t* __restrict__ counts, uint32_t* __restrict__ queue) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_mh[];  // MinMaxHistLds
     uint32_t* s_nz = HistLds::s_nz(lds_mh, bins);
     float* s_mn = MinMaxHistLds::s_mn(lds_mh, bins);
     float* s_mx = MinMaxHistLds::s_mx(lds_mh, bins);
     uint32_t* s_nan = MinMaxHistLds::s_nan(lds_mh, bins);
-    uint32_t k0, k1;
-    block_items(bb, k0, k1);
-    for (uint32_t k = k0; k < k1; ++k) {
-        const dpl_work_item it = items[k];
-        const dpl_hist_range r = snap[it.slot];
-        MinMaxOp m{INFINITY, -INFINITY, 0u};
-        if (r.status != 0u) {  // no guess for this slot (uniform branch)
-            stream_span(segs[it.seg] + it.offset, it.count, m);
-        } else {
-            for (int b = threadIdx.x; b <= bins; b += kBlock) lds_mh[b] = 0u;
-            __syncthreads();
-            if (r.exact_div)
-                minmax_hist_body<false>(it, segs, r, bins, counts, lds_mh, s_nz, m);
-            else
-                minmax_hist_body<true>(it, segs, r, bins, counts, lds_mh, s_nz, m);
+    uint32_t* s_claim = MinMaxHistLds::s_claim(lds_mh, bins);
+    RangeCarry c{RangeCarry::kNoSlot, 0u, 0u, {INFINITY, -INFINITY, 0u}};
+    // the held slot's counters into its row of the entry, its min / max into the accumulators
+    auto close = [&]() {
+        if (c.slot == RangeCarry::kNoSlot) return;
+        const dpl_hist_range r = snap[c.slot];
+        if (r.status == 0u) {
+            dpl_work_item whole{};  // (hist_flush reads the slot and the elements streamed)
+            whole.slot = c.slot;
+            whole.count = c.count;
+            hist_flush(c.nonzero, whole, r, bins, counts, lds_mh, s_nz);
         }
-        minmax_commit(m, it.slot, s_mn, s_mx, s_nan, min_enc, max_enc, nan_flag);
+        minmax_commit(c.m, c.slot, s_mn, s_mx, s_nan, min_enc, max_enc, nan_flag);
+    };
+    uint32_t b = blockIdx.x;
+    for (;;) {
+        const uint32_t k0 = bb ? bb[b] : b, k1 = bb ? bb[b + 1] : b + 1;
+        for (uint32_t k = k0; k < k1; ++k) {
+            const dpl_work_item it = items[k];
+            const dpl_hist_range r = snap[it.slot];
+            if (it.slot != c.slot) {  // (uniform branch)
+                close();
+                c = RangeCarry{it.slot, 0u, 0u, {INFINITY, -INFINITY, 0u}};
+                if (r.status == 0u) {
+                    for (int i = threadIdx.x; i <= bins; i += kBlock) lds_mh[i] = 0u;
+                    __syncthreads();
+                }
+            }
+            c.count += it.count;  // (a slot has fewer than 2^32 elements)
+            if (r.status != 0u)  // no guess for this slot (uniform branch)
+                stream_span(segs[it.seg] + it.offset, it.count, c.m);
+            else if (r.exact_div)
+                minmax_hist_body<false>(it, segs, r, bins, lds_mh, c);
+            else
+                minmax_hist_body<true>(it, segs, r, bins, lds_mh, c);
+        }
+        if (gridDim.x >= n_blocks) break;  // no tail
+        if (threadIdx.x == 0) *s_claim = gridDim.x + atomicAdd(queue, 1u);
+        __syncthreads();
+        b = *s_claim;
+        __syncthreads();
+        if (b >= n_blocks) break;
     }
+    close();
 }
 
 // What the histogram pass does with tensor t, the value of flags[t]: 1 = the entry's row is this batch's histogram and is added
@@ -1014,6 +1064,23 @@ inline int candidate_chunks(const char* who, int64_t n_slots, int64_t n_cand, in
     return 0;
 }
 
+// Compute units of the current device (what dpl_device_info reports), asked of the runtime once per device.
+inline int range_body_cus(int& cus) {
+    static int known[64] = {};  // (by device ordinal; a race writes the same number twice)
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return fail("hipGetDevice", e);
+    int* slot = (dev >= 0 && dev < 64) ? &known[dev] : nullptr;
+    cus = slot ? *slot : 0;
+    if (cus == 0) {
+        e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess) return fail("hipDeviceGetAttribute", e);
+        if (cus < 1) return fail_msg("dpl_minmax_hist_accumulate: the device reports no compute units");
+        if (slot) *slot = cus;
+    }
+    return 0;
+}
+
 }  // namespace
 
 // =================================================================================== C ABI
@@ -1094,14 +1161,20 @@ int dpl_minmax_hist_accumulate(const dpl_work_item* d_items, int64_t n_items, co
     if (n_items <= 0) return 0;
     if (int e = check_blocks("dpl_minmax_hist_accumulate", n_items, d_block_begin, n_blocks)) return e;
     const SpecEntry entry(d_entry, n_slots);
+    uint32_t* queue = SpecEntry::queue(d_entry, n_slots, bins);
     int64_t zb = grid_for(n_slots * (int64_t)bins, kBlock * 8);
     if (zb < grid_for(n_slots, kBlock)) zb = grid_for(n_slots, kBlock);
     if (zb > 1024) zb = 1024;
     hipLaunchKernelGGL(k_hist_snapshot, dim3((unsigned)zb), dim3(kBlock), 0, (hipStream_t)s, d_min_enc, d_max_enc, d_nan,
-                       n_slots, bins, entry.snap, entry.flags, entry.counts);
+                       n_slots, bins, entry.snap, entry.flags, entry.counts, queue);
     DPL_LAUNCH_CHECK("k_hist_snapshot");
-    hipLaunchKernelGGL(k_minmax_hist, dim3((unsigned)n_blocks), dim3(kBlock), MinMaxHistLds::bytes(bins), (hipStream_t)s, d_items,
-                       d_block_begin, d_seg_ptrs, d_min_enc, d_max_enc, d_nan, entry.snap, bins, entry.counts);
+    // The body is what one round of the device holds (3 workgroups per CU at this kernel's registers: the 768 blocks
+    // TensorSetPlan.work("range") makes its balanced shares on MI355X); the blocks behind it are the queue's.
+    int cus = 0;
+    if (int e = range_body_cus(cus)) return e;
+    const int64_t n_body = n_blocks < 3 * (int64_t)cus ? n_blocks : 3 * (int64_t)cus;
+    hipLaunchKernelGGL(k_minmax_hist, dim3((unsigned)n_body), dim3(kBlock), MinMaxHistLds::bytes(bins), (hipStream_t)s, d_items,
+                       d_block_begin, (uint32_t)n_blocks, d_seg_ptrs, d_min_enc, d_max_enc, d_nan, entry.snap, bins, entry.counts, queue);
     DPL_LAUNCH_CHECK("k_minmax_hist");
     return 0;
 }

@@ -45,6 +45,70 @@ def _upload_struct_array(arr, n, device):
 # Workgroups per launch for the balanced partition (tuned on MI355X: few, large, equal shares stream
 # faster from HBM than many small items; the histogram wants a little more latency hiding).
 DEFAULT_BLOCKS = {"minmax": 256, "hist": 768, "octav": 1024, "cos": 512, "fq": 65536}   # measured optima per kernel family
+# The work kind 'range' (the range pass that also histograms, k_minmax_hist): DEFAULT_BLOCKS["hist"] balanced shares over the first
+# 1 - RANGE_TAIL_SHARE of the batch's element stream (the BODY: the launch's grid, 3 workgroups per CU on MI355X), the rest as
+# about RANGE_TAIL_ENTRIES small entries the workgroups claim from a queue as they finish (the TAIL).  Measured on MI355X:
+# profiles/range_queue/README.md.
+RANGE_TAIL_SHARE = 1 / 8
+RANGE_TAIL_ENTRIES = 1536
+
+_WORK_ITEM_DTYPE = np.dtype([("offset", "<u8"), ("count", "<u4"), ("seg", "<u4"), ("slot", "<u4"), ("reserved", "<u4")])
+
+
+def build_range_table(spans, n_body, tail_share=RANGE_TAIL_SHARE, tail_entries=RANGE_TAIL_ENTRIES):
+    """HOST: the two-part work table of kind 'range' over spans = [(seg, offset, count, slot)] -> (items, block_begin, n_body,
+    n_tail): numpy work items (_WORK_ITEM_DTYPE) and the uint32 [n_body + n_tail + 1] block table.
+
+    Body: n_body balanced shares (dpl_build_balanced_items) of the stream up to the cut — the last multiple of 1024 elements of
+    the tensor that position (1 - tail_share) * total falls in.  Tail: every tensor's part behind the cut in equal pieces of
+    about tail_total / tail_entries elements (the same builder, one span at a time: an entry is ONE item and never crosses a
+    tensor).  The queue hands entries out in table order while every workgroup takes about R = n_tail / n_body of them, one per
+    round, so the table holds them ROUND-major — the stream's entries in n_body contiguous runs of R (or R - 1), the runs' first
+    entries, then their second ones, ...: a workgroup's successive claims, n_body places apart, are then neighbours in one
+    tensor, and it keeps its counters across them (one flush instead of R)."""
+    assert _WORK_ITEM_DTYPE.itemsize == C.sizeof(_hip.WorkItem)
+    spans = [tuple(int(v) for v in s) for s in spans]
+    total = sum(s[2] for s in spans)
+    cut = total - int(total * tail_share) if tail_entries > 0 else total
+    body, tail, g = [], [], 0
+    for seg, off, cnt, slot in spans:
+        room = max(0, cut - g)
+        head = cnt if room >= cnt else (room // 1024) * 1024
+        if head:
+            body.append((seg, off, head, slot))
+        if cnt - head:
+            tail.append((seg, off + head, cnt - head, slot))
+        g += cnt
+
+    def as_numpy(arr, n):
+        return np.frombuffer(C.string_at(C.addressof(arr), C.sizeof(_hip.WorkItem) * n), dtype=_WORK_ITEM_DTYPE)
+
+    items, bb = [], [np.zeros(1, np.uint32)]
+    if body:
+        arr, n, b = _hip.build_balanced_items(body, n_body)
+        items.append(as_numpy(arr, n))
+        bb.append(np.frombuffer(bytes(b), dtype=np.uint32)[1:])
+    else:
+        n_body = 0
+    n_items = int(bb[-1][-1])
+    entries = []
+    target = max(1, sum(s[2] for s in tail) // max(1, tail_entries))
+    for s in tail:
+        pieces = max(1, min((s[2] + target // 2) // target, s[2] // 1024))   # (a cut inside a span is a multiple of 1024 elements)
+        arr, n, _ = _hip.build_balanced_items([s], pieces)
+        entries.append(as_numpy(arr, n))
+    if entries:
+        entries = np.concatenate(entries)
+        n_tail = len(entries)
+        e = np.arange(n_tail, dtype=np.int64)
+        run = e * max(1, n_body) // n_tail                  # the contiguous run of the stream's entries that entry e belongs to
+        first = np.searchsorted(run, run, side="left")      # ... and where that run starts
+        items.append(entries[np.lexsort((run, e - first))])  # round-major: by place in the run, then by run
+        bb.append(n_items + 1 + np.arange(n_tail, dtype=np.uint32))
+    else:
+        n_tail = 0
+    items = np.concatenate(items) if items else np.zeros(0, _WORK_ITEM_DTYPE)
+    return items, np.concatenate(bb).astype(np.uint32), n_body, n_tail
 
 
 class WorkSet:
@@ -76,6 +140,7 @@ class TensorSetPlan:
         self.total = sum(self.elems) * self.batch
         self.chunk = int(chunk_elems) if chunk_elems else None
         self._work = {}
+        self.range_kind = "range"   # the work kind of the speculating range pass (a test sets the tuple form: work())
         self._elems_dev = None      # filled by elems_device(): the plan's first range pass
         self._octav_scratch = None  # ... by octav_scratch()
         self._octav_lh = None       # ... by octav_loghist_scratch()
@@ -96,13 +161,22 @@ class TensorSetPlan:
         return [(t, 0, e * self.batch, t) for t, e in enumerate(self.elems)]
 
     def work(self, kind, per_image=False):
-        """WorkSet for kernel family `kind` in {'minmax', 'hist', 'octav', 'cos', 'fq'}."""
-        nb = None if self.chunk else max(1, min(DEFAULT_BLOCKS[kind], (self.total + 4095) // 4096))
-        key = (per_image, nb)
+        """WorkSet for kernel family `kind` in {'minmax', 'hist', 'octav', 'cos', 'fq', 'range'}.  'range' is the two-part table
+        of build_range_table (balanced form only); ('range', n_body, tail_share, tail_entries) overrides its constants — for
+        tests of the schedule, through TensorSetPlan.range_kind."""
+        ranged = kind == "range" or (isinstance(kind, tuple) and kind[0] == "range")
+        nb = None if self.chunk else max(1, min(DEFAULT_BLOCKS["hist" if ranged else kind], (self.total + 4095) // 4096))
+        key = (per_image, kind) if ranged else (per_image, nb)
         w = self._work.get(key)
         if w is None:
             spans = self._spans(per_image)
-            if self.chunk:
+            if ranged:
+                if self.chunk:
+                    raise _hip.DipoorletHipError("work kind 'range' has no chunk_elems form")
+                items, bb, n_body, n_tail = build_range_table(spans, nb) if kind == "range" else build_range_table(spans, *kind[1:])
+                w = WorkSet(torch.from_numpy(items.view(np.uint8).copy()).to(self.device), len(items),
+                            torch.from_numpy(bb.view(np.int32).copy()).to(self.device), n_body + n_tail)
+            elif self.chunk:
                 arr, n = _hip.build_work_items(spans, self.chunk)
                 w = WorkSet(_upload_struct_array(arr, n, self.device), n, None, n)
             else:
@@ -482,7 +556,7 @@ class CalibAccumulators:
         if self.n < (plan.n_pairs if per_image else plan.T):
             raise _hip.DipoorletHipError("accumulator has fewer slots than the plan addresses")
         if self.will_speculate(plan, tensors, per_image):
-            w = plan.work("hist")
+            w = plan.work(plan.range_kind)
             entry = self._entry_for(tensors)
             plan.elems_device()     # (uploaded with the plan's first range pass, not in the middle of the histogram pass)
             _hip.check(_hip.lib().dpl_minmax_hist_accumulate(*w.args(), _ptr(tab), _ptr(self.min_enc), _ptr(self.max_enc),

@@ -152,9 +152,12 @@ int dpl_abs_hist_accumulate(const dpl_work_item* d_items, int64_t n_items, const
  *      dpl_abs_hist_accumulate over the other tensors only (a balanced partition of what remains, derived on the device; no host
  *      round trip).  The counts are the ones dpl_abs_hist_accumulate gives, provided the batch's data did not change in between.
  *      d_entry: dpl_hist_spec_entry_bytes(n_slots, bins) bytes, 16-byte aligned:
- *          dpl_hist_range snapshot[n_slots] | uint32 flags[n_slots] | pad to 16 | uint32 counts[n_slots, bins]
+ *          dpl_hist_range snapshot[n_slots] | uint32 flags[n_slots] | pad to 16 | uint32 counts[n_slots, bins] | pad to 16 | uint32 queue[4]
  *      flags (written by dpl_hist_spec_accumulate): 1 = row added, the tensor was not read; 2 = status != 0, nothing to count; 0 = read.
- *      The items of dpl_minmax_hist_accumulate are any partition with slot < n_slots and fewer than 2^32 elements per slot.
+ *      queue: dpl_minmax_hist_accumulate's own (an entry serves one launch at a time).
+ *      The items of dpl_minmax_hist_accumulate are any partition with slot < n_slots and fewer than 2^32 elements per slot.  Its
+ *      launch is min(n_blocks, 3 x compute units) workgroups: workgroup b streams block b, and the blocks behind those (small ones
+ *      serve best) go one at a time to whichever workgroup is done first, so the launch does not wait for its slowest share.
  *      dpl_hist_spec_accumulate takes the per-tensor form: tensor t = segment t = slot t from offset 0, d_elems[t] (< 2^32) elements,
  *      n_slots <= DPL_HIST_SPEC_MAX_TENSORS, n_blocks workgroups.  d_stats (may be NULL): uint64 [4] += {tensors, tensors not read,
  *      elements, elements not read}. */
